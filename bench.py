@@ -99,7 +99,38 @@ def parse(argv=None):
     ap.add_argument("--stream-test", type=int, default=0, help="diagnosis of the host-traffic cost: 1 no result copies, 2 batches copied device to device, 3 host copies in 16 chunks")
     ap.add_argument("--sdma", type=int, default=-1, help="1 / 0: HSA_ENABLE_SDMA for this process (copy engines or shader copies for the host traffic); -1: leave the environment alone")
     ap.add_argument("--unique-batches", type=int, default=0, help="distinct particle batches cycled from host memory (0: 4 = 16384 particles at --batch 4096)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 or float64, at most "
+                         "64 MB in all; an array over its share is a fixed, seeded sample of its elements): refno, psi, flip, sx, sy, cc per particle "
+                         "and the volume of the run's finish; in flexalign mode the last movie's shifts, spline coefficients and aligned sum. Rank 0 only")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write name -> array as dirname/<name>.npy, float32 kept and everything else as float64, at most `limit` bytes in all.
+    The smallest arrays go first; one larger than its share of what is left is replaced by a sample of its flattened elements at
+    sorted indices drawn by np.random.default_rng(0), so the same arguments sample the same positions.  Returns name -> (shape, sampled)."""
+    os.makedirs(dirname, exist_ok=True)
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left, info = limit - 4096 * len(items), {}           # (4 KB per file for the .npy header)
+    for i, (name, a) in enumerate(items):
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        share = left // (len(items) - i)
+        sampled = a.nbytes > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        info[name] = (list(np.asarray(arrays[name]).shape), bool(sampled))
+    print(f"bench.py: outputs written to {dirname}: {info}", file=sys.stderr, flush=True)
+    return info
 
 
 # bounds the FlexAlign leg asserts: device vs oracle pair shifts of three K3 frames (measured 2.6e-6 px in round 6, once the mean of the
@@ -290,6 +321,8 @@ def main_flexalign(args):
             self.done = [torch.cuda.Event(), torch.cuda.Event()]
             self.timers = {"global_alignment": [], "local_alignment": [], "warp_and_sum": []}
             self.results = []
+            self.last = None            # (movie index, (global, local) results, slot of h_avg) of the last timed movie
+            self.filled = [False, False]    # which of dbuf has ever held a movie
             self.error = None
 
         def timed(self, name, record, fn):
@@ -335,12 +368,14 @@ def main_flexalign(args):
                         if j + 1 < len(movies):
                             self.fetch(j + 1, movies[j + 1])
                         self.stream.wait_event(self.ready[j & 1])
+                        self.filled[j & 1] = True
                         if self.rbuf is not self.dbuf:
                             xa.movie_frames_to_float(self.ctx, self.rbuf[j & 1], out=self.dbuf[j & 1])
                         r = self.align(self.dbuf[j & 1], record, j & 1)
                         self.done[j & 1].record(self.stream)
                         if record:
                             self.results.append((k % nuniq, r[0]))
+                            self.last = (k, r, j & 1)
             except BaseException as e:          # re-raised on the main thread
                 self.error = e
 
@@ -377,6 +412,12 @@ def main_flexalign(args):
     if args.warmup:
         streamed(max(args.warmup, nlanes), False)
     elapsed = streamed(args.steps, True)
+    if args.dump_outputs and rank == 0:
+        # the last timed movie as its caller received it; before the legs below, which reuse the lanes' buffers
+        ln = max((ln_ for ln_ in lanes if ln_.last is not None), key=lambda ln_: ln_.last[0])
+        _, (gl, loc), slot = ln.last
+        dump_outputs(args.dump_outputs, {"shift_x": gl["shiftX"], "shift_y": gl["shiftY"], "patch_shifts": loc["patch_shifts"],
+                                         "coeffs_x": loc["coeffsX"], "coeffs_y": loc["coeffsY"], "aligned_sum": ln.h_avg[slot].numpy()})
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -417,6 +458,9 @@ def main_flexalign(args):
     for ln in lanes:
         ln.timers = {k_: [] for k_ in ln.timers}
     nres = max(2, min(args.steps, 3))
+    if not lanes[0].filled[1]:
+        # (no more steps than lanes, warm-up and timed: lane 0 has seen one movie, and its second buffer was never written)
+        lanes[0].dbuf[1].copy_(lanes[0].dbuf[0])
     barrier()
     tr0 = time.perf_counter()
     with torch.cuda.stream(lanes[0].stream):
@@ -730,6 +774,7 @@ def main():
             timed("gridding_insert_images", record, lambda: rf.insert_images(imgs, ang, ctf_array=ctf_arr))      # CTF planes + FFT + records + gridding
 
     fin_ev = []          # (start, end) event pairs of the tail on the reconstruction stream: its duration on the DEVICE
+    fin_vol = [None]     # the volume of the latest finish (the same page-locked buffer every call)
 
     def finish():
         if rf is None:
@@ -739,7 +784,7 @@ def main():
             e0.record()
             rf.mirror_and_crop()
             xa.allreduce_reconstruction(rf)
-            rf.finish(reuse=True)          # (the volume is not looked at here: one page-locked result buffer for every call)
+            fin_vol[0] = rf.finish(reuse=True)          # (not looked at here: one page-locked result buffer for every call)
             rf.reset()
             e1.record()
             fin_ev.append((e0, e1))
@@ -810,6 +855,15 @@ def main():
 
     t0, t_fin0, t1 = (resident_steps if args.timed == "resident" else streamed_steps)(args.steps, True)
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        # what the caller received from the last timed step (its results in h_out[slot]) and from the finish; before the extra
+        # legs, which reuse both buffers
+        dumped = {}
+        if pm is not None and args.stream_test != 1:
+            dumped.update({k_: t_.numpy().copy() for k_, t_ in h_out[(args.steps - 1) & 1].items()})
+        if fin_vol[0] is not None:
+            dumped["volume"] = fin_vol[0]
+        dump_outputs(args.dump_outputs, dumped)
     # the once-per-run tail (mirror/crop + all-reduce + finaliser + reset) as the device saw it: events on the reconstruction stream
     # around it.  (The host clock from "all steps queued" to the end -- what rounds 3-4 printed here -- also holds the steps the
     # device had not finished yet: 37 ms where the tail itself is 8.)

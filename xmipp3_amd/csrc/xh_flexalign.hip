@@ -1263,7 +1263,7 @@ __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__
             const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wyt), t));
             // (the term's control point comes out of LDS again, a broadcast: two v_readlane of C.x and C.y here were merged by ROCm 7.2's
             // clang into ONE read of C.x feeding both halves of the packed multiply-add below -- seen in the ISA, and in
-            // tests/test_gpu_flexalign.py::test_warp_with_the_usual_control_grid_against_the_oracle as wrong shifts in y)
+            // tests/test_gpu_flexalign.py's warp test with the usual control grid as wrong shifts in y)
             const float *rt = reinterpret_cast<const float *>(sq + 2 * (((t >> 2) & 3) * nq + (yi + (t & 3)) * qx + xi0)) + 2 * (t >> 4);
             const float cx = rt[0], cy = rt[1];
             const int bt = t >> 4;

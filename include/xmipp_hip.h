@@ -129,12 +129,11 @@ typedef struct xh_rf xh_rf;
 int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out);
 int xh_rf_destroy(xh_rf *rf);
 /* profiling / A-B knobs of the reconstruction handle (defaults are the product path): "unit_z" 4 | 8 (depth of a wave's voxel unit in
- * k_rf_grid), "grid_waves" 0 (= the configuration's default) | 8 | 9 | 12 | 16, "fuse_ctf" 1 | 0 (CTF evaluated while the records
- * are packed, or through planes), "ctf_fast" 1 | 0 (CTFs without envelope terms evaluated by the cheap form of preloadCTF's value, or the
- * general double-precision formula for every pixel), "records_from_images" 0 | 1 (records written by the FFT's row pass), "order_spaces" 1 | 0 (the traverse spaces of a launch
- * ordered by plane -- the gridding kernel then shares the voxel queue between projections of one direction -- or in input order; the order
- * permutes the launch's float additions), "shift_bands" 1 | 0 (256-px images shifted band by band out of LDS, or by k_rf_shift: same bits), "tile_max_spaces",
- * "fft_variant" 1 | 2 (columns-first / rows-first projection FFT). Unknown names fail with XH_ERR_ARG. */
+ * k_rf_grid), "grid_waves" 0 (= the configuration's default) | 8 | 9 | 12 | 16, "ctf_fast" 1 | 0 (CTFs without envelope terms evaluated
+ * by the cheap form of preloadCTF's value, or the general double-precision formula for every pixel), "order_spaces" 1 | 0 (the traverse
+ * spaces of a launch ordered by plane -- the gridding kernel then shares the voxel queue between projections of one direction -- or in
+ * input order; the order permutes the launch's float additions), "shift_bands" 1 | 0 (256-px images shifted band by band out of LDS, or
+ * by k_rf_shift: same bits), "tile_max_spaces". Unknown names fail with XH_ERR_ARG. */
 int xh_rf_set_option(xh_rf *rf, const char *name, double value);
 /* derived sizes (RFA:196-199): paddedImgSize P, maxVolumeIndexYZ mv, fft crop sizeX=mv/2, sizeY=mv */
 int xh_rf_sizes(const xh_rf *rf, int32_t *paddedImgSize, int32_t *maxVolumeIndex,
@@ -304,12 +303,13 @@ int xh_pm_rows_pruned(const xh_pm *pm, int64_t *rows_pruned);
  * is cheaper from 9 % on; below 6 % it goes back (set_option "adaptive_finish" 0: never; get_option "dense_chunks": how
  * many chunks of the last call took that form). Identical results either way. */
 int xh_pm_two_level_cut(const xh_pm *pm, int32_t *K0, int32_t *nk);
-/* tuning knobs: fp32 ambiguity margin relative to sum_r 2*pi*r; rows per launch chunk.
+/* tuning knobs: "tau_rel" (fp32 ambiguity margin relative to sum_r 2*pi*r), "chunk_rows" (rows per launch chunk), "prune", "k0",
+ * "mask_lists", "group_high", "high_cap", "adaptive_finish", "tr_chunk_mb", "s6_fp32", "s6_eps", "s6_capture" (see above and below).
  * "threads" n (1..16): the reference program's --thr (angular_projection_matching.cpp:64,631,1018-1108).  Its n worker threads take
  * the positions i % n of a particle's neighbour list and their results are merged, worker 0 first, strictly greater wins -- which
  * only shows where two correlation values are EXACTLY equal (duplicated references): the winner is then the one with the smallest
  * (i % n, position in the image's visiting order) instead of the first visited.  xh_pm_match[_ex] reproduces that order, for the
- * running top-N (n_orient > 1) as well. */
+ * running top-N (n_orient > 1) as well.  Unknown names fail with XH_ERR_ARG. */
 int xh_pm_set_option(xh_pm *pm, const char *name, double value);
 /* current value of "tau_rel" (ambiguity margin of the fp32 coarse search, relative to sum_r 2 pi r) or "s6_eps" (margin of the
  * fp32 pass of xh_pm_translate, relative to the maximum of the correlation map): the tests hold the measured fp32 errors against them;

@@ -924,3 +924,19 @@ def test_constant_particle_in_a_masked_list_search_stays_on_its_list(gpu):
     r = refno.cpu().numpy()
     for i in range(n):
         assert r[i] in lists[i], (i, r[i], lists[i])
+
+
+# options of experiments that were measured and retired (docs/experiments.md): the matcher no longer knows them
+RETIRED_PM_OPTIONS = ["use_mfma", "use_mfma64", "use_idft3", "contract_shape", "contract_dbg", "store_cut", "s6_pair",
+                      "s6_coarse_kernel", "s6_debug", "early_exit", "tail_band", "mirror", "polar_cells", "use_fir", "use_fir64",
+                      "fir64_fused", "tie_rel"]
+
+
+def test_retired_options_are_rejected(gpu):
+    xa, ctx, torch = gpu
+    from xmipp3_amd._lib import lib
+    refs = _library(32, 12)
+    pm = xa.ProjectionMatcher(ctx, torch.from_numpy(refs).cuda())
+    for name in RETIRED_PM_OPTIONS:
+        assert lib().xh_pm_set_option(pm.h, name.encode(), 1.0) == -1, name      # XH_ERR_ARG
+    assert lib().xh_pm_set_option(pm.h, b"tau_rel", pm.get_option("tau_rel")) == 0

@@ -859,3 +859,13 @@ def test_shift_band_by_band_gives_the_same_bits(gpu):
         outs.append(rf.shift_images(imgs, shifts, flips=flips).cpu().numpy())
     assert np.array_equal(outs[0], outs[1])
     assert np.array_equal(outs[0][0], imgs[0].cpu().numpy())
+
+
+def test_retired_options_are_rejected(gpu):
+    """options of experiments that were measured and retired (docs/experiments.md): the gridder no longer knows them"""
+    xa, ctx, torch = gpu
+    from xmipp3_amd._lib import lib
+    rf = xa.RecFourier(ctx, 32)
+    for name in ["fft_variant", "records_from_images", "fuse_ctf", "skip_far_cells", "grid_tile_budget"]:
+        assert lib().xh_rf_set_option(rf.h, name.encode(), 1.0) == -1, name      # XH_ERR_ARG
+    assert lib().xh_rf_set_option(rf.h, b"order_spaces", 1.0) == 0

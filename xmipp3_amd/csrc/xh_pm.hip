@@ -95,7 +95,7 @@ struct xh_pm {
     xh_ctx *ctx;
     Layout L;
     int nrefs, logM, M;
-    double tau_rel, scale, tie_rel;
+    double tau_rel, scale;
     size_t chunk_rows;
     // static device data
     XhBuf d_sin, d_cos, d_ringOfSample, d_nsam, d_soff, d_coff, d_rstart, d_ringW;
@@ -112,7 +112,7 @@ struct xh_pm {
     XhBuf d_coef32, d_polar32, d_A32, d_stat32;     // S1<float>
     XhBuf d_trAngles;                               // S6: cos / sin per particle
     XhBuf d_cellStart, d_cellSamples, d_cellOrg, d_cellData;    // k_pm_polar_cells: samples per image cell
-    int ncells, use_cells;
+    int ncells;
     XhBuf d_coef64, d_polar64, d_A64, d_stat64;     // S1<double> (ambiguous particles)
     XhBuf d_raw, d_rowres, d_desc, d_nbr, d_poff;
     XhBuf d_ambList, d_ambSlot, d_candRow, d_candRes, d_counters, d_offs5d, d_thrLists;
@@ -122,30 +122,20 @@ struct xh_pm {
     int coefFirst, coefCount;      // particles whose fp32 B-spline coefficients d_coef32 holds (last match call)
     hipEvent_t ev[6];
     double stage_ms[8];   // prep32, contract, idft_max, select, rescore(fp64), translate
-    int use_idft3, use_mfma, contract_dbg, use_fir;
-    int store_cut;               // S2 of a bank that is not band limited: frequencies whose coefficients are kept for S3 (0: none, bounds only; -1: all, rounds 1-4)
-    int contract_shape;          // S2: particle x reference tiles per workgroup of k_pm_contract_mfma as a two-digit number (14, 22, 24, 42, 44)
-    int use_mfma64;              // fp64 ring DFT on v_mfma_f64_16x16x4_f64 (0: the direct sum, for A/B)
-    int s6_pair;                 // S6: two particles per inverse transform (k_pm_tr_cols_pair)
-    int s6_coarse_kernel;        // S6: the fp32 pass ends in k_pm_bestshift_coarse (0: k_pm_bestshift<float>, A/B)
-    int fir64_fused;             // the fp64 prefilter: 2 the recursion tile by tile, 1 the 65-tap convolution as one kernel, 0 rows then columns with an intermediate (A/B)
-    int s6_debug;                // profiling: xh_pm_translate returns decision margins instead of shifts
+    int store_cut;               // S2 of a bank that is not band limited: frequencies whose coefficients are kept for S3 (0: none, bounds only; -1: all, the dense finish)
     int s6_capture;              // test hook: 32 / 64 = xh_pm_translate runs only that chain and leaves the correlation maps for xh_pm_debug_s6_maps
     int s6_captured;             // ... precision and count of the maps left behind
     int s6_capturedN;
     int s6_fp32;                 // S6: fp32 pass + double-precision repeat of the ambiguous particles (0: everything in double)
     double s6_eps;               // ... its ambiguity margin relative to the map's maximum
     long long s6_flagged;        // particles the last xh_pm_translate repeated in double precision
-    int use_fir64;               // fp64 prefilter as a 65-tap convolution (1) or the recursion (0)
     XhBuf d_firTmp64;
     int tr_chunk_mb;             // S6: MB of the z buffer per pass (0: default)
     int use_prune;               // S3 branch and bound (k_pm_prune_plan); identical results either way
     int use_mask_lists;          // neighbour-list searches over the whole bank with the off-list references masked (0: gather path)
-    XhBuf d_bpart, d_rowBound, d_rowTail, d_topRows, d_thr, d_survList, d_rowLow, d_survSpan, d_highStore;
+    XhBuf d_bpart, d_rowBound, d_rowTail, d_topRows, d_thr, d_survList, d_survSpan, d_highStore;
     int group_high;              // the surviving rows' frequencies >= K0 particle by particle (k_pm_rows_high; 0: each transforming wave its own, for A/B)
     int high_cap;                // rows of the store behind k_pm_rows_high (0: max(65536, rows / 16); the tests set a few to reach the rows beyond it)
-    int no_mirror;               // option "mirror" 0: the mirrored particle is not searched (rotation estimator)
-    int use_early_exit;          // surviving rows are dropped while their high frequencies are computed, once the bound allows it
     int64_t stat_pruned;
     int lastPruneRows;           // rows of the last chunk that went through k_pm_survivors (0: none)
     // A map with flat correlation peaks lets a third of the rows through the bounds, and a surviving row that contracts its own
@@ -158,7 +148,6 @@ struct xh_pm {
     // two-level S2: the MFMA contraction stops at frequency K0 (multiple of 4; K0 == nk: off), see k_pm_tail_norms
     int K0, K0auto, quadsLow;
     XhBuf d_bT, d_aT, d_kboundsLow, d_bTband;
-    int tail_band;               // k_pm_prune_plan bounds the frequencies >= K0 in bands of XH_TAIL_BAND (1: one by one, for A/B)
     XhBuf d_firTmp, d_polarPart, d_trPart, d_listMask, d_s6Flag, d_s6List, d_s6Parts, d_s6Meta, d_s6Out;
     XhBuf d_qoff, d_Bpack, d_Apack, d_kbounds;
     int totalQuads;
@@ -426,7 +415,7 @@ typedef float xh_f32x16_rd __attribute__((ext_vector_type(16)));
 template <int NA>
 __device__ __forceinline__ void rd_round(float (*sX)[XH_RD_LD], float (*sO)[XH_RD_LD], const xh_cf *sT, const float *__restrict__ polar,
                                          const float *sMean, xh_cf *__restrict__ out, int n, int nk, int kt0,
-                                         int slot0, int nslots, int nsamples, int soffr, int coffr, int ncoef, int conjugate, int dbg)
+                                         int slot0, int nslots, int nsamples, int soffr, int coffr, int ncoef, int conjugate)
 {
     constexpr int NR = NA > 0 ? NA : 1;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -472,7 +461,7 @@ __device__ __forceinline__ void rd_round(float (*sX)[XH_RD_LD], float (*sO)[XH_R
             sO[q][tid] = inRing && !edge ? xa - xb : 0.f;
         }
         __syncthreads();
-        if (NA > 0 && dbg != 2) {
+        if (NA > 0) {
             // A step takes two samples (lanes 0-31 the first, 32-63 the second) through 2 NA matrix instructions. Its
             // operands -- the sample pair and NA twiddles -- are read from LDS one whole step ahead, into the other of two
             // register sets (the loop body is two steps), at the top of the step before: the wave never waits for LDS
@@ -529,7 +518,7 @@ __device__ __forceinline__ void rd_round(float (*sX)[XH_RD_LD], float (*sO)[XH_R
 __global__ void __launch_bounds__(256, 2)
 k_pm_ringdft_mfma(const float *__restrict__ polar, const double *__restrict__ stat, xh_cf *__restrict__ out,
                   const xh_cf *__restrict__ tw, const int *__restrict__ nsam, const int *__restrict__ soff,
-                  const int *__restrict__ coff, int nsamples, int ncoef, int conjugate, int nslots, int nrings, int dbg)
+                  const int *__restrict__ coff, int nsamples, int ncoef, int conjugate, int nslots, int nrings)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float (*sX)[XH_RD_LD] = reinterpret_cast<float (*)[XH_RD_LD]>(smem);
@@ -547,7 +536,7 @@ k_pm_ringdft_mfma(const float *__restrict__ polar, const double *__restrict__ st
     for (int kt0 = 0; kt0 < nkt; kt0 += 4 * XH_RD_KT) {
         const int left = nkt - kt0 - wv;          // tiles kt0+wv, +4, +8, +12 that exist
         const int nact = __builtin_amdgcn_readfirstlane(left <= 0 ? 0 : min(XH_RD_KT, (left + 3) / 4));
-#define XH_RD_GO(NA_) rd_round<NA_>(sX, sO, sT, polar, sMean, out, n, nk, kt0, slot0, nslots, nsamples, soff[r], coff[r], ncoef, conjugate, dbg)
+#define XH_RD_GO(NA_) rd_round<NA_>(sX, sO, sT, polar, sMean, out, n, nk, kt0, slot0, nslots, nsamples, soff[r], coff[r], ncoef, conjugate)
 #if XH_RD_KT >= 4
         if (nact == 4) XH_RD_GO(4);
         else
@@ -786,8 +775,7 @@ __global__ void k_pm_pack_tiles(const xh_cf *__restrict__ src, float4 *__restric
 // PT x QT waves per workgroup: wave (i, j) owns particle tile blockIdx.y PT + i and reference tile blockIdx.x QT + j. The operands
 // come straight from global memory (no LDS): what the waves of a workgroup share -- an A tile among the QT waves of a row, a B tile
 // among the PT waves of a column -- is served by the CU's L1, so the L2 delivers (PT + QT) tiles per PT QT products: 1.25 per
-// product for the 1 x 4 workgroup of rounds 1-4, 0.5 for 4 x 4 (the full-frequency contraction moved 106 GB through the L2s per
-// 4096 particles x 1000 references and was bound by exactly that).
+// product for the 1 x 4 workgroup the search launches (the other shapes measured are in docs/experiments.md).
 // LDS (PT = 1 only): the operands travel global -> LDS by LDS-DMA (global_load_lds_dwordx4: no registers, many quads in flight), a
 // stage of XH_CT_NQ quads at a time into one of two buffers -- the A quads once per workgroup, every wave its own B quads --, and the
 // waves read their float4 out of LDS one quad ahead of the matrix instructions.  The quads of a frequency slice are consecutive in
@@ -799,7 +787,7 @@ template <int PT, int QT, bool LDS = false>
 __global__ void __launch_bounds__(64 * PT * QT)
 k_pm_contract_mfma(const float4 *__restrict__ Apack, const float4 *__restrict__ Bpack, float4 *__restrict__ raw,
                    const int *__restrict__ qoff, const int *__restrict__ kbounds, int nk, int totalQuads, int nparticles,
-                   int nq, int nqtiles, int nptiles, int dbg, float2 *__restrict__ bpart, int rawStride, int kStore)
+                   int nq, int nqtiles, int nptiles, float2 *__restrict__ bpart, int rawStride, int kStore)
 {
     static_assert(!LDS || (PT == 1 && XH_PW2 == 1 && XH_CT_NQ % QT == 0), "the LDS form shares one particle tile per workgroup");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -949,7 +937,7 @@ k_pm_contract_mfma(const float4 *__restrict__ Apack, const float4 *__restrict__ 
                     theirs[0][c] = __shfl_xor(s0, 1, 64);
                     theirs[1][c] = __shfl_xor(s1, 1, 64);
                 }
-                if (ptile0 + t < nptiles && p < nparticles && q < nq && (dbg != 1 || mine[0][0] == 1234.5f)) {
+                if (ptile0 + t < nptiles && p < nparticles && q < nq) {
                     float4 *dst = raw + ((size_t)p * nq + q) * rawStride;
                     const int kA = k0 + (odd ? 2 : 0);
                     float4 o0, o1;
@@ -1000,7 +988,7 @@ __device__ __forceinline__ void d_top2_insert(float v, int i, float &b, int &bi,
 template <int LOGM>
 __global__ void __launch_bounds__(256)
 k_pm_idft_max(const float4 *__restrict__ raw, RowRes *__restrict__ res, const xh_cf *__restrict__ W,
-              const xh_cf *__restrict__ chirp, const xh_cf *__restrict__ vhat, int N, int nk, int nrows, int lpb, int noMirror)
+              const xh_cf *__restrict__ chirp, const xh_cf *__restrict__ vhat, int N, int nk, int nrows, int lpb)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     xh_cf *s = reinterpret_cast<xh_cf *>(smem);
@@ -1044,7 +1032,7 @@ k_pm_idft_max(const float4 *__restrict__ raw, RowRes *__restrict__ res, const xh
         for (int i = tid; i < N; i += nth) {
             const xh_cf z = xh_cmul(s[l * M + i], chirp[i]);
             d_top2_insert(z.x, i, b, bi, sec);
-            if (!noMirror) d_top2_insert(z.y, N + i, b, bi, sec);
+            d_top2_insert(z.y, N + i, b, bi, sec);
         }
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_down(b, o, 64), os = __shfl_down(sec, o, 64);
@@ -1198,11 +1186,7 @@ struct XhHigh {          // what S3 needs to finish a row the contraction left a
     int nrings, ncoef, K0, nq;
     int zeroHigh;        // 1: leave them zero (lower bounds from the low part alone, see k_pm_prune_thr)
     int rawStride;       // float4 per row of the S2 -> S3 intermediate: K0 with the two-level contraction, else nk
-    // bound of a surviving row while its high frequencies are computed (early exit, see k_pm_idft_max3); null: off
-    const float4 *rowLow;        // per row: moduli sums below K0 (straight, mirror), 2 x Cauchy-Schwarz tail, normalisation
-    const float *aT, *bT;        // the per-frequency norms behind that tail: [slot][nk], [nk][nrefs]
-    int nk, nrefs;
-    int noMirror;                // 1: only the straight particle is a candidate (option "mirror" 0: the rotation estimator)
+    int nk;
     // the frequencies >= K0 of the listed rows where k_pm_rows_high left them: [list position][nk - K0], positions < highCap (null: the
     // transforming wave contracts them itself, d_row_high)
     const float4 *highStore;
@@ -1369,8 +1353,7 @@ template <int R1, int R2, int R3>
 __global__ void __launch_bounds__(256, 2)
 k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const xh_cf *__restrict__ Wfull,
                const xh_cf *__restrict__ chirp, const xh_cf *__restrict__ vperm, int N, int nk, int nrows,
-               const int *__restrict__ rowList, const float *__restrict__ rowBound, const float *__restrict__ thr,
-               int rowsPerParticle, int *__restrict__ prunedCounter, XhHigh H, const int *__restrict__ nrowsDev)
+               const int *__restrict__ rowList, XhHigh H, const int *__restrict__ nrowsDev)
 {
     constexpr int M = R1 * R2 * R3;
     constexpr int S3 = R3 + 1;              // padded innermost stride (bank conflicts)
@@ -1388,7 +1371,6 @@ k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const x
     xh_cf *s = sbuf + (size_t)wv * LDSW;
     float4 *sraw = reinterpret_cast<float4 *>(s);     // the row is staged here before pass 1 overwrites it
     const int half = N / 2;
-    int skipped = 0;
     if (nrowsDev) nrows = *nrowsDev;     // length of rowList decided on the device (k_pm_survivors)
     // Which list entries a wave takes.  The lists are particle by particle (the four planned rows, then the ~6 survivors of a particle
     // are neighbours), and rows of one particle read the same 205 KB of its coefficients in d_row_high: chunks of 32 consecutive
@@ -1401,54 +1383,13 @@ k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const x
         if (xcdMap ? 256 * (ex >> 5) >= nrows : it >= nrows) break;
         if (it >= nrows) continue;
         const int row = rowList ? rowList[it] : it;
-        // branch and bound: the row cannot reach (best of its particle - 2 tau), see k_pm_prune_plan
-        if (rowBound && (rowBound[row] == -INFINITY || rowBound[row] < thr[row / rowsPerParticle])) {
-            if (lane == 0) { RowRes r; r.best = -3.0e38f; r.idx = 0; r.second = -3.0e38f; r.pad = 0; res[row] = r; }
-            ++skipped;
-            continue;
-        }
         const float4 *rr = raw + (size_t)row * H.rawStride;
         // ---- stage the row (one coalesced burst), then pull every pass-1 input into registers
         if (H.K0 >= nk) {
             for (int k = lane; k < nk; k += 64) sraw[k] = rr[k];
         } else {
             const int slot = row / H.nq, ref = row - slot * H.nq;
-            if (H.rowLow && !H.zeroHigh) {
-                // The row survived on a bound whose high-frequency part is Cauchy-Schwarz per frequency. As the wave computes
-                // those frequencies (64 at a time, a lane each) it replaces their share of the bound by the moduli it now
-                // knows; once the bound falls below the particle's threshold the row is dropped like a pruned one -- same
-                // criterion, same slack (1.0001 covers the rounding of these fp32 sums as it does in k_pm_prune_plan).
-                const float4 lo = H.rowLow[row];
-                float bS = lo.x + lo.z, bM = lo.y + lo.z;
-                const float th = thr[row / rowsPerParticle], scl = 1.0001f / lo.w;
-                bool dead = false;
-                for (int k0 = 0; k0 < nk; k0 += 64) {
-                    const int k = k0 + lane;
-                    float dS = 0.f, dM = 0.f;
-                    if (k < nk) {
-                        if (k < H.K0) sraw[k] = rr[k];
-                        else {
-                            const float4 o = d_row_high(H, slot, ref, k);
-                            sraw[k] = o;
-                            const float fsr = o.x - o.w, fsi = o.y + o.z, fmr = o.x + o.w, fmi = o.y - o.z;
-                            const float cs = 2.f * H.aT[(size_t)slot * H.nk + k] * H.bT[(size_t)k * H.nrefs + ref];
-                            if (k == nk - 1) { dS = fabsf(fsr) - cs; dM = fabsf(fmr) - cs; }       // c2r drops its imaginary part
-                            else { dS = 2.f * sqrtf(fsr * fsr + fsi * fsi) - cs; dM = 2.f * sqrtf(fmr * fmr + fmi * fmi) - cs; }
-                        }
-                    }
-                    if (k0 + 63 >= H.K0) {
-                        for (int o = 32; o > 0; o >>= 1) { dS += __shfl_xor(dS, o, 64); dM += __shfl_xor(dM, o, 64); }
-                        bS += dS; bM += dM;
-                        if (fmaxf(bS, bM) * scl < th) { dead = true; break; }
-                    }
-                }
-                if (dead) {
-                    if (lane == 0) { RowRes r; r.best = -3.0e38f; r.idx = 0; r.second = -3.0e38f; r.pad = 0; res[row] = r; }
-                    ++skipped;
-                    __builtin_amdgcn_wave_barrier();
-                    continue;
-                }
-            } else if (H.highStore && it < H.highCap) {
+            if (H.highStore && it < H.highCap) {
                 const float4 *hs = H.highStore + (size_t)it * (nk - H.K0);
                 for (int k = lane; k < nk; k += 64) sraw[k] = k < H.K0 ? rr[k] : hs[k - H.K0];
             } else
@@ -1581,7 +1522,7 @@ k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const x
                 if (n < N) {
                     const xh_cf z = xh_cmul(v[n1], chirp[n]);
                     d_top2_insert(z.x, n, b1, bi, sec);
-                    if (!H.noMirror) d_top2_insert(z.y, N + n, b1, bi, sec);
+                    d_top2_insert(z.y, N + n, b1, bi, sec);
                 }
             }
         }
@@ -1594,7 +1535,6 @@ k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const x
         if (lane == 0) { RowRes r; r.best = b1; r.idx = bi; r.second = sec; r.pad = 0; res[row] = r; }
         __builtin_amdgcn_wave_barrier();
     }
-    if (prunedCounter && lane == 0 && skipped) atomicAdd(prunedCounter, skipped);
 }
 
 // =========================================================================== S4
@@ -1603,7 +1543,7 @@ k_pm_idft_max3(const float4 *__restrict__ raw, RowRes *__restrict__ res, const x
 // contiguous, poff[slot]..poff[slot+1]; the rows of a particle are therefore contiguous too.
 // dense (nq > 0): every slot is compared with references 0..nq-1; otherwise rowSlot/refIds give the
 // slot and the reference of every row (neighbour lists, APM:609-626).
-struct RowMap { const int *poff; const int *rowSlot; const int *refIds; int nt, nq; int noMirror = 0; /* 1: the mirrored particle is not a candidate */
+struct RowMap { const int *poff; const int *rowSlot; const int *refIds; int nt, nq;
                 int thr = 1;   /* the program's --thr: list position i belongs to worker i % thr (APM:631), the workers' results are merged (APM:1063-1108) */ };
 __device__ __forceinline__ int d_row_slot(const RowMap &M, int row) { return M.rowSlot ? M.rowSlot[row] : row / M.nq; }
 __device__ __forceinline__ int d_row_ref(const RowMap &M, int row, int slot) { return M.refIds ? M.refIds[row] : row - slot * M.nq; }
@@ -1627,7 +1567,7 @@ __global__ void __launch_bounds__(256)
 k_pm_prune_plan(const float2 *__restrict__ bpart, int nslices, size_t nrowsTotal, RowMap M, const double *__restrict__ refSigma,
                 const double *__restrict__ stat32, float *__restrict__ rowBound, int *__restrict__ topRows,
                 const float *__restrict__ aT, const float *__restrict__ bT, int K0, int nk, int nrefs, float *__restrict__ rowTail,
-                const unsigned *__restrict__ mask, int maskW, float4 *__restrict__ rowLow, const float *__restrict__ bTband, int band)
+                const unsigned *__restrict__ mask, int maskW, const float *__restrict__ bTband, int band)
 {
     __shared__ float sv[256];
     __shared__ int sr[256];
@@ -1640,7 +1580,8 @@ k_pm_prune_plan(const float2 *__restrict__ bpart, int nslices, size_t nrowsTotal
     __shared__ float sAm[1024 / 4];
     // band > 1: the frequencies from the first multiple of band on are bounded band by band, (largest norm of the particle in the band) x
     // (sum of the reference's norms over it, bTband [band index][nrefs]) >= the band's sum of products: an eighth of the multiply-adds
-    // for a tail bound a few per cent larger, where the tail is 1e-5 of the bound
+    // for a tail bound a few per cent larger, where the tail is 1e-5 of the bound. (band is always XH_TAIL_BAND, passed at run time:
+    // as a compile-time constant the compiler unrolls the band loops into 107 registers instead of 88, one wave per SIMD less.)
     const int kAl = band > 1 ? min(nk, (K0 + band - 1) / band * band) : nk;
     const int nhigh = kAl - K0, nbands = band > 1 ? (nk - kAl + band - 1) / band : 0, b0 = band > 1 ? kAl / band : 0;
     for (int it = 0; it < M.nt; ++it) {
@@ -1718,7 +1659,6 @@ k_pm_prune_plan(const float2 *__restrict__ bpart, int nslices, size_t nrowsTotal
                 // 1e-4: rounding of the fp32 sums, of sqrtf and of the fp32 transform itself (all ~1e-6 relative)
                 rowBound[r] = (fmaxf(bs, bm) + 2.f * tail[j]) * 1.0001f / den;
                 rowTail[r] = 2.f * tail[j] * 1.0001f / den;
-                if (rowLow) rowLow[r] = make_float4(bs, bm, 2.f * tail[j], den);
                 // a neighbour-list search run over the whole bank (xh_pm_match_ex): a reference that is not on the particle's
                 // list can never be picked, listed first or survive -- it is not a row of the search
                 if (mask && !((mask[(size_t)p * maskW + (ref[j] >> 5)] >> (ref[j] & 31)) & 1u)) { rowBound[r] = -INFINITY; rowTail[r] = 0.f; }
@@ -1948,7 +1888,7 @@ k_pm_rescore_row(const int *__restrict__ counters, const int *__restrict__ candR
     double best = -1.0e300;
     int bi = 0x7fffffff;
     const int half = N / 2;
-    const int ncand = M.noMirror ? N : 2 * N;
+    const int ncand = 2 * N;
     // a thread owns shift ii of BOTH rows (straight and mirrored): one gather of cs[ii k mod N] serves the two sums (the gathers, not the
     // multiply-adds, are what this loop waits for); every sum is formed exactly as before
     for (int ii = threadIdx.x; ii < N; ii += blockDim.x) {
@@ -1965,7 +1905,6 @@ k_pm_rescore_row(const int *__restrict__ counters, const int *__restrict__ candR
         accS += 2.0 * tS; accM += 2.0 * tM;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (h == 1 && M.noMirror) break;
             const int i = ii + h * N;
             const double v = (h ? accM : accS) / den;
             if (dbgRow) dbgRow[i] = v;
@@ -2008,6 +1947,8 @@ k_pm_rescore_row(const int *__restrict__ counters, const int *__restrict__ candR
 // Among exactly equal values the reference keeps the one it meets first (strict >).  With --thr T worker c = i % T walks the list
 // positions i it owns in the image's visiting order and the merge of the workers' results (APM:1063-1108, strict > again, worker 0
 // first) keeps the lowest worker among equals: the key is (worker, visiting position).
+// Two fp64 values count as equal when they differ by less than XH_TIE_REL, relative to sum_r 2 pi r (the handle's scale).
+#define XH_TIE_REL 1e-12
 __device__ __forceinline__ int d_visit_order(const RowMap &M, int row, bool forward)
 {
     const int slot = d_row_slot(M, row);
@@ -2242,8 +2183,7 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restrict__ zimg, const int *__restrict__ refno,
                const unsigned char *__restrict__ flip, int D, double maxShift, double *__restrict__ shiftX,
-               double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts, int dbgMargins,
-               unsigned char *__restrict__ flag, double eps)
+               double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts)
 {
     __shared__ double red[8];
     __shared__ double sv[256];
@@ -2251,7 +2191,7 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
     __shared__ double sh[2];
     const int p = blockIdx.x;
     if (refno[p] < 0) {
-        if (threadIdx.x == 0) { shiftX[p] = 0; shiftY[p] = 0; maxCC[p] = 0; if (flag) flag[p] = 0; }
+        if (threadIdx.x == 0) { shiftX[p] = 0; shiftY[p] = 0; maxCC[p] = 0; }
         return;
     }
     const int n = D * D, cen = D / 2;
@@ -2325,7 +2265,6 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
             imax = tmax / D + start; jmax = tmax % D + start;
             int nf = min(min(imax - start, fin - imax), min(jmax - start, fin - jmax)) + 1;   // first window that leaves the map
             int tfirst = tmax;
-            double sec = -1.0e300;                          // largest value beside the maximum (flag != nullptr only)
             // raw order (coalesced), XH_BS_U independent loads in flight per thread: a block is alone with its map and would
             // otherwise wait out one memory latency per element
             for (int t0 = threadIdx.x; t0 < n; t0 += XH_BS_U * (int)blockDim.x) {
@@ -2344,16 +2283,7 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
                     const double v = a * (double)rv[u] + b;
                     if (thr > v) nf = min(nf, max(abs(i + start - imax), abs(j + start - jmax)));
                     if (v == mx && t < tfirst) tfirst = t;      // an earlier element that rounds onto the maximum (part != nullptr only)
-                    if (t != tmax) sec = fmax(sec, v);
                 }
-            }
-            if (flag) {
-                __syncthreads();
-                sv[threadIdx.x] = sec;
-                __syncthreads();
-                for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sv[threadIdx.x] = fmax(sv[threadIdx.x], sv[threadIdx.x + o]); __syncthreads(); }
-                if (threadIdx.x == 0) sh[0] = sv[0];
-                __syncthreads();
             }
             si[threadIdx.x] = nf; si2[threadIdx.x] = tfirst;
             __syncthreads();
@@ -2370,27 +2300,6 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
             __syncthreads();
         }
         int n_max = si[0];
-        if (dbgMargins) {
-            // profiling only: how far the window decision and the arg-max are from flipping (relative to the maximum)
-            __syncthreads();
-            double mg = 1.0e300, sec = -1.0e300;
-            for (int t = threadIdx.x; t < n; t += blockDim.x) {
-                const int i = t / D, j = t - i * D;
-                const double v = a * RC(i, j) + b;
-                if (max(abs(i + start - imax), abs(j + start - jmax)) <= n_max) mg = fmin(mg, fabs(v - thr));
-                if (t != tmax) sec = fmax(sec, v);
-            }
-            sv[threadIdx.x] = mg;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sv[threadIdx.x] = fmin(sv[threadIdx.x], sv[threadIdx.x + o]); __syncthreads(); }
-            const double mgAll = sv[0];
-            __syncthreads();
-            sv[threadIdx.x] = sec;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sv[threadIdx.x] = fmax(sv[threadIdx.x], sv[threadIdx.x + o]); __syncthreads(); }
-            if (threadIdx.x == 0) { shiftX[p] = mgAll / fabs(mx); shiftY[p] = (mx - sv[0]) / fabs(mx); maxCC[p] = (double)n_max; }
-            return;
-        }
         __syncthreads();
         if (imax - n_max < start) n_max = min(imax - start, n_max);
         if (imax + n_max > fin) n_max = min(fin - imax, n_max);
@@ -2399,8 +2308,6 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
         // centre of mass of the window (FIL:1700-1716)
         double xmax = 0, ymax = 0, sumcorr = 0;
         const int wd = 2 * n_max + 1;
-        double mg = 1.0e300;                                // how close an element of the window comes to the threshold
-        const double secAll = flag ? sh[0] : 0.0;
         for (int t = threadIdx.x; t < wd * wd; t += blockDim.x) {
             const int i = t / wd - n_max, j = t % wd - n_max;
             const int ia = i + imax, ja = j + jmax;
@@ -2408,30 +2315,12 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
             ymax += ia * val;
             xmax += ja * val;
             sumcorr += val;
-            mg = fmin(mg, fabs(val - thr));
-        }
-        if (flag) {
-            // The coarse (fp32) pass of xh_pm_translate: the arg-max and the window are discrete decisions. Where the
-            // runner-up comes within eps |max| of the maximum, or an element of the window within eps |max| of the
-            // threshold, the particle is flagged and repeated in double precision.
-            __syncthreads();
-            sv[threadIdx.x] = mg;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sv[threadIdx.x] = fmin(sv[threadIdx.x], sv[threadIdx.x + o]); __syncthreads(); }
-            if (threadIdx.x == 0) {
-                const double lim = eps * fabs(mx);
-                flag[p] = !(sv[0] > lim && mx - secAll > lim && sd != 0) ? 1 : 0;     // NaN-safe: anything unclear is repeated
-            }
-            __syncthreads();
         }
         const double YM = d_block_sum(ymax, red), XM = d_block_sum(xmax, red), SC = d_block_sum(sumcorr, red);
         if (threadIdx.x == 0) {
             double ox = 0, oy = 0;
             if (SC != 0) { ox = XM / SC; oy = YM / SC; }
             if (!(maxShift > 0)) ox = oy = 0.;
-            // the rejection of shifts beyond max_shift (APM:841-842) is a discrete decision too: a coarse-pass shift within
-            // 1e-3 px of the limit is repeated in double precision
-            if (flag && maxShift > 0 && fabs(sqrt(ox * ox + oy * oy) - (double)maxShift) < 1e-3) flag[p] = 1;
             if (ox * ox + oy * oy > maxShift * maxShift) ox = oy = 0.;
             sh[0] = ox; sh[1] = oy;
         }
@@ -2743,9 +2632,10 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
 // and ~15 MB of HBM traffic per 256-px particle. Here a thread keeps a whole radix-R butterfly in
 // registers (fp64), LDS is touched once per transform, and the step is three kernels:
 //   k_pm_tr_rows : build z = Mref + i*Mimg (APM:812-828), keep it for correlationIndex, forward row FFTs
-//   k_pm_tr_cols : forward column FFTs, cross-power spectrum of the two packed images, inverse column
-//                  FFTs -- a block owns column pairs (kx, -kx) so the Hermitian partner is in LDS
-//   k_pm_tr_irows: inverse row FFTs, real part only (the correlation map)
+//   k_pm_tr_cols_pair: forward column FFTs, cross-power spectrum of the two packed images, inverse column
+//                  FFTs -- a block owns column pairs (kx, -kx) so the Hermitian partner is in LDS; two particles
+//                  share one inverse transform
+//   k_pm_tr_irows: inverse row FFTs, the real and imaginary parts (the two particles' correlation maps)
 // DIF forward, mirrored inverse: x[n1*R2+n2] <-> X[k1 + R1*k2]; no bit reversal anywhere.
 // z = rotate(BSPLINE3, ref, psi, DONT_WRAP) + i * (mirrored) particle (APM:812-828) for a 16 x 16 output tile per block. The
 // 16 taps of a pixel used to be gathered from the 512-KB coefficient image in global memory (the L1's tag lookups bound
@@ -2942,83 +2832,10 @@ k_pm_tr_rows(const float *__restrict__ particles, const double *__restrict__ ref
     }
 }
 
-template <int R1, int R2>
-__global__ void __launch_bounds__(256)
-k_pm_tr_cols(xh_cd *__restrict__ w, const xh_cd *__restrict__ WD)
-{
-    typedef TrGeom<R1, R2> G;
-    constexpr int D = G::D;
-    constexpr int HP = G::LN / 2;             // column pairs per block
-    extern __shared__ __align__(16) unsigned char smem[];
-    xh_cd *s = reinterpret_cast<xh_cd *>(smem);
-    xh_cd *sW = s + (size_t)G::LN * G::LS;
-    const int tid = threadIdx.x;
-    xh_cd *img = w + (size_t)blockIdx.y * D * D;
-    for (int i = tid; i < D; i += 256) sW[i] = WD[i];
-    // line c < HP: column P = blockIdx.x*HP + c; line c >= HP: its Hermitian partner D - P.
-    // Pair 0 is special: columns 0 and D/2, each its own partner.
-    auto column = [&](int cl) {
-        const int q = cl < HP ? cl : cl - HP;
-        const int P = blockIdx.x * HP + q;
-        if (P == 0) return cl < HP ? 0 : D / 2;
-        return cl < HP ? P : D - P;
-    };
-    xh_cd v[G::RM];
-    __syncthreads();
-    if (tid < G::LN * R2) {
-        const int cl = tid % G::LN, n2 = tid / G::LN;      // neighbouring threads, neighbouring columns
-        const int col = column(cl);
-#pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) v[n1] = img[(size_t)(n1 * R2 + n2) * D + col];
-        tr_fwd1<R1, R2>(v, s + cl * G::LS, sW, n2);
-    }
-    __syncthreads();
-    const int cl2 = tid % G::LN, k1 = tid / G::LN;
-    const bool act2 = tid < G::LN * R1;
-    if (act2) tr_fwd2<R1, R2>(v, s + cl2 * G::LS, k1);
-    __syncthreads();
-    // natural-order spectrum back to LDS: X[k1 + R1*k2] at k1*S1' ... reuse the (a,b) grid with a = k1, b = k2
-    if (act2) {
-#pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) s[cl2 * G::LS + k1 * G::S1 + k2] = v[k2];
-    }
-    __syncthreads();
-    if (act2) {
-        const int q = cl2 < HP ? cl2 : cl2 - HP;
-        const bool special = (blockIdx.x * HP + q) == 0;
-        const int pc = special ? cl2 : (cl2 < HP ? cl2 + HP : cl2 - HP);
-        const double inv = 1.0 / ((double)D * (double)D);
-#pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) {
-            const int ky = k1 + R1 * k2;
-            const int nky = (D - ky) & (D - 1);
-            const xh_cd a = v[k2];
-            const xh_cd b = s[pc * G::LS + (nky % R1) * G::S1 + (nky / R1)];
-            // F1 = (Z[k] + conj Z[-k])/2, F2 = (Z[k] - conj Z[-k])/(2i); product F1 conj(F2) / D^2
-            const xh_cd f1 = xh_cd{0.5 * (a.x + b.x), 0.5 * (a.y - b.y)};
-            const xh_cd f2 = xh_cd{0.5 * (a.y + b.y), -0.5 * (a.x - b.x)};
-            xh_cd r = xh_cmulc(f1, f2);
-            r.x *= inv;
-            r.y *= inv;
-            v[k2] = r;
-        }
-    }
-    __syncthreads();
-    if (act2) tr_inv2<R1, R2>(v, s + cl2 * G::LS, sW, k1);
-    __syncthreads();
-    if (tid < G::LN * R2) {
-        const int cl = tid % G::LN, n2 = tid / G::LN;
-        tr_inv1<R1, R2>(v, s + cl * G::LS, n2);
-        const int col = column(cl);
-#pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) img[(size_t)(n1 * R2 + n2) * D + col] = v[n1];
-    }
-}
-
 // Two particles per block. The cross-power spectra P_a, P_b are those of real maps, so one complex inverse transform carries
 // both: W = P_a + i P_b  ->  R_a = Re, R_b = Im of its inverse. A block forwards LN/2 columns (LN/4 Hermitian pairs) of either
 // particle, forms the two cross-powers, and inverts LN/2 combined columns into particle a's buffer: the inverse column pass,
-// its stores and the whole inverse row pass (k_pm_tr_irows<.., true>) are halved. Particle b = min(a + 1, m - 1): an odd
+// its stores and the whole inverse row pass (k_pm_tr_irows) are halved. Particle b = min(a + 1, m - 1): an odd
 // batch pairs its last particle with itself and the imaginary half is dropped.
 template <int R1, int R2>
 __global__ void __launch_bounds__(256)
@@ -3113,7 +2930,7 @@ k_pm_tr_cols_pair(xh_cd *__restrict__ w, const xh_cd *__restrict__ WD, int m)
     }
 }
 
-template <int R1, int R2, bool PAIR = false>
+template <int R1, int R2>
 __global__ void __launch_bounds__(256)
 k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m)
 {
@@ -3123,8 +2940,8 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
     xh_cd *s = reinterpret_cast<xh_cd *>(smem);
     xh_cd *sW = s + (size_t)G::LN * G::LS;
     const int tid = threadIdx.x;
-    // PAIR: the buffer of particle 2 blockIdx.y holds the combined columns of two particles (k_pm_tr_cols_pair)
-    const int p = PAIR ? 2 * blockIdx.y : blockIdx.y, p2 = PAIR ? min(p + 1, m - 1) : p, row0 = blockIdx.x * G::LN;
+    // the buffer of particle 2 blockIdx.y holds the combined columns of two particles (k_pm_tr_cols_pair)
+    const int p = 2 * blockIdx.y, p2 = min(p + 1, m - 1), row0 = blockIdx.x * G::LN;
     for (int i = tid; i < D; i += 256) sW[i] = WD[i];
     __syncthreads();
     xh_cd v[G::RM];
@@ -3142,7 +2959,7 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
         double *dst = Rout + ((size_t)p * D + row0 + l) * D;
 #pragma unroll
         for (int n1 = 0; n1 < R1; ++n1) dst[n1 * R2 + n2] = v[n1].x;
-        if (PAIR && p2 != p) {
+        if (p2 != p) {
             double *dst2 = Rout + ((size_t)p2 * D + row0 + l) * D;
 #pragma unroll
             for (int n1 = 0; n1 < R1; ++n1) dst2[n1 * R2 + n2] = v[n1].y;
@@ -3153,7 +2970,7 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
     // per block, combined in block order by k_pm_bestshift, which then reads the map once instead of three times.
     double *red = reinterpret_cast<double *>(smem);
     int *redi = reinterpret_cast<int *>(red + 3 * 256);
-    for (int h = 0; h < (PAIR ? 2 : 1); ++h) {
+    for (int h = 0; h < 2; ++h) {
         if (h == 1 && p2 == p) break;
         double s1 = 0, s2 = 0, bv = -1.0e300;
         int bi = 0x7fffffff;
@@ -3448,15 +3265,15 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
     XH_TRY(xh_buf_reserve(ctx, polarBuf, sizeof(T) * nps * L.nsamples));
     XH_TRY(xh_buf_reserve(ctx, outBuf, sizeof(xh_c2<T>) * nps * L.ncoef));
     XH_TRY(xh_buf_reserve(ctx, statBuf, sizeof(double) * 2 * nps));
-    if (std::is_same<T, float>::value && imgsAreFloat && !d_gather && !d_count && pm->use_fir && D >= 2 * XH_FIR_K) {
+    if (std::is_same<T, float>::value && imgsAreFloat && !d_gather && !d_count && D >= 2 * XH_FIR_K) {
         xh_prefilter_fir_launch(ctx->stream, (const float *)imgs, (float *)coefBuf.p, D, (size_t)nslots);
         XH_LAUNCH_CHECK();
-    } else if (std::is_same<T, double>::value && pm->use_fir64 && D >= 16) {
+    } else if (std::is_same<T, double>::value && D >= 16) {
         // fp64: the 65-tap convolution form (source images gathered, device-side count honoured)
         const XhFir64 F = xh_fir64_taps();
         const int segs = (D + XH_FIR64_V - 1) / XH_FIR64_V;
         const size_t nvec = (size_t)nslots * D * segs;
-        if (pm->fir64_fused == 2 && nslots <= 65535 && D >= 2 * XH_REC64_K) {
+        if (nslots <= 65535 && D >= 2 * XH_REC64_K) {
             // the recursion tile by tile (k_pm_prefilter_rec64_2d)
             const int tilesX = (D + 255) / 256, tilesY = (D + XH_REC64_V - 1) / XH_REC64_V;
             if (imgsAreFloat)
@@ -3466,7 +3283,7 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
                 hipLaunchKernelGGL((k_pm_prefilter_rec64_2d<double>), dim3(tilesX * tilesY, nslots), dim3(256), 0, ctx->stream, (const double *)imgs, (double *)coefBuf.p, D, tilesX,
                                    d_gather, d_count);
             XH_LAUNCH_CHECK();
-        } else if (pm->fir64_fused && nslots <= 65535) {
+        } else if (nslots <= 65535) {
             // both passes in one kernel, no intermediate
             const int tilesX = (D + XH_FIR64_TW - 1) / XH_FIR64_TW, tilesY = (D + XH_FIR64_V - 1) / XH_FIR64_V;
             if (imgsAreFloat)
@@ -3503,7 +3320,7 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
                        (T *)coefBuf.p, D, nslots, d_count);
     XH_LAUNCH_CHECK();
     }
-    if (pm->use_cells && nt == 1 && !d_offs && xoff == 0. && yoff == 0. && D >= 64 && L.Ro <= D / 2 - 1) {
+    if (nt == 1 && !d_offs && xoff == 0. && yoff == 0. && D >= 64 && L.Ro <= D / 2 - 1) {
         // zero offsets: sampling cell by cell from LDS-staged patches
         const int nc = pm->ncells;
         XH_TRY(xh_buf_reserve(ctx, pm->d_polarPart, sizeof(double) * 3 * nps * nc));
@@ -3532,17 +3349,17 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
         XH_LAUNCH_CHECK();
     }
     }
-    if (std::is_same<T, float>::value && !d_count && pm->use_mfma) {
+    if (std::is_same<T, float>::value && !d_count) {
         const size_t smemM = sizeof(float) * 64 * XH_RD_LD + sizeof(xh_cf) * (L.N + L.N / 16 + 1);
         XH_HIP(hipFuncSetAttribute((const void *)k_pm_ringdft_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smemM));
         hipLaunchKernelGGL(k_pm_ringdft_mfma, dim3(L.nrings, (unsigned)((nps + 31) / 32)), dim3(256), smemM, ctx->stream,
                            (const float *)polarBuf.p, (const double *)statBuf.p, (xh_cf *)outBuf.p, (const xh_cf *)twBuf.p,
                            (const int *)pm->d_nsam.p, (const int *)pm->d_soff.p, (const int *)pm->d_coff.p, L.nsamples, L.ncoef,
-                           conjugate ? 1 : 0, (int)nps, L.nrings, pm->contract_dbg);
+                           conjugate ? 1 : 0, (int)nps, L.nrings);
         XH_LAUNCH_CHECK();
         return XH_OK;
     }
-    if (std::is_same<T, double>::value && !d_count && pm->use_mfma64) {
+    if (std::is_same<T, double>::value && !d_count) {
         // fp64 on the matrix cores (the re-scored particles, the reference bank)
         const size_t smemD = sizeof(double) * 32 * XH_RD64_LD + sizeof(xh_cd) * (L.N + L.N / 8 + 1);
         hipLaunchKernelGGL(k_pm_ringdft_mfma64, dim3(L.nrings, (unsigned)((nps + 15) / 16)), dim3(256), smemD, ctx->stream,
@@ -3575,7 +3392,7 @@ static void free_all(xh_pm *pm)
                      &pm->d_chirp, &pm->d_vhat, &pm->d_csN, &pm->d_WD64, &pm->d_coef32, &pm->d_polar32, &pm->d_A32,
                      &pm->d_stat32, &pm->d_coef64, &pm->d_polar64, &pm->d_A64, &pm->d_stat64, &pm->d_raw, &pm->d_rowres,
                      &pm->d_desc, &pm->d_nbr, &pm->d_poff, &pm->d_ambList, &pm->d_ambSlot, &pm->d_candRow, &pm->d_candRes,
-                     &pm->d_counters, &pm->d_offs5d, &pm->d_bpart, &pm->d_rowBound, &pm->d_rowLow, &pm->d_rowTail, &pm->d_topRows, &pm->d_survList, &pm->d_survSpan, &pm->d_highStore, &pm->d_thr, &pm->d_bT, &pm->d_bTband, &pm->d_aT, &pm->d_kboundsLow, &pm->d_firTmp, &pm->d_firTmp64, &pm->d_polarPart, &pm->d_t1, &pm->d_t2, &pm->d_t3, &pm->d_trAngles, &pm->d_trPart, &pm->d_listMask, &pm->d_s6Flag, &pm->d_s6List, &pm->d_s6Parts, &pm->d_s6Meta, &pm->d_s6Out, &pm->d_cellStart, &pm->d_cellSamples, &pm->d_cellOrg, &pm->d_cellData, &pm->d_thrLists};
+                     &pm->d_counters, &pm->d_offs5d, &pm->d_bpart, &pm->d_rowBound, &pm->d_rowTail, &pm->d_topRows, &pm->d_survList, &pm->d_survSpan, &pm->d_highStore, &pm->d_thr, &pm->d_bT, &pm->d_bTband, &pm->d_aT, &pm->d_kboundsLow, &pm->d_firTmp, &pm->d_firTmp64, &pm->d_polarPart, &pm->d_t1, &pm->d_t2, &pm->d_t3, &pm->d_trAngles, &pm->d_trPart, &pm->d_listMask, &pm->d_s6Flag, &pm->d_s6List, &pm->d_s6Parts, &pm->d_s6Meta, &pm->d_s6Out, &pm->d_cellStart, &pm->d_cellSamples, &pm->d_cellOrg, &pm->d_cellData, &pm->d_thrLists};
     for (XhBuf *b : bufs) xh_buf_free(*b);
     xh_plan_free(pm->planD);
 }
@@ -3585,7 +3402,7 @@ static void launch_idft(xh_pm *pm, int nrows, int lpb, size_t smem)
 {
     hipLaunchKernelGGL((k_pm_idft_max<LOGM>), dim3((nrows + lpb - 1) / lpb), dim3(256), smem, pm->ctx->stream,
                        (const float4 *)pm->d_raw.p, (RowRes *)pm->d_rowres.p, (const xh_cf *)pm->d_W32.p,
-                       (const xh_cf *)pm->d_chirp.p, (const xh_cf *)pm->d_vhat.p, pm->L.N, pm->L.nk, nrows, lpb, pm->no_mirror);
+                       (const xh_cf *)pm->d_chirp.p, (const xh_cf *)pm->d_vhat.p, pm->L.N, pm->L.nk, nrows, lpb);
 }
 template <int LOGM>
 static void launch_idft_dump(xh_pm *pm, float *d_out, size_t smem)
@@ -3659,13 +3476,6 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     // Relative to S the error grows towards small boxes (2.2e-7 S on four rows at 64 px): below 128 px the margin is 3e-6, where
     // the re-score is cheap anyway. The tests hold the measured error against the margin of the handle they use.
     pm->tau_rel = D >= 128 ? 2e-6 : 3e-6;
-    pm->use_idft3 = 1;
-    pm->use_mfma = 1;
-    pm->use_mfma64 = 1;
-    pm->s6_pair = 1;
-    pm->s6_coarse_kernel = 1;
-    pm->fir64_fused = 2;
-    pm->s6_debug = 0;
     pm->s6_capture = 0;
     pm->s6_captured = 0;
     pm->s6_capturedN = 0;
@@ -3673,8 +3483,6 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     pm->s6_eps = 6.4e-6;      // twenty times the measured error of the fp32 map (3.2e-7 of its maximum at 256 px: tests/test_gpu_pm.py)
     pm->s6_flagged = 0;
     pm->use_prune = 1;
-    pm->no_mirror = 0;
-    pm->use_early_exit = 0;      // measured without gain on the bench gallery (profiles/README.md, round 3): the survivors stay above the threshold to the end
     pm->use_mask_lists = 1;
     pm->tr_chunk_mb = 0;
     pm->stat_pruned = 0;
@@ -3682,15 +3490,9 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     pm->adaptive_finish = 1;
     pm->group_high = 1;
     pm->high_cap = 0;
-    pm->tail_band = XH_TAIL_BAND;
     pm->finish_dense = 0;
     pm->stat_dense_chunks = 0;
-    pm->use_fir = 1;
-    pm->contract_shape = 14;
     pm->store_cut = 0;
-    pm->use_fir64 = 1;
-    pm->contract_dbg = 0;
-    pm->tie_rel = 1e-12;
     pm->chunk_rows = 0;
     pm->stat_rows = pm->stat_resc_p = pm->stat_resc_r = 0;
     pm->coefFirst = pm->coefCount = 0;
@@ -3799,7 +3601,6 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
                     corg.push_back(make_int2(cx * XH_PC - 2, cy * XH_PC - 2));
                 }
             pm->ncells = (int)corg.size();
-            pm->use_cells = 1;
             if (rc == XH_OK) rc = upload(ctx, pm->d_cellStart, cstart);
             if (rc == XH_OK) rc = upload(ctx, pm->d_cellSamples, csamp);
             if (rc == XH_OK) rc = upload(ctx, pm->d_cellOrg, corg);
@@ -4016,26 +3817,14 @@ int xh_pm_set_option(xh_pm *pm, const char *name, double value)
 {
     XH_CHECK(pm && name, XH_ERR_ARG, "null argument");
     if (!strcmp(name, "tau_rel")) pm->tau_rel = value;
-    else if (!strcmp(name, "polar_cells")) pm->use_cells = (int)value;
-    else if (!strcmp(name, "tie_rel")) pm->tie_rel = value;
     else if (!strcmp(name, "chunk_rows")) pm->chunk_rows = (size_t)value;
-    else if (!strcmp(name, "use_idft3")) pm->use_idft3 = (int)value;
-    else if (!strcmp(name, "use_mfma")) pm->use_mfma = (int)value;
-    else if (!strcmp(name, "use_mfma64")) pm->use_mfma64 = (int)value;
-    else if (!strcmp(name, "s6_pair")) pm->s6_pair = (int)value;
-    else if (!strcmp(name, "s6_coarse_kernel")) pm->s6_coarse_kernel = (int)value;
-    else if (!strcmp(name, "fir64_fused")) pm->fir64_fused = (int)value;
-    else if (!strcmp(name, "s6_debug")) pm->s6_debug = (int)value;
     else if (!strcmp(name, "s6_capture")) pm->s6_capture = (int)value;
     else if (!strcmp(name, "s6_fp32")) pm->s6_fp32 = (int)value;
     else if (!strcmp(name, "s6_eps")) pm->s6_eps = value;
     else if (!strcmp(name, "prune")) pm->use_prune = (int)value;
-    else if (!strcmp(name, "early_exit")) pm->use_early_exit = value != 0;
-    else if (!strcmp(name, "mirror")) pm->no_mirror = value == 0;
     else if (!strcmp(name, "mask_lists")) pm->use_mask_lists = (int)value;
     else if (!strcmp(name, "group_high")) pm->group_high = (int)value;
     else if (!strcmp(name, "high_cap")) pm->high_cap = (int)value;
-    else if (!strcmp(name, "tail_band")) pm->tail_band = value > 1 ? XH_TAIL_BAND : 1;
     else if (!strcmp(name, "adaptive_finish")) { pm->adaptive_finish = (int)value; pm->finish_dense = value >= 2; }      // (2: start in the dense form)
     else if (!strcmp(name, "threads")) {
         // the program's --thr: which of two EXACTLY equal correlation values is kept follows the reference's split of a neighbour list over
@@ -4049,11 +3838,6 @@ int xh_pm_set_option(xh_pm *pm, const char *name, double value)
         XH_HIP(hipStreamSynchronize(pm->ctx->stream));
         XH_TRY(set_k0(pm, value <= 0 ? pm->K0auto : (int)value));
     }
-    else if (!strcmp(name, "use_fir")) pm->use_fir = (int)value;
-    else if (!strcmp(name, "contract_shape")) pm->contract_shape = (int)value;
-    else if (!strcmp(name, "store_cut")) pm->store_cut = (int)value;
-    else if (!strcmp(name, "use_fir64")) pm->use_fir64 = (int)value;
-    else if (!strcmp(name, "contract_dbg")) pm->contract_dbg = (int)value;
     else { xh_set_error("xh_pm_set_option: unknown option %s", name); return XH_ERR_ARG; }
     return XH_OK;
 }
@@ -4110,20 +3894,10 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
     const int nrows = poff[m];
     if (nrows == 0) return XH_OK;
     XH_TRY(xh_buf_reserve(ctx, pm->d_rowres, sizeof(RowRes) * (size_t)nrows));
+    // dense: the whole bank, contracted on the matrix cores from packed operands (no tile descriptors); lists: k_pm_contract
+    XH_CHECK(!dense || nq == pm->nrefs, XH_ERR_STATE, "xh_pm_match: internal error, a dense search covers the whole bank");
     std::vector<BlockDesc> desc;
-    const int PT = 4, QT = 4;
-    const bool mfma = dense && pm->use_mfma && nq == pm->nrefs;
-    if (mfma) {
-        // packed-operand MFMA path needs no tile descriptors
-    } else if (dense) {
-        for (int p0 = 0; p0 < m; p0 += PT)
-            for (int q0 = 0; q0 < nq; q0 += QT) {
-                BlockDesc d;
-                d.p0 = p0; d.np = std::min(PT, m - p0); d.qoff = q0; d.nq = std::min(QT, nq - q0);
-                d.row0 = p0 * nq + q0; d.rowstride = nq;
-                desc.push_back(d);
-            }
-    } else {
+    if (!dense) {
         for (int p = 0; p < m; ++p)
             for (int q0 = poff[p]; q0 < poff[p + 1]; q0 += 8) {
                 BlockDesc d;
@@ -4131,14 +3905,12 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
                 d.row0 = q0; d.rowstride = 0;
                 desc.push_back(d);
             }
-    }
-    if (!desc.empty()) {
         XH_TRY(xh_buf_reserve(ctx, pm->d_desc, sizeof(BlockDesc) * desc.size()));
         XH_HIP(hipMemcpyAsync(pm->d_desc.p, desc.data(), sizeof(BlockDesc) * desc.size(), hipMemcpyHostToDevice, ctx->stream));
         XH_HIP(hipStreamSynchronize(ctx->stream));
     }
     const int nt = ((L.nk + 63) / 64) * 64;
-    const bool pruning = mfma && prune && pm->use_prune && pm->R1 && pm->use_idft3 && nparticles > 0 && nrows % nparticles == 0;
+    const bool pruning = dense && prune && pm->use_prune && pm->R1 && nparticles > 0 && nrows % nparticles == 0;
     XH_CHECK(!d_mask || pruning, XH_ERR_STATE, "xh_pm_match: internal error, a masked search must take the pruning path");
     if (pruning) XH_TRY(xh_buf_reserve(ctx, pm->d_bpart, sizeof(float2) * (size_t)XH_KSPLIT * nrows));
     const int K0 = pruning ? pm->K0 : L.nk;          // two-level S2 needs the bounds
@@ -4152,9 +3924,9 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
     XhHigh H;
     H.A = (const xh_cf *)pm->d_A32.p; H.B = (const xh_cf *)pm->d_refsB.p; H.coff = (const int *)pm->d_coff.p;
     H.rstart = (const int *)pm->d_rstart.p; H.nrings = L.nrings; H.ncoef = L.ncoef; H.K0 = boundsOnly ? rawStride : K0; H.nq = nq; H.zeroHigh = 0; H.rawStride = rawStride;
-    H.rowLow = nullptr; H.aT = H.bT = nullptr; H.nk = L.nk; H.nrefs = pm->nrefs; H.noMirror = pm->no_mirror;
+    H.nk = L.nk;
     H.highStore = nullptr; H.highCap = 0;
-    if (mfma) {
+    if (dense) {
         const int ptiles = (m + 15) / 16, qtiles = (nq + 15) / 16;
         const size_t nvec = (size_t)ptiles * pm->totalQuads * 64;
         XH_TRY(xh_buf_reserve(ctx, pm->d_Apack, nvec * sizeof(float4)));
@@ -4163,32 +3935,19 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
                            (const int *)pm->d_nsam.p, L.nrings, L.ncoef, L.nk, pm->totalQuads, m, (const int *)nullptr,
                            K0 < L.nk ? pm->quadsLow : pm->totalQuads);
         XH_LAUNCH_CHECK();
-#define XH_CONTRACT(PT_, QT_)                                                                                                                    \
-        hipLaunchKernelGGL((k_pm_contract_mfma<PT_, QT_>), dim3((qtiles + QT_ - 1) / QT_, (ptiles + PT_ * XH_PW2 - 1) / (PT_ * XH_PW2), XH_KSPLIT),     \
-                           dim3(64 * PT_ * QT_), 0, ctx->stream, (const float4 *)pm->d_Apack.p,                                                      \
-                           (const float4 *)pm->d_Bpack.p, (float4 *)pm->d_raw.p, (const int *)pm->d_qoff.p,                                          \
-                           (const int *)(K0 < L.nk ? pm->d_kboundsLow.p : pm->d_kbounds.p), L.nk, pm->totalQuads, m, nq, qtiles, ptiles,             \
-                           pm->contract_dbg, pruning ? (float2 *)pm->d_bpart.p : (float2 *)nullptr, rawStride, rawStride)
         // the LDS-DMA form pays where a frequency has many quads (the two-level cut keeps the low frequencies: every ring, 16 quads each:
         // 1.87 -> 1.73 ms per 4096 x 1000 rows); over all frequencies its barriers cost more than the deeper pipeline saves (11.7 -> 12.6 ms)
-        if (pm->contract_shape == 141 || (pm->contract_shape == 14 && K0 < L.nk)) {
-            hipLaunchKernelGGL((k_pm_contract_mfma<1, 4, true>), dim3((qtiles + 3) / 4, ptiles, XH_KSPLIT), dim3(256), 0, ctx->stream, (const float4 *)pm->d_Apack.p,
-                               (const float4 *)pm->d_Bpack.p, (float4 *)pm->d_raw.p, (const int *)pm->d_qoff.p,
-                               (const int *)(K0 < L.nk ? pm->d_kboundsLow.p : pm->d_kbounds.p), L.nk, pm->totalQuads, m, nq, qtiles, ptiles,
-                               pm->contract_dbg, pruning ? (float2 *)pm->d_bpart.p : (float2 *)nullptr, rawStride, rawStride);
-        } else
-        if (pm->contract_shape == 44) XH_CONTRACT(4, 4);
-        else if (pm->contract_shape == 24) XH_CONTRACT(2, 4);
-        else if (pm->contract_shape == 22) XH_CONTRACT(2, 2);
-        else if (pm->contract_shape == 42) XH_CONTRACT(4, 2);
-        else XH_CONTRACT(1, 4);
-#undef XH_CONTRACT
-    } else if (dense)
-        hipLaunchKernelGGL((k_pm_contract<4, 4>), dim3((unsigned)desc.size()), dim3(nt), 0, ctx->stream,
-                           (const BlockDesc *)pm->d_desc.p, (const xh_cf *)pm->d_A32.p, (const xh_cf *)pm->d_refsB.p,
-                           (const int *)nullptr, (float4 *)pm->d_raw.p, (const int *)pm->d_coff.p, (const int *)pm->d_rstart.p,
-                           L.nrings, L.ncoef, L.nk);
-    else
+        const int *kb = (const int *)(K0 < L.nk ? pm->d_kboundsLow.p : pm->d_kbounds.p);
+        float2 *bpart = pruning ? (float2 *)pm->d_bpart.p : (float2 *)nullptr;
+        if (K0 < L.nk)
+            hipLaunchKernelGGL((k_pm_contract_mfma<1, 4, true>), dim3((qtiles + 3) / 4, ptiles, XH_KSPLIT), dim3(256), 0, ctx->stream,
+                               (const float4 *)pm->d_Apack.p, (const float4 *)pm->d_Bpack.p, (float4 *)pm->d_raw.p, (const int *)pm->d_qoff.p,
+                               kb, L.nk, pm->totalQuads, m, nq, qtiles, ptiles, bpart, rawStride, rawStride);
+        else
+            hipLaunchKernelGGL((k_pm_contract_mfma<1, 4>), dim3((qtiles + 3) / 4, (ptiles + XH_PW2 - 1) / XH_PW2, XH_KSPLIT), dim3(256), 0, ctx->stream,
+                               (const float4 *)pm->d_Apack.p, (const float4 *)pm->d_Bpack.p, (float4 *)pm->d_raw.p, (const int *)pm->d_qoff.p,
+                               kb, L.nk, pm->totalQuads, m, nq, qtiles, ptiles, bpart, rawStride, rawStride);
+    } else
         hipLaunchKernelGGL((k_pm_contract<1, 8>), dim3((unsigned)desc.size()), dim3(nt), 0, ctx->stream,
                            (const BlockDesc *)pm->d_desc.p, (const xh_cf *)pm->d_A32.p, (const xh_cf *)pm->d_refsB.p, d_ids,
                            (float4 *)pm->d_raw.p, (const int *)pm->d_coff.p, (const int *)pm->d_rstart.p, L.nrings, L.ncoef, L.nk);
@@ -4196,21 +3955,19 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
     if (evMid) XH_HIP(hipEventRecord(evMid, ctx->stream));
     const int lpb = std::max(1, std::min(4, (60 * 1024) / (int)(pm->M * sizeof(xh_cf))));
     const size_t smem = (size_t)lpb * pm->M * sizeof(xh_cf);
-    if (pm->R1 && pm->use_idft3) {
+    if (pm->R1) {
 #define XH_IDFT3(A_, B_, C_)                                                                                  \
     hipLaunchKernelGGL((k_pm_idft_max3<A_, B_, C_>), dim3(grid), dim3(256), 0, ctx->stream, (const float4 *)pm->d_raw.p, \
                        (RowRes *)pm->d_rowres.p, (const xh_cf *)pm->d_Wfull.p, (const xh_cf *)pm->d_chirp.p,       \
-                       (const xh_cf *)pm->d_vperm.p, L.N, L.nk, nr, rowList, rowBound, thr, rowsPer, prunedCnt, H, nrDev)
+                       (const xh_cf *)pm->d_vperm.p, L.N, L.nk, nr, rowList, H, nrDev)
 #define XH_IDFT3_ANY()                                  \
     do {                                                \
         if (pm->logM == 9) XH_IDFT3(8, 8, 8);           \
         else if (pm->logM == 10) XH_IDFT3(16, 8, 8);    \
         else XH_IDFT3(16, 16, 8);                       \
     } while (0)
-        int nr = nrows, rowsPer = 1;
+        int nr = nrows;
         const int *rowList = nullptr, *nrDev = nullptr;
-        const float *rowBound = nullptr, *thr = nullptr;
-        int *prunedCnt = nullptr;
         int grid;
         if (pruning) {
             // bounds + the most promising rows of every particle, those rows first, then everything that can still win
@@ -4219,8 +3976,6 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
             XH_TRY(xh_buf_reserve(ctx, pm->d_topRows, sizeof(int) * (size_t)nparticles * XH_PRUNE_T));
             XH_TRY(xh_buf_reserve(ctx, pm->d_thr, sizeof(float) * (size_t)nparticles));
             XH_TRY(xh_buf_reserve(ctx, pm->d_aT, sizeof(float) * (size_t)m * L.nk));
-            const bool earlyExit = pm->use_early_exit && K0 < L.nk && !d_mask;
-            if (earlyExit) XH_TRY(xh_buf_reserve(ctx, pm->d_rowLow, sizeof(float4) * (size_t)nrows));
             if (K0 < L.nk) {
                 hipLaunchKernelGGL(k_pm_tail_norms, dim3((L.nk - K0 + 63) / 64, m), dim3(64), 0, ctx->stream, (const xh_cf *)pm->d_A32.p,
                                    (float *)pm->d_aT.p, (const int *)pm->d_coff.p, (const int *)pm->d_rstart.p, L.nrings, L.ncoef, L.nk, K0,
@@ -4230,8 +3985,7 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
             hipLaunchKernelGGL(k_pm_prune_plan, dim3(nparticles), dim3(256), 0, ctx->stream, (const float2 *)pm->d_bpart.p, XH_KSPLIT,
                                (size_t)nrows, *prune, (const double *)pm->d_refSigma.p, (const double *)pm->d_stat32.p,
                                (float *)pm->d_rowBound.p, (int *)pm->d_topRows.p, (const float *)pm->d_aT.p, (const float *)pm->d_bT.p,
-                               K0, L.nk, pm->nrefs, (float *)pm->d_rowTail.p, d_mask, maskW, earlyExit ? (float4 *)pm->d_rowLow.p : (float4 *)nullptr,
-                               (const float *)pm->d_bTband.p, earlyExit ? 1 : pm->tail_band);
+                               K0, L.nk, pm->nrefs, (float *)pm->d_rowTail.p, d_mask, maskW, (const float *)pm->d_bTband.p, XH_TAIL_BAND);
             XH_LAUNCH_CHECK();
             nr = nparticles * XH_PRUNE_T;
             rowList = (const int *)pm->d_topRows.p;
@@ -4246,11 +4000,10 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
             XH_LAUNCH_CHECK();
             // survivors, compacted on the device; d_pruned[1] counts them (the host derives the pruned rows)
             XH_TRY(xh_buf_reserve(ctx, pm->d_survList, sizeof(int) * (size_t)nrows));
-            // the survivors' frequencies >= K0 particle by particle (k_pm_rows_high) unless the early exit wants them one at a time; the
-            // store holds what an ordinary gallery leaves (rows beyond it are finished by the transforming wave, and a gallery that
+            // the survivors' frequencies >= K0 particle by particle (k_pm_rows_high); the store holds what an ordinary gallery leaves (rows beyond it are finished by the transforming wave, and a gallery that
             // leaves that many switches its next chunk to the full contraction anyway)
             const int nkHigh = L.nk - H.K0;
-            const bool grouped = pm->group_high && !earlyExit && nkHigh > 0 && H.nq > 0;
+            const bool grouped = pm->group_high && nkHigh > 0 && H.nq > 0;
             const int highCap = !grouped ? 0 : pm->high_cap > 0 ? std::min(nrows, pm->high_cap)
                                          : (int)std::min<size_t>((size_t)nrows, std::max<size_t>(65536, (size_t)nrows / 16));
             int2 *d_items = nullptr;
@@ -4276,7 +4029,6 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
                                    (const int2 *)d_items, (const int *)d_nitems, (float4 *)pm->d_highStore.p);
                 XH_LAUNCH_CHECK();
             }
-            if (earlyExit) { thr = (const float *)pm->d_thr.p; rowsPer = nrows / nparticles; H.rowLow = (const float4 *)pm->d_rowLow.p; H.aT = (const float *)pm->d_aT.p; H.bT = (const float *)pm->d_bT.p; H.nk = L.nk; H.nrefs = pm->nrefs; }
         }
         grid = std::max(8, std::min((nr + 3) / 4, ctx->num_cus * 8) / 8 * 8);
         XH_IDFT3_ANY();
@@ -4289,9 +4041,6 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
         case 6: launch_idft<6>(pm, nrows, lpb, smem); break;
         case 7: launch_idft<7>(pm, nrows, lpb, smem); break;
         case 8: launch_idft<8>(pm, nrows, lpb, smem); break;
-        case 9: launch_idft<9>(pm, nrows, lpb, smem); break;
-        case 10: launch_idft<10>(pm, nrows, lpb, smem); break;
-        case 11: launch_idft<11>(pm, nrows, lpb, smem); break;
         default: launch_idft<12>(pm, nrows, lpb, smem); break;
     }
     XH_LAUNCH_CHECK();
@@ -4332,7 +4081,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
     // order and results are those of the list search. Lists in another order keep the gather path below.
     bool masked = false;
     // (with --thr > 1 a row's worker is its LIST position modulo thr, which the whole-bank rows of this mode do not carry: lists are gathered)
-    if (!dense && pm->use_mask_lists && pm->use_mfma && pm->use_prune && pm->R1 && pm->use_idft3 && n_orient == 1 && pm->ref_threads <= 1) {
+    if (!dense && pm->use_mask_lists && pm->use_prune && pm->R1 && n_orient == 1 && pm->ref_threads <= 1) {
         masked = true;
         for (int p = 0; p < n && masked; ++p) {
             masked = h_nbr_off[p + 1] > h_nbr_off[p];
@@ -4358,10 +4107,10 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
     // chunking: bound the S2->S3 intermediate (rows * nk * 16 B)
     // the S2->S3 intermediate is sized for parallelism (thousands of tiles in flight), not thrift: 4 GiB of 288
     // (with the two-level contraction a row only holds the frequencies below K0: far more rows per chunk)
-    const bool willPrune = !lists && pm->use_mfma && pm->use_prune && pm->R1 && pm->use_idft3 && n_orient == 1;
+    const bool willPrune = !lists && pm->use_prune && pm->R1 && n_orient == 1;
     const size_t maxSlots = n_orient > 1 ? 2048 : 32768;      // grid.y limit of the ring DFT / fp64 footprint
     const float tauAbs = (float)(pm->tau_rel * pm->scale);
-    const double tieAbs = pm->tie_rel * pm->scale;
+    const double tieAbs = XH_TIE_REL * pm->scale;
     // the cut and what is kept, as configured; a chunk in the dense form (pm->finish_dense) replaces them for its own duration
     struct CutGuard {
         xh_pm *pm; int K0, store;
@@ -4427,7 +4176,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
         }
         XH_HIP(hipStreamSynchronize(ctx->stream));   // host vectors go out of scope per iteration
         RowMap M;
-        M.poff = d_poff; M.rowSlot = d_rowSlot; M.refIds = d_ids; M.nt = nt; M.nq = !lists ? pm->nrefs : 0; M.noMirror = pm->no_mirror;
+        M.poff = d_poff; M.rowSlot = d_rowSlot; M.refIds = d_ids; M.nt = nt; M.nq = !lists ? pm->nrefs : 0;
         M.thr = pm->ref_threads;
         pm->stat_rows += masked ? listedRows : nrows;
         const size_t smem64 = sizeof(xh_cd) * (2 * (size_t)L.nk + L.N) + (n_orient > 1 ? sizeof(double) * 2 * L.N : 0);
@@ -4446,7 +4195,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
                                    (const int *)nullptr, M, (const int *)nullptr, (const xh_cd *)pm->d_A64.p,
                                    (const xh_cd *)pm->d_refs64.p, (const double *)pm->d_refSigma.p, (const double *)pm->d_stat64.p,
                                    (const xh_cd *)pm->d_csN.p, (const int *)pm->d_nsam.p, (const int *)pm->d_coff.p, L.nrings, L.Ri,
-                                   L.ncoef, L.N, L.nk, (CandRes *)pm->d_candRes.p, (double *)nullptr, n_orient, pm->tie_rel);
+                                   L.ncoef, L.N, L.nk, (CandRes *)pm->d_candRes.p, (double *)nullptr, n_orient, XH_TIE_REL);
                 XH_LAUNCH_CHECK();
             }
             double *wcorr = nullptr;
@@ -4457,7 +4206,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
                 wcorr = (double *)pm->d_thrLists.p; wref = (int *)(wcorr + e); wpsi = wref + e;
             }
             hipLaunchKernelGGL(k_pm_pick_multi, dim3((m + 63) / 64), dim3(64), 0, ctx->stream, (const CandRes *)pm->d_candRes.p, M, m,
-                               p0, parity, L.N, n_orient, pm->tie_rel, d_refno, d_psi, d_flip, wcorr, wref, wpsi);
+                               p0, parity, L.N, n_orient, XH_TIE_REL, d_refno, d_psi, d_flip, wcorr, wref, wpsi);
             XH_LAUNCH_CHECK();
             XH_HIP(hipEventRecord(pm->ev[5], ctx->stream));
             XH_HIP(hipEventSynchronize(pm->ev[5]));
@@ -4472,7 +4221,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
         XH_HIP(hipEventRecord(pm->ev[0], ctx->stream));
         XH_TRY(run_prep<float>(pm, d_particles + (size_t)p0 * D * D, true, nullptr, m, nullptr, pm->d_coef32, pm->d_polar32,
                                pm->d_A32, pm->d_stat32, pm->d_tw32, false, 0., 0., nt, d_offs));
-        pm->coefFirst = p0; pm->coefCount = (pm->use_fir && D >= 2 * XH_FIR_K) ? m : 0;   // the recursive form rounds differently
+        pm->coefFirst = p0; pm->coefCount = D >= 2 * XH_FIR_K ? m : 0;   // the recursive form rounds differently
         XH_HIP(hipEventRecord(pm->ev[1], ctx->stream));
         // S2 + S3
         XH_TRY(xh_buf_reserve(ctx, pm->d_counters, sizeof(int) * 4));
@@ -4617,8 +4366,8 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         typedef TrGeom<A_, B_> G;                                                                                           \
         if (G::smem > 64 * 1024) {                                                                                          \
             XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_rows<A_, B_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem));  \
-            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_cols<A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem));  \
-            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_irows<A_, B_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem)); \
+            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_cols_pair<A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem));  \
+            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_irows<A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem)); \
         }                                                                                                                   \
         hipLaunchKernelGGL(k_pm_tr_angles, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, psi,                            \
                            (double2 *)pm->d_trAngles.p, m, L.N);                                                            \
@@ -4628,19 +4377,10 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         hipLaunchKernelGGL((k_pm_tr_rows<A_, B_, true>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream,                \
                            parts, (const double *)pm->d_refCoef.p, refno, psi,                                              \
                            flip, z, w, (const xh_cd *)pm->d_WD64.p, L.N);                                                   \
-        if (pm->s6_pair) {                                                                                                  \
-            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_cols_pair<A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem));  \
-            XH_HIP(hipFuncSetAttribute((const void *)k_pm_tr_irows<A_, B_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem)); \
-            hipLaunchKernelGGL((k_pm_tr_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
-                               (const xh_cd *)pm->d_WD64.p, m);                                                             \
-            hipLaunchKernelGGL((k_pm_tr_irows<A_, B_, true>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, \
-                               (const xh_cd *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m);            \
-        } else {                                                                                                            \
-        hipLaunchKernelGGL((k_pm_tr_cols<A_, B_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, w,                   \
-                           (const xh_cd *)pm->d_WD64.p);                                                                    \
-        hipLaunchKernelGGL((k_pm_tr_irows<A_, B_, false>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const xh_cd *)w, R, \
-                           (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m);                                     \
-        }                                                                                                                   \
+        hipLaunchKernelGGL((k_pm_tr_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
+                           (const xh_cd *)pm->d_WD64.p, m);                                                                 \
+        hipLaunchKernelGGL((k_pm_tr_irows<A_, B_>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream,     \
+                           (const xh_cd *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m);                \
         nparts = D / G::LN;                                                                                                 \
     }
             if (D == 64) XH_TR(8, 8)
@@ -4649,8 +4389,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
 #undef XH_TR
             XH_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_pm_bestshift<double>, dim3(m), dim3(256), 0, ctx->stream, (const double *)R, 1, (const xh_cd *)z, refno,
-                               flip, D, max_shift, sx, sy, cc, (const XhTrPart *)pm->d_trPart.p, nparts, pm->s6_debug,
-                               (unsigned char *)nullptr, 0.0);
+                               flip, D, max_shift, sx, sy, cc, (const XhTrPart *)pm->d_trPart.p, nparts);
             XH_LAUNCH_CHECK();
             return XH_OK;
         };
@@ -4680,17 +4419,13 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
             else XH_TRF(16, 16)
 #undef XH_TRF
             XH_LAUNCH_CHECK();
-            if (pm->s6_coarse_kernel)
-                hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const xh_cf *)z, refno, flip, D, max_shift, sx, sy, cc,
-                                   (const XhTrPart *)pm->d_trPart.p, nparts, flag, pm->s6_eps);
-            else
-                hipLaunchKernelGGL(k_pm_bestshift<float>, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, 1, (const xh_cf *)z, refno,
-                                   flip, D, max_shift, sx, sy, cc, (const XhTrPart *)pm->d_trPart.p, nparts, 0, flag, pm->s6_eps);
+            hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const xh_cf *)z, refno, flip, D, max_shift, sx, sy, cc,
+                               (const XhTrPart *)pm->d_trPart.p, nparts, flag, pm->s6_eps);
             XH_LAUNCH_CHECK();
             return XH_OK;
         };
         pm->s6_flagged = 0;
-        if (pm->s6_fp32 && !pm->s6_debug && !pm->d_refCoef32.p) {
+        if (pm->s6_fp32 && !pm->d_refCoef32.p) {
             // the references' B-spline coefficients once more in fp32 for the coarse pass (half the patch traffic of its build)
             const size_t tot = (size_t)pm->nrefs * per;
             XH_TRY(xh_buf_alloc(ctx, pm->d_refCoef32, sizeof(float) * tot));
@@ -4701,7 +4436,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         for (int p0 = 0; p0 < n; p0 += chunk) {
             const int m = std::min(chunk, n - p0);
             const float *parts = d_particles + (size_t)p0 * per;
-            if (!pm->s6_fp32 || pm->s6_debug || pm->s6_capture == 64) {
+            if (!pm->s6_fp32 || pm->s6_capture == 64) {
                 XH_TRY(chain64(parts, d_refno + p0, d_psi + p0, d_flip + p0, m, d_sx + p0, d_sy + p0, d_cc + p0));
                 if (pm->s6_capture == 64) { pm->s6_captured = 64; pm->s6_capturedN = m; }
                 continue;
@@ -4767,7 +4502,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
                            pw, planD, nlines, (size_t)D, per, (size_t)1, (size_t)D, lpb);
         XH_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_pm_bestshift<double>, dim3(m), dim3(256), 0, ctx->stream, (const double *)pw, 2, (const xh_cd *)z, d_refno + p0,
-                           d_flip + p0, D, max_shift, d_sx + p0, d_sy + p0, d_cc + p0, (const XhTrPart *)nullptr, 0, 0, (unsigned char *)nullptr, 0.0);
+                           d_flip + p0, D, max_shift, d_sx + p0, d_sy + p0, d_cc + p0, (const XhTrPart *)nullptr, 0);
         XH_LAUNCH_CHECK();
     }
     return XH_OK;

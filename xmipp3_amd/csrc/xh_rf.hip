@@ -239,7 +239,7 @@ struct xh_rf {
     XhBuf d_shiftCoef, d_shiftXY;   // xh_rf_shift_images scratch
     XhBuf d_tileCounter;            // ints [32,41): class offsets of the tile list, [128,384): the stream counters
     XhBuf d_cull, d_pack, d_superList, d_superCount, d_superVec;
-    XhBuf d_gtiles[2], d_grecs, d_gweights, d_planes, d_spectra;   // d_planes, d_spectra: scratch of xh_rf_insert_images   // k_rf_grid: tile list (16 x 16 x 8 tiles), records, per-image weights
+    XhBuf d_gtiles[2], d_grecs, d_gweights, d_spectra;   // d_spectra: scratch of xh_rf_insert_images   // k_rf_grid: tile list (16 x 16 x 8 tiles), records, per-image weights
     // pinned staging of the small host arrays (records, shifts, CTF parameters): uploads never wait for the stream
     // pinned staging area of the small per-call host arrays: two halves used in turn, an event per half (recorded after the half's last
     // copy).  Entering a half waits for ITS event -- recorded a whole half ago -- so the host never waits for the copy it has just
@@ -252,9 +252,7 @@ struct xh_rf {
     bool stagePending[2] = {false, false};
     XhBuf d_sym, d_angles;          // device-side inputs of k_rf_spaces
     bool packCtf = false;           // xh_rf_insert_images: the pack kernel evaluates the CTF of d_ctfp itself
-    const float *packImgs = nullptr; // ... and the records come straight from the images (k_rf_colsA + k_rf_rowsB<PACK>)
     int tile_max_spaces;
-    int fft_variant;      // 0: register-blocked 2-D FFT of the projections where P allows; 1: radix-2 LDS kernels
     // HIP-event bracket of every gridding-kernel launch (bench.py's roofline), drained lazily
     std::vector<hipEvent_t> evPool;
     size_t evUsed;
@@ -264,17 +262,12 @@ struct xh_rf {
     bool cropped;
     int unit_z = 4;       // depth of a gridding unit (8 x 8 x unit_z voxels per wave): 4 or 8
     int grid_waves = 0;   // waves per CU of the gridding kernel; 0: the default of the unit depth
-    int grid_tile_budget = 0;   // tiles a workgroup of the gridding kernel processes before it retires; 0: persistent workgroups, one per CU
-    int ntiles[2] = {0, 0};
-    int fuse_ctf = 1;     // xh_rf_insert_images: evaluate the CTF inside the pack kernel (0: through planes, for A/B)
     XhBuf d_finSpec, d_finVol, d_finFbt;   // the finaliser's expanded spectrum, output volume and Fourier blob table
     int shift_bands = 1;  // 256-px images shifted band by band out of LDS (k_rf_shift_band; 0: k_rf_shift, for A/B)
-    int skip_far_cells = 1;   // the pack kernels skip the record cells no tap can reach (0: every cell written, for A/B)
     int fftSkipR2 = 0x7fffffff;   // set by xh_rf_insert_images* around its own projection FFT: spectra cells beyond that radius are not stored
     int order_spaces = 1; // the traverse spaces of a launch ordered by plane, so that k_rf_grid reuses voxel queues (0: input order, for A/B)
     XhBuf d_spacePos;
     int ctf_fast = 1;     // envelope-free CTFs through d_ctf_pixel_fast (0: the general double-precision formula everywhere, for A/B)
-    int records_from_images = 0;   // ... and write the records from the row pass of the FFT (measured slower: profiles/README.md)
 };
 
 // Copies a host array to the device behind everything already enqueued, without waiting for the stream: the bytes pass
@@ -554,120 +547,12 @@ struct XhCtfDev {
     double amp = 0, phi = 0, E0 = 0, c2az = 0, s2az = 0;
     int fast = 0, pad_ = 0;
 };
-// ---- register-blocked variants of k_rf_rows / k_rf_cols for P = R1*R2 (xh_fftreg.h) ---------------
-// Same arithmetic contract (pad about the Xmipp origin, CenterFFT, forward FFT, crop, 1/P^2), one LDS
-// round trip per transform instead of log2(P), no zero-fill pass: the padding is known by position.
-template <int R1, int R2>
-__global__ void __launch_bounds__(256)
-k_rf_rows2(const float *__restrict__ imgs, xh_cf *__restrict__ rows, const xh_cf *__restrict__ W, int D, int sizeX, int totalLines)
-{
-    typedef TrGeom<R1, R2, float> G;
-    constexpr int P = G::D;
-    extern __shared__ __align__(16) unsigned char smem[];
-    xh_cf *s = reinterpret_cast<xh_cf *>(smem);
-    xh_cf *sW = s + (size_t)G::LN * G::LS;
-    const int tid = threadIdx.x;
-    const int line0 = blockIdx.x * G::LN;
-    for (int i = tid; i < P; i += 256) sW[i] = W[i];
-    __syncthreads();
-    const int half = D / 2;
-    xh_cf v[G::RM];
-    if (tid < G::LN * R2) {
-        const int l = tid / R2, n2 = tid - l * R2;
-        const bool live = line0 + l < totalLines;
-        const float *src = imgs + (size_t)(line0 + l) * D;
-#pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) {
-            const int px = n1 * R2 + n2;          // padded, centred position: logical x = px (px < half) or px - P
-            float val = 0.f;
-            if (live) {
-                if (px < D - half) val = src[px + half];
-                else if (px >= P - half) val = src[px - P + half];
-            }
-            v[n1] = xh_cf{val, 0.f};
-        }
-        tr_fwd1<R1, R2>(v, s + l * G::LS, sW, n2);
-    }
-    __syncthreads();
-    if (tid < G::LN * R1) {
-        const int l = tid / R1, k1 = tid - l * R1;
-        tr_fwd2<R1, R2>(v, s + l * G::LS, k1);
-        if (line0 + l < totalLines) {
-            xh_cf *dst = rows + (size_t)(line0 + l) * sizeX;
-#pragma unroll
-            for (int k2 = 0; k2 < R2; ++k2)
-                if (k1 + R1 * k2 < sizeX) dst[k1 + R1 * k2] = v[k2];
-        }
-    }
-}
-
-template <int R1, int R2>
-__global__ void __launch_bounds__(256)
-k_rf_cols2(const xh_cf *__restrict__ rows, xh_cf *__restrict__ out, const xh_cf *__restrict__ W, int D, int sizeX, double maxResSqr)
-{
-    typedef TrGeom<R1, R2, float> G;
-    constexpr int P = G::D;
-    extern __shared__ __align__(16) unsigned char smem[];
-    xh_cf *s = reinterpret_cast<xh_cf *>(smem);
-    xh_cf *sW = s + (size_t)G::LN * G::LS;
-    const int tid = threadIdx.x;
-    const int groupsPerImg = (sizeX + G::LN - 1) / G::LN;
-    const int img = blockIdx.x / groupsPerImg;
-    const int kx0 = (blockIdx.x - img * groupsPerImg) * G::LN;
-    for (int i = tid; i < P; i += 256) sW[i] = W[i];
-    __syncthreads();
-    const int half = D / 2;
-    const xh_cf *src = rows + (size_t)img * D * sizeX;
-    xh_cf v[G::RM];
-    if (tid < G::LN * R2) {
-        const int cl = tid % G::LN, n2 = tid / G::LN;      // neighbouring threads, neighbouring columns
-        const bool live = kx0 + cl < sizeX;
-#pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) {
-            const int py = n1 * R2 + n2;
-            xh_cf val = xh_cf{0.f, 0.f};
-            if (live) {
-                if (py < D - half) val = src[(size_t)(py + half) * sizeX + kx0 + cl];
-                else if (py >= P - half) val = src[(size_t)(py - P + half) * sizeX + kx0 + cl];
-            }
-            v[n1] = val;
-        }
-        tr_fwd1<R1, R2>(v, s + cl * G::LS, sW, n2);
-    }
-    __syncthreads();
-    if (tid < G::LN * R1) {
-        const int cl = tid % G::LN, k1 = tid / G::LN;
-        tr_fwd2<R1, R2>(v, s + cl * G::LS, k1);
-        const int j = kx0 + cl;
-        if (j < sizeX) {
-            const float scale = 1.0f / ((float)P * (float)P);
-            const int sizeY = 2 * sizeX;
-            xh_cf *dst = out + (size_t)img * sizeY * sizeX;
-            const double fx = (double)j / (double)P;                  // j <= P/2
-#pragma unroll
-            for (int k2 = 0; k2 < R2; ++k2) {
-                const int ii = k1 + R1 * k2;                           // FFT row index
-                int r;                                                 // output row (myPadI)
-                if (ii < sizeX) r = ii + sizeX;
-                else if (ii >= P - sizeX) r = ii - (P - sizeX);
-                else continue;                                         // cropped away (only when P > 2*sizeX)
-                const double fy = (double)(ii <= P / 2 ? ii : ii - P) / (double)P;
-                xh_cf o = xh_cf{0.f, 0.f};
-                if (!(fx * fx + fy * fy > maxResSqr)) { o = v[k2]; o.x *= scale; o.y *= scale; }
-                dst[(size_t)r * sizeX + j] = o;
-            }
-        }
-    }
-}
-
 // ---- the same transform, columns first (k_rf_colsA), rows last (k_rf_rowsB) ------------------------------------------
 // The projections are real: the column pass transforms two image columns per complex line and keeps ky = 0 .. sizeX
 // ([m][sizeX + 1][D] complex, as many bytes as the row-first intermediate); the row pass then runs over contiguous lines
 // and every transformed line ky gives two output rows, F(kx, ky) and F(kx, -ky) = conj F(-kx, ky), each written as one
-// contiguous row -- of the half spectrum (xh_rf_prepare_images) or, with PACK, of the padded records the gridding kernel
-// reads, CTF factor and modulator evaluated on the spot (xh_rf_insert_images: the half spectra and the CTF planes are
-// never written). Same conventions as k_rf_rows2 / k_rf_cols2: pad about the Xmipp origin, CenterFFT, forward FFT, crop,
-// 1/P^2, cut beyond max_resolution.
+// contiguous row of the half spectrum. Same conventions as k_rf_rows / k_rf_cols: pad about the Xmipp origin, CenterFFT,
+// forward FFT, crop, 1/P^2, cut beyond max_resolution; one LDS round trip per transform instead of log2(P).
 // where k_rf_colsA<.., LN> stores image column x of a line of T
 template <int LN> __device__ __forceinline__ int xh_rf_tpos(int x)
 {
@@ -900,20 +785,18 @@ __global__ void k_rf_ctf(const XhCtfDev *__restrict__ cp, float *__restrict__ ct
     }
 }
 
-template <int R1, int R2, bool PACK>
+template <int R1, int R2>
 __global__ void __launch_bounds__(256)
-k_rf_rowsB(const xh_cf *__restrict__ T, xh_cf *__restrict__ out, XgCell *__restrict__ pk, const XhCtfDev *__restrict__ cp,
-           const float *__restrict__ weights, const xh_cf *__restrict__ W, int D, int TD, int sizeX, double maxResSqr, int nlines,
-           double iTs, double minCTF, int phaseFlipped, int skipR2)
+k_rf_rowsB(const xh_cf *__restrict__ T, xh_cf *__restrict__ out, const xh_cf *__restrict__ W, int D, int TD, int sizeX, double maxResSqr,
+           int nlines, int skipR2)
 {
     typedef TrGeom<R1, R2, float> G;
     constexpr int P = G::D, ZS = P + 1;
-    constexpr int PAD = PACK ? XG_PAD : 0;
     extern __shared__ __align__(16) unsigned char smem[];
     xh_cf *s = reinterpret_cast<xh_cf *>(smem);
     xh_cf *sW = s + (size_t)G::LN * G::LS;
     const int tid = threadIdx.x;
-    const int groupsPerImg = (nlines + G::LN - 1) / G::LN;    // nlines = sizeX + 1 (+ PAD: the zero rows of the frame)
+    const int groupsPerImg = (nlines + G::LN - 1) / G::LN;    // nlines = sizeX + 1
     const int img = blockIdx.x / groupsPerImg;
     const int k0 = (blockIdx.x - img * groupsPerImg) * G::LN;
     for (int i = tid; i < P; i += 256) sW[i] = W[i];
@@ -950,24 +833,12 @@ k_rf_rowsB(const xh_cf *__restrict__ T, xh_cf *__restrict__ out, XgCell *__restr
     }
     __syncthreads();
     const float scale = 1.0f / ((float)P * (float)P);
-    const int SX = sizeX + 2 * PAD, SY = sizeY + 2 * PAD;
-    XhCtfDev par;
-    float w = 1.f;
-    if (PACK) { par = cp[img]; w = weights ? weights[img] : 1.f; }
     for (int l = 0; l < G::LN; ++l) {
         const int k = k0 + l;
         if (k >= nlines) break;
         const int r1 = sizeX + k, r2 = sizeX - k;            // output rows of ky = k and ky = -k
-        const bool row1 = r1 < sizeY + PAD, row2 = k >= 1 && r2 >= -PAD;
         const double fy = (double)k / (double)P;
-        if (PACK && tid < 2 * PAD) {                          // the frame cells left and right of the two rows
-            const int xc = tid < PAD ? tid : sizeX + tid;
-            XgCell *dst = pk + (size_t)img * SX * SY;
-            if (row1) xg_put(dst + (size_t)(r1 + PAD) * SX + xc, 0.f, 0.f, 0.f);
-            if (row2) xg_put(dst + (size_t)(r2 + PAD) * SX + xc, 0.f, 0.f, 0.f);
-        }
-        for (int j = tid; j < sizeX; j += 256) {             // thread <-> kx: every wave has the same number of CTF values to find
-            const int xc = j + PAD;
+        for (int j = tid; j < sizeX; j += 256) {
             const bool in1 = r1 < sizeY, in2 = k >= 1 && r2 >= 0;
             xh_cf o1 = xh_cf{0.f, 0.f}, o2 = o1;
             if (in1 || in2) {
@@ -978,29 +849,10 @@ k_rf_rowsB(const xh_cf *__restrict__ T, xh_cf *__restrict__ out, XgCell *__restr
                     o2 = xh_cf{b.x * scale, -b.y * scale};
                 }
             }
-            if constexpr (!PACK) {
-                // (skipR2: the caller is the gridding path, which never looks at a pixel beyond every tap's reach, k_rf_pack_grid_ctf)
-                if (j * j + k * k > skipR2) continue;
-                if (in1) out[((size_t)img * sizeY + r1) * sizeX + j] = o1;
-                if (in2) out[((size_t)img * sizeY + r2) * sizeX + j] = o2;
-            } else {
-                float cv = 0.f, mv_ = 0.f;
-                float4 v1 = make_float4(0.f, 0.f, 0.f, 0.f), v2 = v1;
-                if (in1) {
-                    d_ctf_eval<true>(par, j, r1, P, iTs, minCTF, phaseFlipped, cv, mv_);
-                    const float mw = mv_ * w;
-                    v1 = make_float4(o1.x * mw * cv, o1.y * mw * cv, mw, 0.f);
-                }
-                if (in2) {
-                    // rows sizeX + k and sizeX - k have opposite freqY (sizeX = P / 2, P even): see k_rf_ctf
-                    if (!(in1 && par.defocus_deviation == 0)) d_ctf_eval<true>(par, j, r2, P, iTs, minCTF, phaseFlipped, cv, mv_);
-                    const float mw = mv_ * w;
-                    v2 = make_float4(o2.x * mw * cv, o2.y * mw * cv, mw, 0.f);
-                }
-                XgCell *dst = pk + (size_t)img * SX * SY;
-                if (row1) xg_put(dst + (size_t)(r1 + PAD) * SX + xc, v1.x, v1.y, v1.z);
-                if (row2) xg_put(dst + (size_t)(r2 + PAD) * SX + xc, v2.x, v2.y, v2.z);
-            }
+            // (skipR2: the caller is the gridding path, which never looks at a pixel beyond every tap's reach, k_rf_pack_grid_ctf)
+            if (j * j + k * k > skipR2) continue;
+            if (in1) out[((size_t)img * sizeY + r1) * sizeX + j] = o1;
+            if (in2) out[((size_t)img * sizeY + r2) * sizeX + j] = o2;
         }
     }
 }
@@ -1432,7 +1284,6 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
     rf->d_temp = nullptr;
     rf->cropped = false;
     rf->tile_max_spaces = 8192;
-    rf->fft_variant = 0;
     rf->evUsed = 0;
     rf->kernelMs = 0;
     rf->kernelLaunches = 0;
@@ -1477,7 +1328,6 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
         };
         for (int c = 0; c < 8; ++c)
             std::sort(packed.begin() + classOff[c], packed.begin() + classOff[c + 1], [&](unsigned u, unsigned w) { return key(u) < key(w); });
-        rf->ntiles[v] = (int)packed.size();
         r = xh_buf_alloc(ctx, rf->d_gtiles[v], sizeof(unsigned) * std::max<size_t>(1, packed.size()));
         if (r == XH_OK) r = (hipMemcpy(rf->d_gtiles[v].p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) == hipSuccess) ? XH_OK : XH_ERR_HIP;
         if (r == XH_OK) r = (hipMemcpy((int *)rf->d_tileCounter.p + 32 + 16 * v, classOff, sizeof(classOff), hipMemcpyHostToDevice) == hipSuccess) ? XH_OK : XH_ERR_HIP;
@@ -1504,7 +1354,7 @@ int xh_rf_destroy(xh_rf *rf)
     if (rf->h_stage) (void)hipHostFree(rf->h_stage);
     for (int h = 0; h < 2; ++h)
         if (rf->stageEv[h]) (void)hipEventDestroy(rf->stageEv[h]);
-    xh_buf_free(rf->d_gtiles[0]); xh_buf_free(rf->d_gtiles[1]); xh_buf_free(rf->d_grecs); xh_buf_free(rf->d_gweights); xh_buf_free(rf->d_planes); xh_buf_free(rf->d_spectra);
+    xh_buf_free(rf->d_gtiles[0]); xh_buf_free(rf->d_gtiles[1]); xh_buf_free(rf->d_grecs); xh_buf_free(rf->d_gweights); xh_buf_free(rf->d_spectra);
     for (hipEvent_t e : rf->evPool) (void)hipEventDestroy(e);
     delete rf;
     return XH_OK;
@@ -1528,22 +1378,10 @@ int xh_rf_set_option(xh_rf *rf, const char *name, double value)
         rf->unit_z = (int)value;
     }
     else if (!strcmp(name, "grid_waves")) rf->grid_waves = (int)value;
-    else if (!strcmp(name, "grid_tile_budget")) {
-#ifdef XH_DEBUG_HOOKS
-        rf->grid_tile_budget = std::max(-1, (int)value);     // (-1: experiment, every interior visit reuses the previous queue: timing only, WRONG volume)
-#else
-        XH_CHECK(value >= 0, XH_ERR_ARG, "xh_rf_set_option: grid_tile_budget -1 (timing experiment with a wrong volume) needs a library built with XH_DEBUG_HOOKS");
-        rf->grid_tile_budget = (int)value;
-#endif
-    }
-    else if (!strcmp(name, "fuse_ctf")) rf->fuse_ctf = (int)value;
     else if (!strcmp(name, "ctf_fast")) rf->ctf_fast = (int)value;
     else if (!strcmp(name, "order_spaces")) rf->order_spaces = (int)value;
-    else if (!strcmp(name, "skip_far_cells")) rf->skip_far_cells = (int)value;
     else if (!strcmp(name, "shift_bands")) rf->shift_bands = (int)value;
-    else if (!strcmp(name, "records_from_images")) rf->records_from_images = (int)value;
     else if (!strcmp(name, "tile_max_spaces")) rf->tile_max_spaces = (int)value;
-    else if (!strcmp(name, "fft_variant")) rf->fft_variant = (int)value;
     else { xh_set_error("xh_rf_set_option: unknown option %s", name); return XH_ERR_ARG; }
     return XH_OK;
 }
@@ -1615,13 +1453,20 @@ int xh_rf_reset(xh_rf *rf)
     return XH_OK;
 }
 
+// squared radius beyond which a pixel of the half spectrum is out of every tap's reach, sizeX + 2 r (+ 2) (xh_rf_grid.h): the pack
+// kernels leave those record cells alone, and the projection FFT of xh_rf_insert_images* does not store them
+static int far_r2(const xh_rf *rf)
+{
+    const int r = rf->sizeX + (int)std::ceil(2.0 * rf->p.blob_radius) + 2;
+    return r * r;
+}
 // can the projections take the columns-first / rows-last transform (k_rf_colsA, k_rf_rowsB)?
 static bool fft_cols_rows_ok(const xh_rf *rf)
 {
-    return (rf->P == 512 || rf->P == 256 || rf->P == 128) && rf->sizeY == rf->P && rf->fft_variant == 0;
+    return (rf->P == 512 || rf->P == 256 || rf->P == 128) && rf->sizeY == rf->P;
 }
-// n images -> half spectra (d_fft) or, with d_pk, the gridding kernel's padded records (CTF of rf->d_ctfp, weights or null)
-static int fft_cols_rows(xh_rf *rf, const float *d_imgs, int n, xh_cf *d_fft, XgCell *d_pk, const float *d_weights)
+// n images -> half spectra (d_fft)
+static int fft_cols_rows(xh_rf *rf, const float *d_imgs, int n, xh_cf *d_fft)
 {
     xh_ctx *ctx = rf->ctx;
     const int D = rf->D, P = rf->P, sizeX = rf->sizeX;
@@ -1631,8 +1476,7 @@ static int fft_cols_rows(xh_rf *rf, const float *d_imgs, int n, xh_cf *d_fft, Xg
     const int chunk = std::max(1, std::min(n, (int)((256u << 20) / perImg)));
     XH_TRY(xh_buf_reserve(ctx, rf->d_rows, (size_t)chunk * perImg));
     const double maxResSqr = rf->p.max_resolution * rf->p.max_resolution;
-    const int nlines = sizeX + 1 + (d_pk ? XG_PAD : 0);
-    const size_t recCells = (size_t)(sizeX + 2 * XG_PAD) * (rf->sizeY + 2 * XG_PAD);
+    const int nlines = sizeX + 1;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
 #define XH_RFB(A_, B_)                                                                                                              \
@@ -1640,17 +1484,9 @@ static int fft_cols_rows(xh_rf *rf, const float *d_imgs, int n, xh_cf *d_fft, Xg
         typedef TrGeom<A_, B_, float> G;                                                                                            \
         hipLaunchKernelGGL((k_rf_colsA<A_, B_>), dim3(m * ((D + 4 * G::LN - 1) / (4 * G::LN))), dim3(256), G::smem, ctx->stream,      \
                            d_imgs + (size_t)i0 * D * D, (xh_cf *)rf->d_rows.p, (const xh_cf *)rf->d_twP32.p, D, TD, sizeX);          \
-        if (d_pk)                                                                                                                   \
-            hipLaunchKernelGGL((k_rf_rowsB<A_, B_, true>), dim3(m * ((nlines + G::LN - 1) / G::LN)), dim3(256), G::smem, ctx->stream, \
-                               (const xh_cf *)rf->d_rows.p, (xh_cf *)nullptr, d_pk + (size_t)i0 * recCells,                          \
-                               (const XhCtfDev *)rf->d_ctfp.p + i0, d_weights ? d_weights + i0 : nullptr,                           \
-                               (const xh_cf *)rf->d_twP32.p, D, TD, sizeX, maxResSqr, nlines, 1.0 / rf->p.sampling, rf->p.min_ctf,    \
-                               rf->p.phase_flipped, 0x7fffffff);                                                                    \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((k_rf_rowsB<A_, B_, false>), dim3(m * ((nlines + G::LN - 1) / G::LN)), dim3(256), G::smem, ctx->stream, \
-                               (const xh_cf *)rf->d_rows.p, d_fft + (size_t)i0 * rf->sizeY * sizeX, (XgCell *)nullptr,               \
-                               (const XhCtfDev *)nullptr, (const float *)nullptr, (const xh_cf *)rf->d_twP32.p, D, TD, sizeX, maxResSqr, \
-                               nlines, 0.0, 0.0, 0, rf->fftSkipR2);                                                                 \
+        hipLaunchKernelGGL((k_rf_rowsB<A_, B_>), dim3(m * ((nlines + G::LN - 1) / G::LN)), dim3(256), G::smem, ctx->stream,         \
+                           (const xh_cf *)rf->d_rows.p, d_fft + (size_t)i0 * rf->sizeY * sizeX, (const xh_cf *)rf->d_twP32.p, D, TD,    \
+                           sizeX, maxResSqr, nlines, rf->fftSkipR2);                                                                \
     }
         if (P == 512) XH_RFB(16, 32)
         else if (P == 256) XH_RFB(16, 16)
@@ -1667,8 +1503,8 @@ int xh_rf_prepare_images(xh_rf *rf, const float *d_imgs, int32_t n, float *d_fft
     XH_HIP(hipSetDevice(rf->ctx->device));
     if (n == 0) return XH_OK;
     xh_ctx *ctx = rf->ctx;
-    if (fft_cols_rows_ok(rf)) return fft_cols_rows(rf, d_imgs, n, (xh_cf *)d_fft, nullptr, nullptr);
-    const int D = rf->D, P = rf->P, sizeX = rf->sizeX;
+    if (fft_cols_rows_ok(rf)) return fft_cols_rows(rf, d_imgs, n, (xh_cf *)d_fft);
+    const int D = rf->D, sizeX = rf->sizeX;
     // chunk so that the row-pass intermediate stays modest
     const int chunk = std::max(1, std::min(n, (int)((256u << 20) / ((size_t)D * sizeX * sizeof(xh_cf)))));
     XH_TRY(xh_buf_reserve(ctx, rf->d_rows, (size_t)chunk * D * sizeX * sizeof(xh_cf)));
@@ -1679,23 +1515,6 @@ int xh_rf_prepare_images(xh_rf *rf, const float *d_imgs, int32_t n, float *d_fft
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         const int totalLines = m * D;
-        if ((P == 512 || P == 256 || P == 128) && rf->sizeY == P && rf->fft_variant == 2) {     // the row-first form, kept for A/B
-#define XH_RF2(A_, B_)                                                                                                          \
-    {                                                                                                                           \
-        typedef TrGeom<A_, B_, float> G;                                                                                        \
-        hipLaunchKernelGGL((k_rf_rows2<A_, B_>), dim3((totalLines + G::LN - 1) / G::LN), dim3(256), G::smem, ctx->stream,         \
-                           d_imgs + (size_t)i0 * D * D, (xh_cf *)rf->d_rows.p, (const xh_cf *)rf->d_twP32.p, D, sizeX, totalLines); \
-        hipLaunchKernelGGL((k_rf_cols2<A_, B_>), dim3(m * ((sizeX + G::LN - 1) / G::LN)), dim3(256), G::smem, ctx->stream,        \
-                           (const xh_cf *)rf->d_rows.p, (xh_cf *)d_fft + (size_t)i0 * rf->sizeY * sizeX,                        \
-                           (const xh_cf *)rf->d_twP32.p, D, sizeX, maxResSqr);                                                \
-    }
-            if (P == 512) XH_RF2(16, 32)
-            else if (P == 256) XH_RF2(16, 16)
-            else XH_RF2(16, 8)
-#undef XH_RF2
-            XH_LAUNCH_CHECK();
-            continue;
-        }
         hipLaunchKernelGGL(k_rf_rows, dim3((totalLines + lpb - 1) / lpb), dim3(256), smem, ctx->stream,
                            d_imgs + (size_t)i0 * D * D, (xh_cf *)rf->d_rows.p, plan, D, sizeX, totalLines, lpb);
         XH_LAUNCH_CHECK();
@@ -1895,10 +1714,7 @@ static int grid_run(xh_rf *rf, int ns, const float *d_fft, const float *d_ctf, c
         XH_TRY(xh_buf_reserve(ctx, rf->d_pack, cells * sizeof(XgCell) + 16));          // (the patch copy reads 16 bytes from the last record too)
         if (rf->d_pack.p != before) XH_HIP(hipMemsetAsync(rf->d_pack.p, 0, rf->d_pack.bytes, ctx->stream));
     }
-    // pixels further than sizeX + 2 r (+ 2) from the origin of the half spectrum are beyond every tap (xh_rf_grid.h)
-    const int skipR = rf->sizeX + (int)std::ceil(2.0 * br) + 2, skipR2 = rf->skip_far_cells ? skipR * skipR : 0x7fffffff;
-    if (rf->packImgs) XH_TRY(fft_cols_rows(rf, rf->packImgs, n, nullptr, (XgCell *)rf->d_pack.p, d_weights));
-    else
+    const int skipR2 = far_r2(rf);
     for (int i0 = 0; i0 < n; i0 += 65535) {          // blockIdx.y: image
         const int m = std::min(65535, n - i0);
         const size_t o = (size_t)i0 * rf->sizeX * rf->sizeY;
@@ -1948,10 +1764,8 @@ static int grid_run(xh_rf *rf, int ns, const float *d_fft, const float *d_ctf, c
         // accumulator block per wave, which the LDS holds for nine waves instead of twelve
         const int uz = rf->unit_z, tl = uz == 8 ? 1 : 0;
         const int nw = rf->grid_waves ? rf->grid_waves : (uz == 8 ? (br < 2.0 || fast ? 9 : 8) : 12);      // (6 x 6 footprints: larger patches)
-        // persistent workgroups (one per CU, multiples of eight: XCD classes), or, with a tile budget, as many as the tiles need plus
-        // one round of CUs (a workgroup that finds its streams empty retires at once)
-        const unsigned cuBlocks = 8u * (unsigned)std::max(1, ctx->num_cus / 8);
-        const unsigned gridBlocks = rf->grid_tile_budget > 0 ? cuBlocks + 8u * (unsigned)((rf->ntiles[tl] / rf->grid_tile_budget + 7) / 8) : cuBlocks;
+        // persistent workgroups: one per CU, multiples of eight (XCD classes)
+        const unsigned gridBlocks = 8u * (unsigned)std::max(1, ctx->num_cus / 8);
 #ifndef XG_ABL
 #define XG_ABL 0
 #endif
@@ -1960,7 +1774,7 @@ static int grid_run(xh_rf *rf, int ns, const float *d_fft, const float *d_ctf, c
                        (const XgRec *)rf->d_grecs.p + s0, (const XgCell *)rf->d_pack.p, (const float *)rf->d_blob.p, tempV, tempW, \
                        rf->mv, rf->iDeltaSqrt, br, (const unsigned *)rf->d_gtiles[tl].p, (const int *)rf->d_tileCounter.p + 32 + 16 * tl, \
                        (int *)rf->d_tileCounter.p + 128, (const int *)rf->d_superList.p, (const int *)rf->d_superCount.p,         \
-                       superDim, m, (const float4 *)superN, (const float4 *)superX, reach, rf->grid_tile_budget)
+                       superDim, m, (const float4 *)superN, (const float4 *)superX, reach)
 #define XH_GRID_WF(W_, F_)                                                                                                       \
     do {                                                                                                                         \
         if (uz == 8 && nw == 9 && W_ == 4) XH_GRID(4, F_, 8, 9);                                                                 \
@@ -2045,6 +1859,19 @@ int xh_rf_insert(xh_rf *rf, const float *d_fft, const float *d_ctf, const float 
     return insert_common(rf, d_fft, d_ctf, d_mod, ainv.data(), h_weights, n, h_sym, nsym);
 }
 
+// The first half of xh_rf_insert_images*: the CTF parameters of the pack kernel (h_ctf may be null) and the projections'
+// half spectra in rf->d_spectra. The spectra go to the pack kernels only, which skip what no tap can reach: the row pass
+// need not store it.
+static int spectra_for_pack(xh_rf *rf, const float *d_imgs, const xh_ctf_params *h_ctf, int n)
+{
+    if (h_ctf) XH_TRY(ctf_params_upload(rf, h_ctf, n));
+    XH_TRY(xh_buf_reserve(rf->ctx, rf->d_spectra, (size_t)n * rf->sizeX * rf->sizeY * sizeof(xh_cf)));
+    rf->fftSkipR2 = far_r2(rf);
+    const int rc = xh_rf_prepare_images(rf, d_imgs, n, (float *)rf->d_spectra.p);
+    rf->fftSkipR2 = 0x7fffffff;
+    return rc;
+}
+
 // processBufferGPU in one call (reconstruction_cuda/cuda_gpu_reconstruct_fourier.h:130-157 takes images and does the FFT on the
 // device too): shifted images + CTF parameters + orientations -> temp spaces = xh_rf_ctf_arrays + xh_rf_prepare_images +
 // xh_rf_insert on scratch owned by the handle. (Letting the column pass of the FFT write the packed records itself was built
@@ -2057,31 +1884,10 @@ int xh_rf_insert_images(xh_rf *rf, const float *d_imgs, const xh_ctf_params *h_c
     XH_CHECK(!rf->cropped, XH_ERR_STATE, "xh_rf_insert_images: temp spaces already mirrored/cropped; call xh_rf_reset");
     XH_HIP(hipSetDevice(rf->ctx->device));
     if (n == 0) return XH_OK;
-    xh_ctx *ctx = rf->ctx;
-    const size_t plane = (size_t)n * rf->sizeX * rf->sizeY;
-    float *d_ctf = nullptr, *d_mod = nullptr;
-    const bool fuse = h_ctf && rf->fuse_ctf;
-    if (fuse) XH_TRY(ctf_params_upload(rf, h_ctf, n));      // the pack kernel evaluates the CTF: no planes
-    else if (h_ctf) {
-        XH_TRY(xh_buf_reserve(ctx, rf->d_planes, 2 * plane * sizeof(float)));
-        d_ctf = (float *)rf->d_planes.p; d_mod = d_ctf + plane;
-        XH_TRY(xh_rf_ctf_arrays(rf, h_ctf, n, d_ctf, d_mod));
-    }
-    const bool fromImages = fuse && rf->records_from_images && fft_cols_rows_ok(rf);   // records straight from the images (A/B)
-    if (!fromImages) {
-        XH_TRY(xh_buf_reserve(ctx, rf->d_spectra, plane * sizeof(xh_cf)));
-        // (the spectra go to the pack kernels only, which skip what no tap can reach: the row pass need not store it)
-        const int skipR = rf->sizeX + (int)std::ceil(2.0 * rf->p.blob_radius) + 2;
-        rf->fftSkipR2 = rf->skip_far_cells ? skipR * skipR : 0x7fffffff;
-        const int rcp = xh_rf_prepare_images(rf, d_imgs, n, (float *)rf->d_spectra.p);
-        rf->fftSkipR2 = 0x7fffffff;
-        if (rcp != XH_OK) return rcp;
-    }
-    rf->packCtf = fuse;
-    rf->packImgs = fromImages ? d_imgs : nullptr;
-    const int rc = xh_rf_insert(rf, fromImages ? d_imgs : (const float *)rf->d_spectra.p, d_ctf, d_mod, h_angles, h_weights, n, h_sym, nsym);
+    XH_TRY(spectra_for_pack(rf, d_imgs, h_ctf, n));
+    rf->packCtf = h_ctf != nullptr;
+    const int rc = xh_rf_insert(rf, (const float *)rf->d_spectra.p, nullptr, nullptr, h_angles, h_weights, n, h_sym, nsym);
     rf->packCtf = false;
-    rf->packImgs = nullptr;
     return rc;
 }
 
@@ -2099,24 +1905,7 @@ int xh_rf_insert_images_dev(xh_rf *rf, const float *d_imgs, const xh_ctf_params 
     xh_ctx *ctx = rf->ctx;
     if (!h_sym) nsym = 1;
     XH_CHECK(nsym >= 1 && (size_t)n * nsym < ((size_t)1 << 30), XH_ERR_ARG, "xh_rf_insert_images_dev: bad symmetry count");
-    const size_t plane = (size_t)n * rf->sizeX * rf->sizeY;
-    float *d_ctf = nullptr, *d_mod = nullptr;
-    const bool fuse = h_ctf && rf->fuse_ctf;
-    if (fuse) XH_TRY(ctf_params_upload(rf, h_ctf, n));      // the pack kernel evaluates the CTF: no planes
-    else if (h_ctf) {
-        XH_TRY(xh_buf_reserve(ctx, rf->d_planes, 2 * plane * sizeof(float)));
-        d_ctf = (float *)rf->d_planes.p; d_mod = d_ctf + plane;
-        XH_TRY(xh_rf_ctf_arrays(rf, h_ctf, n, d_ctf, d_mod));
-    }
-    const bool fromImages = fuse && rf->records_from_images && fft_cols_rows_ok(rf);   // records straight from the images (A/B)
-    if (!fromImages) {
-        XH_TRY(xh_buf_reserve(ctx, rf->d_spectra, plane * sizeof(xh_cf)));
-        const int skipR = rf->sizeX + (int)std::ceil(2.0 * rf->p.blob_radius) + 2;      // (as in xh_rf_insert_images)
-        rf->fftSkipR2 = rf->skip_far_cells ? skipR * skipR : 0x7fffffff;
-        const int rcp = xh_rf_prepare_images(rf, d_imgs, n, (float *)rf->d_spectra.p);
-        rf->fftSkipR2 = 0x7fffffff;
-        if (rcp != XH_OK) return rcp;
-    }
+    XH_TRY(spectra_for_pack(rf, d_imgs, h_ctf, n));
     const int ns = n * nsym;
     const double *d_sym = nullptr;
     if (h_sym) {
@@ -2135,11 +1924,9 @@ int xh_rf_insert_images_dev(xh_rf *rf, const float *d_imgs, const xh_ctf_params 
     hipLaunchKernelGGL(k_rf_spaces, dim3((ns + 63) / 64), dim3(64), 0, ctx->stream, d_angles, d_weights, d_sym, n, nsym, rf->mv,
                        rf->p.blob_radius, rf->p.use_fast, (XgRec *)rf->d_grecs.p, (float4 *)rf->d_cull.p, (float4 *)rf->d_cull.p + ns, d_pos);
     XH_LAUNCH_CHECK();
-    rf->packCtf = fuse;
-    rf->packImgs = fromImages ? d_imgs : nullptr;
-    const int rc = grid_run(rf, ns, fromImages ? d_imgs : (const float *)rf->d_spectra.p, d_ctf, d_mod, d_weights, n);
+    rf->packCtf = h_ctf != nullptr;
+    const int rc = grid_run(rf, ns, (const float *)rf->d_spectra.p, nullptr, nullptr, d_weights, n);
     rf->packCtf = false;
-    rf->packImgs = nullptr;
     return rc;
 }
 

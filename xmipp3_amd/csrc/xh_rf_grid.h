@@ -346,7 +346,7 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
           float *__restrict__ tempV, float *__restrict__ tempW, int mv, float iDeltaSqrt, double blobRadius,
           const unsigned *__restrict__ tileList, const int *__restrict__ classOff, int *__restrict__ counter,
           const int *__restrict__ superList, const int *__restrict__ superCount, int superDim, int superCap,
-          const float4 *__restrict__ superN, const float4 *__restrict__ superX, float4 reach, int tileBudget)
+          const float4 *__restrict__ superN, const float4 *__restrict__ superX, float4 reach)
 {
     using C = XgCfg<W, ZD, NW>;
     constexpr int PW = C::PW, PN = C::PN, NDMA = C::NDMA, NVOX = C::NVOX, KCAP = C::KCAP;
@@ -393,9 +393,6 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
     auto produce = [&](int q) {
         while (q > 0 && atomicAdd(&sReady[(q - 1) % RS], 0) != q) __builtin_amdgcn_s_sleep(1);
         int tile = -1;
-        // tileBudget > 0: a workgroup retires after that many tiles and the launch has more workgroups than CUs (bounded residency: the
-        // kernels of another stream get CUs every few milliseconds instead of after the whole launch)
-        if (!(tileBudget > 0 && q >= tileBudget))
         for (;;) {
             const int hop = atomicAdd(sHop, 0);
             if (hop >= 8 * NSUB) break;
@@ -583,7 +580,7 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                 const int yy = __float_as_int(R1.w), zz = __float_as_int(R2.w);
                 const bool yok = !(y < (yy & 0xffff) || y > (yy >> 16));
                 const float ax = R0.x * px + R0.y * py, ay = R1.x * px + R1.y * py, az = R2.x * px + R2.y * py;
-                const bool sameQueue = interior && prevInterior && ((R2.x == pNx && R2.y == pNy && R2.z == pNz) || tileBudget == -1);
+                const bool sameQueue = interior && prevInterior && (R2.x == pNx && R2.y == pNy && R2.z == pNz);
                 pNx = R2.x; pNy = R2.y; pNz = R2.z; prevInterior = interior;
                 if (!sameQueue) qn = 0;
                 if constexpr (ABL != 7) {

@@ -547,6 +547,42 @@ int xh_correlation_merit(xh_ctx *ctx, const float *d_ref, const float *d_others,
 int xh_iterative_alignment(xh_ctx *ctx, const float *d_ref, const float *d_others, int32_t n, int32_t D, int32_t max_shift, int32_t first_ring,
                            int32_t last_ring, int32_t iters, float *h_poses, float *h_merit);
 
+/* ---- xmipp_align_significant (reconstruction/aalign_significant.cpp, reconstruction_adapt_cuda/align_significant_gpu.cpp) ----
+ * Every (reference, image) pair aligned with the chain of xh_iterative_alignment, computed for batches of pairs, pair g = r N + i.
+ * The references' polar transforms, shift spectra and pixels are prepared once per load; every step's pose algebra (the rotation2DMatrix
+ * product, the shift add, M3x3_INV with its double reciprocal) runs on the device. Same arithmetic as xh_iterative_alignment: the two
+ * agree pair for pair.
+ * create: images of D x D pixels (even), up to max_refs references loaded at a time (<= 65535; per-reference buffers of about 22 bytes per
+ * pixel are kept for them, none for the images, which may be any number), batch_pairs pairs per batch (<= 65535; the work space is
+ * about 600 KB per pair at D = 128), max_shift < D / 2. The CUDA program's settings (align_significant_gpu.cpp:315-375) are max_shift
+ * = D / 4, the default rings (first max(2, D / 20), last (D - 3) / 2) and iters = 3. */
+typedef struct xh_align_sig xh_align_sig;
+int xh_align_sig_create(xh_ctx *ctx, int32_t D, int32_t max_refs, int32_t batch_pairs, int32_t max_shift, int32_t first_ring, int32_t last_ring,
+                        int32_t iters, xh_align_sig **out);
+int xh_align_sig_destroy(xh_align_sig *h);
+/* d_refs [R][D][D] on the device, R <= max_refs; replaces the references loaded before */
+int xh_align_sig_load_references(xh_align_sig *h, const float *d_refs, int32_t R);
+/* d_images [N][D][D] against the R loaded references -> d_poses [R][N][9] (3 x 3 float, row major) and d_merit [R][N], device memory */
+int xh_align_sig_align(xh_align_sig *h, const float *d_images, int32_t N, float *d_poses, float *d_merit);
+/* computeWeightsAndSave (aalign_significant.cpp:233-311) on the device: d_merit [R][N] -> d_weights [R][N]. Reference r takes the merits of
+ * every reference q with r == q or Euler_distanceBetweenAngleSets(rot_r, tilt_r, 0, rot_q, tilt_q, 0, true) <= ang_distance (degrees
+ * between the projection directions); c = the rank of merit (r, s) in ascending order among those count N values; weight = merit /
+ * maxMerit . c / (count N - 1) in float if merit > 0, else 0. Equal merits are ranked by (reference, image) index, as a stable sort of
+ * the list the reference builds would rank them (std::sort leaves their order unspecified).
+ * Deviation: where count N is 1 (one image, a reference that selects only itself) the reference computes c / 0 = NaN; the weight is 0.
+ * Cost: every weight counts over all count N merits, O(count N^2) comparisons per reference (tools/bench_align_sig.py times it). */
+int xh_align_sig_weights(xh_align_sig *h, const float *h_rot, const float *h_tilt, double ang_distance, const float *d_merit, int32_t R, int32_t N,
+                         float *d_weights);
+/* updateRefs (align_significant_gpu.cpp:174-287, aalign_significant.cpp:470-573): for each of R references r (none need to be loaded;
+ * R <= 65535), the sum over its assignments k (h_ref_idx[k] == r) of h_weight[k] times image h_img_idx[k] of d_images [N][D][D] interpolated by the inverse (M3x3_INV)
+ * of its pose h_pose[k] (3 x 3, LINEAR, outside 0), divided by a normaliser -> d_out_refs [R][D][D].
+ * Cumulative normaliser: as the reference program, which declares its norm before the loop over references, reference r is divided by
+ * the running sum of the weights of references 0 .. r in index order, not by its own sum.
+ * Deviation: a reference without assignments is zeros (the reference's memset), and so is any reference whose running sum is still 0,
+ * where the reference program would divide 0 by 0 and write NaN. */
+int xh_align_sig_update_refs(xh_align_sig *h, const float *d_images, int32_t N, int32_t R, int32_t n_assign, const int32_t *h_ref_idx,
+                             const int32_t *h_img_idx, const float *h_weight, const float *h_pose, float *d_out_refs);
+
 #ifdef __cplusplus
 }
 #endif

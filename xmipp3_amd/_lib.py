@@ -106,6 +106,12 @@ SIGNATURES = {
     "xh_apply_geometry2d": (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
     "xh_correlation_merit": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "xh_iterative_alignment": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "xh_align_sig_create": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, pvp]),
+    "xh_align_sig_destroy": (C.c_int, [vp]),
+    "xh_align_sig_load_references": (C.c_int, [vp, vp, i32]),
+    "xh_align_sig_align": (C.c_int, [vp, vp, i32, vp, vp]),
+    "xh_align_sig_weights": (C.c_int, [vp, vp, vp, d, vp, i32, i32, vp]),
+    "xh_align_sig_update_refs": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

@@ -634,6 +634,85 @@ class ShiftCorrEstimator:
         return inout
 
 
+class AlignSignificant:
+    """The device side of xmipp_align_significant: every (reference, image) pair aligned with the chain of iterative_alignment, in
+    batches of pairs; the significance weights; the weighted reference update. Defaults are the CUDA program's: max_shift D / 4, the
+    default rings, iters 3."""
+
+    def __init__(self, ctx, D, max_refs, batch_pairs=1024, max_shift=None, first_ring=None, last_ring=None, iters=3):
+        self.ctx, self.D = ctx, int(D)
+        if max_shift is None:
+            max_shift = self.D // 4
+        if first_ring is None:
+            first_ring = max(2, self.D // 20)
+        if last_ring is None:
+            last_ring = (self.D - 3) // 2
+        h = C.c_void_p()
+        check(lib().xh_align_sig_create(ctx.h, self.D, int(max_refs), int(batch_pairs), int(max_shift), int(first_ring), int(last_ring), int(iters), C.byref(h)))
+        self.h = h
+        self.R = 0
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                lib().xh_align_sig_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _images(self, t):
+        torch = _torch()
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and tuple(t.shape[1:]) == (self.D, self.D)
+        return t
+
+    def load_references(self, refs):
+        """refs [R, D, D] float32 on the device"""
+        refs = self._images(refs)
+        check(lib().xh_align_sig_load_references(self.h, _ptr(refs), refs.shape[0]))
+        self.R = refs.shape[0]
+
+    def align(self, images):
+        """images [N, D, D] -> (poses [R, N, 3, 3], merit [R, N]) float32 tensors on the device"""
+        torch = _torch()
+        images = self._images(images)
+        N = images.shape[0]
+        poses = torch.empty((self.R, N, 3, 3), dtype=torch.float32, device=images.device)
+        merit = torch.empty((self.R, N), dtype=torch.float32, device=images.device)
+        check(lib().xh_align_sig_align(self.h, _ptr(images), N, _ptr(poses), _ptr(merit)))
+        return poses, merit
+
+    def weights(self, rot, tilt, ang_distance, merit):
+        """computeWeightsAndSave: reference angles rot, tilt [R] (degrees), merit [R, N] on the device -> weights [R, N] on the device"""
+        torch = _torch()
+        assert merit.is_cuda and merit.dtype == torch.float32 and merit.is_contiguous() and merit.dim() == 2
+        R, N = merit.shape
+        rot, tilt = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(tilt, np.float32)
+        assert rot.shape == (R,) and tilt.shape == (R,)
+        out = torch.empty_like(merit)
+        check(lib().xh_align_sig_weights(self.h, _np_ptr(rot), _np_ptr(tilt), float(ang_distance), _ptr(merit), R, N, _ptr(out)))
+        return out
+
+    def update_refs(self, images, ref_idx, img_idx, weight, pose, n_refs=None):
+        """updateRefs: the assignments (ref_idx, img_idx, weight [n], pose [n, 3, 3]) -> the updated references [n_refs, D, D] on the
+        device (n_refs: the number of references, by default the number loaded), each divided by the running sum of the weights of
+        references 0 .. r (see include/xmipp_hip.h)"""
+        R = self.R if n_refs is None else int(n_refs)
+        torch = _torch()
+        images = self._images(images)
+        ref_idx, img_idx = np.ascontiguousarray(ref_idx, np.int32), np.ascontiguousarray(img_idx, np.int32)
+        weight, pose = np.ascontiguousarray(weight, np.float32), np.ascontiguousarray(pose, np.float32).reshape(-1, 9)
+        n = ref_idx.shape[0]
+        assert img_idx.shape == (n,) and weight.shape == (n,) and pose.shape == (n, 9)
+        out = torch.empty((R, self.D, self.D), dtype=torch.float32, device=images.device)
+        check(lib().xh_align_sig_update_refs(self.h, _ptr(images), images.shape[0], R, n, _np_ptr(ref_idx), _np_ptr(img_idx), _np_ptr(weight), _np_ptr(pose), _ptr(out)))
+        return out
+
+
 def movie_binned_size(Y, X, binning):
     """AProgMovieAlignmentCorrelation::getMovieSize (movie_alignment_correlation_base.cpp:356-370): float arithmetic, truncated"""
     f = np.float32

@@ -583,6 +583,60 @@ int xh_align_sig_weights(xh_align_sig *h, const float *h_rot, const float *h_til
 int xh_align_sig_update_refs(xh_align_sig *h, const float *d_images, int32_t N, int32_t R, int32_t n_assign, const int32_t *h_ref_idx,
                              const int32_t *h_img_idx, const float *h_weight, const float *h_pose, float *d_out_refs);
 
+/* ---- xmipp_volume_halves_restoration (reconstruction_cuda/cuda_volume_halves_restorator.cpp, cuda_volume_restoration_kernels.cpp,
+ * cuda_cdf.cpp; CPU counterpart reconstruction/volume_halves_restoration.cpp) ----
+ * Two half maps [Z][Y][X] (fp64, any size up to 1024 per axis, X >= 2) restored in place by the reference's four stages, in the order of
+ * VolumeHalvesRestorator::apply: denoise, deconvolve, filter_bank, difference. A stage given 0 iterations (filter bank: step 0) does
+ * nothing and leaves its output absent. create sizes every buffer once (13 volumes' worth); the stages allocate nothing.
+ * Masks are int32 [Z][Y][X] on the device, nonzero = inside. Inputs must be finite.
+ * Deviations from the reference (each where it divides 0 by 0, reads out of bounds or does not terminate; details in xh_halves.hip):
+ * a weight of 0 where the difference's standard deviation is 0, where weightFun 2 has w1 + w2 = 0, and for weightFun 3; the true half
+ * spectrum size Z Y (X/2 + 1) where the reference uses X Y (Z/2 + 1); CDF ranks clamped to N - 1; an empty mask and a filter step
+ * (1 - overlap) <= 0 refused with XH_ERR_ARG. Like the reference, weightPower is truncated to an integer. */
+typedef struct xh_halves xh_halves;
+int xh_halves_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_halves **out);
+int xh_halves_destroy(xh_halves *h);
+/* copies the two half maps into the handle; every output but the two restored volumes becomes absent */
+int xh_halves_load(xh_halves *h, const double *d_v1, const double *d_v2);
+/* denoise (significanceRealSpace); d_mask may be null */
+int xh_halves_denoise(xh_halves *h, int32_t iters, const int32_t *d_mask);
+/* deconvolution: sigmas searched on the host by Powell (xmipp3_amd/host/powell.h, ftol 0.01) over the device cost; h_sigmas (nullable)
+ * receives the (sigma1, sigma2) of each iteration, 2 iters values. Outputs deconvolved and convolved. Synchronous. */
+int xh_halves_deconvolve(xh_halves *h, int32_t iters, double sigma0, double lambda, double *h_sigmas);
+/* filter bank; weightFun 0 mean, 1 min, 2 mean*diff, 3 (weight 0). Output filterBank. */
+int xh_halves_filter_bank(xh_halves *h, double step, double overlap, int32_t weightFun, double weightPower);
+/* difference; d_mask may be null. Output avgDiff. Synchronous. */
+int xh_halves_difference(xh_halves *h, int32_t iters, double K, const int32_t *d_mask);
+/* which: 0 restored1, 1 restored2, 2 filterBank, 3 deconvolved, 4 convolved, 5 avgDiff. *present = whether its stage ran; if it did and
+ * d_out is not null, the volume is copied to d_out [Z][Y][X] */
+int xh_halves_output(xh_halves *h, int32_t which, double *d_out, int32_t *present);
+/* one deconvolution iteration's spectra from the current volumes (estimateS, then fft of S, V1, V2), and restorationSigmaCost's error
+ * on them (synchronous): the pieces of xh_halves_deconvolve, exposed for tests */
+int xh_halves_deconv_spectra(xh_halves *h);
+int xh_halves_sigma_cost(xh_halves *h, double sigma1, double sigma2, double *h_cost);
+/* the handle's 3-D transforms: r2c d_in [Z][Y][X] -> d_out [Z][Y][X/2+1] complex (interleaved doubles), un-normalised; c2r back, times
+ * scale (d_in is not modified) */
+int xh_halves_fft_r2c(xh_halves *h, const double *d_in, void *d_out);
+int xh_halves_fft_c2r(xh_halves *h, const void *d_in, double *d_out, double scale);
+/* Gpu::CDF: keys d_a^2 (d_b null) or mult (d_a - d_b)^2 over the voxels of d_mask (null: all) -> h_table [202]: the minimum, the 200 order
+ * statistics of ranks round(p N) (N - 1 at most), p = 0.0025, 0.0075, ... as the reference's float loop makes them, the maximum.
+ * Synchronous. */
+int xh_halves_cdf(xh_halves *h, const double *d_a, const double *d_b, const int32_t *d_mask, double mult, double *h_table);
+/* filter-bank timing (events around each band's transforms, CDF and weights; synchronises once per band when on) */
+int xh_halves_set_timing(xh_halves *h, int32_t on);
+int xh_halves_band_timing(xh_halves *h, int32_t *bands, double *h_ms);
+
+/* host only, no device needed: the program's two mask types. circular: BinaryCircularMask about the Xmipp origin (index - size / 2)
+ * shifted by (x0, y0, z0); R1 < 0 keeps r <= |R1|, R1 > 0 keeps r >= R1. binary: a mask file's values truncated to int, nonzero -> 1. */
+int xh_halves_circular_mask(int32_t Z, int32_t Y, int32_t X, double R1, double x0, double y0, double z0, int32_t *h_mask);
+int xh_halves_binary_mask(const float *h_values, size_t n, int32_t *h_mask);
+
+/* Powell's direction-set minimiser of xmipp3_amd/host/powell.h (host only, no device needed): minimises f over p[0 .. n-1] starting with
+ * the axis directions scaled by steps, stopping at a relative decrease below ftol. f reads the variables 1-based, x[1] .. x[n], as
+ * xmippCore's powellOptimizer passes them. The minimum may differ from xmippCore's within ftol. */
+typedef double (*xh_cost_fn)(double *x, void *user);
+int xh_powell_minimize(int32_t n, double *p, const double *steps, double ftol, xh_cost_fn f, void *user, double *fret, int32_t *iter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,6 @@ for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     def g(k):
         m = re.search(k + r": (\d+)", b)
         return int(m.group(1)) if m else -1
-    name = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0]
+    name = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]
     print("%-72s VGPR %4d AGPR %4d SGPR %4d LDS %6d scratch %5d occupancy %d" % (name[-72:], g("VGPRs"), g("AGPRs"), g("SGPRs"), g(r"LDS Size \[bytes/block\]"),
                                                                      g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))

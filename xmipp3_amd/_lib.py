@@ -31,6 +31,8 @@ class CtfParams(C.Structure):
 # every symbol include/xmipp_hip.h declares: name -> (restype, argtypes)
 vp, i32, i64, d, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 pvp = C.POINTER(C.c_void_p)
+# xh_cost_fn: double (*)(double *x, void *user), x read 1-based
+COST_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
 SIGNATURES = {
     "xh_last_error": (C.c_char_p, []),
     "xh_version": (C.c_char_p, []),
@@ -112,6 +114,24 @@ SIGNATURES = {
     "xh_align_sig_align": (C.c_int, [vp, vp, i32, vp, vp]),
     "xh_align_sig_weights": (C.c_int, [vp, vp, vp, d, vp, i32, i32, vp]),
     "xh_align_sig_update_refs": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "xh_halves_create": (C.c_int, [vp, i32, i32, i32, pvp]),
+    "xh_halves_destroy": (C.c_int, [vp]),
+    "xh_halves_load": (C.c_int, [vp, vp, vp]),
+    "xh_halves_denoise": (C.c_int, [vp, i32, vp]),
+    "xh_halves_deconvolve": (C.c_int, [vp, i32, d, d, vp]),
+    "xh_halves_filter_bank": (C.c_int, [vp, d, d, i32, d]),
+    "xh_halves_difference": (C.c_int, [vp, i32, d, vp]),
+    "xh_halves_output": (C.c_int, [vp, i32, vp, C.POINTER(C.c_int32)]),
+    "xh_halves_deconv_spectra": (C.c_int, [vp]),
+    "xh_halves_sigma_cost": (C.c_int, [vp, d, d, C.POINTER(C.c_double)]),
+    "xh_halves_fft_r2c": (C.c_int, [vp, vp, vp]),
+    "xh_halves_fft_c2r": (C.c_int, [vp, vp, vp, d]),
+    "xh_halves_cdf": (C.c_int, [vp, vp, vp, vp, d, vp]),
+    "xh_halves_set_timing": (C.c_int, [vp, i32]),
+    "xh_halves_band_timing": (C.c_int, [vp, C.POINTER(C.c_int32), vp]),
+    "xh_halves_circular_mask": (C.c_int, [i32, i32, i32, d, d, d, d, vp]),
+    "xh_halves_binary_mask": (C.c_int, [vp, sz, vp]),
+    "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

@@ -713,6 +713,140 @@ class AlignSignificant:
         return out
 
 
+class HalvesRestoration:
+    """The device side of xmipp_volume_halves_restoration (VolumeHalvesRestorator<double>): two half maps [Z, Y, X] float64 restored in
+    place by denoise, deconvolve, filter_bank and difference, in that order, as the reference's apply runs them."""
+
+    OUTPUTS = ("restored1", "restored2", "filterBank", "deconvolved", "convolved", "avgDiff")
+
+    def __init__(self, ctx, shape):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        h = C.c_void_p()
+        check(lib().xh_halves_create(ctx.h, *self.shape, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                lib().xh_halves_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _vol(self, t, dtype=None):
+        torch = _torch()
+        dtype = dtype or torch.float64
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == self.shape, (t.shape, t.dtype)
+        return t
+
+    def _mask(self, mask):
+        return None if mask is None else _ptr(self._vol(mask, _torch().int32))
+
+    def load(self, v1, v2):
+        check(lib().xh_halves_load(self.h, _ptr(self._vol(v1)), _ptr(self._vol(v2))))
+
+    def denoise(self, iters, mask=None):
+        check(lib().xh_halves_denoise(self.h, int(iters), self._mask(mask)))
+
+    def deconvolve(self, iters, sigma0=0.2, lam=0.001):
+        """returns the (sigma1, sigma2) the Powell search chose in each iteration, [iters, 2]"""
+        sig = np.zeros((max(1, int(iters)), 2))
+        check(lib().xh_halves_deconvolve(self.h, int(iters), float(sigma0), float(lam), _np_ptr(sig)))
+        return sig[:int(iters)]
+
+    def filter_bank(self, step, overlap=0.5, weight_fun=1, weight_power=3.0):
+        check(lib().xh_halves_filter_bank(self.h, float(step), float(overlap), int(weight_fun), float(weight_power)))
+
+    def difference(self, iters, K=1.5, mask=None):
+        check(lib().xh_halves_difference(self.h, int(iters), float(K), self._mask(mask)))
+
+    def output(self, name):
+        """one of OUTPUTS as a new device tensor, or None where its stage did not run"""
+        torch = _torch()
+        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        present = C.c_int32()
+        check(lib().xh_halves_output(self.h, self.OUTPUTS.index(name), _ptr(out), C.byref(present)))
+        return out if present.value else None
+
+    def deconv_spectra(self):
+        check(lib().xh_halves_deconv_spectra(self.h))
+
+    def sigma_cost(self, sigma1, sigma2):
+        c = C.c_double()
+        check(lib().xh_halves_sigma_cost(self.h, float(sigma1), float(sigma2), C.byref(c)))
+        return c.value
+
+    def rfft(self, v):
+        """un-normalised r2c: [Z, Y, X] float64 -> [Z, Y, X // 2 + 1] complex128"""
+        torch = _torch()
+        Z, Y, X = self.shape
+        out = torch.empty((Z, Y, X // 2 + 1), dtype=torch.complex128, device="cuda")
+        check(lib().xh_halves_fft_r2c(self.h, _ptr(self._vol(v)), _ptr(out)))
+        return out
+
+    def irfft(self, F, scale=1.0):
+        """un-normalised c2r times scale: [Z, Y, X // 2 + 1] complex128 -> [Z, Y, X] float64 (F is not modified)"""
+        torch = _torch()
+        Z, Y, X = self.shape
+        assert F.is_cuda and F.dtype == torch.complex128 and F.is_contiguous() and tuple(F.shape) == (Z, Y, X // 2 + 1)
+        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        check(lib().xh_halves_fft_c2r(self.h, _ptr(F), _ptr(out), float(scale)))
+        return out
+
+    def cdf(self, a, b=None, mask=None, mult=1.0):
+        """Gpu::CDF table [202]: minimum, the 200 order statistics, maximum of a^2 or mult (a - b)^2 over the mask"""
+        t = np.zeros(202)
+        check(lib().xh_halves_cdf(self.h, _ptr(self._vol(a)), None if b is None else _ptr(self._vol(b)), self._mask(mask), float(mult), _np_ptr(t)))
+        return t
+
+    def set_timing(self, on):
+        check(lib().xh_halves_set_timing(self.h, int(bool(on))))
+
+    def band_timing(self):
+        """(bands, [transforms, cdf, weights] ms summed over the last filter bank's bands)"""
+        n = C.c_int32()
+        ms = np.zeros(3)
+        check(lib().xh_halves_band_timing(self.h, C.byref(n), _np_ptr(ms)))
+        return n.value, ms
+
+
+def halves_circular_mask(shape, R1, center=(0.0, 0.0, 0.0)):
+    """the program's --mask circular R1 [--center x0 y0 z0] as an int32 array (host only)"""
+    Z, Y, X = (int(s) for s in shape)
+    m = np.zeros((Z, Y, X), np.int32)
+    check(lib().xh_halves_circular_mask(Z, Y, X, float(R1), float(center[0]), float(center[1]), float(center[2]), _np_ptr(m)))
+    return m
+
+
+def halves_binary_mask(values):
+    """the program's --mask binary_file: a file's float values -> int32 0 / 1 (host only)"""
+    v = np.ascontiguousarray(values, np.float32)
+    m = np.zeros(v.shape, np.int32)
+    check(lib().xh_halves_binary_mask(_np_ptr(v), v.size, _np_ptr(m)))
+    return m
+
+def powell_minimize(f, p, steps=None, ftol=0.01):
+    """Powell's method of xmipp3_amd/host/powell.h (host only): f(x) takes the list of variables; returns (p, fmin, iterations)"""
+    from ._lib import COST_FN
+    p = np.ascontiguousarray(p, np.float64).copy()
+    n = p.shape[0]
+    steps = np.ones(n) if steps is None else np.ascontiguousarray(steps, np.float64)
+
+    def cb(x, _user):
+        return float(f([x[i + 1] for i in range(n)]))
+    cfn = COST_FN(cb)
+    fret, it = C.c_double(), C.c_int32()
+    check(lib().xh_powell_minimize(n, _np_ptr(p), _np_ptr(steps), float(ftol), cfn, None, C.byref(fret), C.byref(it)))
+    return p, fret.value, it.value
+
+
 def movie_binned_size(Y, X, binning):
     """AProgMovieAlignmentCorrelation::getMovieSize (movie_alignment_correlation_base.cpp:356-370): float arithmetic, truncated"""
     f = np.float32

@@ -1,0 +1,112 @@
+// xh_fft3d.h -- fp64 3-D real transforms of any size (line FFTs of xh_plan.h) in FFTW layout: real [Z][Y][X] <-> half spectrum
+// [Z][Y][X/2+1]. Both directions are un-normalised, as FFTW's and cuFFT's plans are; a caller that wants the 1/N of an inverse passes it
+// as `scale`, which multiplies each result once, the same single rounding as a separate pass over the output.
+// Used by xh_fsc.hip (forward) and xh_halves.hip (both).
+#ifndef XH_FFT3D_H
+#define XH_FFT3D_H
+#include "xh_common.h"
+#include "xh_plan.h"
+
+namespace {
+
+// x lines: real input [nlines][X] (times scale) -> half spectrum [nlines][xh], forward, un-normalised
+__global__ void __launch_bounds__(256)
+k_fft3d_rows_r2c(const double *__restrict__ in, xh_cd *__restrict__ out, XhPlan<double> plan, size_t nlines, int X, int xh, int lpb, double scale)
+{
+    extern __shared__ __align__(16) unsigned char fft3d_smem[];
+    xh_cd *s = reinterpret_cast<xh_cd *>(fft3d_smem);
+    const int M = 1 << plan.logM;
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const size_t line0 = (size_t)blockIdx.x * lpb;
+    const int nl = (int)min((size_t)lpb, nlines - line0);
+    for (int i = tid; i < lpb * X; i += nth) {
+        const int l = i / X, e = i - l * X;
+        const double v = l < nl ? in[(line0 + l) * X + e] * scale : 0.0;
+        s[l * M + xh_plan_pos(plan, e)] = xh_cd{v, 0.0};
+    }
+    __syncthreads();
+    xh_plan_exec<double, false>(s, plan, lpb, tid, nth);
+    for (int i = tid; i < nl * xh; i += nth) {
+        const int l = i / xh, e = i - l * xh;
+        out[(line0 + l) * xh + e] = s[l * M + e];
+    }
+}
+
+// x lines: half spectrum [nlines][xh] -> real [nlines][X] times scale, inverse, un-normalised. The line is completed by Hermitian
+// symmetry (element e >= xh is conj(F[X - e])) and the real part kept: the imaginary parts of the DC and Nyquist terms drop out,
+// as in FFTW's c2r.
+__global__ void __launch_bounds__(256)
+k_fft3d_rows_c2r(const xh_cd *__restrict__ in, double *__restrict__ out, XhPlan<double> plan, size_t nlines, int X, int xh, int lpb, double scale)
+{
+    extern __shared__ __align__(16) unsigned char fft3d_smem[];
+    xh_cd *s = reinterpret_cast<xh_cd *>(fft3d_smem);
+    const int M = 1 << plan.logM;
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const size_t line0 = (size_t)blockIdx.x * lpb;
+    const int nl = (int)min((size_t)lpb, nlines - line0);
+    for (int i = tid; i < lpb * X; i += nth) {
+        const int l = i / X, e = i - l * X;
+        xh_cd v = xh_cd{0.0, 0.0};
+        if (l < nl) {
+            if (e < xh) v = in[(line0 + l) * xh + e];
+            else { v = in[(line0 + l) * xh + (X - e)]; v.y = -v.y; }
+        }
+        s[l * M + xh_plan_pos(plan, e)] = v;
+    }
+    __syncthreads();
+    xh_plan_exec<double, true>(s, plan, lpb, tid, nth);
+    for (int i = tid; i < nl * X; i += nth) {
+        const int l = i / X, e = i - l * X;
+        out[(line0 + l) * X + e] = s[l * M + e].x * scale;
+    }
+}
+
+// y and z lines of a half spectrum, in place
+template <bool INV>
+int fft3d_yz(xh_ctx *ctx, xh_cd *F, int Z, int Y, int xh, const XhPlan<double> &py, const XhPlan<double> &pz)
+{
+    if (Y > 1) {   // y lines: (k,j) -> offset k*Y*xh + j, element stride xh
+        const int lpb = xh_plan_lpb(py, 64 * 1024, 8);
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << py.logM, nlines = (size_t)Z * xh;
+        hipLaunchKernelGGL((xh_k_fft_lines<double, INV>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, py,
+                           nlines, (size_t)xh, (size_t)Y * xh, (size_t)1, (size_t)xh, lpb);
+        XH_LAUNCH_CHECK();
+    }
+    if (Z > 1) {   // z lines: (i,j) -> offset i*xh + j, element stride Y*xh
+        const int lpb = xh_plan_lpb(pz, 64 * 1024, 8);
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << pz.logM, nlines = (size_t)Y * xh;
+        hipLaunchKernelGGL((xh_k_fft_lines<double, INV>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, pz,
+                           nlines, nlines, (size_t)0, (size_t)1, (size_t)Y * xh, lpb);
+        XH_LAUNCH_CHECK();
+    }
+    return XH_OK;
+}
+
+// forward: d_in [Z][Y][X] (each value times scale) -> F [Z][Y][X/2+1]
+int fft3d_r2c(xh_ctx *ctx, const double *d_in, xh_cd *F, int Z, int Y, int X, const XhPlan<double> &px, const XhPlan<double> &py,
+              const XhPlan<double> &pz, double scale = 1.0)
+{
+    const int xh = X / 2 + 1;
+    const int lpb = xh_plan_lpb(px, 64 * 1024, 8);
+    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.logM, nlines = (size_t)Z * Y;
+    hipLaunchKernelGGL(k_fft3d_rows_r2c, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, d_in, F, px, nlines, X, xh, lpb, scale);
+    XH_LAUNCH_CHECK();
+    return fft3d_yz<false>(ctx, F, Z, Y, xh, py, pz);
+}
+
+// inverse: F [Z][Y][X/2+1] (overwritten) -> d_out [Z][Y][X], each value times scale
+int fft3d_c2r(xh_ctx *ctx, xh_cd *F, double *d_out, int Z, int Y, int X, const XhPlan<double> &px, const XhPlan<double> &py,
+              const XhPlan<double> &pz, double scale)
+{
+    const int xh = X / 2 + 1;
+    XH_TRY(fft3d_yz<true>(ctx, F, Z, Y, xh, py, pz));
+    const int lpb = xh_plan_lpb(px, 64 * 1024, 8);
+    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.logM, nlines = (size_t)Z * Y;
+    hipLaunchKernelGGL(k_fft3d_rows_c2r, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, d_out, px, nlines, X, xh, lpb, scale);
+    XH_LAUNCH_CHECK();
+    return XH_OK;
+}
+
+}  // namespace
+
+#endif

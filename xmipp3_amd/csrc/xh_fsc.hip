@@ -1,7 +1,7 @@
 // xh_fsc.hip -- Fourier ring / shell correlation of two images or volumes on gfx950: the numerical core of
 // xmipp_resolution_fsc (reconstruction/resolution_fsc.cpp:179-203), i.e. xmippCore's frc_dpr. SURVEY.md 8f rank 2.
 //
-//   r2c 3-D FFT (fp64, line transforms of xh_plan.h: any length) of both inputs into [Z][Y][X/2+1]
+//   r2c 3-D FFT (fp64, xh_fft3d.h: line transforms of xh_plan.h, any length) of both inputs into [Z][Y][X/2+1]
 //   one pass over the half-complex coefficients: shell = round(R * X), seven sums per shell accumulated in an
 //     LDS table per workgroup (ds_add_f64), flushed once with global atomics; R-factor sums ride along
 //   the host turns the sums into freq / frc / frc_noise / dpr / error_l2 (X/2+1 values each).
@@ -9,33 +9,10 @@
 // built with -ffp-contract=off); the sums differ from a sequential loop only by fp64 summation order.
 // HBM bound: 2 volumes read once (8 B/voxel), 2 half-spectra written and re-read by three line passes.
 #include "xh_common.h"
-#include "xh_plan.h"
+#include "xh_fft3d.h"
 #include "../../include/xmipp_hip.h"
 
 namespace {
-
-// x lines: real input [nlines][X] -> half spectrum [nlines][xh], forward, un-normalised
-__global__ void __launch_bounds__(256)
-k_fsc_rows(const double *__restrict__ in, xh_cd *__restrict__ out, XhPlan<double> plan, size_t nlines, int X, int xh, int lpb)
-{
-    extern __shared__ __align__(16) unsigned char fsc_smem[];
-    xh_cd *s = reinterpret_cast<xh_cd *>(fsc_smem);
-    const int M = 1 << plan.logM;
-    const int tid = threadIdx.x, nth = blockDim.x;
-    const size_t line0 = (size_t)blockIdx.x * lpb;
-    const int nl = (int)min((size_t)lpb, nlines - line0);
-    for (int i = tid; i < lpb * X; i += nth) {
-        const int l = i / X, e = i - l * X;
-        const double v = l < nl ? in[(line0 + l) * X + e] : 0.0;
-        s[l * M + xh_plan_pos(plan, e)] = xh_cd{v, 0.0};
-    }
-    __syncthreads();
-    xh_plan_exec<double, false>(s, plan, lpb, tid, nth);
-    for (int i = tid; i < nl * xh; i += nth) {
-        const int l = i / xh, e = i - l * xh;
-        out[(line0 + l) * xh + e] = s[l * M + e];
-    }
-}
 
 // FFT_IDX2DIGFREQ_FAST (xmippCore xmipp_fft.h)
 __device__ __forceinline__ double digfreq(int idx, int size) { return (double)(idx <= size / 2 ? idx : idx - size) / (double)size; }
@@ -95,33 +72,6 @@ k_fsc_shells(const xh_cd *__restrict__ F1, const xh_cd *__restrict__ F2, int Z, 
     __syncthreads();
     for (int i = threadIdx.x; i < nt; i += blockDim.x)
         if (t[i] != 0.0) atomicAdd(&sums[i], t[i]);
-}
-
-int fft3d_r2c(xh_ctx *ctx, const double *d_in, xh_cd *F, int Z, int Y, int X, const XhPlan<double> &px, const XhPlan<double> &py,
-              const XhPlan<double> &pz)
-{
-    const int xh = X / 2 + 1;
-    {
-        const int lpb = xh_plan_lpb(px, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.logM, nlines = (size_t)Z * Y;
-        hipLaunchKernelGGL(k_fsc_rows, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, d_in, F, px, nlines, X, xh, lpb);
-        XH_LAUNCH_CHECK();
-    }
-    if (Y > 1) {   // y lines: (k,j) -> offset k*Y*xh + j, element stride xh
-        const int lpb = xh_plan_lpb(py, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << py.logM, nlines = (size_t)Z * xh;
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, py,
-                           nlines, (size_t)xh, (size_t)Y * xh, (size_t)1, (size_t)xh, lpb);
-        XH_LAUNCH_CHECK();
-    }
-    if (Z > 1) {   // z lines: (i,j) -> offset i*xh + j, element stride Y*xh
-        const int lpb = xh_plan_lpb(pz, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << pz.logM, nlines = (size_t)Y * xh;
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, pz,
-                           nlines, nlines, (size_t)0, (size_t)1, (size_t)Y * xh, lpb);
-        XH_LAUNCH_CHECK();
-    }
-    return XH_OK;
 }
 
 }  // namespace

@@ -16,5 +16,6 @@ $CXX $FLAGS ctf_correct_wiener2d_main.cpp -o ../bin/xmipp_ctf_correct_wiener2d $
 $CXX $FLAGS movie_alignment_correlation_main.cpp -o ../bin/xmipp_movie_alignment_correlation $LINK &
 $CXX $FLAGS movie_filter_dose_main.cpp -o ../bin/xmipp_movie_filter_dose $LINK &
 $CXX $FLAGS align_significant_main.cpp -o ../bin/xmipp_align_significant $LINK &
+$CXX $FLAGS volume_halves_restoration_main.cpp -o ../bin/xmipp_volume_halves_restoration $LINK &
 wait
-echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant}"
+echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration}"

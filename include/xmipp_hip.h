@@ -71,6 +71,9 @@ int xh_free(xh_ctx *ctx, void *d_ptr);
 int xh_memset(xh_ctx *ctx, void *d_ptr, int value, size_t bytes);
 int xh_memcpy_h2d(xh_ctx *ctx, void *d_dst, const void *h_src, size_t bytes); /* synchronous */
 int xh_memcpy_d2h(xh_ctx *ctx, void *h_dst, const void *d_src, size_t bytes); /* synchronous */
+/* bytes of device memory the library's handles and calls hold right now, over all contexts of the process
+ * (xh_malloc'd memory not included): every handle's destroy returns what it held */
+int xh_device_bytes_held(int64_t *bytes);
 /* Page-locked host memory and copies that only enqueue: what a loader thread needs to feed the device while it computes
  * (pinMemory / unpinMemory, cuda_gpu_reconstruct_fourier.h:134-136, gpu.h:78-113; the loader of
  * reconstruct_fourier_accel.cpp:300-388).  The async copies return when enqueued on the context's stream; the host

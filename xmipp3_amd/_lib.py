@@ -48,6 +48,7 @@ SIGNATURES = {
     "xh_memset": (C.c_int, [vp, vp, C.c_int, sz]),
     "xh_memcpy_h2d": (C.c_int, [vp, vp, vp, sz]),
     "xh_memcpy_d2h": (C.c_int, [vp, vp, vp, sz]),
+    "xh_device_bytes_held": (C.c_int, [C.POINTER(C.c_int64)]),
     "xh_host_alloc": (C.c_int, [vp, sz, pvp]),
     "xh_host_free": (C.c_int, [vp, vp]),
     "xh_memcpy_h2d_async": (C.c_int, [vp, vp, vp, sz]),

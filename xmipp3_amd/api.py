@@ -99,6 +99,29 @@ class _Timer:
             pass
 
 
+class _Handle:
+    """A library handle made on a Context: destroyed by close() or when collected, and by its context's close() before the context
+    goes. Subclasses name their xh_*_destroy in _destroy."""
+
+    _destroy = None
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                getattr(lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _ptr(t, dtype=None):
     if t is None:
         return None
@@ -121,8 +144,10 @@ def ctf_params(**kw):
     return p
 
 
-class RecFourier:
+class RecFourier(_Handle):
     """Device side of ProgRecFourierAccel (reconstruction/reconstruct_fourier_accel.cpp)."""
+
+    _destroy = "xh_rf_destroy"
 
     def __init__(self, ctx, imgSize, padding_proj=2.0, padding_vol=2.0, max_resolution=0.5,
                  blob_radius=1.9, blob_order=0, blob_alpha=15.0, fast=False, phase_flipped=False,
@@ -133,8 +158,7 @@ class RecFourier:
                      int(blob_order), blob_alpha, int(fast), int(phase_flipped), min_ctf, sampling)
         h = C.c_void_p()
         check(lib().xh_rf_create(ctx.h, C.byref(p), C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         P, mv, sx, sy = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().xh_rf_sizes(h, C.byref(P), C.byref(mv), C.byref(sx), C.byref(sy)))
         self.D, self.P, self.mv, self.sizeX, self.sizeY = int(imgSize), P.value, mv.value, sx.value, sy.value
@@ -142,18 +166,6 @@ class RecFourier:
         self.temp = torch.zeros(lib().xh_rf_temp_floats(h), dtype=torch.float32, device=ctx.torch_device)
         check(lib().xh_rf_attach_temp(h, _ptr(self.temp)))
         self.cropped = False
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_rf_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_option(self, name, value):
         check(lib().xh_rf_set_option(self.h, name.encode(), float(value)))
@@ -302,9 +314,11 @@ class RecFourier:
         return out
 
 
-class RecFourier2:
+class RecFourier2(_Handle):
     """Device side of ProgRecFourier (reconstruction/reconstruct_fourier.cpp), the double-precision program behind the name
     xmipp_reconstruct_fourier. Keeps what it inserted so that finish() can replay it for --iter > 1 (correctWeight)."""
+
+    _destroy = "xh_rf2_destroy"
 
     def __init__(self, ctx, imgSize, padding_proj=2.0, padding_vol=2.0, max_resolution=0.5, blob_radius=1.9, blob_order=0, blob_alpha=15.0,
                  niter_weight=1, phase_flipped=False, min_ctf=0.01, sampling=1.0):
@@ -312,21 +326,8 @@ class RecFourier2:
         p = RfParams(self.D, padding_proj, padding_vol, max_resolution, blob_radius, int(blob_order), blob_alpha, 0, int(phase_flipped), min_ctf, sampling)
         h = C.c_void_p()
         check(lib().xh_rf2_create(ctx.h, C.byref(p), self.niter, C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         self._calls = []
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_rf2_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _insert(self, imgs, ctfs, ang, w, s, reprocess):
         n = ang.shape[0]
@@ -388,31 +389,20 @@ def allreduce_reconstruction(rf):
         dist.all_reduce(rf.cropped_view(), op=dist.ReduceOp.SUM)
 
 
-class Fft2D:
+class Fft2D(_Handle):
     """In-place complex 2-D FFT of an [ny, nx] complex64 cuda tensor, lines of any factorisable length (xh_fft2d_*: the
     four-step transform FlexAlign's movie frames need)."""
+
+    _destroy = "xh_fft2d_destroy"
 
     def __init__(self, ctx, ny, nx):
         self.ctx, self.ny, self.nx = ctx, int(ny), int(nx)
         h = C.c_void_p()
         check(lib().xh_fft2d_create(ctx.h, self.ny, self.nx, C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         f = np.zeros(4, np.int32)
         check(lib().xh_fft2d_factors(h, _np_ptr(f)))
         self.factors = tuple(int(v) for v in f)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_fft2d_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __call__(self, data, inverse=False):
         torch = _torch()
@@ -421,30 +411,19 @@ class Fft2D:
         return data
 
 
-class FlexAlign:
+class FlexAlign(_Handle):
     """Global alignment of a movie (ProgMovieAlignmentCorrelation*::computeGlobalAlignment) for frames of one size."""
+
+    _destroy = "xh_fa_destroy"
 
     def __init__(self, ctx, Y, X, sampling_rate=1.0, max_res=30.0):
         self.ctx, self.Y, self.X = ctx, int(Y), int(X)
         h = C.c_void_p()
         check(lib().xh_fa_create(ctx.h, self.Y, self.X, float(sampling_rate), float(max_res), C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         a, b, f = C.c_int32(), C.c_int32(), C.c_double()
         check(lib().xh_fa_info(h, C.byref(a), C.byref(b), C.byref(f)))
         self.new_dims, self.size_factor = (a.value, b.value), f.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_fa_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_option(self, name, value):
         check(lib().xh_fa_set_option(self.h, name.encode(), float(value)))
@@ -589,27 +568,16 @@ def iterative_alignment(ctx, ref, others, max_shift, iters=3, first_ring=None, l
     return poses.reshape(n, 3, 3), merit
 
 
-class ShiftCorrEstimator:
+class ShiftCorrEstimator(_Handle):
     """Alignment::ShiftCorrEstimator<float>, AlignType::OneToN, for images of x by y pixels (even)."""
+
+    _destroy = "xh_shiftcorr_destroy"
 
     def __init__(self, ctx, x, y, max_shift):
         self.ctx, self.x, self.y = ctx, int(x), int(y)
         h = C.c_void_p()
         check(lib().xh_shiftcorr_create(ctx.h, self.x, self.y, int(max_shift), C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_shiftcorr_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, h)
 
     def load_reference(self, ref):
         torch = _torch()
@@ -634,10 +602,12 @@ class ShiftCorrEstimator:
         return inout
 
 
-class AlignSignificant:
+class AlignSignificant(_Handle):
     """The device side of xmipp_align_significant: every (reference, image) pair aligned with the chain of iterative_alignment, in
     batches of pairs; the significance weights; the weighted reference update. Defaults are the CUDA program's: max_shift D / 4, the
     default rings, iters 3."""
+
+    _destroy = "xh_align_sig_destroy"
 
     def __init__(self, ctx, D, max_refs, batch_pairs=1024, max_shift=None, first_ring=None, last_ring=None, iters=3):
         self.ctx, self.D = ctx, int(D)
@@ -649,21 +619,8 @@ class AlignSignificant:
             last_ring = (self.D - 3) // 2
         h = C.c_void_p()
         check(lib().xh_align_sig_create(ctx.h, self.D, int(max_refs), int(batch_pairs), int(max_shift), int(first_ring), int(last_ring), int(iters), C.byref(h)))
-        self.h = h
+        super().__init__(ctx, h)
         self.R = 0
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_align_sig_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _images(self, t):
         torch = _torch()
@@ -713,9 +670,11 @@ class AlignSignificant:
         return out
 
 
-class HalvesRestoration:
+class HalvesRestoration(_Handle):
     """The device side of xmipp_volume_halves_restoration (VolumeHalvesRestorator<double>): two half maps [Z, Y, X] float64 restored in
     place by denoise, deconvolve, filter_bank and difference, in that order, as the reference's apply runs them."""
+
+    _destroy = "xh_halves_destroy"
 
     OUTPUTS = ("restored1", "restored2", "filterBank", "deconvolved", "convolved", "avgDiff")
 
@@ -725,20 +684,7 @@ class HalvesRestoration:
         assert len(self.shape) == 3
         h = C.c_void_p()
         check(lib().xh_halves_create(ctx.h, *self.shape, C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_halves_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, h)
 
     def _vol(self, t, dtype=None):
         torch = _torch()
@@ -895,28 +841,17 @@ def fa_correlate(ctx, frames, max_dist):
     return pos
 
 
-class CtfOps:
+class CtfOps(_Handle):
     """CTF pre-steps on the device: actualPhaseFlip (reconstruction/ctf_phase_flip.cpp:88-117) and
     Wiener2D::applyWienerFilter (data/wiener2d.cpp:101-141) for images of one size."""
+
+    _destroy = "xh_ctfop_destroy"
 
     def __init__(self, ctx, ydim, xdim, pad=1.0):
         self.ctx, self.ydim, self.xdim = ctx, int(ydim), int(xdim)
         h = C.c_void_p()
         check(lib().xh_ctfop_create(ctx.h, self.ydim, self.xdim, float(pad), C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_ctfop_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, h)
 
     def phase_flip(self, img, ctf, sampling_rate):
         """img: [ydim, xdim] float32 on the device, flipped in place"""
@@ -936,9 +871,11 @@ class CtfOps:
         return imgs
 
 
-class FourierProjector:
+class FourierProjector(_Handle):
     """Device side of FourierProjector (data/fourier_projection.cpp): central-slice projections of a
     volume `[z][y][x]` (float32, cuda) with cubic B-spline interpolation in Fourier space."""
+
+    _destroy = "xh_fp_destroy"
 
     def __init__(self, ctx, vol, padding=2.0, max_freq=0.5, degree=3):
         torch = _torch()
@@ -947,23 +884,10 @@ class FourierProjector:
         self.D = vol.shape[0]
         h = C.c_void_p()
         check(lib().xh_fp_create(ctx.h, _ptr(vol), self.D, float(padding), float(max_freq), int(degree), C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().xh_fp_info(h, C.byref(a), C.byref(b), C.byref(c)))
         self.P, self.cdim, self.cstart = a.value, b.value, c.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_fp_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def coefs(self):
         re = np.empty((self.cdim,) * 3, np.float64)
@@ -981,9 +905,11 @@ class FourierProjector:
         return out
 
 
-class ProjectionMatcher:
+class ProjectionMatcher(_Handle):
     """Device side of ProgAngularProjectionMatching
     (reconstruction/angular_projection_matching.cpp)."""
+
+    _destroy = "xh_pm_destroy"
 
     def __init__(self, ctx, refs, Ri=1, Ro=-1, Mctf=None, paddim=0):
         torch = _torch()
@@ -993,23 +919,10 @@ class ProjectionMatcher:
         h = C.c_void_p()
         m = None if Mctf is None else np.ascontiguousarray(Mctf, np.float64)
         check(lib().xh_pm_create(ctx.h, self.D, Ri, Ro, self.nrefs, _ptr(refs), _np_ptr(m), paddim, C.byref(h)))
-        self.h = h
-        ctx._children.add(self)
+        super().__init__(ctx, h)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib().xh_pm_info(h, C.byref(a), C.byref(b), C.byref(c)))
         self.N, self.ncoef, self.nsamples = a.value, b.value, c.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.ctx, "h", None):
-                lib().xh_pm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_option(self, name, value):
         check(lib().xh_pm_set_option(self.h, name.encode(), float(value)))

@@ -203,14 +203,12 @@ struct xh_align_sig {
     EsFft2d64 fft;
     XhBuf Fref, refSpec, refs;        // per reference: polar ring DFT, shift spectrum, pixels (for the merit)
     XhBuf dest, work, map, pos, pose, A, meritSR;
+    ~xh_align_sig()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
 };
-
-static void as_free(xh_align_sig *h)
-{
-    es_rotation_free(h->rot);
-    es_fft2d64_free(h->fft);
-    for (XhBuf *b : {&h->Fref, &h->refSpec, &h->refs, &h->dest, &h->work, &h->map, &h->pos, &h->pose, &h->A, &h->meritSR}) xh_buf_free(*b);
-}
 
 static unsigned as_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -287,10 +285,6 @@ extern "C" {
 
 int xh_align_sig_destroy(xh_align_sig *h)
 {
-    if (!h) return XH_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    as_free(h);
     delete h;
     return XH_OK;
 }
@@ -304,29 +298,28 @@ int xh_align_sig_create(xh_ctx *ctx, int32_t D, int32_t max_refs, int32_t batch_
     XH_CHECK(D >= 2 && (D & 1) == 0, XH_ERR_ARG, "xh_align_sig_create: only even sizes are supported");
     XH_CHECK(max_shift > 0 && max_shift < D / 2, XH_ERR_ARG, "xh_align_sig_create: the maximal shift must be positive and sharply less than half of the size");
     XH_HIP(hipSetDevice(ctx->device));
-    xh_align_sig *h = new xh_align_sig;
+    std::unique_ptr<xh_align_sig> h(new xh_align_sig);
     h->ctx = ctx; h->D = D; h->maxRefs = max_refs; h->batch = batch_pairs; h->maxShift = max_shift; h->iters = iters;
     const size_t per = (size_t)D * D, B = (size_t)batch_pairs;
-    int rc = es_rotation_plan(ctx, D, first_ring, last_ring, h->rot);
-    if (rc == XH_OK) rc = es_fft2d64_create(ctx, D, D, h->fft, "xh_align_sig_create");
+    XH_TRY(es_rotation_plan(ctx, D, first_ring, last_ring, h->rot));
+    XH_TRY(es_fft2d64_create(ctx, D, D, h->fft, "xh_align_sig_create"));
     EsRotation &R = h->rot;
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->Fref, sizeof(double2) * (size_t)R.ncoefs * max_refs);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->refSpec, sizeof(xh_cd) * per * max_refs);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->refs, sizeof(float) * per * max_refs);
-    if (rc == XH_OK) rc = xh_buf_reserve(ctx, R.rings, sizeof(double) * (size_t)R.nsamples * std::max<size_t>(B, max_refs));
-    if (rc == XH_OK) rc = xh_buf_reserve(ctx, R.coefs, sizeof(double2) * (size_t)R.ncoefs * B);
-    if (rc == XH_OK) rc = xh_buf_reserve(ctx, R.Fsum, sizeof(double2) * (size_t)R.N * B);
-    if (rc == XH_OK) rc = xh_buf_reserve(ctx, R.corr, sizeof(double) * (size_t)R.len * B);
-    if (rc == XH_OK) rc = xh_buf_reserve(ctx, R.imax, sizeof(int) * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->dest, sizeof(float) * per * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->work, sizeof(xh_cd) * per * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->map, sizeof(float) * per * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->pos, sizeof(float) * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->pose, sizeof(float) * 9 * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->A, sizeof(double) * 9 * B);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->meritSR, sizeof(float) * B);
-    if (rc != XH_OK) { xh_align_sig_destroy(h); return rc; }
-    *out = h;
+    XH_TRY(xh_buf_alloc(ctx, h->Fref, sizeof(double2) * (size_t)R.ncoefs * max_refs));
+    XH_TRY(xh_buf_alloc(ctx, h->refSpec, sizeof(xh_cd) * per * max_refs));
+    XH_TRY(xh_buf_alloc(ctx, h->refs, sizeof(float) * per * max_refs));
+    XH_TRY(xh_buf_reserve(ctx, R.rings, sizeof(double) * (size_t)R.nsamples * std::max<size_t>(B, max_refs)));
+    XH_TRY(xh_buf_reserve(ctx, R.coefs, sizeof(double2) * (size_t)R.ncoefs * B));
+    XH_TRY(xh_buf_reserve(ctx, R.Fsum, sizeof(double2) * (size_t)R.N * B));
+    XH_TRY(xh_buf_reserve(ctx, R.corr, sizeof(double) * (size_t)R.len * B));
+    XH_TRY(xh_buf_reserve(ctx, R.imax, sizeof(int) * B));
+    XH_TRY(xh_buf_alloc(ctx, h->dest, sizeof(float) * per * B));
+    XH_TRY(xh_buf_alloc(ctx, h->work, sizeof(xh_cd) * per * B));
+    XH_TRY(xh_buf_alloc(ctx, h->map, sizeof(float) * per * B));
+    XH_TRY(xh_buf_alloc(ctx, h->pos, sizeof(float) * B));
+    XH_TRY(xh_buf_alloc(ctx, h->pose, sizeof(float) * 9 * B));
+    XH_TRY(xh_buf_alloc(ctx, h->A, sizeof(double) * 9 * B));
+    XH_TRY(xh_buf_alloc(ctx, h->meritSR, sizeof(float) * B));
+    *out = h.release();
     return XH_OK;
 }
 
@@ -387,17 +380,16 @@ int xh_align_sig_weights(xh_align_sig *h, const float *h_rot, const float *h_til
             mask[(size_t)r * R + q] = (r == q || ang <= ang_distance) ? 1 : 0;
         }
     XhBuf bMask, bMax;
-    int rc = xh_buf_alloc(ctx, bMask, mask.size());
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bMax, sizeof(float) * R);
-    if (rc == XH_OK && hipMemcpyAsync(bMask.p, mask.data(), mask.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK) {
+    XH_TRY(xh_buf_alloc(ctx, bMask, mask.size()));
+    XH_TRY(xh_buf_alloc(ctx, bMax, sizeof(float) * R));
+    bool ok = hipMemcpyAsync(bMask.p, mask.data(), mask.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok) {
         hipLaunchKernelGGL(k_as_masked_max, dim3(R), dim3(256), 0, ctx->stream, d_merit, (const unsigned char *)bMask.p, R, N, (float *)bMax.p);
         hipLaunchKernelGGL(k_as_weights, dim3(as_blocks(N), R), dim3(256), 0, ctx->stream, d_merit, (const unsigned char *)bMask.p, (const float *)bMax.p, R, N, d_weights);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
-    xh_buf_free(bMask); xh_buf_free(bMax);
-    if (rc == XH_ERR_HIP) xh_set_error("xh_align_sig_weights: device error");
-    return rc;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_align_sig_weights: device error");
+    return XH_OK;
 }
 
 int xh_align_sig_update_refs(xh_align_sig *h, const float *d_images, int32_t N, int32_t R, int32_t n_assign, const int32_t *h_ref_idx, const int32_t *h_img_idx,
@@ -431,27 +423,23 @@ int xh_align_sig_update_refs(xh_align_sig *h, const float *d_images, int32_t N, 
         norm[r] = running;
     }
     XhBuf bOff, bImg, bW, bA, bNorm;
-    int rc = xh_buf_alloc(ctx, bOff, sizeof(int) * off.size());
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bImg, sizeof(int) * img.size());
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bW, sizeof(float) * w.size());
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bA, sizeof(double) * A.size());
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bNorm, sizeof(float) * norm.size());
-    if (rc == XH_OK) {
-        if (hipMemcpyAsync(bOff.p, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(bImg.p, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(bW.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(bA.p, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(bNorm.p, norm.data(), sizeof(float) * norm.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-            rc = XH_ERR_HIP;
-    }
-    if (rc == XH_OK) {
+    XH_TRY(xh_buf_alloc(ctx, bOff, sizeof(int) * off.size()));
+    XH_TRY(xh_buf_alloc(ctx, bImg, sizeof(int) * img.size()));
+    XH_TRY(xh_buf_alloc(ctx, bW, sizeof(float) * w.size()));
+    XH_TRY(xh_buf_alloc(ctx, bA, sizeof(double) * A.size()));
+    XH_TRY(xh_buf_alloc(ctx, bNorm, sizeof(float) * norm.size()));
+    bool ok = hipMemcpyAsync(bOff.p, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+              hipMemcpyAsync(bImg.p, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+              hipMemcpyAsync(bW.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+              hipMemcpyAsync(bA.p, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+              hipMemcpyAsync(bNorm.p, norm.data(), sizeof(float) * norm.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok) {
         hipLaunchKernelGGL(k_as_update_refs, dim3(as_blocks((size_t)h->D * h->D), R), dim3(256), 0, ctx->stream, d_images, (const int *)bOff.p, (const int *)bImg.p,
                            (const float *)bW.p, (const double *)bA.p, (const float *)bNorm.p, h->D, d_out_refs);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
-    for (XhBuf *b : {&bOff, &bImg, &bW, &bA, &bNorm}) xh_buf_free(*b);
-    if (rc == XH_ERR_HIP) xh_set_error("xh_align_sig_update_refs: device error");
-    return rc;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_align_sig_update_refs: device error");
+    return XH_OK;
 }
 
 }  // extern "C"

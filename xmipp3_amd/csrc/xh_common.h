@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/xmipp_hip.h"
@@ -44,15 +45,38 @@ struct xh_ctx {
     int num_cus;
 };
 
-// RAII-less tracked device allocation helper for handles
+// A device allocation with one owner (a handle member or a local of an entry point): move-only, freed by its
+// destructor, counted in xh_device_bytes_held.  A local freed at scope exit on an error path needs no prior
+// synchronisation: hipFree synchronises the device before it releases the memory.
+struct XhBuf;
+void xh_buf_free(XhBuf &b);   // early release; the buffer is empty afterwards
 struct XhBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    XhBuf() = default;
+    XhBuf(const XhBuf &) = delete;
+    XhBuf &operator=(const XhBuf &) = delete;
+    XhBuf(XhBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    XhBuf &operator=(XhBuf &&o) noexcept
+    {
+        if (this != &o) {
+            xh_buf_free(*this);
+            p = o.p;
+            bytes = o.bytes;
+            o.p = nullptr;
+            o.bytes = 0;
+        }
+        return *this;
+    }
+    ~XhBuf() { xh_buf_free(*this); }
 };
+// frees b, then allocates `bytes` (none for 0)
 int xh_buf_alloc(xh_ctx *ctx, XhBuf &b, size_t bytes);
-void xh_buf_free(XhBuf &b);
-// grow-only scratch
-int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes);
+// xh_buf_alloc, then a synchronous copy of `bytes` from the host
+int xh_buf_upload(xh_ctx *ctx, XhBuf &b, const void *src, size_t bytes);
+// grow-only scratch: reallocates (after synchronising the stream) only when it holds fewer than `bytes`;
+// *grown tells whether it did
+int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes, bool *grown = nullptr);
 
 // a grow-only device buffer that lives with a 2-D transform plan (frame-after-frame callers: dose filter, binning)
 int xh_fft2d_user_scratch(xh_fft2d *f, size_t bytes, void **p);
@@ -62,7 +86,7 @@ int xh_fft2d_rows_of_real_pairs_kept(xh_fft2d *f, const float *d_frame, const fl
 // A/B and test knobs read from the environment (XH_FA_PB, XH_FA_COPY_PATCHES, XH_FA_WARP_PLAIN, XH_PREFILTER_FORM, XH_FFT2D_NO_SMALL,
 // XH_FFT2D_N1, XH_FFT2D_NO_45: other correct forms of a kernel; XH_ES_ORDER: one half of xh_iterative_alignment's compute(), a WRONG
 // result by design, for tools/diag_iterative.py) exist only in a library built with -DXH_DEBUG_HOOKS (XH_DEBUG_HOOKS=1 csrc/build.sh);
-// the product build never looks at them.  XH_ALLOC_TRACE and XH_FA_TIMING only print.
+// the product build never looks at them.  XH_FA_TIMING only prints.
 static inline const char *xh_debug_env(const char *name)
 {
 #ifdef XH_DEBUG_HOOKS

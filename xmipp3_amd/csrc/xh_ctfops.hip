@@ -163,8 +163,14 @@ __global__ void __launch_bounds__(256) k_ctf_wiener_apply(xc_cf *__restrict__ F,
 struct xh_ctfop {
     xh_ctx *ctx;
     int ydim, xdim, pY, pX;
-    xh_fft2d *fft;
+    xh_fft2d *fft = nullptr;
     XhBuf work, ctfIm, sum;
+    ~xh_ctfop()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        xh_fft2d_destroy(fft);
+    }
 };
 
 extern "C" {
@@ -174,25 +180,18 @@ int xh_ctfop_create(xh_ctx *ctx, int32_t ydim, int32_t xdim, double pad, xh_ctfo
     XH_CHECK(ctx && out && ydim >= 2 && xdim >= 2, XH_ERR_ARG, "xh_ctfop_create: bad argument");
     XH_HIP(hipSetDevice(ctx->device));
     if (!(pad >= 1.)) pad = 1.;                 // XMIPP_MAX(1., pad), ctf_correct_wiener2d.cpp:34
-    xh_ctfop *h = new xh_ctfop;
+    std::unique_ptr<xh_ctfop> h(new xh_ctfop);
     h->ctx = ctx; h->ydim = ydim; h->xdim = xdim;
     h->pY = (int)(ydim * pad); h->pX = (int)(xdim * pad);        // wiener2d.cpp:31-33
-    h->fft = nullptr;
-    int rc = xh_fft2d_create(ctx, h->pY, h->pX, &h->fft);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->work, sizeof(xc_cf) * (size_t)h->pY * h->pX);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->sum, sizeof(double));
-    if (rc != XH_OK) { xh_ctfop_destroy(h); return rc; }
-    *out = h;
+    XH_TRY(xh_fft2d_create(ctx, h->pY, h->pX, &h->fft));
+    XH_TRY(xh_buf_alloc(ctx, h->work, sizeof(xc_cf) * (size_t)h->pY * h->pX));
+    XH_TRY(xh_buf_alloc(ctx, h->sum, sizeof(double)));
+    *out = h.release();
     return XH_OK;
 }
 
 int xh_ctfop_destroy(xh_ctfop *h)
 {
-    if (!h) return XH_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->fft) xh_fft2d_destroy(h->fft);
-    xh_buf_free(h->work); xh_buf_free(h->ctfIm); xh_buf_free(h->sum);
     delete h;
     return XH_OK;
 }

@@ -2,6 +2,7 @@
 #include "xh_common.h"
 #include <cstring>
 #include <cctype>
+#include <atomic>
 
 static thread_local std::string g_err;
 
@@ -15,6 +16,8 @@ void xh_set_error(const char *fmt, ...)
     g_err = buf;
 }
 
+static std::atomic<int64_t> g_bytes_held{0};
+
 int xh_buf_alloc(xh_ctx *ctx, XhBuf &b, size_t bytes)
 {
     xh_buf_free(b);
@@ -27,27 +30,46 @@ int xh_buf_alloc(xh_ctx *ctx, XhBuf &b, size_t bytes)
         return XH_ERR_NOMEM;
     }
     b.bytes = bytes;
-    if (getenv("XH_ALLOC_TRACE")) fprintf(stderr, "xh_buf_alloc %zu bytes -> %p\n", bytes, b.p);
+    g_bytes_held += (int64_t)bytes;
+    return XH_OK;
+}
+int xh_buf_upload(xh_ctx *ctx, XhBuf &b, const void *src, size_t bytes)
+{
+    XH_TRY(xh_buf_alloc(ctx, b, bytes));
+    if (bytes) XH_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
     return XH_OK;
 }
 void xh_buf_free(XhBuf &b)
 {
-    if (b.p) (void)hipFree(b.p);
+    if (b.p) {
+        (void)hipFree(b.p);
+        g_bytes_held -= (int64_t)b.bytes;
+    }
     b.p = nullptr;
     b.bytes = 0;
 }
-int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes)
+int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes, bool *grown)
 {
+    if (grown) *grown = false;
     if (b.bytes >= bytes) return XH_OK;
     // the stream may still be using the old buffer
     XH_HIP(hipStreamSynchronize(ctx->stream));
-    return xh_buf_alloc(ctx, b, bytes);
+    XH_TRY(xh_buf_alloc(ctx, b, bytes));
+    if (grown) *grown = true;
+    return XH_OK;
 }
 
 extern "C" {
 
 const char *xh_last_error(void) { return g_err.c_str(); }
 const char *xh_version(void) { return "xmipp3_amd 0.1 (gfx950)"; }
+
+int xh_device_bytes_held(int64_t *bytes)
+{
+    XH_CHECK(bytes, XH_ERR_ARG, "xh_device_bytes_held: null pointer");
+    *bytes = g_bytes_held.load();
+    return XH_OK;
+}
 
 int xh_device_count(int *count)
 {

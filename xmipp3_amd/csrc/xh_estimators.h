@@ -267,12 +267,6 @@ struct EsRotation {
     XhBuf ringTab, sx, sy, Fref, rings, coefs, Fsum, corr, imax;
 };
 
-static void es_rotation_free(EsRotation &R)
-{
-    xh_buf_free(R.ringTab); xh_buf_free(R.sx); xh_buf_free(R.sy); xh_buf_free(R.Fref); xh_buf_free(R.rings); xh_buf_free(R.coefs);
-    xh_buf_free(R.Fsum); xh_buf_free(R.corr); xh_buf_free(R.imax);
-}
-
 // polarFourierTransform<false>(..., BsplineOrder = 1) of n images [n][D][D] (float) into coefs [n][ncoefs]
 static int es_rotation_transform(EsRotation &R, const float *d_imgs, int n, int conjugate, double2 *d_coefs)
 {
@@ -347,18 +341,14 @@ struct EsFft2d64 {
     XhPlanBufs<double> planX, planY;
 };
 
-static void es_fft2d64_free(EsFft2d64 &P) { xh_plan_free(P.planX); xh_plan_free(P.planY); }
-
 static int es_fft2d64_create(xh_ctx *ctx, int x, int y, EsFft2d64 &P, const char *who)
 {
     P.x = x; P.y = y;
-    int rc = xh_plan_create<double>(ctx, x, P.planX);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, y, P.planY);
-    if (rc == XH_OK && ((sizeof(xh_cd) << P.planX.plan.logM) > 64 * 1024 || (sizeof(xh_cd) << P.planY.plan.logM) > 64 * 1024)) {
-        xh_set_error("%s: a line of %d x %d does not fit the LDS of the double-precision transform", who, x, y);
-        rc = XH_ERR_UNSUPPORTED;
-    }
-    return rc;
+    XH_TRY(xh_plan_create<double>(ctx, x, P.planX));
+    XH_TRY(xh_plan_create<double>(ctx, y, P.planY));
+    XH_CHECK((sizeof(xh_cd) << P.planX.plan.logM) <= 64 * 1024 && (sizeof(xh_cd) << P.planY.plan.logM) <= 64 * 1024, XH_ERR_UNSUPPORTED,
+             "%s: a line of %d x %d does not fit the LDS of the double-precision transform", who, x, y);
+    return XH_OK;
 }
 
 // 2-D complex transform of n images [n][y][x] (double) in place, un-normalised: rows then columns

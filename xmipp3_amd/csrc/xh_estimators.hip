@@ -107,6 +107,11 @@ struct xh_shiftcorr {
     EsFft2d64 fft;                        // line transforms of any length (xh_plan.h), double precision
     XhBuf ref, work, map, pos;
     bool refLoaded;
+    ~xh_shiftcorr()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
 };
 
 static int es_fft2d64(xh_shiftcorr *h, xh_cd *d, int n, bool inverse) { return es_fft2d64(h->ctx, h->fft, d, n, inverse); }
@@ -129,30 +134,22 @@ int xh_extrema_find(xh_ctx *ctx, const float *d_data, int32_t n, int32_t zdim, i
     const int empty = around && (maxDist > xdim / 2 || maxDist > ydim / 2);
     XhBuf bPos, bVal;
     XH_TRY(xh_buf_alloc(ctx, bPos, sizeof(float) * n));
-    int rc = xh_buf_alloc(ctx, bVal, sizeof(float) * n);
-    if (rc == XH_OK) {
-        const size_t elems = (size_t)zdim * ydim * xdim;
-        if (search_type & 1)
-            hipLaunchKernelGGL((k_es_extrema<true>), dim3(n), dim3(256), 0, ctx->stream, d_data, elems, ydim, xdim, around, maxDist, empty, (float *)bPos.p, (float *)bVal.p);
-        else
-            hipLaunchKernelGGL((k_es_extrema<false>), dim3(n), dim3(256), 0, ctx->stream, d_data, elems, ydim, xdim, around, maxDist, empty, (float *)bPos.p, (float *)bVal.p);
-        if (hipGetLastError() != hipSuccess) rc = XH_ERR_HIP;
-        if (rc == XH_OK && h_positions && hipMemcpyAsync(h_positions, bPos.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-        if (rc == XH_OK && h_values && hipMemcpyAsync(h_values, bVal.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-        if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    }
-    xh_buf_free(bPos); xh_buf_free(bVal);
-    if (rc == XH_ERR_HIP) xh_set_error("xh_extrema_find: device error");
-    return rc;
+    XH_TRY(xh_buf_alloc(ctx, bVal, sizeof(float) * n));
+    const size_t elems = (size_t)zdim * ydim * xdim;
+    if (search_type & 1)
+        hipLaunchKernelGGL((k_es_extrema<true>), dim3(n), dim3(256), 0, ctx->stream, d_data, elems, ydim, xdim, around, maxDist, empty, (float *)bPos.p, (float *)bVal.p);
+    else
+        hipLaunchKernelGGL((k_es_extrema<false>), dim3(n), dim3(256), 0, ctx->stream, d_data, elems, ydim, xdim, around, maxDist, empty, (float *)bPos.p, (float *)bVal.p);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && (!h_positions || hipMemcpyAsync(h_positions, bPos.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    ok = ok && (!h_values || hipMemcpyAsync(h_values, bVal.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_extrema_find: device error");
+    return XH_OK;
 }
 
 int xh_shiftcorr_destroy(xh_shiftcorr *h)
 {
-    if (!h) return XH_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    es_fft2d64_free(h->fft);
-    xh_buf_free(h->ref); xh_buf_free(h->work); xh_buf_free(h->map); xh_buf_free(h->pos);
     delete h;
     return XH_OK;
 }
@@ -165,15 +162,14 @@ int xh_shiftcorr_create(xh_ctx *ctx, int32_t xdim, int32_t ydim, int32_t max_shi
     XH_CHECK((xdim & 1) == 0 && (ydim & 1) == 0, XH_ERR_ARG, "xh_shiftcorr_create: only even sizes are supported");
     XH_CHECK(max_shift > 0 && max_shift < xdim / 2 && max_shift < ydim / 2, XH_ERR_ARG, "xh_shiftcorr_create: the maximal shift must be positive and sharply less than half of the size");
     XH_HIP(hipSetDevice(ctx->device));
-    xh_shiftcorr *h = new xh_shiftcorr;
+    std::unique_ptr<xh_shiftcorr> h(new xh_shiftcorr);
     h->ctx = ctx; h->x = xdim; h->y = ydim; h->maxShift = max_shift; h->refLoaded = false;
     // The reference's ShiftCorrEstimator<float> transforms with fftwf; its test images (one-pixel lines) give correlation maps full of
     // exact ties, which single-precision rounding breaks at random.  The device transforms in double and compares the map as floats,
     // so that the first maximum in raster order is the one exact arithmetic has.
-    int rc = es_fft2d64_create(ctx, xdim, ydim, h->fft, "xh_shiftcorr_create");
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->ref, sizeof(xh_cd) * (size_t)xdim * ydim);
-    if (rc != XH_OK) { xh_shiftcorr_destroy(h); return rc; }
-    *out = h;
+    XH_TRY(es_fft2d64_create(ctx, xdim, ydim, h->fft, "xh_shiftcorr_create"));
+    XH_TRY(xh_buf_alloc(ctx, h->ref, sizeof(xh_cd) * (size_t)xdim * ydim));
+    *out = h.release();
     return XH_OK;
 }
 
@@ -248,11 +244,10 @@ int xh_rotation_estimate(xh_ctx *ctx, const float *d_ref, const float *d_others,
     XH_CHECK(ctx && d_ref && d_others && h_rotations && n >= 1, XH_ERR_ARG, "xh_rotation_estimate: bad argument");
     XH_HIP(hipSetDevice(ctx->device));
     EsRotation R;
-    int rc = es_rotation_create(ctx, d_ref, D, first_ring, last_ring, R);
-    if (rc == XH_OK) rc = es_rotation_run(R, d_others, n, h_rotations);
+    XH_TRY(es_rotation_create(ctx, d_ref, D, first_ring, last_ring, R));
+    XH_TRY(es_rotation_run(R, d_others, n, h_rotations));
     (void)hipStreamSynchronize(ctx->stream);
-    es_rotation_free(R);
-    return rc;
+    return XH_OK;
 }
 
 // BSplineGeoTransformer<T>::interpolate (bspline_geo_transformer.cpp:103-137): image i of d_src through matrix h_matrices[i] (3 x 3, row
@@ -265,16 +260,14 @@ int xh_apply_geometry2d(xh_ctx *ctx, const float *d_src, int32_t n, int32_t ydim
     for (size_t i = 0; i < A.size(); ++i) A[i] = (double)h_matrices[i];
     XhBuf bA;
     XH_TRY(xh_buf_alloc(ctx, bA, sizeof(double) * A.size()));
-    int rc = XH_OK;
-    if (hipMemcpyAsync(bA.p, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK) {
+    bool ok = hipMemcpyAsync(bA.p, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
+    if (ok) {
         const size_t per = (size_t)ydim * xdim;
         hipLaunchKernelGGL(k_es_apply_geometry, dim3((unsigned)((per + 255) / 256), n), dim3(256), 0, ctx->stream, d_src, (const double *)bA.p, d_dst, ydim, xdim);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
-    xh_buf_free(bA);
-    if (rc == XH_ERR_HIP) xh_set_error("xh_apply_geometry2d: device error");
-    return rc;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_apply_geometry2d: device error");
+    return XH_OK;
 }
 
 // CorrelationComputer<T>::compute, MeritType::OneToN, normalizeResult (correlation_computer.cpp:30-56): correlationIndex(ref, other)
@@ -284,14 +277,12 @@ int xh_correlation_merit(xh_ctx *ctx, const float *d_ref, const float *d_others,
     XH_HIP(hipSetDevice(ctx->device));
     XhBuf b;
     XH_TRY(xh_buf_alloc(ctx, b, sizeof(float) * n));
-    int rc = XH_OK;
     hipLaunchKernelGGL(k_es_corr_index, dim3(n), dim3(256), 0, ctx->stream, d_ref, d_others, (size_t)ydim * xdim, (float *)b.p);
-    if (hipGetLastError() != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK && hipMemcpyAsync(h_merit, b.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    xh_buf_free(b);
-    if (rc == XH_ERR_HIP) xh_set_error("xh_correlation_merit: device error");
-    return rc;
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(h_merit, b.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_correlation_merit: device error");
+    return XH_OK;
 }
 
 // IterativeAlignmentEstimator<T>::compute(others, iters) (iterative_alignment_estimator.cpp:96-176) for n square images of D pixels (even)
@@ -303,15 +294,13 @@ int xh_iterative_alignment(xh_ctx *ctx, const float *d_ref, const float *d_other
     XH_HIP(hipSetDevice(ctx->device));
     xh_shiftcorr *sc = nullptr;
     XH_TRY(xh_shiftcorr_create(ctx, D, D, max_shift, &sc));
+    std::unique_ptr<xh_shiftcorr> scOwner(sc);         // destroyed last: its destructor waits for the stream
     EsRotation rotEst;                   // the rotation estimator: the reference's polar transform once for all rounds
-    {
-        const int r0 = es_rotation_create(ctx, d_ref, D, first_ring, last_ring, rotEst);
-        if (r0 != XH_OK) { es_rotation_free(rotEst); xh_shiftcorr_destroy(sc); return r0; }
-    }
+    XH_TRY(es_rotation_create(ctx, d_ref, D, first_ring, last_ring, rotEst));
     const size_t per = (size_t)D * D;
     XhBuf bDest;
-    int rc = xh_buf_alloc(ctx, bDest, sizeof(float) * per * (size_t)n);
-    if (rc == XH_OK) rc = xh_shiftcorr_load_reference(sc, d_ref);
+    XH_TRY(xh_buf_alloc(ctx, bDest, sizeof(float) * per * (size_t)n));
+    XH_TRY(xh_shiftcorr_load_reference(sc, d_ref));
     float *dest = (float *)bDest.p;
     std::vector<float> rot(n), sh(2 * (size_t)n), inv(9 * (size_t)n);
     auto applyTransform = [&](const std::vector<float> &poses) {
@@ -365,20 +354,15 @@ int xh_iterative_alignment(xh_ctx *ctx, const float *d_ref, const float *d_other
     std::vector<float> pRS, mRS, pSR, mSR;
     // test hook (tools/diag_iterative.py): XH_ES_ORDER=RS / SR returns that half of compute() alone
     const char *only = xh_debug_env("XH_ES_ORDER");
-    if (rc == XH_OK) rc = pass(!(only && !strcmp(only, "SR")), pRS, mRS);
+    XH_TRY(pass(!(only && !strcmp(only, "SR")), pRS, mRS));
     if (only) { pSR = pRS; mSR = mRS; }
-    else if (rc == XH_OK) rc = pass(false, pSR, mSR);
-    if (rc == XH_OK)
-        for (int j = 0; j < n; ++j) {
-            const bool sr = mRS[j] < mSR[j];
-            h_merit[j] = sr ? mSR[j] : mRS[j];
-            std::memcpy(h_poses + 9 * (size_t)j, (sr ? pSR : pRS).data() + 9 * (size_t)j, 9 * sizeof(float));
-        }
-    xh_buf_free(bDest);
-    xh_shiftcorr_destroy(sc);
-    (void)hipStreamSynchronize(ctx->stream);
-    es_rotation_free(rotEst);
-    return rc;
+    else XH_TRY(pass(false, pSR, mSR));
+    for (int j = 0; j < n; ++j) {
+        const bool sr = mRS[j] < mSR[j];
+        h_merit[j] = sr ? mSR[j] : mRS[j];
+        std::memcpy(h_poses + 9 * (size_t)j, (sr ? pSR : pRS).data() + 9 * (size_t)j, 9 * sizeof(float));
+    }
+    return XH_OK;
 }
 
 }  // extern "C"

@@ -424,14 +424,6 @@ int axis_create(xh_ctx *ctx, int n, Axis &A)
     return XH_OK;
 }
 
-void axis_free(Axis &A)
-{
-    xh_plan_free(A.p1);
-    xh_plan_free(A.p2);
-    xh_buf_free(A.tw);
-    xh_buf_free(A.tw1);
-}
-
 int lines(xh_ctx *ctx, xh_cf *data, const XhPlan<float> &plan, size_t nlines, size_t inner, size_t outerStride, size_t innerStride,
           size_t elemStride, bool inverse)
 {
@@ -502,6 +494,11 @@ struct xh_fft2d {
     XhBuf keptW;         // xh_fft2d_rows_of_real_pairs_kept: exp(-2 pi i m k2 / 128) of the kept k2, [128][32]
     int keptPL = 0;
     XhBuf user;          // scratch of the callers that transform frame after frame with one plan (xh_fft2d_user_scratch): grow-only
+    ~xh_fft2d()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
 };
 
 // internal (xh_common.h): a device buffer of at least `bytes` that lives with the plan
@@ -585,23 +582,18 @@ int xh_fft2d_create(xh_ctx *ctx, int32_t ny, int32_t nx, xh_fft2d **out)
 {
     XH_CHECK(ctx && out && ny >= 1 && nx >= 1, XH_ERR_ARG, "xh_fft2d_create: bad argument");
     XH_HIP(hipSetDevice(ctx->device));
-    xh_fft2d *f = new xh_fft2d;
+    std::unique_ptr<xh_fft2d> f(new xh_fft2d);
     f->ctx = ctx; f->ny = ny; f->nx = nx;
-    int rc = axis_create(ctx, nx, f->ax);
-    if (rc == XH_OK) rc = axis_create(ctx, ny, f->ay);
-    if (rc == XH_OK && (f->ax.n2 > 1 || f->ay.n2 > 1)) rc = xh_buf_alloc(ctx, f->tmp, sizeof(xh_cf) * (size_t)ny * nx);
-    if (rc != XH_OK) { axis_free(f->ax); axis_free(f->ay); xh_buf_free(f->tmp); delete f; return rc; }
-    *out = f;
+    XH_TRY(axis_create(ctx, nx, f->ax));
+    XH_TRY(axis_create(ctx, ny, f->ay));
+    if (f->ax.n2 > 1 || f->ay.n2 > 1) XH_TRY(xh_buf_alloc(ctx, f->tmp, sizeof(xh_cf) * (size_t)ny * nx));
+    *out = f.release();
     return XH_OK;
 }
 
 int xh_fft2d_destroy(xh_fft2d *f)
 {
-    if (!f) return XH_OK;
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipStreamSynchronize(f->ctx->stream);
-    axis_free(f->ax); axis_free(f->ay); xh_buf_free(f->tmp);
-    xh_buf_free(f->user); xh_buf_free(f->keptW); delete f;
+    delete f;
     return XH_OK;
 }
 

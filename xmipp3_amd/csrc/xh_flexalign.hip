@@ -1469,13 +1469,6 @@ std::vector<float> fa_make_lpf(double Tsp, float maxRes, int nX, int nY, double 
         }
     return lpf;
 }
-int fa_upload(const void *src, XhBuf &b, size_t bytes, xh_ctx *ctx)
-{
-    XH_TRY(xh_buf_alloc(ctx, b, bytes));
-    XH_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    XH_HIP(hipStreamSynchronize(ctx->stream));          // the source is a host temporary
-    return XH_OK;
-}
 }  // namespace
 
 struct xh_fa {
@@ -1483,7 +1476,7 @@ struct xh_fa {
     int Y, X, nY, nX;
     float Ts, maxRes;
     double sizeFactor;
-    xh_fft2d *rows, *cols, *small;        // rows: (Y+1)/2 packed rows of X points; cols: the nc kept columns of Y points; small: a pair map
+    xh_fft2d *rows = nullptr, *cols = nullptr, *small = nullptr;        // rows: (Y+1)/2 packed rows of X points; cols: the nc kept columns of Y points; small: a pair map
     int nc;                               // columns of the frame transform the reduced frame keeps (nX/2 + 1)
     int lastFull = 0;                     // pairs of the last global alignment that went through the full transform
     int use_mfma = 1;                     // the pruned-DFT products of the local alignment on the matrix cores (0: the vector-ALU kernel)
@@ -1506,6 +1499,14 @@ struct xh_fa {
     int prefilter_ahead = 0;
     const float *aheadBase = nullptr, *aheadDark = nullptr, *aheadGain = nullptr;
     int aheadN = 0;
+    ~xh_fa()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        xh_fft2d_destroy(rows);
+        xh_fft2d_destroy(cols);
+        xh_fft2d_destroy(small);
+    }
 };
 
 // rows per thread of k_fa_pairwin_a2 for a window of wy rows: the group size in {12, 16, 20} that pads wy least, the larger on a tie
@@ -1534,14 +1535,6 @@ extern "C" {
 
 int xh_fa_destroy(xh_fa *h)
 {
-    if (!h) return XH_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->rows) xh_fft2d_destroy(h->rows);
-    if (h->cols) xh_fft2d_destroy(h->cols);
-    if (h->small) xh_fft2d_destroy(h->small);
-    xh_buf_free(h->work); xh_buf_free(h->spectra); xh_buf_free(h->lpf); xh_buf_free(h->pair); xh_buf_free(h->part); xh_buf_free(h->res); xh_buf_free(h->warpC);
-    for (auto &kv : h->cache) xh_buf_free(kv.second);
     delete h;
     return XH_OK;
 }
@@ -1556,30 +1549,25 @@ int xh_fa_create(xh_ctx *ctx, int32_t Y, int32_t X, float sampling_rate, float m
     const float scale = sampling_rate / tsPrime;
     XH_CHECK(scale < 1, XH_ERR_ARG, "xh_fa_create: the correlation scale factor is bigger than one; for this sampling rate use a maximal resolution of %g or higher "
              "(checkSettings, movie_alignment_correlation_base.cpp:74-79)", (double)(sampling_rate * 8 * c));
-    xh_fa *h = new xh_fa;
+    std::unique_ptr<xh_fa> h(new xh_fa);
     h->ctx = ctx; h->Y = Y; h->X = X; h->Ts = sampling_rate; h->maxRes = max_res_for_correlation;
     h->sizeFactor = scale;
     h->nX = (int)(X * h->sizeFactor); h->nY = (int)(Y * h->sizeFactor);       // loadData, movie_alignment_correlation.cpp:101-102
-    h->rows = h->cols = h->small = nullptr;
     h->capFrames = 0;
     h->nc = h->nX / 2 + 1;
-    int rc = (h->nX >= 4 && h->nY >= 4) ? XH_OK : XH_ERR_ARG;
-    if (rc != XH_OK) xh_set_error("xh_fa_create: reduced frames of %d x %d pixels", h->nY, h->nX);
-    if (rc == XH_OK) rc = xh_fft2d_create(ctx, (Y + 1) / 2, X, &h->rows);
-    if (rc == XH_OK) rc = xh_fft2d_create(ctx, Y, h->nc, &h->cols);
-    if (rc == XH_OK) rc = xh_fft2d_create(ctx, h->nY, h->nX, &h->small);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->work, sizeof(fa_cf) * (size_t)Y * X);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->pair, sizeof(fa_cf) * (size_t)h->nY * h->nX);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->part, sizeof(double) * 2 * 256);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->res, sizeof(double) * 4);
-    if (rc == XH_OK) {
-        const double Tsp = (double)(sampling_rate / (float)h->sizeFactor);       // getPixelResolution (float)
-        const std::vector<float> lpf = fa_make_lpf(Tsp, max_res_for_correlation, h->nX, h->nY, 1.0);
-        rc = xh_buf_alloc(ctx, h->lpf, sizeof(float) * lpf.size());
-        if (rc == XH_OK && hipMemcpy(h->lpf.p, lpf.data(), sizeof(float) * lpf.size(), hipMemcpyHostToDevice) != hipSuccess) rc = XH_ERR_HIP;
-    }
-    if (rc != XH_OK) { xh_fa_destroy(h); return rc; }
-    *out = h;
+    XH_CHECK(h->nX >= 4 && h->nY >= 4, XH_ERR_ARG, "xh_fa_create: reduced frames of %d x %d pixels", h->nY, h->nX);
+    XH_TRY(xh_fft2d_create(ctx, (Y + 1) / 2, X, &h->rows));
+    XH_TRY(xh_fft2d_create(ctx, Y, h->nc, &h->cols));
+    XH_TRY(xh_fft2d_create(ctx, h->nY, h->nX, &h->small));
+    XH_TRY(xh_buf_alloc(ctx, h->work, sizeof(fa_cf) * (size_t)Y * X));
+    XH_TRY(xh_buf_alloc(ctx, h->pair, sizeof(fa_cf) * (size_t)h->nY * h->nX));
+    XH_TRY(xh_buf_alloc(ctx, h->part, sizeof(double) * 2 * 256));
+    XH_TRY(xh_buf_alloc(ctx, h->res, sizeof(double) * 4));
+    const double Tsp = (double)(sampling_rate / (float)h->sizeFactor);       // getPixelResolution (float)
+    const std::vector<float> lpf = fa_make_lpf(Tsp, max_res_for_correlation, h->nX, h->nY, 1.0);
+    XH_TRY(xh_buf_alloc(ctx, h->lpf, sizeof(float) * lpf.size()));
+    if (hipMemcpy(h->lpf.p, lpf.data(), sizeof(float) * lpf.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+    *out = h.release();
     return XH_OK;
 }
 
@@ -1805,7 +1793,7 @@ int xh_fa_global_alignment(xh_fa *h, const float *d_frames, int32_t N, const flo
                     const long long m = (((long long)kx * (xx - hx)) % nX + nX) % nX;
                     twX[(size_t)kx * wx + xx] = fa_cf{(float)std::cos(twoPi * m / nX), (float)std::sin(twoPi * m / nX)};
                 }
-            rc = fa_table(h, "g_twY", twY.data(), sizeof(fa_cf) * twY.size(), &pTwY);
+            XH_TRY(fa_table(h, "g_twY", twY.data(), sizeof(fa_cf) * twY.size(), &pTwY));
             {
                 // the same factors in rows of wyp = whole groups of rwSel(wy) entries, zeros beyond wy (k_fa_pairwin_a2)
                 const int rw = fa_rw_sel(wy), wyp = (wy + rw - 1) / rw * rw;
@@ -1813,24 +1801,22 @@ int xh_fa_global_alignment(xh_fa *h, const float *d_frames, int32_t N, const flo
                 for (int ky = 0; ky < nY; ++ky)
                     for (int yy = 0; yy < wy; ++yy) twYp[(size_t)ky * wyp + yy] = twY[(size_t)ky * wy + yy];
                 XhBuf *pP = nullptr;
-                if (rc == XH_OK) rc = fa_table(h, "g_twYp", twYp.data(), sizeof(fa_cf) * twYp.size(), &pP);
+                XH_TRY(fa_table(h, "g_twYp", twYp.data(), sizeof(fa_cf) * twYp.size(), &pP));
             }
-            if (rc == XH_OK) rc = fa_table(h, "g_twX", twX.data(), sizeof(fa_cf) * twX.size(), &pTwX);
-            if (rc == XH_OK) h->gKey = key;
+            XH_TRY(fa_table(h, "g_twX", twX.data(), sizeof(fa_cf) * twX.size(), &pTwX));
+            h->gKey = key;
         }
-        if (rc == XH_OK) rc = fa_scratch(h, "g_twY", 0, &pTwY);
-        if (rc == XH_OK) rc = fa_scratch(h, "g_twX", 0, &pTwX);
-        if (rc == XH_OK) rc = fa_scratch(h, "g_U", sizeof(fa_cf) * (size_t)rows * wy * nxh, &pU);
-        if (rc == XH_OK) rc = fa_scratch(h, "g_W", sizeof(float) * (size_t)rows * wy * wx, &pW);
-        if (rc == XH_OK) rc = fa_scratch(h, "g_stat", sizeof(double) * 2 * (size_t)rows, &pStat);
-        if (rc == XH_OK) rc = fa_scratch(h, "g_out", sizeof(double) * 4 * (size_t)rows, &pOut);
-        auto freeWin = [&]() {};
-        if (rc != XH_OK) return rc;
+        XhBuf *pTwYp = nullptr;
+        XH_TRY(fa_scratch(h, "g_twY", 0, &pTwY));
+        XH_TRY(fa_scratch(h, "g_twYp", 0, &pTwYp));
+        XH_TRY(fa_scratch(h, "g_twX", 0, &pTwX));
+        XH_TRY(fa_scratch(h, "g_U", sizeof(fa_cf) * (size_t)rows * wy * nxh, &pU));
+        XH_TRY(fa_scratch(h, "g_W", sizeof(float) * (size_t)rows * wy * wx, &pW));
+        XH_TRY(fa_scratch(h, "g_stat", sizeof(double) * 2 * (size_t)rows, &pStat));
+        XH_TRY(fa_scratch(h, "g_out", sizeof(double) * 4 * (size_t)rows, &pOut));
         XhBuf &bTwY = *pTwY, &bTwX = *pTwX, &bU = *pU, &bW = *pW, &bStat = *pStat, &bOut = *pOut;
         if (hipMemsetAsync(bStat.p, 0, sizeof(double) * 2 * (size_t)rows, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
         std::vector<double> out4(4 * (size_t)rows);
-        XhBuf *pTwYp = nullptr;
-        if (rc == XH_OK) rc = fa_scratch(h, "g_twYp", 0, &pTwYp);
         if (rc == XH_OK) {
             const int rw = fa_rw_sel(wy), nz = (wy + rw - 1) / rw, wyp = nz * rw;
             if (h->pairwin_form == 0) {
@@ -1855,7 +1841,6 @@ int xh_fa_global_alignment(xh_fa *h, const float *d_frames, int32_t N, const flo
         }
         if (rc == XH_OK && hipMemcpyAsync(out4.data(), bOut.p, sizeof(double) * out4.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
         if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-        freeWin();
         // pairs whose maximum is so wide that the square grown around it leaves the window: through the full transform
         std::vector<int> redo;
         int idx = 0;
@@ -2003,7 +1988,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     const size_t E = (size_t)CY * cxh;
     XhBuf *pOffs = nullptr, *pWx = nullptr, *pWy = nullptr, *pTabY = nullptr, *pTabX = nullptr, *pFilter = nullptr, *pPatch = nullptr, *pT = nullptr, *pSingle = nullptr, *pS = nullptr,
           *pU = nullptr, *pW = nullptr, *pRes = nullptr;
-    int rc = XH_OK;
     char key[160];
     snprintf(key, sizeof(key), "%d %d %d %d %d %d %d %d %.9g %.9g", PX, PY, CX, CY, y0, wy, x0, wx, (double)(h->Ts / actualScale), (double)h->maxRes);
     if (h->lKey != key) {
@@ -2021,46 +2005,45 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
             for (int yy = 0; yy < wy; ++yy) { const double a = twoPi * (double)(((long long)ky * (y0 + yy)) % CY) / CY; tabY[(size_t)ky * wy + yy] = fa_cf{(float)std::cos(a), (float)std::sin(a)}; }
         for (int kx = 0; kx < cxh; ++kx)
             for (int xx = 0; xx < wx; ++xx) { const double a = twoPi * (double)(((long long)kx * (x0 + xx)) % CX) / CX; tabX[(size_t)kx * wx + xx] = fa_cf{(float)std::cos(a), (float)std::sin(a)}; }
-        rc = fa_table(h, "l_Wx", Wx.data(), sizeof(fa_cf) * Wx.size(), &pWx);
-        if (rc == XH_OK && wy <= 32) {
+        XH_TRY(fa_table(h, "l_Wx", Wx.data(), sizeof(fa_cf) * Wx.size(), &pWx));
+        if (wy <= 32) {
             // the window's row factors in groups of rwp = wy rounded up to a multiple of four entries per ky, zeros beyond wy (k_fa_patch_corr2)
             const int rwp = (wy + 3) / 4 * 4;
             std::vector<fa_cf> tabYp((size_t)CY * rwp, fa_cf{0.f, 0.f});
             for (int ky = 0; ky < CY; ++ky)
                 for (int yy = 0; yy < wy; ++yy) tabYp[(size_t)ky * rwp + yy] = tabY[(size_t)ky * wy + yy];
             XhBuf *pP = nullptr;
-            rc = fa_table(h, "l_tabYp", tabYp.data(), sizeof(fa_cf) * tabYp.size(), &pP);
+            XH_TRY(fa_table(h, "l_tabYp", tabYp.data(), sizeof(fa_cf) * tabYp.size(), &pP));
         }
-        if (rc == XH_OK) rc = fa_table(h, "l_Wy", Wy.data(), sizeof(fa_cf) * Wy.size(), &pWy);
-        if (rc == XH_OK) rc = fa_table(h, "l_tabY", tabY.data(), sizeof(fa_cf) * tabY.size(), &pTabY);
-        if (rc == XH_OK) rc = fa_table(h, "l_tabX", tabX.data(), sizeof(fa_cf) * tabX.size(), &pTabX);
-        if (rc == XH_OK) rc = fa_table(h, "l_filter", filter.data(), sizeof(float) * filter.size(), &pFilter);
-        if (rc == XH_OK) h->lKey = key;
+        XH_TRY(fa_table(h, "l_Wy", Wy.data(), sizeof(fa_cf) * Wy.size(), &pWy));
+        XH_TRY(fa_table(h, "l_tabY", tabY.data(), sizeof(fa_cf) * tabY.size(), &pTabY));
+        XH_TRY(fa_table(h, "l_tabX", tabX.data(), sizeof(fa_cf) * tabX.size(), &pTabX));
+        XH_TRY(fa_table(h, "l_filter", filter.data(), sizeof(float) * filter.size(), &pFilter));
+        h->lKey = key;
     }
     const double tB = now();
-    if (rc == XH_OK) rc = fa_scratch(h, "l_Wx", 0, &pWx);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_Wy", 0, &pWy);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_tabY", 0, &pTabY);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_tabX", 0, &pTabX);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_filter", 0, &pFilter);
-    if (rc == XH_OK) rc = fa_table(h, "l_offs", offs.data(), sizeof(int) * offs.size(), &pOffs);          // the patch corners move with the global shifts
+    XH_TRY(fa_scratch(h, "l_Wx", 0, &pWx));
+    XH_TRY(fa_scratch(h, "l_Wy", 0, &pWy));
+    XH_TRY(fa_scratch(h, "l_tabY", 0, &pTabY));
+    XH_TRY(fa_scratch(h, "l_tabX", 0, &pTabX));
+    XH_TRY(fa_scratch(h, "l_filter", 0, &pFilter));
+    XH_TRY(fa_table(h, "l_offs", offs.data(), sizeof(int) * offs.size(), &pOffs));          // the patch corners move with the global shifts
     // PB patches at a time: the pair kernel has one wave per frame pair, the second product one workgroup per patch frame -- a single patch (780
     // waves, 40 workgroups for 40 frames) leaves most of the device idle; 36 (three launches for the 108 patches of a K3 movie) against
     // 16: local alignment 18.5 -> 17.5 ms per movie
     static const int pbEnv = xh_debug_env("XH_FA_PB") ? atoi(xh_debug_env("XH_FA_PB")) : 0;        // A/B runs
     const int PB = std::min(nP, pbEnv > 0 ? pbEnv : 36);
     static const bool copyPatchesEnv = xh_debug_env("XH_FA_COPY_PATCHES") != nullptr;
-    if (rc == XH_OK) rc = fa_scratch(h, "l_patch", (h->use_mfma && !copyPatchesEnv) ? 16 : sizeof(float) * (size_t)PB * N * PY * PX, &pPatch);      // the fused product reads the frames
-    if (rc == XH_OK) rc = fa_scratch(h, "l_T", sizeof(fa_cf) * (size_t)PB * N * PY * cxh, &pT);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_single", sizeof(fa_cf) * (size_t)PB * N * E, &pSingle);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_S", sizeof(fa_cf) * (size_t)PB * N * E, &pS);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_U", sizeof(fa_cf) * (size_t)PB * rows * wy * cxh, &pU);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_W", sizeof(float) * (size_t)PB * rows * wy * wx, &pW);
-    if (rc == XH_OK) rc = fa_scratch(h, "l_res", sizeof(double) * 2 * (size_t)rows * nP, &pRes);
-    if (rc != XH_OK) return rc;
+    XH_TRY(fa_scratch(h, "l_patch", (h->use_mfma && !copyPatchesEnv) ? 16 : sizeof(float) * (size_t)PB * N * PY * PX, &pPatch));      // the fused product reads the frames
+    XH_TRY(fa_scratch(h, "l_T", sizeof(fa_cf) * (size_t)PB * N * PY * cxh, &pT));
+    XH_TRY(fa_scratch(h, "l_single", sizeof(fa_cf) * (size_t)PB * N * E, &pSingle));
+    XH_TRY(fa_scratch(h, "l_S", sizeof(fa_cf) * (size_t)PB * N * E, &pS));
+    XH_TRY(fa_scratch(h, "l_U", sizeof(fa_cf) * (size_t)PB * rows * wy * cxh, &pU));
+    XH_TRY(fa_scratch(h, "l_W", sizeof(float) * (size_t)PB * rows * wy * wx, &pW));
+    XH_TRY(fa_scratch(h, "l_res", sizeof(double) * 2 * (size_t)rows * nP, &pRes));
     XhBuf &bOffs = *pOffs, &bWx = *pWx, &bWy = *pWy, &bTabY = *pTabY, &bTabX = *pTabX, &bFilter = *pFilter, &bPatch = *pPatch, &bT = *pT, &bSingle = *pSingle, &bS = *pS, &bU = *pU,
           &bW = *pW, &bRes = *pRes;
-    auto freeAll = [&]() {};
+    int rc = XH_OK;
     const double tC = now();
     for (int p0 = 0; p0 < nP && rc == XH_OK; p0 += PB) {
         const int pb = std::min(PB, nP - p0), nf = pb * N;
@@ -2121,7 +2104,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     if (rc == XH_OK && hipMemcpyAsync(res.data(), bRes.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
     if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
     const double tD = now();
-    freeAll();
     h->aheadBase = nullptr;
     if (rc == XH_OK && h->prefilter_ahead) {
         // the warp's prefilter of every frame, behind the results' copy: runs while the host solves below
@@ -2193,31 +2175,27 @@ int xh_fa_correlate(xh_ctx *ctx, const float *d_frames, int32_t N, int32_t Y, in
     for (int kx = 0; kx < xh; ++kx)
         for (int xx = 0; xx < wx; ++xx) { const double a = twoPi * (double)(((long long)kx * (x0 + xx)) % X) / X; tabX[(size_t)kx * wx + xx] = fa_cf{(float)std::cos(a), (float)std::sin(a)}; }
     XhBuf bWx, bWy, bTabY, bTabX, bT, bS, bU, bW, bRes;
-    auto freeAll = [&]() { XhBuf *all[] = {&bWx, &bWy, &bTabY, &bTabX, &bT, &bS, &bU, &bW, &bRes}; for (XhBuf *q : all) xh_buf_free(*q); };
     const size_t E = (size_t)Y * xh;
-    int rc = fa_upload(Wx.data(), bWx, sizeof(fa_cf) * Wx.size(), ctx);
-    if (rc == XH_OK) rc = fa_upload(Wy.data(), bWy, sizeof(fa_cf) * Wy.size(), ctx);
-    if (rc == XH_OK) rc = fa_upload(tabY.data(), bTabY, sizeof(fa_cf) * tabY.size(), ctx);
-    if (rc == XH_OK) rc = fa_upload(tabX.data(), bTabX, sizeof(fa_cf) * tabX.size(), ctx);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bT, sizeof(fa_cf) * (size_t)N * E);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bS, sizeof(fa_cf) * (size_t)N * E);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bU, sizeof(fa_cf) * (size_t)rows * wy * xh);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bW, sizeof(float) * (size_t)rows * wy * wx);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, bRes, sizeof(double) * 2 * (size_t)rows);
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL((k_fa_gemm<false>), dim3((xh + 31) / 32, (unsigned)(((size_t)N * Y + 63) / 64), 1), dim3(256), 0, ctx->stream, d_frames, (size_t)X, (size_t)0,
-                           (const fa_cf *)bWx.p, (size_t)xh, (size_t)0, (fa_cf *)bT.p, (size_t)xh, (size_t)0, N * Y, xh, X);
-        hipLaunchKernelGGL((k_fa_gemm<true>), dim3((xh + 31) / 32, (Y + 63) / 64, N), dim3(256), 0, ctx->stream, (const float *)bWy.p, (size_t)Y, (size_t)0, (const fa_cf *)bT.p,
-                           (size_t)xh, E, (fa_cf *)bS.p, (size_t)xh, E, Y, xh, Y);
-        hipLaunchKernelGGL(k_fa_patch_corr, dim3(rows, 1), dim3(std::min(256, 64 * ((xh + 63) / 64))), 0, ctx->stream, (const fa_cf *)bS.p, N, Y, X, (const fa_cf *)bTabY.p,
-                           (const fa_cf *)bTabX.p, y0, wy, x0, wx, maxDist, (fa_cf *)bU.p, (float *)bW.p, (double *)bRes.p);
-        if (hipGetLastError() != hipSuccess) rc = XH_ERR_HIP;
-    }
-    if (rc == XH_OK && hipMemcpyAsync(h_pos, bRes.p, sizeof(double) * 2 * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    freeAll();
-    if (rc == XH_ERR_HIP) xh_set_error("xh_fa_correlate: device error");
-    return rc;
+    XH_TRY(xh_buf_upload(ctx, bWx, Wx.data(), sizeof(fa_cf) * Wx.size()));
+    XH_TRY(xh_buf_upload(ctx, bWy, Wy.data(), sizeof(fa_cf) * Wy.size()));
+    XH_TRY(xh_buf_upload(ctx, bTabY, tabY.data(), sizeof(fa_cf) * tabY.size()));
+    XH_TRY(xh_buf_upload(ctx, bTabX, tabX.data(), sizeof(fa_cf) * tabX.size()));
+    XH_TRY(xh_buf_alloc(ctx, bT, sizeof(fa_cf) * (size_t)N * E));
+    XH_TRY(xh_buf_alloc(ctx, bS, sizeof(fa_cf) * (size_t)N * E));
+    XH_TRY(xh_buf_alloc(ctx, bU, sizeof(fa_cf) * (size_t)rows * wy * xh));
+    XH_TRY(xh_buf_alloc(ctx, bW, sizeof(float) * (size_t)rows * wy * wx));
+    XH_TRY(xh_buf_alloc(ctx, bRes, sizeof(double) * 2 * (size_t)rows));
+    hipLaunchKernelGGL((k_fa_gemm<false>), dim3((xh + 31) / 32, (unsigned)(((size_t)N * Y + 63) / 64), 1), dim3(256), 0, ctx->stream, d_frames, (size_t)X, (size_t)0,
+                       (const fa_cf *)bWx.p, (size_t)xh, (size_t)0, (fa_cf *)bT.p, (size_t)xh, (size_t)0, N * Y, xh, X);
+    hipLaunchKernelGGL((k_fa_gemm<true>), dim3((xh + 31) / 32, (Y + 63) / 64, N), dim3(256), 0, ctx->stream, (const float *)bWy.p, (size_t)Y, (size_t)0, (const fa_cf *)bT.p,
+                       (size_t)xh, E, (fa_cf *)bS.p, (size_t)xh, E, Y, xh, Y);
+    hipLaunchKernelGGL(k_fa_patch_corr, dim3(rows, 1), dim3(std::min(256, 64 * ((xh + 63) / 64))), 0, ctx->stream, (const fa_cf *)bS.p, N, Y, X, (const fa_cf *)bTabY.p,
+                       (const fa_cf *)bTabX.p, y0, wy, x0, wx, maxDist, (fa_cf *)bU.p, (float *)bW.p, (double *)bRes.p);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(h_pos, bRes.p, sizeof(double) * 2 * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
+    XH_CHECK(ok, XH_ERR_HIP, "xh_fa_correlate: device error");
+    return XH_OK;
 }
 
 // localFromGlobal (movie_alignment_correlation_gpu.cpp:432-456): the B-spline of a movie aligned globally only -- every patch
@@ -2344,16 +2322,12 @@ int xh_movie_dose_filter(xh_ctx *ctx, xh_fft2d *plan, float *d_frame, int32_t Y,
     fa_cf *F = (fa_cf *)wp;
     const unsigned grid = (unsigned)((tot + 255) / 256);
     hipLaunchKernelGGL(k_fa_load, dim3(grid), dim3(256), 0, ctx->stream, (const float *)d_frame, (const float *)nullptr, (const float *)nullptr, F, tot);
-    int rc = xh_fft2d_exec(plan, (float *)F, 0);
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL(k_dose_apply, dim3(grid), dim3(256), 0, ctx->stream, F, Y, X, pixel_size, vscale, dose_start, dose_finish);
-        rc = xh_fft2d_exec(plan, (float *)F, 1);
-    }
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL(k_dose_store, dim3(grid), dim3(256), 0, ctx->stream, (const fa_cf *)F, d_frame, tot);
-        if (hipGetLastError() != hipSuccess) { xh_set_error("xh_movie_dose_filter: device error"); rc = XH_ERR_HIP; }        // (no synchronisation: stream order)
-    }
-    return rc;
+    XH_TRY(xh_fft2d_exec(plan, (float *)F, 0));
+    hipLaunchKernelGGL(k_dose_apply, dim3(grid), dim3(256), 0, ctx->stream, F, Y, X, pixel_size, vscale, dose_start, dose_finish);
+    XH_TRY(xh_fft2d_exec(plan, (float *)F, 1));
+    hipLaunchKernelGGL(k_dose_store, dim3(grid), dim3(256), 0, ctx->stream, (const fa_cf *)F, d_frame, tot);
+    XH_CHECK(hipGetLastError() == hipSuccess, XH_ERR_HIP, "xh_movie_dose_filter: device error");        // (no synchronisation: stream order)
+    return XH_OK;
 }
 
 }  // extern "C"
@@ -2451,21 +2425,15 @@ int xh_movie_bin_frame(xh_ctx *ctx, xh_fft2d *planRaw, xh_fft2d *planBinned, con
     const size_t tot = (size_t)Y * X, totb = (size_t)Yb * Xb;
     struct { void *p; } wa{nullptr}, wb{nullptr};
     XH_TRY(xh_fft2d_user_scratch(planRaw, sizeof(fa_cf) * tot, &wa.p));
-    int rc = xh_fft2d_user_scratch(planBinned, sizeof(fa_cf) * totb, &wb.p);
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL(k_fa_load, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, d_frame, d_dark, d_gain, (fa_cf *)wa.p, tot);
-        rc = xh_fft2d_exec(planRaw, (float *)wa.p, 0);
-    }
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL(k_bin_crop, dim3((unsigned)((totb + 255) / 256)), dim3(256), 0, ctx->stream, (const fa_cf *)wa.p, (fa_cf *)wb.p, Y, X, Yb, Xb,
-                           ((float)Xb * (float)Yb) / ((float)X * (float)Y));        // 1 / (X Y) of the reference; xh_fft2d's inverse divides by Xb Yb, cuFFT's does not
-        rc = xh_fft2d_exec(planBinned, (float *)wb.p, 1);
-    }
-    if (rc == XH_OK) {
-        hipLaunchKernelGGL(k_dose_store, dim3((unsigned)((totb + 255) / 256)), dim3(256), 0, ctx->stream, (const fa_cf *)wb.p, d_out, totb);
-        if (hipGetLastError() != hipSuccess) { xh_set_error("xh_movie_bin_frame: device error"); rc = XH_ERR_HIP; }
-    }
-    return rc;
+    XH_TRY(xh_fft2d_user_scratch(planBinned, sizeof(fa_cf) * totb, &wb.p));
+    hipLaunchKernelGGL(k_fa_load, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, d_frame, d_dark, d_gain, (fa_cf *)wa.p, tot);
+    XH_TRY(xh_fft2d_exec(planRaw, (float *)wa.p, 0));
+    hipLaunchKernelGGL(k_bin_crop, dim3((unsigned)((totb + 255) / 256)), dim3(256), 0, ctx->stream, (const fa_cf *)wa.p, (fa_cf *)wb.p, Y, X, Yb, Xb,
+                       ((float)Xb * (float)Yb) / ((float)X * (float)Y));        // 1 / (X Y) of the reference; xh_fft2d's inverse divides by Xb Yb, cuFFT's does not
+    XH_TRY(xh_fft2d_exec(planBinned, (float *)wb.p, 1));
+    hipLaunchKernelGGL(k_dose_store, dim3((unsigned)((totb + 255) / 256)), dim3(256), 0, ctx->stream, (const fa_cf *)wb.p, d_out, totb);
+    XH_CHECK(hipGetLastError() == hipSuccess, XH_ERR_HIP, "xh_movie_bin_frame: device error");
+    return XH_OK;
 }
 
 }  // extern "C"

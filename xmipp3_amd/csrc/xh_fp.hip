@@ -180,6 +180,11 @@ struct xh_fp {
     XhBuf d_re, d_im;            // cropped B-spline coefficient cubes [cdim]^3 double
     XhBuf d_pf, d_eul;           // per-call scratch
     XhPlanBufs<double> planD;
+    ~xh_fp()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
 };
 
 extern "C" {
@@ -192,7 +197,7 @@ int xh_fp_create(xh_ctx *ctx, const float *d_vol, int32_t D, double padding, dou
     const int P = (int)(padding * D);
     XH_CHECK(P <= 1024, XH_ERR_UNSUPPORTED, "xh_fp_create: padded size %d exceeds 1024", P);
     XH_HIP(hipSetDevice(ctx->device));
-    xh_fp *fp = new xh_fp;
+    std::unique_ptr<xh_fp> fp(new xh_fp);
     fp->ctx = ctx; fp->D = D; fp->P = P; fp->maxFreq = max_freq;
     int idxMax = (int)(max_freq * P + 10);                    // L281: +10 is a safety guard
     const int lastP = -(P / 2) + P - 1, firstP = -(P / 2);
@@ -203,66 +208,51 @@ int xh_fp_create(xh_ctx *ctx, const float *d_vol, int32_t D, double padding, dou
     const size_t P3 = (size_t)P * P * P, c3 = (size_t)fp->cdim * fp->cdim * fp->cdim;
     XhBuf F, re, im;
     XhPlanBufs<double> planP;
-    int rc = xh_buf_alloc(ctx, F, sizeof(xh_cd) * P3);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, re, sizeof(double) * P3);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, im, sizeof(double) * P3);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, P, planP);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, D, fp->planD);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, fp->d_re, sizeof(double) * c3);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, fp->d_im, sizeof(double) * c3);
-    hipError_t e = hipSuccess;
-    if (rc == XH_OK) {
-        const unsigned gb = (unsigned)((P3 + 255) / 256);
-        hipLaunchKernelGGL(k_fp_pad, dim3(gb), dim3(256), 0, ctx->stream, d_vol, (xh_cd *)F.p, D, P, -(D / 2) + P / 2);
-        const int lpb = xh_plan_lpb(planP.plan, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << planP.plan.logM;
-        const size_t nlines = (size_t)P * P;
-        const unsigned gl = (unsigned)((nlines + lpb - 1) / lpb);
-        // x lines: (k,i) -> offset (k*P+i)*P, element stride 1
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
-                           (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
-        // y lines: (k,j) -> offset k*P*P + j, element stride P
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
-                           (size_t)P, (size_t)P * P, (size_t)1, (size_t)P, lpb);
-        // z lines: (i,j) -> offset i*P + j, element stride P*P
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
-                           nlines, (size_t)0, (size_t)1, (size_t)P * P, lpb);
-        hipLaunchKernelGGL(k_fp_center_split, dim3(gb), dim3(256), 0, ctx->stream, (const xh_cd *)F.p, (double *)re.p, (double *)im.p, P, D);
-        // produceSplineCoefficients on both volumes: x (LDS row tiles), y (thread per column), z
-        const int TR = std::max(1, std::min(32, (int)(60000 / ((P + 1) * sizeof(double)))));
-        const int tiles = (P + TR - 1) / TR;
-        for (XhBuf *b : {&re, &im}) {
-            hipLaunchKernelGGL((k_pm_prefilter_rows<double, double>), dim3(P * tiles), dim3(64), sizeof(double) * TR * (P + 1), ctx->stream,
-                               (const double *)b->p, (const int *)nullptr, (double *)b->p, P, TR, (const int *)nullptr);
-            hipLaunchKernelGGL((k_pm_prefilter_cols<double>), dim3((P * P + 63) / 64), dim3(64), 0, ctx->stream, (double *)b->p, P, P,
-                               (const int *)nullptr);
-            hipLaunchKernelGGL(k_fp_prefilter_z, dim3((P * P + 63) / 64), dim3(64), 0, ctx->stream, (double *)b->p, P);
-        }
-        const unsigned gc = (unsigned)((c3 + 255) / 256);
-        hipLaunchKernelGGL(k_fp_crop, dim3(gc), dim3(256), 0, ctx->stream, (const double *)re.p, (double *)fp->d_re.p, P, fp->cdim, idxMin - firstP);
-        hipLaunchKernelGGL(k_fp_crop, dim3(gc), dim3(256), 0, ctx->stream, (const double *)im.p, (double *)fp->d_im.p, P, fp->cdim, idxMin - firstP);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    XH_TRY(xh_buf_alloc(ctx, F, sizeof(xh_cd) * P3));
+    XH_TRY(xh_buf_alloc(ctx, re, sizeof(double) * P3));
+    XH_TRY(xh_buf_alloc(ctx, im, sizeof(double) * P3));
+    XH_TRY(xh_plan_create<double>(ctx, P, planP));
+    XH_TRY(xh_plan_create<double>(ctx, D, fp->planD));
+    XH_TRY(xh_buf_alloc(ctx, fp->d_re, sizeof(double) * c3));
+    XH_TRY(xh_buf_alloc(ctx, fp->d_im, sizeof(double) * c3));
+    const unsigned gb = (unsigned)((P3 + 255) / 256);
+    hipLaunchKernelGGL(k_fp_pad, dim3(gb), dim3(256), 0, ctx->stream, d_vol, (xh_cd *)F.p, D, P, -(D / 2) + P / 2);
+    const int lpb = xh_plan_lpb(planP.plan, 64 * 1024, 8);
+    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << planP.plan.logM;
+    const size_t nlines = (size_t)P * P;
+    const unsigned gl = (unsigned)((nlines + lpb - 1) / lpb);
+    // x lines: (k,i) -> offset (k*P+i)*P, element stride 1
+    hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
+                       (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
+    // y lines: (k,j) -> offset k*P*P + j, element stride P
+    hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
+                       (size_t)P, (size_t)P * P, (size_t)1, (size_t)P, lpb);
+    // z lines: (i,j) -> offset i*P + j, element stride P*P
+    hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)F.p, planP.plan, nlines,
+                       nlines, (size_t)0, (size_t)1, (size_t)P * P, lpb);
+    hipLaunchKernelGGL(k_fp_center_split, dim3(gb), dim3(256), 0, ctx->stream, (const xh_cd *)F.p, (double *)re.p, (double *)im.p, P, D);
+    // produceSplineCoefficients on both volumes: x (LDS row tiles), y (thread per column), z
+    const int TR = std::max(1, std::min(32, (int)(60000 / ((P + 1) * sizeof(double)))));
+    const int tiles = (P + TR - 1) / TR;
+    for (XhBuf *b : {&re, &im}) {
+        hipLaunchKernelGGL((k_pm_prefilter_rows<double, double>), dim3(P * tiles), dim3(64), sizeof(double) * TR * (P + 1), ctx->stream,
+                           (const double *)b->p, (const int *)nullptr, (double *)b->p, P, TR, (const int *)nullptr);
+        hipLaunchKernelGGL((k_pm_prefilter_cols<double>), dim3((P * P + 63) / 64), dim3(64), 0, ctx->stream, (double *)b->p, P, P,
+                           (const int *)nullptr);
+        hipLaunchKernelGGL(k_fp_prefilter_z, dim3((P * P + 63) / 64), dim3(64), 0, ctx->stream, (double *)b->p, P);
     }
-    xh_buf_free(F); xh_buf_free(re); xh_buf_free(im);
-    xh_plan_free(planP);
-    if (rc == XH_OK && e != hipSuccess) { xh_set_error("xh_fp_create: %s", hipGetErrorString(e)); rc = XH_ERR_HIP; }
-    if (rc != XH_OK) {
-        xh_buf_free(fp->d_re); xh_buf_free(fp->d_im); xh_plan_free(fp->planD);
-        delete fp;
-        return rc;
-    }
-    *out = fp;
+    const unsigned gc = (unsigned)((c3 + 255) / 256);
+    hipLaunchKernelGGL(k_fp_crop, dim3(gc), dim3(256), 0, ctx->stream, (const double *)re.p, (double *)fp->d_re.p, P, fp->cdim, idxMin - firstP);
+    hipLaunchKernelGGL(k_fp_crop, dim3(gc), dim3(256), 0, ctx->stream, (const double *)im.p, (double *)fp->d_im.p, P, fp->cdim, idxMin - firstP);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_fp_create: %s", hipGetErrorString(e));
+    *out = fp.release();
     return XH_OK;
 }
 
 int xh_fp_destroy(xh_fp *fp)
 {
-    if (!fp) return XH_OK;
-    (void)hipSetDevice(fp->ctx->device);
-    (void)hipStreamSynchronize(fp->ctx->stream);
-    xh_buf_free(fp->d_re); xh_buf_free(fp->d_im); xh_buf_free(fp->d_pf); xh_buf_free(fp->d_eul);
-    xh_plan_free(fp->planD);
     delete fp;
     return XH_OK;
 }

@@ -91,30 +91,25 @@ extern "C" int xh_frc_dpr(xh_ctx *ctx, const double *d_m1, const double *d_m2, i
     const size_t total = (size_t)Z * Y * xh;
     XhPlanBufs<double> px, py, pz;
     XhBuf F1, F2, sums;
-    int rc = xh_plan_create<double>(ctx, X, px);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, Y, py);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, Z, pz);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, F1, sizeof(xh_cd) * total);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, F2, sizeof(xh_cd) * total);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, sums, sizeof(double) * nt);
+    XH_TRY(xh_plan_create<double>(ctx, X, px));
+    XH_TRY(xh_plan_create<double>(ctx, Y, py));
+    XH_TRY(xh_plan_create<double>(ctx, Z, pz));
+    XH_TRY(xh_buf_alloc(ctx, F1, sizeof(xh_cd) * total));
+    XH_TRY(xh_buf_alloc(ctx, F2, sizeof(xh_cd) * total));
+    XH_TRY(xh_buf_alloc(ctx, sums, sizeof(double) * nt));
     std::vector<double> h((size_t)nt, 0.0);
-    if (rc == XH_OK) rc = fft3d_r2c(ctx, d_m1, (xh_cd *)F1.p, Z, Y, X, px.plan, py.plan, pz.plan);
-    if (rc == XH_OK) rc = fft3d_r2c(ctx, d_m2, (xh_cd *)F2.p, Z, Y, X, px.plan, py.plan, pz.plan);
-    if (rc == XH_OK) {
-        hipError_t e = hipMemsetAsync(sums.p, 0, sums.bytes, ctx->stream);
-        if (e == hipSuccess) {
-            const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->num_cus * 8);
-            hipLaunchKernelGGL(k_fsc_shells, dim3(grid), dim3(256), sizeof(double) * nt, ctx->stream, (const xh_cd *)F1.p, (const xh_cd *)F2.p,
-                               Z, Y, X, xh, L, 1.0 / ((double)Z * Y * X), do_dpr, do_rfactor, minFreq, maxFreq, (double *)sums.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), sums.p, sums.bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { xh_set_error("xh_frc_dpr: %s", hipGetErrorString(e)); rc = XH_ERR_HIP; }
+    XH_TRY(fft3d_r2c(ctx, d_m1, (xh_cd *)F1.p, Z, Y, X, px.plan, py.plan, pz.plan));
+    XH_TRY(fft3d_r2c(ctx, d_m2, (xh_cd *)F2.p, Z, Y, X, px.plan, py.plan, pz.plan));
+    hipError_t e = hipMemsetAsync(sums.p, 0, sums.bytes, ctx->stream);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->num_cus * 8);
+        hipLaunchKernelGGL(k_fsc_shells, dim3(grid), dim3(256), sizeof(double) * nt, ctx->stream, (const xh_cd *)F1.p, (const xh_cd *)F2.p,
+                           Z, Y, X, xh, L, 1.0 / ((double)Z * Y * X), do_dpr, do_rfactor, minFreq, maxFreq, (double *)sums.p);
+        e = hipGetLastError();
     }
-    xh_buf_free(F1); xh_buf_free(F2); xh_buf_free(sums);
-    xh_plan_free(px); xh_plan_free(py); xh_plan_free(pz);
-    if (rc != XH_OK) return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), sums.p, sums.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_frc_dpr: %s", hipGetErrorString(e));
     for (int i = 0; i < L; ++i) {
         const double count = h[(size_t)S_COUNT * L + i];
         h_freq[i] = (double)i / (X * sampling_rate);

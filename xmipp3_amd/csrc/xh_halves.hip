@@ -432,6 +432,11 @@ struct xh_halves {
     double band_ms[3] = {0, 0, 0};
     int bands = 0;
     int costRc = XH_OK;
+    ~xh_halves()
+    {
+        if (ctx) (void)hipSetDevice(ctx->device);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace {
@@ -522,47 +527,34 @@ int xh_halves_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_halves **o
     XH_CHECK(Z >= 1 && Y >= 1 && X >= 2, XH_ERR_ARG, "xh_halves_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_halves_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
     XH_HIP(hipSetDevice(ctx->device));
-    xh_halves *h = new xh_halves;
+    std::unique_ptr<xh_halves> h(new xh_halves);
     h->ctx = ctx; h->Z = Z; h->Y = Y; h->X = X; h->xh = X / 2 + 1;
     h->N = (size_t)Z * Y * X;
     h->NF = (size_t)Z * Y * h->xh;
     h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->NF + 255) / 256, (size_t)ctx->num_cus * 4));
     h->gridPass = (unsigned)std::max<size_t>(1, std::min<size_t>((h->N + 255) / 256, (size_t)ctx->num_cus * 2));
     const size_t vb = sizeof(double) * h->N, fb = sizeof(xh_cd) * h->NF;
-    int rc = xh_plan_create<double>(ctx, X, h->px);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, Y, h->py);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, Z, h->pz);
-    XhBuf *vols[] = {&h->V1, &h->V2, &h->S, &h->B2, &h->B3, &h->keys, &h->out[0], &h->out[1], &h->out[2], &h->out[3]};
-    for (XhBuf *b : vols) if (rc == XH_OK) rc = xh_buf_alloc(ctx, *b, vb);
-    XhBuf *specs[] = {&h->C1, &h->C2, &h->C3};
-    for (XhBuf *b : specs) if (rc == XH_OK) rc = xh_buf_alloc(ctx, *b, fb);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->cdf, sizeof(CdfDev));
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->partials, sizeof(double) * 2 * h->grid);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->result, sizeof(double) * 2);
-    if (rc == XH_OK) {
-        std::vector<double> prob;
-        for (double p = 0.005 / 2; p < 1; p += 0.005) prob.push_back(p);     // CDF<double>::_updateProbabilities
-        if (prob.size() != HV_NSTEPS) { xh_set_error("xh_halves_create: %zu CDF steps", prob.size()); rc = XH_ERR_STATE; }
-        hipError_t e = hipSuccess;
-        if (rc == XH_OK) e = hipMemset(h->cdf.p, 0, sizeof(CdfDev));
-        if (rc == XH_OK && e == hipSuccess) e = hipMemcpy((char *)h->cdf.p + offsetof(CdfDev, prob), prob.data(), sizeof(double) * HV_NSTEPS, hipMemcpyHostToDevice);
-        for (int i = 0; i < 4 && rc == XH_OK && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-        if (rc == XH_OK && e != hipSuccess) { xh_set_error("xh_halves_create: %s", hipGetErrorString(e)); rc = XH_ERR_HIP; }
-    }
-    if (rc != XH_OK) { xh_halves_destroy(h); return rc; }
-    *out = h;
+    XH_TRY(xh_plan_create<double>(ctx, X, h->px));
+    XH_TRY(xh_plan_create<double>(ctx, Y, h->py));
+    XH_TRY(xh_plan_create<double>(ctx, Z, h->pz));
+    for (XhBuf *b : {&h->V1, &h->V2, &h->S, &h->B2, &h->B3, &h->keys, &h->out[0], &h->out[1], &h->out[2], &h->out[3]}) XH_TRY(xh_buf_alloc(ctx, *b, vb));
+    for (XhBuf *b : {&h->C1, &h->C2, &h->C3}) XH_TRY(xh_buf_alloc(ctx, *b, fb));
+    XH_TRY(xh_buf_alloc(ctx, h->cdf, sizeof(CdfDev)));
+    XH_TRY(xh_buf_alloc(ctx, h->partials, sizeof(double) * 2 * h->grid));
+    XH_TRY(xh_buf_alloc(ctx, h->result, sizeof(double) * 2));
+    std::vector<double> prob;
+    for (double p = 0.005 / 2; p < 1; p += 0.005) prob.push_back(p);     // CDF<double>::_updateProbabilities
+    XH_CHECK(prob.size() == HV_NSTEPS, XH_ERR_STATE, "xh_halves_create: %zu CDF steps", prob.size());
+    hipError_t e = hipMemset(h->cdf.p, 0, sizeof(CdfDev));
+    if (e == hipSuccess) e = hipMemcpy((char *)h->cdf.p + offsetof(CdfDev, prob), prob.data(), sizeof(double) * HV_NSTEPS, hipMemcpyHostToDevice);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
+    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_halves_create: %s", hipGetErrorString(e));
+    *out = h.release();
     return XH_OK;
 }
 
 int xh_halves_destroy(xh_halves *h)
 {
-    if (!h) return XH_OK;
-    if (h->ctx) (void)hipSetDevice(h->ctx->device);
-    XhBuf *all[] = {&h->V1, &h->V2, &h->S, &h->B2, &h->B3, &h->keys, &h->C1, &h->C2, &h->C3, &h->cdf, &h->partials, &h->result,
-                    &h->out[0], &h->out[1], &h->out[2], &h->out[3]};
-    for (XhBuf *b : all) xh_buf_free(*b);
-    xh_plan_free(h->px); xh_plan_free(h->py); xh_plan_free(h->pz);
-    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
     delete h;
     return XH_OK;
 }

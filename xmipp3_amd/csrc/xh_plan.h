@@ -176,13 +176,6 @@ template <typename T> static int xh_plan_create(xh_ctx *ctx, int n, XhPlanBufs<T
     return XH_OK;
 }
 
-template <typename T> static void xh_plan_free(XhPlanBufs<T> &b)
-{
-    xh_buf_free(b.W);
-    xh_buf_free(b.chirp);
-    xh_buf_free(b.vhat);
-}
-
 // lines per 256-thread workgroup for a plan, within `budget` bytes of LDS
 template <typename T> static int xh_plan_lpb(const XhPlan<T> &p, size_t budget, int maxLines)
 {

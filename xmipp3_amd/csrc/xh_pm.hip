@@ -120,7 +120,7 @@ struct xh_pm {
     XhBuf d_t1, d_t2, d_t3;      // S6 scratch
     int64_t stat_rows, stat_resc_p, stat_resc_r;
     int coefFirst, coefCount;      // particles whose fp32 B-spline coefficients d_coef32 holds (last match call)
-    hipEvent_t ev[6];
+    hipEvent_t ev[6] = {};
     double stage_ms[8];   // prep32, contract, idft_max, select, rescore(fp64), translate
     int store_cut;               // S2 of a bank that is not band limited: frequencies whose coefficients are kept for S3 (0: none, bounds only; -1: all, the dense finish)
     int s6_capture;              // test hook: 32 / 64 = xh_pm_translate runs only that chain and leaves the correlation maps for xh_pm_debug_s6_maps
@@ -151,6 +151,13 @@ struct xh_pm {
     XhBuf d_firTmp, d_polarPart, d_trPart, d_listMask, d_s6Flag, d_s6List, d_s6Parts, d_s6Meta, d_s6Out;
     XhBuf d_qoff, d_Bpack, d_Apack, d_kbounds;
     int totalQuads;
+    ~xh_pm()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 // =========================================================================== S1 kernels
@@ -3380,21 +3387,7 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
 
 template <typename T> static int upload(xh_ctx *ctx, XhBuf &b, const std::vector<T> &v)
 {
-    XH_TRY(xh_buf_alloc(ctx, b, sizeof(T) * v.size()));
-    XH_HIP(hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
-    return XH_OK;
-}
-
-static void free_all(xh_pm *pm)
-{
-    XhBuf *bufs[] = {&pm->d_sin, &pm->d_cos, &pm->d_ringOfSample, &pm->d_nsam, &pm->d_soff, &pm->d_coff, &pm->d_rstart, &pm->d_ringW,
-                     &pm->d_tw32, &pm->d_tw64, &pm->d_refs64, &pm->d_refsB, &pm->d_refSigma, &pm->d_refCoef, &pm->d_refCoef32, &pm->d_W32, &pm->d_Wfull, &pm->d_vperm, &pm->d_qoff, &pm->d_Bpack, &pm->d_Apack, &pm->d_kbounds,
-                     &pm->d_chirp, &pm->d_vhat, &pm->d_csN, &pm->d_WD64, &pm->d_coef32, &pm->d_polar32, &pm->d_A32,
-                     &pm->d_stat32, &pm->d_coef64, &pm->d_polar64, &pm->d_A64, &pm->d_stat64, &pm->d_raw, &pm->d_rowres,
-                     &pm->d_desc, &pm->d_nbr, &pm->d_poff, &pm->d_ambList, &pm->d_ambSlot, &pm->d_candRow, &pm->d_candRes,
-                     &pm->d_counters, &pm->d_offs5d, &pm->d_bpart, &pm->d_rowBound, &pm->d_rowTail, &pm->d_topRows, &pm->d_survList, &pm->d_survSpan, &pm->d_highStore, &pm->d_thr, &pm->d_bT, &pm->d_bTband, &pm->d_aT, &pm->d_kboundsLow, &pm->d_firTmp, &pm->d_firTmp64, &pm->d_polarPart, &pm->d_t1, &pm->d_t2, &pm->d_t3, &pm->d_trAngles, &pm->d_trPart, &pm->d_listMask, &pm->d_s6Flag, &pm->d_s6List, &pm->d_s6Parts, &pm->d_s6Meta, &pm->d_s6Out, &pm->d_cellStart, &pm->d_cellSamples, &pm->d_cellOrg, &pm->d_cellData, &pm->d_thrLists};
-    for (XhBuf *b : bufs) xh_buf_free(*b);
-    xh_plan_free(pm->planD);
+    return xh_buf_upload(ctx, b, v.data(), sizeof(T) * v.size());
 }
 
 template <int LOGM>
@@ -3447,24 +3440,17 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     if (Ro < 0) Ro = (D / 2) - 1;
     XH_CHECK(D >= 8 && Ro >= Ri && Ro < D, XH_ERR_ARG, "xh_pm_create: bad geometry D=%d Ri=%d Ro=%d", D, Ri, Ro);
     XH_HIP(hipSetDevice(ctx->device));
-    xh_pm *pm = new xh_pm;
+    std::unique_ptr<xh_pm> pm(new xh_pm);
     pm->ctx = ctx;
     pm->nrefs = nrefs;
     make_layout(pm->L, D, Ri, Ro);
     Layout &L = pm->L;
-    if (L.nk > 1024 || L.nrings > 512) {
-        xh_set_error("xh_pm_create: Ro=%d gives %d angular frequencies / %d rings; limits are 1024 / 512", Ro, L.nk, L.nrings);
-        delete pm;
-        return XH_ERR_UNSUPPORTED;
-    }
+    XH_CHECK(L.nk <= 1024 && L.nrings <= 512, XH_ERR_UNSUPPORTED, "xh_pm_create: Ro=%d gives %d angular frequencies / %d rings; limits are 1024 / 512",
+             Ro, L.nk, L.nrings);
     pm->M = 1;
     while (pm->M < 2 * L.N - 1) pm->M <<= 1;
     pm->logM = xh_ilog2(pm->M);
-    if (pm->logM < 6 || pm->logM > 12) {
-        xh_set_error("xh_pm_create: convolution length %d outside the supported 64..4096", pm->M);
-        delete pm;
-        return XH_ERR_UNSUPPORTED;
-    }
+    XH_CHECK(pm->logM >= 6 && pm->logM <= 12, XH_ERR_UNSUPPORTED, "xh_pm_create: convolution length %d outside the supported 64..4096", pm->M);
     pm->scale = 0;
     for (int r = 0; r < L.nrings; ++r) pm->scale += 2. * kPI * (r + Ri);
     // ambiguity margin of the coarse pass. Measured error of a normalised fp32 row against its fp64 evaluation, relative to S
@@ -3498,7 +3484,6 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     pm->coefFirst = pm->coefCount = 0;
     for (int i = 0; i < 8; ++i) pm->stage_ms[i] = 0;
     for (int i = 0; i < 6; ++i) (void)hipEventCreate(&pm->ev[i]);
-    int rc = XH_OK;
     {
         // float angle cache, polar.cpp:57-83
         std::vector<float> sn(L.nsamples), cs(L.nsamples);
@@ -3576,8 +3561,8 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
             WD[j] = xh_cd{(double)cosl(a), (double)sinl(a)};
         }
         XhBuf d_ringOfCoef;
-        if (rc == XH_OK) rc = upload(ctx, pm->d_sin, sn);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_cos, cs);
+        XH_TRY(upload(ctx, pm->d_sin, sn));
+        XH_TRY(upload(ctx, pm->d_cos, cs));
         {
             // k_pm_polar_cells: samples binned by the image cell their position (x - start, y - start) falls into; the
             // patch of a cell starts two pixels before it (footprints begin at ceil(p - 2)) and is XH_PC + 4 wide
@@ -3601,9 +3586,9 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
                     corg.push_back(make_int2(cx * XH_PC - 2, cy * XH_PC - 2));
                 }
             pm->ncells = (int)corg.size();
-            if (rc == XH_OK) rc = upload(ctx, pm->d_cellStart, cstart);
-            if (rc == XH_OK) rc = upload(ctx, pm->d_cellSamples, csamp);
-            if (rc == XH_OK) rc = upload(ctx, pm->d_cellOrg, corg);
+            XH_TRY(upload(ctx, pm->d_cellStart, cstart));
+            XH_TRY(upload(ctx, pm->d_cellSamples, csamp));
+            XH_TRY(upload(ctx, pm->d_cellOrg, corg));
             // everything a sample needs in list order: (x, y, sample index, ring) in one 16-byte load
             std::vector<float4> cdata(csamp.size());
             for (size_t q = 0; q < csamp.size(); ++q) {
@@ -3612,118 +3597,111 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
                 memcpy(&fi, &i, 4); memcpy(&fr, &ring, 4);
                 cdata[q] = make_float4(sn[i], cs[i], fi, fr);
             }
-            if (rc == XH_OK) rc = upload(ctx, pm->d_cellData, cdata);
+            XH_TRY(upload(ctx, pm->d_cellData, cdata));
         }
-        if (rc == XH_OK) rc = upload(ctx, pm->d_ringOfSample, ringOf);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_nsam, L.nsam);
-        if (rc == XH_OK) {
+        XH_TRY(upload(ctx, pm->d_ringOfSample, ringOf));
+        XH_TRY(upload(ctx, pm->d_nsam, L.nsam));
+        {
             std::vector<double> ringW(L.nrings);
             for (int r = 0; r < L.nrings; ++r) ringW[r] = (6.2831853071795864769 * (double)(r + L.Ri)) / (double)L.nsam[r];
-            rc = upload(ctx, pm->d_ringW, ringW);
+            XH_TRY(upload(ctx, pm->d_ringW, ringW));
         }
-        if (rc == XH_OK) rc = upload(ctx, pm->d_soff, L.soff);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_coff, L.coff);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_rstart, rstart);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_tw32, tw32);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_tw64, tw64);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_W32, W32);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_Wfull, Wfull);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_vperm, vperm);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_chirp, chirp);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_vhat, vbr);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_csN, csN);
-        if (rc == XH_OK) rc = upload(ctx, pm->d_WD64, WD);
-        if (rc == XH_OK) rc = xh_plan_create<double>(ctx, D, pm->planD);
-        if (rc == XH_OK) rc = upload(ctx, d_ringOfCoef, ringOfCoef);
+        XH_TRY(upload(ctx, pm->d_soff, L.soff));
+        XH_TRY(upload(ctx, pm->d_coff, L.coff));
+        XH_TRY(upload(ctx, pm->d_rstart, rstart));
+        XH_TRY(upload(ctx, pm->d_tw32, tw32));
+        XH_TRY(upload(ctx, pm->d_tw64, tw64));
+        XH_TRY(upload(ctx, pm->d_W32, W32));
+        XH_TRY(upload(ctx, pm->d_Wfull, Wfull));
+        XH_TRY(upload(ctx, pm->d_vperm, vperm));
+        XH_TRY(upload(ctx, pm->d_chirp, chirp));
+        XH_TRY(upload(ctx, pm->d_vhat, vbr));
+        XH_TRY(upload(ctx, pm->d_csN, csN));
+        XH_TRY(upload(ctx, pm->d_WD64, WD));
+        XH_TRY(xh_plan_create<double>(ctx, D, pm->planD));
+        XH_TRY(upload(ctx, d_ringOfCoef, ringOfCoef));
         // reference library in fp64: getCurrentReference (APM:484-488) for every reference
         const int RB = 64;   // references per batch
-        if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_refs64, sizeof(xh_cd) * (size_t)nrefs * L.ncoef);
-        if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_refsB, sizeof(xh_cf) * (size_t)nrefs * L.ncoef);
-        if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_refSigma, sizeof(double) * nrefs);
-        if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_refCoef, sizeof(double) * (size_t)nrefs * D * D);
+        XH_TRY(xh_buf_alloc(ctx, pm->d_refs64, sizeof(xh_cd) * (size_t)nrefs * L.ncoef));
+        XH_TRY(xh_buf_alloc(ctx, pm->d_refsB, sizeof(xh_cf) * (size_t)nrefs * L.ncoef));
+        XH_TRY(xh_buf_alloc(ctx, pm->d_refSigma, sizeof(double) * nrefs));
+        XH_TRY(xh_buf_alloc(ctx, pm->d_refCoef, sizeof(double) * (size_t)nrefs * D * D));
         std::vector<double> stat(2 * RB), sig(nrefs);
-        XhBuf d_zpad, d_Mfull, d_refD;
-        XhPlanBufs<double> planP;
-        if (h_Mctf && rc == XH_OK) {
-            const int P = paddim;
-            // full-spectrum multiplier: the reference multiplies the half spectrum (j <= P/2) index-wise; the
-            // c2r inverse mirrors it onto j > P/2. Forward normalisation 1/P^2 folded in.
-            std::vector<double> Mfull((size_t)P * P);
-            for (int i = 0; i < P; ++i)
-                for (int j = 0; j < P; ++j) {
-                    const double mv = j <= P / 2 ? h_Mctf[(size_t)i * P + j] : h_Mctf[(size_t)((P - i) % P) * P + (P - j)];
-                    Mfull[(size_t)i * P + j] = mv / ((double)P * P);
-                }
-            rc = upload(ctx, d_Mfull, Mfull);
-            if (rc == XH_OK) rc = xh_plan_create<double>(ctx, P, planP);
-            if (rc == XH_OK) rc = xh_buf_alloc(ctx, d_zpad, sizeof(xh_cd) * (size_t)RB * P * P);
-            if (rc == XH_OK) rc = xh_buf_alloc(ctx, d_refD, sizeof(double) * (size_t)RB * D * D);
-        }
-        for (int r0 = 0; r0 < nrefs && rc == XH_OK; r0 += RB) {
-            const int m = std::min(RB, nrefs - r0);
+        {
+            XhBuf d_zpad, d_Mfull, d_refD;      // the CTF filter's scratch: gone before the packing below
+            XhPlanBufs<double> planP;
             if (h_Mctf) {
-                // pad -> FFT -> x Mctf -> IFFT -> crop (APM:457-481), then the same preparation on the filtered image
                 const int P = paddim;
-                const size_t perP = (size_t)P * P;
-                const int lpb = xh_plan_lpb(planP.plan, 64 * 1024, 16);
-                const size_t smemF = ((size_t)lpb * sizeof(xh_cd)) << planP.plan.logM;
-                const size_t nlines = (size_t)m * P;
-                xh_cd *z = (xh_cd *)d_zpad.p;
-                hipLaunchKernelGGL(k_pm_pad_complex, dim3((unsigned)((perP + 255) / 256), m), dim3(256), 0, ctx->stream,
-                                   d_refs + (size_t)r0 * D * D, z, D, P);
-                hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
-                                   z, planP.plan, nlines, (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
-                hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
-                                   z, planP.plan, nlines, (size_t)P, perP, (size_t)1, (size_t)P, lpb);
-                hipLaunchKernelGGL(k_pm_mul_filter, dim3((unsigned)((perP + 255) / 256), m), dim3(256), 0, ctx->stream, z, (const double *)d_Mfull.p, P);
-                hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
-                                   z, planP.plan, nlines, (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
-                hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
-                                   z, planP.plan, nlines, (size_t)P, perP, (size_t)1, (size_t)P, lpb);
-                hipLaunchKernelGGL(k_pm_crop_real, dim3((unsigned)(((size_t)D * D + 255) / 256), m), dim3(256), 0, ctx->stream, (const xh_cd *)z,
-                                   (double *)d_refD.p, D, P);
-                if (hipGetLastError() != hipSuccess) { xh_set_error("xh_pm_create: CTF filtering of the references failed"); rc = XH_ERR_HIP; break; }
-                rc = run_prep<double>(pm, d_refD.p, false, nullptr, m, nullptr, pm->d_coef64, pm->d_polar64, pm->d_A64, pm->d_stat64,
-                                      pm->d_tw64, true, 0., 0.);
-            } else
-                rc = run_prep<double>(pm, d_refs + (size_t)r0 * D * D, true, nullptr, m, nullptr, pm->d_coef64, pm->d_polar64,
-                                      pm->d_A64, pm->d_stat64, pm->d_tw64, true, 0., 0.);
-            if (rc != XH_OK) break;
-            if (hipMemcpyAsync((xh_cd *)pm->d_refs64.p + (size_t)r0 * L.ncoef, pm->d_A64.p, sizeof(xh_cd) * (size_t)m * L.ncoef,
-                               hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync((double *)pm->d_refCoef.p + (size_t)r0 * D * D, pm->d_coef64.p, sizeof(double) * (size_t)m * D * D,
-                               hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(stat.data(), pm->d_stat64.p, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                xh_set_error("xh_pm_create: reference library copy failed: %s", hipGetErrorString(hipGetLastError()));
-                rc = XH_ERR_HIP;
-                break;
+                // full-spectrum multiplier: the reference multiplies the half spectrum (j <= P/2) index-wise; the
+                // c2r inverse mirrors it onto j > P/2. Forward normalisation 1/P^2 folded in.
+                std::vector<double> Mfull((size_t)P * P);
+                for (int i = 0; i < P; ++i)
+                    for (int j = 0; j < P; ++j) {
+                        const double mv = j <= P / 2 ? h_Mctf[(size_t)i * P + j] : h_Mctf[(size_t)((P - i) % P) * P + (P - j)];
+                        Mfull[(size_t)i * P + j] = mv / ((double)P * P);
+                    }
+                XH_TRY(upload(ctx, d_Mfull, Mfull));
+                XH_TRY(xh_plan_create<double>(ctx, P, planP));
+                XH_TRY(xh_buf_alloc(ctx, d_zpad, sizeof(xh_cd) * (size_t)RB * P * P));
+                XH_TRY(xh_buf_alloc(ctx, d_refD, sizeof(double) * (size_t)RB * D * D));
             }
-            for (int i = 0; i < m; ++i) sig[r0 + i] = stat[2 * i + 1];
+            for (int r0 = 0; r0 < nrefs; r0 += RB) {
+                const int m = std::min(RB, nrefs - r0);
+                if (h_Mctf) {
+                    // pad -> FFT -> x Mctf -> IFFT -> crop (APM:457-481), then the same preparation on the filtered image
+                    const int P = paddim;
+                    const size_t perP = (size_t)P * P;
+                    const int lpb = xh_plan_lpb(planP.plan, 64 * 1024, 16);
+                    const size_t smemF = ((size_t)lpb * sizeof(xh_cd)) << planP.plan.logM;
+                    const size_t nlines = (size_t)m * P;
+                    xh_cd *z = (xh_cd *)d_zpad.p;
+                    hipLaunchKernelGGL(k_pm_pad_complex, dim3((unsigned)((perP + 255) / 256), m), dim3(256), 0, ctx->stream,
+                                       d_refs + (size_t)r0 * D * D, z, D, P);
+                    hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
+                                       z, planP.plan, nlines, (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
+                    hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
+                                       z, planP.plan, nlines, (size_t)P, perP, (size_t)1, (size_t)P, lpb);
+                    hipLaunchKernelGGL(k_pm_mul_filter, dim3((unsigned)((perP + 255) / 256), m), dim3(256), 0, ctx->stream, z, (const double *)d_Mfull.p, P);
+                    hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
+                                       z, planP.plan, nlines, (size_t)1, (size_t)P, (size_t)0, (size_t)1, lpb);
+                    hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smemF, ctx->stream,
+                                       z, planP.plan, nlines, (size_t)P, perP, (size_t)1, (size_t)P, lpb);
+                    hipLaunchKernelGGL(k_pm_crop_real, dim3((unsigned)(((size_t)D * D + 255) / 256), m), dim3(256), 0, ctx->stream, (const xh_cd *)z,
+                                       (double *)d_refD.p, D, P);
+                    XH_CHECK(hipGetLastError() == hipSuccess, XH_ERR_HIP, "xh_pm_create: CTF filtering of the references failed");
+                    XH_TRY(run_prep<double>(pm.get(), d_refD.p, false, nullptr, m, nullptr, pm->d_coef64, pm->d_polar64, pm->d_A64, pm->d_stat64,
+                                            pm->d_tw64, true, 0., 0.));
+                } else
+                    XH_TRY(run_prep<double>(pm.get(), d_refs + (size_t)r0 * D * D, true, nullptr, m, nullptr, pm->d_coef64, pm->d_polar64,
+                                            pm->d_A64, pm->d_stat64, pm->d_tw64, true, 0., 0.));
+                if (hipMemcpyAsync((xh_cd *)pm->d_refs64.p + (size_t)r0 * L.ncoef, pm->d_A64.p, sizeof(xh_cd) * (size_t)m * L.ncoef,
+                                   hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                    hipMemcpyAsync((double *)pm->d_refCoef.p + (size_t)r0 * D * D, pm->d_coef64.p, sizeof(double) * (size_t)m * D * D,
+                                   hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                    hipMemcpyAsync(stat.data(), pm->d_stat64.p, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                    hipStreamSynchronize(ctx->stream) != hipSuccess) {
+                    xh_set_error("xh_pm_create: reference library copy failed: %s", hipGetErrorString(hipGetLastError()));
+                    return XH_ERR_HIP;
+                }
+                for (int i = 0; i < m; ++i) sig[r0 + i] = stat[2 * i + 1];
+            }
+            (void)hipStreamSynchronize(ctx->stream);
         }
-        (void)hipStreamSynchronize(ctx->stream);
-        xh_buf_free(d_zpad); xh_plan_free(planP); xh_buf_free(d_Mfull); xh_buf_free(d_refD);
-        if (rc == XH_OK && hipMemcpy(pm->d_refSigma.p, sig.data(), sizeof(double) * nrefs, hipMemcpyHostToDevice) != hipSuccess) {
-            xh_set_error("xh_pm_create: sigma upload failed");
-            rc = XH_ERR_HIP;
-        }
-        if (rc == XH_OK) {
+        XH_CHECK(hipMemcpy(pm->d_refSigma.p, sig.data(), sizeof(double) * nrefs, hipMemcpyHostToDevice) == hipSuccess, XH_ERR_HIP,
+                 "xh_pm_create: sigma upload failed");
+        {
             const size_t total = (size_t)nrefs * L.ncoef;
             hipLaunchKernelGGL(k_pm_pack_refs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
                                (const xh_cd *)pm->d_refs64.p, (xh_cf *)pm->d_refsB.p, (const short *)d_ringOfCoef.p, Ri, L.ncoef, total);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                xh_set_error("xh_pm_create: pack kernel failed");
-                rc = XH_ERR_HIP;
-            }
+            XH_CHECK(hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess, XH_ERR_HIP, "xh_pm_create: pack kernel failed");
         }
-        xh_buf_free(d_ringOfCoef);
-        if (rc == XH_OK) {
+        {
             // packed operand tiles for the MFMA contraction
             std::vector<int> qoff(L.nk + 1);
             qoff[0] = 0;
             for (int k = 0; k < L.nk; ++k) qoff[k + 1] = qoff[k] + (L.nrings - rstart[k] + 7) / 8;
             pm->totalQuads = qoff[L.nk];
-            rc = upload(ctx, pm->d_qoff, qoff);
+            XH_TRY(upload(ctx, pm->d_qoff, qoff));
             {
                 // frequency slices of equal MFMA work, boundaries on multiples of 4 (the store blocking)
                 std::vector<int> kb(XH_KSPLIT + 1, L.nk);
@@ -3734,30 +3712,29 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
                     while (k < L.nk && qoff[k] < target) ++k;
                     kb[sidx] = std::min(L.nk, (k + 3) / 4 * 4);
                 }
-                if (rc == XH_OK) rc = upload(ctx, pm->d_kbounds, kb);
+                XH_TRY(upload(ctx, pm->d_kbounds, kb));
             }
             const int ntiles = (nrefs + 15) / 16;
             const size_t nvec = (size_t)ntiles * pm->totalQuads * 64;
-            if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_Bpack, nvec * sizeof(float4));
-            if (rc == XH_OK) {
+            XH_TRY(xh_buf_alloc(ctx, pm->d_Bpack, nvec * sizeof(float4)));
+            {
                 hipLaunchKernelGGL(k_pm_pack_tiles, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, ctx->stream, (const xh_cf *)pm->d_refsB.p,
                                    (float4 *)pm->d_Bpack.p, (const int *)pm->d_qoff.p, (const int *)pm->d_rstart.p, (const int *)pm->d_coff.p,
                                    (const int *)pm->d_nsam.p, L.nrings, L.ncoef, L.nk, pm->totalQuads, nrefs, (const int *)nullptr, pm->totalQuads);
-                if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { xh_set_error("xh_pm_create: operand packing failed"); rc = XH_ERR_HIP; }
+                XH_CHECK(hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess, XH_ERR_HIP, "xh_pm_create: operand packing failed");
             }
             // two-level S2: per-frequency norms of the weighted reference coefficients and the cut K0
             pm->K0 = pm->K0auto = L.nk;
             pm->quadsLow = pm->totalQuads;
-            if (rc == XH_OK) rc = xh_buf_alloc(ctx, pm->d_bT, sizeof(float) * (size_t)L.nk * nrefs);
-            if (rc == XH_OK) {
+            XH_TRY(xh_buf_alloc(ctx, pm->d_bT, sizeof(float) * (size_t)L.nk * nrefs));
+            {
                 hipLaunchKernelGGL(k_pm_tail_norms, dim3((L.nk + 63) / 64, nrefs), dim3(64), 0, ctx->stream, (const xh_cf *)pm->d_refsB.p,
                                    (float *)pm->d_bT.p, (const int *)pm->d_coff.p, (const int *)pm->d_rstart.p, L.nrings, L.ncoef, L.nk, 0,
                                    nrefs, (size_t)1, (size_t)nrefs);
                 std::vector<float> bT((size_t)L.nk * nrefs);
-                if (hipGetLastError() != hipSuccess || hipMemcpy(bT.data(), pm->d_bT.p, pm->d_bT.bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-                    xh_set_error("xh_pm_create: reference norms failed");
-                    rc = XH_ERR_HIP;
-                } else {
+                XH_CHECK(hipGetLastError() == hipSuccess && hipMemcpy(bT.data(), pm->d_bT.p, pm->d_bT.bytes, hipMemcpyDeviceToHost) == hipSuccess, XH_ERR_HIP,
+                         "xh_pm_create: reference norms failed");
+                {
                     // smallest cut whose tail holds less than 1e-5 of the summed norms; not worth it above 0.6 nk
                     std::vector<double> mean(L.nk, 0.);
                     double all = 0;
@@ -3776,30 +3753,24 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
                     if (K0 < 8) K0 = 8;
                     if (K0 > (int)(0.6 * L.nk)) K0 = L.nk;
                     pm->K0auto = K0;
-                    rc = set_k0(pm, K0);
+                    XH_TRY(set_k0(pm.get(), K0));
                     // the norms summed over bands of XH_TAIL_BAND frequencies (k_pm_prune_plan), rounded up
                     const int nb = (L.nk + XH_TAIL_BAND - 1) / XH_TAIL_BAND;
                     std::vector<float> bb((size_t)nb * nrefs, 0.f);
                     for (int k = 0; k < L.nk; ++k)
                         for (int r = 0; r < nrefs; ++r) bb[(size_t)(k / XH_TAIL_BAND) * nrefs + r] += bT[(size_t)k * nrefs + r];
                     for (float &v : bb) v *= 1.000002f;
-                    if (rc == XH_OK) rc = upload(ctx, pm->d_bTband, bb);
+                    XH_TRY(upload(ctx, pm->d_bTband, bb));
                 }
             }
         }
     }
-    if (rc != XH_OK) { free_all(pm); delete pm; return rc; }
-    *out = pm;
+    *out = pm.release();
     return XH_OK;
 }
 
 int xh_pm_destroy(xh_pm *pm)
 {
-    if (!pm) return XH_OK;
-    (void)hipSetDevice(pm->ctx->device);
-    (void)hipStreamSynchronize(pm->ctx->stream);
-    for (int i = 0; i < 6; ++i) (void)hipEventDestroy(pm->ev[i]);
-    free_all(pm);
     delete pm;
     return XH_OK;
 }
@@ -4609,7 +4580,6 @@ int xh_pm_debug_corr_rows(xh_pm *pm, const float *d_particle, int32_t ref, int32
         if (e == hipSuccess) e = hipMemcpyAsync(stat, pm->d_stat32.p, sizeof(stat), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&sig, (const double *)pm->d_refSigma.p + ref, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        xh_buf_free(out);
         if (e != hipSuccess) { xh_set_error("debug_corr_rows: %s", hipGetErrorString(e)); return XH_ERR_HIP; }
         const float den = (float)sig * (float)stat[1];
         for (int i = 0; i < 2 * N; ++i) h_corr2N[i] = tmp[i] / den;
@@ -4640,8 +4610,6 @@ int xh_pm_debug_corr_rows(xh_pm *pm, const float *d_particle, int32_t ref, int32
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_corr2N, dbg.p, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    xh_buf_free(misc);
-    xh_buf_free(dbg);
     if (e != hipSuccess) { xh_set_error("debug_corr_rows(64): %s", hipGetErrorString(e)); return XH_ERR_HIP; }
     return XH_OK;
 }

@@ -268,6 +268,15 @@ struct xh_rf {
     int order_spaces = 1; // the traverse spaces of a launch ordered by plane, so that k_rf_grid reuses voxel queues (0: input order, for A/B)
     XhBuf d_spacePos;
     int ctf_fast = 1;     // envelope-free CTFs through d_ctf_pixel_fast (0: the general double-precision formula everywhere, for A/B)
+    ~xh_rf()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        if (h_stage) (void)hipHostFree(h_stage);
+        for (hipEvent_t e : stageEv)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : evPool) (void)hipEventDestroy(e);
+    }
 };
 
 // Copies a host array to the device behind everything already enqueued, without waiting for the stream: the bytes pass
@@ -1246,7 +1255,7 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
              "xh_rf_create: blob order %d unsupported (kaiser_Fourier_value handles 0 and 2 only, blobs.cpp:146-147)",
              p->blob_order);
     XH_HIP(hipSetDevice(ctx->device));
-    xh_rf *rf = new xh_rf;
+    std::unique_ptr<xh_rf> rf(new xh_rf);
     rf->ctx = ctx;
     rf->p = *p;
     rf->D = p->imgSize;
@@ -1257,12 +1266,9 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
     rf->mv = 2 * (int)conserveRows;
     rf->sizeX = rf->mv / 2;
     rf->sizeY = rf->mv;
-    if (rf->P > 2048 || rf->mv > rf->P) {
-        xh_set_error("xh_rf_create: padded size %d (imgSize %d x padding %g) must be <= 2048 "
-                     "and max_resolution <= 0.5 for the device FFT", rf->P, rf->D, p->padding_vol);
-        delete rf;
-        return XH_ERR_UNSUPPORTED;
-    }
+    XH_CHECK(rf->P <= 2048 && rf->mv <= rf->P, XH_ERR_UNSUPPORTED,
+             "xh_rf_create: padded size %d (imgSize %d x padding %g) must be <= 2048 "
+             "and max_resolution <= 0.5 for the device FFT", rf->P, rf->D, p->padding_vol);
     // tables, RFA:201-239
     rf->blobTableSqrt.resize(XH_BLOB_TABLE);
     rf->fourierBlobTable.resize(XH_BLOB_TABLE);
@@ -1288,19 +1294,19 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
     rf->kernelMs = 0;
     rf->kernelLaunches = 0;
     rf->meanFactor2 = -1;
-    int r = xh_buf_alloc(ctx, rf->d_blob, sizeof(float) * XH_BLOB_TABLE);
-    if (r == XH_OK) r = (hipMemcpy(rf->d_blob.p, rf->blobTableSqrt.data(), rf->d_blob.bytes, hipMemcpyHostToDevice) == hipSuccess) ? XH_OK : XH_ERR_HIP;
-    if (r == XH_OK) r = make_twiddles(ctx, rf->P, rf->d_twP32, rf->d_twP64);
-    if (r == XH_OK) r = xh_plan_create<float>(ctx, rf->P, rf->planP32);
-    if (r == XH_OK) r = xh_plan_create<double>(ctx, rf->P, rf->planP64);
-    if (r == XH_OK) r = xh_buf_alloc(ctx, rf->d_tileCounter, sizeof(int) * 512);
+    XH_TRY(xh_buf_alloc(ctx, rf->d_blob, sizeof(float) * XH_BLOB_TABLE));
+    if (hipMemcpy(rf->d_blob.p, rf->blobTableSqrt.data(), rf->d_blob.bytes, hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+    XH_TRY(make_twiddles(ctx, rf->P, rf->d_twP32, rf->d_twP64));
+    XH_TRY(xh_plan_create<float>(ctx, rf->P, rf->planP32));
+    XH_TRY(xh_plan_create<double>(ctx, rf->P, rf->planP64));
+    XH_TRY(xh_buf_alloc(ctx, rf->d_tileCounter, sizeof(int) * 512));
     // k_rf_grid: tiles of 2 x 2 x 2 units (16 x 16 x 8 voxels for units 4 deep, 16^3 for units 8 deep) that a projection can
     // reach (sphere of radius sizeX + blob), in raster order (z, y, x) cut into 8 contiguous z-slabs of equal estimated work, one
     // per XCD (block b runs on XCD b % 8: a projection's patch is pulled into one or two L2s instead of all eight). A tile at
     // distance rho from the centre is crossed by a fraction ~1/rho of all central planes: that is its weight. Inside a class
     // Morton order (the waves of the chip work on a narrow band of consecutive tiles, and a compact band shares more of the
     // projections' patches in the L2 than a row of the raster). Class offsets at d_tileCounter + 32 (units 4 deep) and + 48 (8).
-    for (int v = 0; v < 2 && r == XH_OK; ++v) {
+    for (int v = 0; v < 2; ++v) {
         const int tzs = v ? 16 : 8;                            // voxels per tile in z
         const int tpx = (rf->mv + 1 + 15) / 16, tpz = (rf->mv + 1 + tzs - 1) / tzs;
         const double hz = 0.5 * tzs - 0.5;
@@ -1328,34 +1334,16 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
         };
         for (int c = 0; c < 8; ++c)
             std::sort(packed.begin() + classOff[c], packed.begin() + classOff[c + 1], [&](unsigned u, unsigned w) { return key(u) < key(w); });
-        r = xh_buf_alloc(ctx, rf->d_gtiles[v], sizeof(unsigned) * std::max<size_t>(1, packed.size()));
-        if (r == XH_OK) r = (hipMemcpy(rf->d_gtiles[v].p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) == hipSuccess) ? XH_OK : XH_ERR_HIP;
-        if (r == XH_OK) r = (hipMemcpy((int *)rf->d_tileCounter.p + 32 + 16 * v, classOff, sizeof(classOff), hipMemcpyHostToDevice) == hipSuccess) ? XH_OK : XH_ERR_HIP;
+        XH_TRY(xh_buf_alloc(ctx, rf->d_gtiles[v], sizeof(unsigned) * std::max<size_t>(1, packed.size())));
+        if (hipMemcpy(rf->d_gtiles[v].p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+        if (hipMemcpy((int *)rf->d_tileCounter.p + 32 + 16 * v, classOff, sizeof(classOff), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
     }
-    if (r != XH_OK) { xh_rf_destroy(rf); return r; }
-    *out = rf;
+    *out = rf.release();
     return XH_OK;
 }
 
 int xh_rf_destroy(xh_rf *rf)
 {
-    if (!rf) return XH_OK;
-    (void)hipSetDevice(rf->ctx->device);
-    (void)hipStreamSynchronize(rf->ctx->stream);
-    xh_buf_free(rf->d_blob); xh_buf_free(rf->d_twP32); xh_buf_free(rf->d_twP64);
-    xh_plan_free(rf->planP32); xh_plan_free(rf->planP64);
-    xh_buf_free(rf->own_temp); xh_buf_free(rf->d_rows);
-    xh_buf_free(rf->d_ctfp); xh_buf_free(rf->d_fin);
-    xh_buf_free(rf->d_shiftCoef); xh_buf_free(rf->d_shiftXY);
-    xh_buf_free(rf->d_tileCounter); xh_buf_free(rf->d_cull); xh_buf_free(rf->d_pack);
-    xh_buf_free(rf->d_superList); xh_buf_free(rf->d_superCount); xh_buf_free(rf->d_superVec);
-    xh_buf_free(rf->d_sym); xh_buf_free(rf->d_angles); xh_buf_free(rf->d_spacePos);
-    xh_buf_free(rf->d_finSpec); xh_buf_free(rf->d_finVol); xh_buf_free(rf->d_finFbt);
-    if (rf->h_stage) (void)hipHostFree(rf->h_stage);
-    for (int h = 0; h < 2; ++h)
-        if (rf->stageEv[h]) (void)hipEventDestroy(rf->stageEv[h]);
-    xh_buf_free(rf->d_gtiles[0]); xh_buf_free(rf->d_gtiles[1]); xh_buf_free(rf->d_grecs); xh_buf_free(rf->d_gweights); xh_buf_free(rf->d_spectra);
-    for (hipEvent_t e : rf->evPool) (void)hipEventDestroy(e);
     delete rf;
     return XH_OK;
 }
@@ -1709,10 +1697,11 @@ static int grid_run(xh_rf *rf, int ns, const float *d_fft, const float *d_ctf, c
     float *tempV = rf->d_temp, *tempW = rf->d_temp + 2 * d * d * d;
     {
         // the record buffer is zeroed when it is (re)allocated: the pack kernels leave the cells no tap can reach alone, and what lies there
-        // must be finite (it only ever meets the table's zero entry)
-        const void *before = rf->d_pack.p;
-        XH_TRY(xh_buf_reserve(ctx, rf->d_pack, cells * sizeof(XgCell) + 16));          // (the patch copy reads 16 bytes from the last record too)
-        if (rf->d_pack.p != before) XH_HIP(hipMemsetAsync(rf->d_pack.p, 0, rf->d_pack.bytes, ctx->stream));
+        // must be finite (it only ever meets the table's zero entry).  Keyed on the reallocation itself: hipMalloc may hand back the
+        // address it has just freed.
+        bool grown = false;
+        XH_TRY(xh_buf_reserve(ctx, rf->d_pack, cells * sizeof(XgCell) + 16, &grown));   // (the patch copy reads 16 bytes from the last record too)
+        if (grown) XH_HIP(hipMemsetAsync(rf->d_pack.p, 0, rf->d_pack.bytes, ctx->stream));
     }
     const int skipR2 = far_r2(rf);
     for (int i0 = 0; i0 < n; i0 += 65535) {          // blockIdx.y: image
@@ -2158,23 +2147,16 @@ int xh_rf_finish(xh_rf *rf, double *h_volume)
     // (kept with the handle: allocating and freeing 1.2 GB per call -- hipFree waits for the device -- was most of the 36-60 ms a
     // finish took; its kernels are 10 ms)
     XhBuf &spec = rf->d_finSpec, &vol = rf->d_finVol, &fbt = rf->d_finFbt;
-    int r = xh_buf_reserve(ctx, spec, specElems * sizeof(xh_cd));
-    if (r == XH_OK) r = xh_buf_reserve(ctx, vol, sizeof(double) * (size_t)D * D * D);
-    if (r == XH_OK) r = xh_buf_reserve(ctx, fbt, sizeof(double) * XH_BLOB_TABLE);
-    if (r != XH_OK) return r;
-    auto cleanup = [&]() {};
-#define XH_HIP_C(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { xh_set_error("%s failed: %s", #call, hipGetErrorString(e_)); cleanup(); return XH_ERR_HIP; } } while (0)
+    XH_TRY(xh_buf_reserve(ctx, spec, specElems * sizeof(xh_cd)));
+    XH_TRY(xh_buf_reserve(ctx, vol, sizeof(double) * (size_t)D * D * D));
+    XH_TRY(xh_buf_reserve(ctx, fbt, sizeof(double) * XH_BLOB_TABLE));
+#define XH_HIP_C(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { xh_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return XH_ERR_HIP; } } while (0)
     XH_HIP_C(hipMemcpyAsync(fbt.p, rf->fourierBlobTable.data(), fbt.bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_rf_expand, dim3((unsigned)((specElems + 255) / 256)), dim3(256), 0, ctx->stream, (const xh_cf *)V, (xh_cd *)spec.p, mv, P);
     XH_HIP_C(hipGetLastError());
-    {
-        const int rc = finish_from_spectrum(ctx, rf->planP64.plan, (xh_cd *)spec.p, (double *)vol.p, (const double *)fbt.p, D, (double)rf->iDeltaFourier,
-                                            rf->p.padding_proj, rf->p.padding_vol, rf->meanFactor2, true, h_volume);
-        if (rc != XH_OK) { cleanup(); return rc; }
-    }
 #undef XH_HIP_C
-    cleanup();
-    return XH_OK;
+    return finish_from_spectrum(ctx, rf->planP64.plan, (xh_cd *)spec.p, (double *)vol.p, (const double *)fbt.p, D, (double)rf->iDeltaFourier,
+                                rf->p.padding_proj, rf->p.padding_vol, rf->meanFactor2, true, h_volume);
 }
 
 
@@ -2340,18 +2322,17 @@ struct xh_rf2 {
     XhPlanBufs<double> planP, planV;
     XhBuf d_F, d_W, d_Fsave, d_table, d_spec, d_A, d_img, d_w, d_ctf, d_imgOf;
     size_t nF;
+    ~xh_rf2()
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
 };
 
 extern "C" {
 
 int xh_rf2_destroy(xh_rf2 *h)
 {
-    if (!h) return XH_OK;
-    (void)hipSetDevice(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    xh_plan_free(h->planP); xh_plan_free(h->planV);
-    xh_buf_free(h->d_F); xh_buf_free(h->d_W); xh_buf_free(h->d_Fsave); xh_buf_free(h->d_table); xh_buf_free(h->d_spec); xh_buf_free(h->d_A);
-    xh_buf_free(h->d_img); xh_buf_free(h->d_w); xh_buf_free(h->d_ctf); xh_buf_free(h->d_imgOf);
     delete h;
     return XH_OK;
 }
@@ -2371,7 +2352,7 @@ int xh_rf2_create(xh_ctx *ctx, const xh_rf_params *p, int32_t niter_weight, xh_r
     XH_CHECK(p->imgSize >= 4 && (p->blob_order == 0 || p->blob_order == 2), XH_ERR_ARG, "xh_rf2_create: bad image size or blob order");
     XH_CHECK(!p->use_fast, XH_ERR_UNSUPPORTED, "xh_rf2_create: ProgRecFourier has no --fast");
     XH_HIP(hipSetDevice(ctx->device));
-    xh_rf2 *h = new xh_rf2;
+    std::unique_ptr<xh_rf2> h(new xh_rf2);
     h->ctx = ctx; h->p = *p; h->D = p->imgSize; h->niter = niter_weight;
     h->P = (int)(h->D * p->padding_proj);            // RF:229-231
     h->V = (int)(h->D * p->padding_vol);
@@ -2392,18 +2373,16 @@ int xh_rf2_create(xh_ctx *ctx, const xh_rf_params *p, int32_t niter_weight, xh_r
         h->ftable[i] = h_kaiser_fourier(deltaFourier * i, rFourier, p->blob_alpha, p->blob_order) * pad3 * iw0;
     }
     h->iDeltaSqrt = 1 / deltaSqrt; h->iDeltaFourier = 1 / deltaFourier;
-    int rc = (h->P <= 2048 && h->V <= 2048) ? XH_OK : XH_ERR_UNSUPPORTED;
-    if (rc != XH_OK) xh_set_error("xh_rf2_create: padded sizes %d / %d exceed 2048", h->P, h->V);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, h->P, h->planP);
-    if (rc == XH_OK) rc = xh_plan_create<double>(ctx, h->V, h->planV);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->d_F, sizeof(xh_cd) * h->nF);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->d_W, sizeof(double) * h->nF);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, h->d_table, sizeof(double) * 2 * XH_BLOB_TABLE);
-    if (rc == XH_OK && hipMemcpy(h->d_table.p, h->table.data(), sizeof(double) * XH_BLOB_TABLE, hipMemcpyHostToDevice) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK && hipMemcpy((double *)h->d_table.p + XH_BLOB_TABLE, h->ftable.data(), sizeof(double) * XH_BLOB_TABLE, hipMemcpyHostToDevice) != hipSuccess) rc = XH_ERR_HIP;
-    if (rc == XH_OK) rc = xh_rf2_reset(h);
-    if (rc != XH_OK) { xh_rf2_destroy(h); return rc; }
-    *out = h;
+    XH_CHECK(h->P <= 2048 && h->V <= 2048, XH_ERR_UNSUPPORTED, "xh_rf2_create: padded sizes %d / %d exceed 2048", h->P, h->V);
+    XH_TRY(xh_plan_create<double>(ctx, h->P, h->planP));
+    XH_TRY(xh_plan_create<double>(ctx, h->V, h->planV));
+    XH_TRY(xh_buf_alloc(ctx, h->d_F, sizeof(xh_cd) * h->nF));
+    XH_TRY(xh_buf_alloc(ctx, h->d_W, sizeof(double) * h->nF));
+    XH_TRY(xh_buf_alloc(ctx, h->d_table, sizeof(double) * 2 * XH_BLOB_TABLE));
+    if (hipMemcpy(h->d_table.p, h->table.data(), sizeof(double) * XH_BLOB_TABLE, hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+    if (hipMemcpy((double *)h->d_table.p + XH_BLOB_TABLE, h->ftable.data(), sizeof(double) * XH_BLOB_TABLE, hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+    XH_TRY(xh_rf2_reset(h.get()));
+    *out = h.release();
     return XH_OK;
 }
 
@@ -2564,21 +2543,16 @@ int xh_rf2_finish(xh_rf2 *h, double *h_volume)
     const int V = h->V, D = h->D;
     int half = V / 2; if (V % 2 == 0) half--;
     XhBuf spec, vol;
-    int rc = xh_buf_alloc(ctx, spec, sizeof(xh_cd) * h->nF);
-    if (rc == XH_OK) rc = xh_buf_alloc(ctx, vol, sizeof(double) * (size_t)D * D * D);
-    if (rc == XH_OK) {
-        // on a copy: the symmetrised coefficients are what the reference transforms, and it transforms in place
-        hipLaunchKernelGGL(k_rf2_plane_symmetry, dim3((unsigned)((V * half + half + 255) / 256)), dim3(256), 0, ctx->stream, (xh_cd *)h->d_F.p, (double *)h->d_W.p, V, 1);
-        const double corr2D_3D = std::pow(h->p.padding_proj, 2.) / (D * std::pow(h->p.padding_vol, 3.));
-        hipLaunchKernelGGL(k_rf2_process_weights, dim3((unsigned)((h->nF + 255) / 256)), dim3(256), 0, ctx->stream, (const xh_cd *)h->d_F.p, (const double *)h->d_W.p,
-                           (xh_cd *)spec.p, h->nF, corr2D_3D, h->niter);
-        if (hipGetLastError() != hipSuccess) { xh_set_error("xh_rf2_finish: kernel launch failed"); rc = XH_ERR_HIP; }
-    }
-    if (rc == XH_OK)
-        rc = finish_from_spectrum(ctx, h->planV.plan, (xh_cd *)spec.p, (double *)vol.p, (const double *)h->d_table.p + XH_BLOB_TABLE, D, h->iDeltaFourier,
-                                  h->p.padding_proj, h->p.padding_vol, h->meanFactor2, h->niter != 0, h_volume);
-    xh_buf_free(spec); xh_buf_free(vol);
-    return rc;
+    XH_TRY(xh_buf_alloc(ctx, spec, sizeof(xh_cd) * h->nF));
+    XH_TRY(xh_buf_alloc(ctx, vol, sizeof(double) * (size_t)D * D * D));
+    // on a copy: the symmetrised coefficients are what the reference transforms, and it transforms in place
+    hipLaunchKernelGGL(k_rf2_plane_symmetry, dim3((unsigned)((V * half + half + 255) / 256)), dim3(256), 0, ctx->stream, (xh_cd *)h->d_F.p, (double *)h->d_W.p, V, 1);
+    const double corr2D_3D = std::pow(h->p.padding_proj, 2.) / (D * std::pow(h->p.padding_vol, 3.));
+    hipLaunchKernelGGL(k_rf2_process_weights, dim3((unsigned)((h->nF + 255) / 256)), dim3(256), 0, ctx->stream, (const xh_cd *)h->d_F.p, (const double *)h->d_W.p,
+                       (xh_cd *)spec.p, h->nF, corr2D_3D, h->niter);
+    XH_CHECK(hipGetLastError() == hipSuccess, XH_ERR_HIP, "xh_rf2_finish: kernel launch failed");
+    return finish_from_spectrum(ctx, h->planV.plan, (xh_cd *)spec.p, (double *)vol.p, (const double *)h->d_table.p + XH_BLOB_TABLE, D, h->iDeltaFourier,
+                                h->p.padding_proj, h->p.padding_vol, h->meanFactor2, h->niter != 0, h_volume);
 }
 
 }  // extern "C"

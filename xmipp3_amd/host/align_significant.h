@@ -220,28 +220,28 @@ public:
         const int D = (int)refs.x;
         const size_t per = (size_t)D * D, R = refs.n, N = imgs.n;
 
-        struct { xh_ctx *c = nullptr; } g;
-        struct CtxGuard { decltype(g) &x; ~CtxGuard() { if (x.c) xh_ctx_destroy(x.c); } } cg{g};
-        xhCheck(xh_ctx_create_private(device, &g.c));
+        xh_ctx *ctx = nullptr;
+        xhCheck(xh_ctx_create_private(device, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         xh_align_sig *h = nullptr;
         const int batch = (int)std::min<size_t>(R * N, 1024);
         // room for the R references the alignment loads (the input's references, or its images when the roles are swapped), never for
         // the N images: the update of the references takes its count and loads none
-        xhCheck(xh_align_sig_create(g.c, D, (int)R, batch, D / 4, std::max(2, D / 20), (D - 3) / 2, 3, &h));
-        struct Guard { xh_align_sig *h; ~Guard() { xh_align_sig_destroy(h); } } hg{h};
+        xhCheck(xh_align_sig_create(ctx, D, (int)R, batch, D / 4, std::max(2, D / 20), (D - 3) / 2, 3, &h));
+        XhOwner<xh_align_sig> hOwner(h);
         DeviceBuffer dRefs, dImgs, dPoses, dMerit, dWeights;
-        dRefs.reserve(g.c, sizeof(float) * per * R);
-        dImgs.reserve(g.c, sizeof(float) * per * N);
-        dPoses.reserve(g.c, sizeof(float) * 9 * R * N);
-        dMerit.reserve(g.c, sizeof(float) * R * N);
-        dWeights.reserve(g.c, sizeof(float) * R * N);
-        xhCheck(xh_memcpy_h2d(g.c, dRefs.p, refs.data.data(), sizeof(float) * per * R));
-        xhCheck(xh_memcpy_h2d(g.c, dImgs.p, imgs.data.data(), sizeof(float) * per * N));
+        dRefs.reserve(ctx, sizeof(float) * per * R);
+        dImgs.reserve(ctx, sizeof(float) * per * N);
+        dPoses.reserve(ctx, sizeof(float) * 9 * R * N);
+        dMerit.reserve(ctx, sizeof(float) * R * N);
+        dWeights.reserve(ctx, sizeof(float) * R * N);
+        xhCheck(xh_memcpy_h2d(ctx, dRefs.p, refs.data.data(), sizeof(float) * per * R));
+        xhCheck(xh_memcpy_h2d(ctx, dImgs.p, imgs.data.data(), sizeof(float) * per * N));
         xhCheck(xh_align_sig_load_references(h, dRefs.as<float>(), (int)R));
         xhCheck(xh_align_sig_align(h, dImgs.as<float>(), (int)N, dPoses.as<float>(), dMerit.as<float>()));
         std::vector<float> poses(9 * R * N), merit(R * N);
-        xhCheck(xh_memcpy_d2h(g.c, poses.data(), dPoses.p, sizeof(float) * poses.size()));
-        xhCheck(xh_memcpy_d2h(g.c, merit.data(), dMerit.p, sizeof(float) * merit.size()));
+        xhCheck(xh_memcpy_d2h(ctx, poses.data(), dPoses.p, sizeof(float) * poses.size()));
+        xhCheck(xh_memcpy_d2h(ctx, merit.data(), dMerit.p, sizeof(float) * merit.size()));
 
         // from here on in the roles of the input: R0 references, N0 images; an estimation made with swapped roles is read transposed,
         // its pose inverted (the IS_ESTIMATION_TRANSPOSED branches of computeWeightsAndSave and computeAssignment)
@@ -255,10 +255,10 @@ public:
                 if (swapped) inverse(&poses[9 * e], &pose0[9 * (r * N0 + s)]);
                 else memcpy(&pose0[9 * (r * N0 + s)], &poses[9 * e], 9 * sizeof(float));
             }
-        if (swapped) xhCheck(xh_memcpy_h2d(g.c, dMerit.p, merit0.data(), sizeof(float) * merit0.size()));
+        if (swapped) xhCheck(xh_memcpy_h2d(ctx, dMerit.p, merit0.data(), sizeof(float) * merit0.size()));
         xhCheck(xh_align_sig_weights(h, refs.rots.data(), refs.tilts.data(), angDistance, dMerit.as<float>(), (int)R0, (int)N0, dWeights.as<float>()));
         std::vector<float> weights(R0 * N0);
-        xhCheck(xh_memcpy_d2h(g.c, weights.data(), dWeights.p, sizeof(float) * weights.size()));
+        xhCheck(xh_memcpy_d2h(ctx, weights.data(), dWeights.p, sizeof(float) * weights.size()));
 
         // computeAssignment (:372-412): the best keepBestN per image, first maximum, values <= 0 skipped
         for (size_t i = 0; i < N0; ++i) {
@@ -275,7 +275,7 @@ public:
             }
         }
         storeAlignedImages();
-        if (doUpdate) updateRefs(g.c, h);
+        if (doUpdate) updateRefs(ctx, h);
     }
 
     // storeAlignedImages (:415-468): rows sorted by image, then by the criterion; maxCC is the image's best value

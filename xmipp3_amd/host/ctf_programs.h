@@ -22,11 +22,6 @@ inline void readCtfRow(const MetaDataVec &md, size_t id, xh_ctf_params &c)
     c.phase_shift = md.getDouble("ctfPhaseShift", id, 0); c.VPP_radius = md.getDouble("ctfVPPRadius", id, 0);
 }
 
-struct CtxGuard {
-    xh_ctx *c = nullptr;
-    ~CtxGuard() { if (c) xh_ctx_destroy(c); }
-};
-
 class ProgCTFPhaseFlipping : public XmippProgram {
 public:
     std::string fn_in, fn_out, fnt_ctf;
@@ -86,18 +81,18 @@ public:
         xh_ctf_params c;
         readCtfRow(md, 0, c);
         const double sampling = Tm < 0 ? c.Tm * downsampling : Tm;       // changeSamplingRate
-        CtxGuard g;
-        xhCheck(xh_ctx_create_private(device, &g.c));
+        xh_ctx *ctx = nullptr;
+        xhCheck(xh_ctx_create_private(device, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         {
             DeviceBuffer d;
-            d.reserve(g.c, img.size() * sizeof(float));
-            xhCheck(xh_memcpy_h2d(g.c, d.p, img.data(), img.size() * sizeof(float)));
+            d.reserve(ctx, img.size() * sizeof(float));
+            xhCheck(xh_memcpy_h2d(ctx, d.p, img.data(), img.size() * sizeof(float)));
             xh_ctfop *op = nullptr;
-            xhCheck(xh_ctfop_create(g.c, (int)I.y, (int)I.x, 1.0, &op));
-            const int rc = xh_ctfop_phase_flip(op, d.as<float>(), &c, sampling);
-            if (rc == XH_OK) xhCheck(xh_memcpy_d2h(g.c, img.data(), d.p, img.size() * sizeof(float)));
-            xh_ctfop_destroy(op);
-            xhCheck(rc);
+            xhCheck(xh_ctfop_create(ctx, (int)I.y, (int)I.x, 1.0, &op));
+            XhOwner<xh_ctfop> opOwner(op);
+            xhCheck(xh_ctfop_phase_flip(op, d.as<float>(), &c, sampling));
+            xhCheck(xh_memcpy_d2h(ctx, img.data(), d.p, img.size() * sizeof(float)));
         }
         std::vector<double> out(img.begin(), img.end());
         writeVolume(fn_out, out.data(), I.x, I.y, 1);
@@ -155,17 +150,18 @@ public:
         md.getValue("image", fn0, 0);
         const ImageInfo I0 = readInfo(fn0);
         const size_t per = I0.x * I0.y;
-        CtxGuard g;
-        xhCheck(xh_ctx_create_private(device, &g.c));
+        xh_ctx *ctx = nullptr;
+        xhCheck(xh_ctx_create_private(device, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         xh_ctfop *op = nullptr;
-        xhCheck(xh_ctfop_create(g.c, (int)I0.y, (int)I0.x, pad, &op));
-        struct OpGuard { xh_ctfop *o; ~OpGuard() { xh_ctfop_destroy(o); } } og{op};
+        xhCheck(xh_ctfop_create(ctx, (int)I0.y, (int)I0.x, pad, &op));
+        XhOwner<xh_ctfop> opOwner(op);
         // one device batch on the host at a time: every corrected batch goes into its slots of the output stack as soon as it is back
         // (the reference reads, filters and writes image by image; a set of 1e6 particles does not fit a host buffer)
         std::vector<float> hb((size_t)batch * per), one;
         StackWriter stack(fn_out, I0.x, I0.y, n);
         DeviceBuffer d;
-        d.reserve(g.c, (size_t)batch * per * sizeof(float));
+        d.reserve(ctx, (size_t)batch * per * sizeof(float));
         for (size_t b0 = 0; b0 < n; b0 += (size_t)batch) {
             const size_t m = std::min((size_t)batch, n - b0);
             std::vector<xh_ctf_params> ctfs(m);
@@ -178,9 +174,9 @@ public:
                 std::copy(one.begin(), one.end(), hb.begin() + k * per);
                 readCtfRow(md, b0 + k, ctfs[k]);        // ctf.readFromMdRow(rowIn), wiener2d.cpp:148
             }
-            xhCheck(xh_memcpy_h2d(g.c, d.p, hb.data(), m * per * sizeof(float)));
+            xhCheck(xh_memcpy_h2d(ctx, d.p, hb.data(), m * per * sizeof(float)));
             xhCheck(xh_ctfop_wiener2d(op, d.as<float>(), (int)m, ctfs.data(), sampling_rate, phase_flipped, isIsotropic, wiener_constant, correct_envelope));
-            xhCheck(xh_memcpy_d2h(g.c, hb.data(), d.p, m * per * sizeof(float)));
+            xhCheck(xh_memcpy_d2h(ctx, hb.data(), d.p, m * per * sizeof(float)));
             for (size_t k = 0; k < m; ++k) stack.write(b0 + k, hb.data() + k * per);
         }
         stack.finish();

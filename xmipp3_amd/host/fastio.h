@@ -38,6 +38,22 @@ namespace mc {
 
 inline void xhCheck(int rc) { if (rc != XH_OK) REPORT_ERROR(ERR_GPU, std::string("xmipp_hip: ") + xh_last_error()); }
 
+// Owner of a library handle: destroys it with the matching xh_*_destroy. A context must outlive the handles made on it: declare
+// its owner before theirs, so that it is destroyed after them.
+struct XhDestroy {
+    void operator()(xh_ctx *h) const { xh_ctx_destroy(h); }
+    void operator()(xh_pm *h) const { xh_pm_destroy(h); }
+    void operator()(xh_rf *h) const { xh_rf_destroy(h); }
+    void operator()(xh_rf2 *h) const { xh_rf2_destroy(h); }
+    void operator()(xh_fp *h) const { xh_fp_destroy(h); }
+    void operator()(xh_ctfop *h) const { xh_ctfop_destroy(h); }
+    void operator()(xh_fa *h) const { xh_fa_destroy(h); }
+    void operator()(xh_fft2d *h) const { xh_fft2d_destroy(h); }
+    void operator()(xh_align_sig *h) const { xh_align_sig_destroy(h); }
+    void operator()(xh_halves *h) const { xh_halves_destroy(h); }
+};
+template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
+
 inline double nowSeconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // f(g) for g < n, one host thread per g; the first exception is re-thrown on the caller's thread

@@ -193,8 +193,9 @@ public:
                                    << cropX << " x " << cropY << " of " << I.x << " x " << I.y << "\n";
         }
         if (verbose) std::cout << "Computing global alignment ...\n";
-        CtxGuard g;
-        xhCheck(xh_ctx_create_private(device, &g.c));
+        xh_ctx *ctx = nullptr;
+        xhCheck(xh_ctx_create_private(device, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         std::vector<double> sx(N), sy(N), initial, average;
         const int nC = cpX * cpY * cpT;
         std::vector<double> coeffsX(nC), coeffsY(nC), centers, patchShifts;
@@ -202,12 +203,12 @@ public:
         int ref = 0, Nsum = 0;
         {
             xh_fa *fa = nullptr;
-            xhCheck(xh_fa_create(g.c, (int)I.y, (int)I.x, Ts, maxResForCorrelation, &fa));
-            struct FaGuard { xh_fa *f; ~FaGuard() { xh_fa_destroy(f); } } fg{fa};
+            xhCheck(xh_fa_create(ctx, (int)I.y, (int)I.x, Ts, maxResForCorrelation, &fa));
+            XhOwner<xh_fa> faOwner(fa);
             // the warp's prefilter of the frames runs while the host fits the spline (not with --oavgInitial: its sum leaves the prefilter pass)
             if (!skipLocalAlignment && fnInitialAvg.empty() && (!fnAvg.empty() || !fnAligned.empty())) xhCheck(xh_fa_set_option(fa, "prefilter_ahead", 1));
             DeviceBuffer d_frames, d_dark, d_gain, d_out, d_sum, d_initial;
-            d_frames.reserve(g.c, (size_t)N * per * sizeof(float));
+            d_frames.reserve(ctx, (size_t)N * per * sizeof(float));
             // the frames are read a few ahead by their own threads while the one before them goes to the device (the reference loads
             // with a thread pool beside its two GPU streams, movie_alignment_correlation_gpu.cpp:667-691)
             // (frames of integer counts -- MRC modes 0, 1, 6 -- travel as they are and become floats on the device, xh_movie_frame_to_float)
@@ -223,16 +224,18 @@ public:
             // --bin: a frame is corrected (dark, gain) and binned on its way in (loadFrame + CUDAFlexAlignScale::runScaleIFT,
             // movie_alignment_correlation_gpu.cpp:667-691); everything after works on binned frames without dark / gain
             xh_fft2d *planRaw = nullptr, *planBin = nullptr;
-            struct PlanGuard { xh_fft2d **a, **b; ~PlanGuard() { if (*a) xh_fft2d_destroy(*a); if (*b) xh_fft2d_destroy(*b); } } planGuard{&planRaw, &planBin};
+            XhOwner<xh_fft2d> planRawOwner, planBinOwner;
             DeviceBuffer d_raw, d_counts;
             const size_t rawBytes = perRaw * Iraw.bytesPerPixel();
-            if (Iraw.mode != 2) d_counts.reserve(g.c, rawBytes);
+            if (Iraw.mode != 2) d_counts.reserve(ctx, rawBytes);
             if (doBin) {
-                xhCheck(xh_fft2d_create(g.c, (int)Iraw.y, (int)Iraw.x, &planRaw));
-                xhCheck(xh_fft2d_create(g.c, (int)I.y, (int)I.x, &planBin));
-                d_raw.reserve(g.c, perRaw * sizeof(float));
-                if (!dark.empty()) { d_dark.reserve(g.c, perRaw * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_dark.p, dark.data(), perRaw * sizeof(float))); }
-                if (!gain.empty()) { d_gain.reserve(g.c, perRaw * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_gain.p, gain.data(), perRaw * sizeof(float))); }
+                xhCheck(xh_fft2d_create(ctx, (int)Iraw.y, (int)Iraw.x, &planRaw));
+                planRawOwner.reset(planRaw);
+                xhCheck(xh_fft2d_create(ctx, (int)I.y, (int)I.x, &planBin));
+                planBinOwner.reset(planBin);
+                d_raw.reserve(ctx, perRaw * sizeof(float));
+                if (!dark.empty()) { d_dark.reserve(ctx, perRaw * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_dark.p, dark.data(), perRaw * sizeof(float))); }
+                if (!gain.empty()) { d_gain.reserve(ctx, perRaw * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_gain.p, gain.data(), perRaw * sizeof(float))); }
             }
             // four reader threads for the whole movie, reader w takes frames w, w + 4, ... (a thread per frame -- std::async -- opened and
             // parsed the stack anew for every frame: readImageRaw's header / stream cache is thread_local); a reader runs at most two
@@ -266,31 +269,31 @@ public:
                 { std::lock_guard<std::mutex> lk(rdM); consumed = n + 1; }
                 rdCv.notify_all();
                 float *dst = doBin ? d_raw.as<float>() : d_frames.as<float>() + (size_t)n * per;
-                if (Iraw.mode == 2) xhCheck(xh_memcpy_h2d(g.c, dst, cur.data(), rawBytes));
+                if (Iraw.mode == 2) xhCheck(xh_memcpy_h2d(ctx, dst, cur.data(), rawBytes));
                 else {
-                    xhCheck(xh_memcpy_h2d(g.c, d_counts.p, cur.data(), rawBytes));
-                    xhCheck(xh_movie_frame_to_float(g.c, d_counts.p, Iraw.mode, (int64_t)perRaw, dst));
+                    xhCheck(xh_memcpy_h2d(ctx, d_counts.p, cur.data(), rawBytes));
+                    xhCheck(xh_movie_frame_to_float(ctx, d_counts.p, Iraw.mode, (int64_t)perRaw, dst));
                 }
                 if (doBin)
-                    xhCheck(xh_movie_bin_frame(g.c, planRaw, planBin, d_raw.as<float>(), dark.empty() ? nullptr : d_dark.as<float>(), gain.empty() ? nullptr : d_gain.as<float>(),
+                    xhCheck(xh_movie_bin_frame(ctx, planRaw, planBin, d_raw.as<float>(), dark.empty() ? nullptr : d_dark.as<float>(), gain.empty() ? nullptr : d_gain.as<float>(),
                                                (int)Iraw.y, (int)Iraw.x, d_frames.as<float>() + (size_t)n * per, (int)I.y, (int)I.x));
             }
             if (!doBin) {
-                if (!dark.empty()) { d_dark.reserve(g.c, per * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_dark.p, dark.data(), per * sizeof(float))); }
-                if (!gain.empty()) { d_gain.reserve(g.c, per * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_gain.p, gain.data(), per * sizeof(float))); }
+                if (!dark.empty()) { d_dark.reserve(ctx, per * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_dark.p, dark.data(), per * sizeof(float))); }
+                if (!gain.empty()) { d_gain.reserve(ctx, per * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_gain.p, gain.data(), per * sizeof(float))); }
             }
             const float *pd = (dark.empty() || doBin) ? nullptr : d_dark.as<float>(), *pg = (gain.empty() || doBin) ? nullptr : d_gain.as<float>();
             if (cropX != I.x || cropY != I.y) {
                 // getCroppedFrame (:727-734): the correlations see the top-left window of every frame (and of dark / gain); everything after
                 // the global alignment works on the whole frames again
                 xh_fa *faCrop = nullptr;
-                xhCheck(xh_fa_create(g.c, (int)cropY, (int)cropX, Ts, maxResForCorrelation, &faCrop));
-                struct FaGuard2 { xh_fa *f; ~FaGuard2() { xh_fa_destroy(f); } } fg2{faCrop};
+                xhCheck(xh_fa_create(ctx, (int)cropY, (int)cropX, Ts, maxResForCorrelation, &faCrop));
+                XhOwner<xh_fa> faCropOwner(faCrop);
                 DeviceBuffer d_crop, d_dc, d_gc;
-                d_crop.reserve(g.c, (size_t)N * cropX * cropY * sizeof(float));
-                xhCheck(xh_movie_crop_frames(g.c, d_frames.as<float>(), N, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_crop.as<float>()));
-                if (pd) { d_dc.reserve(g.c, cropX * cropY * sizeof(float)); xhCheck(xh_movie_crop_frames(g.c, pd, 1, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_dc.as<float>())); }
-                if (pg) { d_gc.reserve(g.c, cropX * cropY * sizeof(float)); xhCheck(xh_movie_crop_frames(g.c, pg, 1, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_gc.as<float>())); }
+                d_crop.reserve(ctx, (size_t)N * cropX * cropY * sizeof(float));
+                xhCheck(xh_movie_crop_frames(ctx, d_frames.as<float>(), N, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_crop.as<float>()));
+                if (pd) { d_dc.reserve(ctx, cropX * cropY * sizeof(float)); xhCheck(xh_movie_crop_frames(ctx, pd, 1, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_dc.as<float>())); }
+                if (pg) { d_gc.reserve(ctx, cropX * cropY * sizeof(float)); xhCheck(xh_movie_crop_frames(ctx, pg, 1, (int)I.y, (int)I.x, (int)cropY, (int)cropX, d_gc.as<float>())); }
                 xhCheck(xh_fa_global_alignment(faCrop, d_crop.as<float>(), N, pd ? d_dc.as<float>() : nullptr, pg ? d_gc.as<float>() : nullptr, maxShift, nullptr, nullptr,
                                                sx.data(), sy.data(), &ref));
             } else
@@ -316,14 +319,14 @@ public:
             // applyShiftsComputeAverage (:479-570): every summed frame warped by the B-spline, the sums kept on the device
             if (wantAligned || wantAvg || wantInitial) {
                 if (wantAligned) {
-                    d_out.reserve(g.c, per * sizeof(float));
+                    d_out.reserve(ctx, per * sizeof(float));
                     // frame fi goes to slot fi - nfirst of the stack (tmp.write(fnAligned, frameOffset + 1, true, WRITE_REPLACE),
                     // movie_alignment_correlation_gpu.cpp:528,540): with --frameRangeSum inside --frameRange the leading slots stay empty
                     alignedStack.reset(new StackWriter(fnAligned, I.x, I.y, (size_t)(nlastSum - nfirst + 1)));
                 }
                 std::vector<float> host(per, 0.f);
-                if (wantAvg) { d_sum.reserve(g.c, per * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_sum.p, host.data(), per * sizeof(float))); }
-                if (wantInitial) { d_initial.reserve(g.c, per * sizeof(float)); xhCheck(xh_memcpy_h2d(g.c, d_initial.p, host.data(), per * sizeof(float))); }
+                if (wantAvg) { d_sum.reserve(ctx, per * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_sum.p, host.data(), per * sizeof(float))); }
+                if (wantInitial) { d_initial.reserve(ctx, per * sizeof(float)); xhCheck(xh_memcpy_h2d(ctx, d_initial.p, host.data(), per * sizeof(float))); }
                 if (!wantAligned) {
                     // only sums are asked for: the whole loop in one call
                     xhCheck(xh_fa_apply_bspline_frames(fa, d_frames.as<float>(), N, nfirstSum - nfirst, nlastSum - nfirst, pd, pg, coeffsX.data(), coeffsY.data(), cpX, cpY, cpT,
@@ -335,14 +338,14 @@ public:
                     xhCheck(xh_fa_apply_bspline(fa, d_frames.as<float>() + (size_t)off * per, pd, pg, coeffsX.data(), coeffsY.data(), cpX, cpY, cpT, N, off,
                                                 wantAligned ? d_out.as<float>() : nullptr, wantAvg ? d_sum.as<float>() : nullptr, wantInitial ? d_initial.as<float>() : nullptr));
                     if (wantAligned) {
-                        xhCheck(xh_memcpy_d2h(g.c, host.data(), d_out.p, per * sizeof(float)));
+                        xhCheck(xh_memcpy_d2h(ctx, host.data(), d_out.p, per * sizeof(float)));
                         alignedStack->write((size_t)off, host.data());
                     }
                     ++Nsum;
                 }
                 if (wantAligned) alignedStack->finish();
-                if (wantAvg) { xhCheck(xh_memcpy_d2h(g.c, host.data(), d_sum.p, per * sizeof(float))); average.assign(host.begin(), host.end()); }
-                if (wantInitial) { xhCheck(xh_memcpy_d2h(g.c, host.data(), d_initial.p, per * sizeof(float))); initial.assign(host.begin(), host.end()); }
+                if (wantAvg) { xhCheck(xh_memcpy_d2h(ctx, host.data(), d_sum.p, per * sizeof(float))); average.assign(host.begin(), host.end()); }
+                if (wantInitial) { xhCheck(xh_memcpy_d2h(ctx, host.data(), d_initial.p, per * sizeof(float))); initial.assign(host.begin(), host.end()); }
             }
         }
         // storeGlobalShifts (:364-396): the shift that should be applied is the negative of the estimated one
@@ -458,12 +461,13 @@ public:
         if (first < 0) first = 0;
         if (last < 0) last = (int)movie.size() - 1;
         if (last >= (int)movie.size() || last < first) REPORT_ERROR(ERR_ARG_INCORRECT, "--frameRange outside the movie");
-        CtxGuard g;
-        xhCheck(xh_ctx_create_private(device, &g.c));
+        xh_ctx *ctx = nullptr;
+        xhCheck(xh_ctx_create_private(device, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         std::vector<float> frame;
         ImageInfo I0;
         xh_fft2d *plan = nullptr;
-        struct PlanGuard { xh_fft2d **p; ~PlanGuard() { if (*p) xh_fft2d_destroy(*p); } } pg{&plan};
+        XhOwner<xh_fft2d> planOwner;
         DeviceBuffer d_frame;
         std::unique_ptr<StackWriter> stack;            // the frames keep their place in the stack (frame.write(fn, n + 1, ...)); one frame on the host at a time
         for (int n = 0; n <= last; ++n) {
@@ -474,15 +478,16 @@ public:
             readImage(fn, frame, I);
             if (!plan) {
                 I0 = I;
-                xhCheck(xh_fft2d_create(g.c, (int)I.y, (int)I.x, &plan));
-                d_frame.reserve(g.c, I.x * I.y * sizeof(float));
+                xhCheck(xh_fft2d_create(ctx, (int)I.y, (int)I.x, &plan));
+                planOwner.reset(plan);
+                d_frame.reserve(ctx, I.x * I.y * sizeof(float));
                 stack.reset(new StackWriter(fnOut, I.x, I.y, (size_t)(last + 1)));
             } else if (I.x != I0.x || I.y != I0.y) REPORT_ERROR(ERR_MULTIDIM_SIZE, "frames of different sizes in " + fnIn);
             const size_t per = I.x * I.y;
-            xhCheck(xh_memcpy_h2d(g.c, d_frame.p, frame.data(), per * sizeof(float)));
-            xhCheck(xh_movie_dose_filter(g.c, plan, d_frame.as<float>(), (int)I.y, (int)I.x, pixel_size, acceleration_voltage, (n * dose_per_frame) + pre_exposure_amount,
+            xhCheck(xh_memcpy_h2d(ctx, d_frame.p, frame.data(), per * sizeof(float)));
+            xhCheck(xh_movie_dose_filter(ctx, plan, d_frame.as<float>(), (int)I.y, (int)I.x, pixel_size, acceleration_voltage, (n * dose_per_frame) + pre_exposure_amount,
                                          ((n + 1) * dose_per_frame) + pre_exposure_amount));
-            xhCheck(xh_memcpy_d2h(g.c, frame.data(), d_frame.p, per * sizeof(float)));
+            xhCheck(xh_memcpy_d2h(ctx, frame.data(), d_frame.p, per * sizeof(float)));
             stack->write((size_t)n, frame.data());
         }
         if (stack) stack->finish();

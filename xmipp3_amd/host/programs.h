@@ -147,23 +147,13 @@ public:
     // one slot per device, each with the whole reference bank (particles are independent)
     struct Slot {
         int device = 0;
-        xh_ctx *ctx = nullptr;
-        xh_pm *pm = nullptr;
-        xh_rf *shifter = nullptr;   // only used for xh_rf_shift_images (previous shifts, APM:1228-1233)
+        XhOwner<xh_ctx> ctx;
+        XhOwner<xh_rf> shifter;     // only used for xh_rf_shift_images (previous shifts, APM:1228-1233)
+        XhOwner<xh_pm> pm;
         std::unique_ptr<BatchFeeder> feeder;   // loader threads + page-locked pieces + the two device batches (fastio.h)
     };
     std::vector<Slot> slots;
     int N = 0;
-
-    ~ProgAngularProjectionMatching() override
-    {
-        for (Slot &s : slots) {
-            s.feeder.reset();
-            if (s.pm) xh_pm_destroy(s.pm);
-            if (s.shifter) xh_rf_destroy(s.shifter);
-            if (s.ctx) xh_ctx_destroy(s.ctx);
-        }
-    }
 
     void defineParams() override
     {
@@ -362,22 +352,26 @@ public:
         runOnSlots(slots.size(), [&](size_t g) {
             Slot &s = slots[g];
             bindToDeviceNode(s.device);
-            xhCheck(xh_ctx_create_private(s.device, &s.ctx));
+            xh_ctx *ctx = nullptr;
+            xhCheck(xh_ctx_create_private(s.device, &ctx));
+            s.ctx.reset(ctx);
             // the loader (page-locking its pieces takes tens of ms) is set up beside the reference bank
             s.feeder.reset(new BatchFeeder);
             auto feederReady = std::async(std::launch::async, [&] {
                 s.feeder->create(s.device, dim, std::min((size_t)batch, DFexp.size()), std::max(1, hostThreads(readers) / (int)slots.size()), nullptr);
             });
             DeviceBuffer d_refs;
-            d_refs.reserve(s.ctx, refs.size() * sizeof(float));
-            xhCheck(xh_memcpy_h2d(s.ctx, d_refs.p, refs.data(), refs.size() * sizeof(float)));
-            xhCheck(xh_pm_create(s.ctx, (int)dim, Ri, Ro, (int)total_nr_refs, d_refs.as<float>(), Mctf.empty() ? nullptr : Mctf.data(), paddim, &s.pm));
+            d_refs.reserve(ctx, refs.size() * sizeof(float));
+            xhCheck(xh_memcpy_h2d(ctx, d_refs.p, refs.data(), refs.size() * sizeof(float)));
+            xh_pm *pm = nullptr;
+            xhCheck(xh_pm_create(ctx, (int)dim, Ri, Ro, (int)total_nr_refs, d_refs.as<float>(), Mctf.empty() ? nullptr : Mctf.data(), paddim, &pm));
+            s.pm.reset(pm);
             // which of two exactly equal correlation values wins follows the reference's worker threads (APM:631,1063-1108)
-            if (threads > 1) xhCheck(xh_pm_set_option(s.pm, "threads", (double)std::min(threads, 16)));
+            if (threads > 1) xhCheck(xh_pm_set_option(pm, "threads", (double)std::min(threads, 16)));
             feederReady.get();
         });
         int32_t nn;
-        xhCheck(xh_pm_info(slots[0].pm, &nn, nullptr, nullptr));
+        xhCheck(xh_pm_info(slots[0].pm.get(), &nn, nullptr, nullptr));
         N = nn;
         timing.bank += nowSeconds() - tb0;
     }
@@ -439,9 +433,9 @@ public:
         // APM:991-1192, batched and pipelined: reader threads + copy stream (fastio.h: BatchFeeder) fill batch k + 1, a worker
         // assembles the lists of batch k + 2 and another turns the matches of batch k - 1 into rows while the device is on
         // batch k. Row order and labels as APM:1149-1165.
-        xh_ctx *ctx = slot.ctx;
-        xh_pm *pm = slot.pm;
-        xh_rf *&shifter = slot.shifter;
+        xh_ctx *ctx = slot.ctx.get();
+        xh_pm *pm = slot.pm.get();
+        XhOwner<xh_rf> &shifter = slot.shifter;
         const size_t per = dim * dim, total = imagesToProcess.size(), B = (size_t)batch, nb = (total + B - 1) / B;
         if (!total) return;
         DeviceBuffer d_shifted, d_i32a, d_i32b, d_u8, d_f64;
@@ -536,10 +530,12 @@ public:
                     xh_rf_params p{};
                     p.imgSize = (int)dim; p.padding_proj = p.padding_vol = 2; p.max_resolution = 0.5;
                     p.blob_radius = 1.9; p.blob_order = 0; p.blob_alpha = 15; p.min_ctf = 0.01; p.sampling = 1;
-                    xhCheck(xh_rf_create(ctx, &p, &shifter));
+                    xh_rf *rf = nullptr;
+                    xhCheck(xh_rf_create(ctx, &p, &rf));
+                    shifter.reset(rf);
                 }
                 d_shifted.reserve(ctx, B * per * sizeof(float));
-                xhCheck(xh_rf_shift_images(shifter, d_imgs, cur.prevShift.data(), nullptr, (int)n, d_shifted.as<float>()));
+                xhCheck(xh_rf_shift_images(shifter.get(), d_imgs, cur.prevShift.data(), nullptr, (int)n, d_shifted.as<float>()));
                 d_imgs = d_shifted.as<float>();
             }
             d_i32a.reserve(ctx, B * K * 4); d_i32b.reserve(ctx, B * K * 4); d_u8.reserve(ctx, B * K); d_f64.reserve(ctx, B * 8 * 3);
@@ -624,22 +620,13 @@ public:
     size_t imgSize = 0;
     std::vector<double> R_repository;   // nsym x 9
     // one slot per device: its own context (stream), gridding handle and temp spaces; slot 0 finishes
-    struct Slot { int device = 0; xh_ctx *ctx = nullptr; xh_rf *rf = nullptr; xh_rf2 *rf2 = nullptr; std::unique_ptr<BatchFeeder> feeder; };
+    struct Slot { int device = 0; XhOwner<xh_ctx> ctx; XhOwner<xh_rf> rf; XhOwner<xh_rf2> rf2; std::unique_ptr<BatchFeeder> feeder; };
     std::vector<Slot> slots;
     // xmipp_reconstruct_fourier (ProgRecFourier, reconstruction/reconstruct_fourier.cpp): its own double-precision arithmetic on the
     // device (xh_rf2_*); NiterWeight = --iter (RF:44,96)
     bool rfArithmetic = false;
     int NiterWeight = 1;
 
-    ~ProgRecFourierAccel() override
-    {
-        for (Slot &s : slots) {
-            s.feeder.reset();
-            if (s.rf2) xh_rf2_destroy(s.rf2);
-            if (s.rf) xh_rf_destroy(s.rf);
-            if (s.ctx) xh_ctx_destroy(s.ctx);
-        }
-    }
     void setIO(const std::string &in, const std::string &out) { fn_in = in; fn_out = out; }
 
     void defineParams() override
@@ -762,15 +749,22 @@ public:
         runOnSlots(slots.size(), [&](size_t g) {
             Slot &s = slots[g];
             bindToDeviceNode(s.device);
-            xhCheck(xh_ctx_create_private(s.device, &s.ctx));
+            xh_ctx *ctx = nullptr;
+            xhCheck(xh_ctx_create_private(s.device, &ctx));
+            s.ctx.reset(ctx);
             // the loader (page-locking its pieces takes tens of ms) is set up beside the temp spaces
             s.feeder.reset(new BatchFeeder);
             auto feederReady = std::async(std::launch::async, [&] {
                 s.feeder->create(s.device, imgSize, std::min((size_t)batch, SF.size()), std::max(1, hostThreads(readers) / (int)slots.size()), nullptr);
             });
-            xhCheck(xh_rf_create(s.ctx, &p, &s.rf));       // (the double-precision program uses it for the shifts of readApplyGeo only)
-            if (rfArithmetic) xhCheck(xh_rf2_create(s.ctx, &p, NiterWeight, &s.rf2));
-            else xhCheck(xh_rf_reset(s.rf));
+            xh_rf *rf = nullptr;
+            xhCheck(xh_rf_create(ctx, &p, &rf));       // (the double-precision program uses it for the shifts of readApplyGeo only)
+            s.rf.reset(rf);
+            if (rfArithmetic) {
+                xh_rf2 *rf2 = nullptr;
+                xhCheck(xh_rf2_create(ctx, &p, NiterWeight, &rf2));
+                s.rf2.reset(rf2);
+            } else xhCheck(xh_rf_reset(rf));
             feederReady.get();
         });
         timing.setup += nowSeconds() - tc0;
@@ -796,13 +790,13 @@ public:
     {
         std::vector<xh_rf *> h;
         for (Slot &s : slots) {
-            xhCheck(xh_rf_mirror_and_crop(s.rf));
-            h.push_back(s.rf);
+            xhCheck(xh_rf_mirror_and_crop(s.rf.get()));
+            h.push_back(s.rf.get());
         }
         if (h.size() > 1) xhCheck(xh_rf_reduce(h.data(), (int)h.size()));
     }
 
-    void resetSpaces() { for (Slot &s : slots) xhCheck(xh_rf_reset(s.rf)); }
+    void resetSpaces() { for (Slot &s : slots) xhCheck(xh_rf_reset(s.rf.get())); }
 
     // the host's view of one device batch, assembled by a worker thread while the device is on the previous one
     struct BatchInput {
@@ -820,8 +814,8 @@ public:
         // loadImageThread/preloadBuffer + processBuffer (RFA:300-388,939-966), batched on the device: reader threads and a copy stream
         // bring batch k + 1 into HBM (fastio.h: BatchFeeder), a worker reads the metadata columns of batch k + 2, the device grids batch k;
         // nothing on this thread waits for the device inside the loop -- the copy stream waits, on the device, for the batch whose buffer it reuses
-        xh_ctx *ctx = slot.ctx;
-        xh_rf *rf = slot.rf;
+        xh_ctx *ctx = slot.ctx.get();
+        xh_rf *rf = slot.rf.get();
         const size_t per = imgSize * imgSize, B = (size_t)batch, total = last - first + 1, nb = (total + B - 1) / B;
         const bool hasCTF = useCTF && (SF.containsLabel("ctfModel") || SF.containsLabel("ctfDefocusU"));
         if (hasCTF && !SF.containsLabel("ctfDefocusU"))
@@ -894,7 +888,7 @@ public:
             // processBufferGPU in one call (RFG:417-473): FFT, CTF factor and modulator evaluated while the gridding records
             // are packed (no CTF planes, same records bit for bit as the three separate steps), insertion
             if (rfArithmetic)
-                xhCheck(xh_rf2_insert(slot.rf2, imgs, hasCTF ? cur.ctfs.data() : nullptr, cur.ang.data(), do_weights ? cur.w.data() : nullptr, (int)n,
+                xhCheck(xh_rf2_insert(slot.rf2.get(), imgs, hasCTF ? cur.ctfs.data() : nullptr, cur.ang.data(), do_weights ? cur.w.data() : nullptr, (int)n,
                                       R_repository.data(), (int)(R_repository.size() / 9), 0));
             else
                 xhCheck(xh_rf_insert_images(rf, imgs, hasCTF ? cur.ctfs.data() : nullptr, cur.ang.data(), do_weights ? cur.w.data() : nullptr, (int)n,
@@ -915,7 +909,7 @@ public:
     {
         const double t0 = nowSeconds();
         std::vector<double> vol(imgSize * imgSize * imgSize);
-        xhCheck(xh_rf_finish(slots[0].rf, vol.data()));
+        xhCheck(xh_rf_finish(slots[0].rf.get(), vol.data()));
         const double t1 = nowSeconds();
         writeVolume(out_name, vol.data(), imgSize, imgSize, imgSize);
         timing.finish += t1 - t0;
@@ -926,26 +920,26 @@ public:
     void gatherDouble()
     {
         if (slots.size() < 2) return;
-        const size_t nd = xh_rf2_state_doubles(slots[0].rf2);
+        const size_t nd = xh_rf2_state_doubles(slots[0].rf2.get());
         std::vector<double> host(nd);
         DeviceBuffer d0;
-        d0.reserve(slots[0].ctx, nd * sizeof(double));
+        d0.reserve(slots[0].ctx.get(), nd * sizeof(double));
         for (size_t g = 1; g < slots.size(); ++g) {
             DeviceBuffer dg;
-            dg.reserve(slots[g].ctx, nd * sizeof(double));
-            xhCheck(xh_rf2_state_export(slots[g].rf2, dg.as<double>()));
-            xhCheck(xh_memcpy_d2h(slots[g].ctx, host.data(), dg.p, nd * sizeof(double)));
-            xhCheck(xh_memcpy_h2d(slots[0].ctx, d0.p, host.data(), nd * sizeof(double)));
-            xhCheck(xh_rf2_state_import(slots[0].rf2, d0.as<double>(), 1));
-            xhCheck(xh_ctx_sync(slots[0].ctx));
-            xhCheck(xh_rf2_reset(slots[g].rf2));
+            dg.reserve(slots[g].ctx.get(), nd * sizeof(double));
+            xhCheck(xh_rf2_state_export(slots[g].rf2.get(), dg.as<double>()));
+            xhCheck(xh_memcpy_d2h(slots[g].ctx.get(), host.data(), dg.p, nd * sizeof(double)));
+            xhCheck(xh_memcpy_h2d(slots[0].ctx.get(), d0.p, host.data(), nd * sizeof(double)));
+            xhCheck(xh_rf2_state_import(slots[0].rf2.get(), d0.as<double>(), 1));
+            xhCheck(xh_ctx_sync(slots[0].ctx.get()));
+            xhCheck(xh_rf2_reset(slots[g].rf2.get()));
         }
     }
 
     // correctWeight (RF:836-990,1056-1101): the re-processing passes replay orientations, weights and symmetry only
     void correctWeightDouble()
     {
-        xh_rf2 *h = slots[0].rf2;
+        xh_rf2 *h = slots[0].rf2.get();
         xhCheck(xh_rf2_weights_step(h, 0));
         for (int it = 1; it < NiterWeight; ++it) {
             xhCheck(xh_rf2_weights_step(h, 1));
@@ -968,14 +962,14 @@ public:
     void finishDouble(const std::string &out_name)
     {
         std::vector<double> vol(imgSize * imgSize * imgSize);
-        xhCheck(xh_rf2_finish(slots[0].rf2, vol.data()));
+        xhCheck(xh_rf2_finish(slots[0].rf2.get(), vol.data()));
         writeVolume(out_name, vol.data(), imgSize, imgSize, imgSize);
     }
 
     void runDouble()
     {
         const size_t last = SF.size() - 1;
-        xh_rf2 *h = slots[0].rf2;
+        xh_rf2 *h = slots[0].rf2.get();
         if (fn_fsc.empty()) {
             processImages(0, last);
             gatherDouble();
@@ -984,7 +978,7 @@ public:
             // multiplies by the raw weights; kept -- and their Fourier volumes and weights summed for the final volume
             const size_t FSCIndex = last / 2, nd = xh_rf2_state_doubles(h);
             DeviceBuffer half1;
-            half1.reserve(slots[0].ctx, nd * sizeof(double));
+            half1.reserve(slots[0].ctx.get(), nd * sizeof(double));
             processImages(0, FSCIndex);
             gatherDouble();
             xhCheck(xh_rf2_state_export(h, half1.as<double>()));
@@ -1023,8 +1017,8 @@ public:
         // volumes and weights. The reference parks the halves in <root>_{1,2}_{Fourier,Weights}.vol and deletes
         // them afterwards; here they stay in device memory.
         const size_t FSCIndex = last / 2;
-        xh_ctx *ctx0 = slots[0].ctx;
-        xh_rf *rf0 = slots[0].rf;
+        xh_ctx *ctx0 = slots[0].ctx.get();
+        xh_rf *rf0 = slots[0].rf.get();
         const size_t bytes = sizeof(float) * xh_rf_cropped_floats(rf0);
         DeviceBuffer half1, half2;
         half1.reserve(ctx0, bytes);
@@ -1236,11 +1230,13 @@ public:
         const size_t D = vi.x;
         xh_ctx *ctx = nullptr;
         xhCheck(xh_ctx_create_private(device, &ctx));
-        struct Guard { xh_ctx *c; xh_fp *f = nullptr; ~Guard() { if (f) xh_fp_destroy(f); if (c) xh_ctx_destroy(c); } } guard{ctx};
+        XhOwner<xh_ctx> ctxOwner(ctx);
         DeviceBuffer d_vol, d_out;
         d_vol.reserve(ctx, vol.size() * sizeof(float));
         xhCheck(xh_memcpy_h2d(ctx, d_vol.p, vol.data(), vol.size() * sizeof(float)));
-        xhCheck(xh_fp_create(ctx, d_vol.as<float>(), (int)D, paddFactor, maxFrequency, 3, &guard.f));
+        xh_fp *fp = nullptr;
+        xhCheck(xh_fp_create(ctx, d_vol.as<float>(), (int)D, paddFactor, maxFrequency, 3, &fp));
+        XhOwner<xh_fp> fpOwner(fp);
         d_vol.release();
         const size_t total = nDir * (size_t)numberStepsPsi;
         std::vector<float> gallery(total * D * D);
@@ -1255,7 +1251,7 @@ public:
                 ang[3 * k + 1] = mysampling.no_redundant_sampling_points_angles[index][1];
                 ang[3 * k + 2] = psiIndex * psi_sampling + mysampling.no_redundant_sampling_points_angles[index][2];
             }
-            xhCheck(xh_fp_project(guard.f, ang.data(), (int)m, nullptr, d_out.as<float>()));
+            xhCheck(xh_fp_project(fp, ang.data(), (int)m, nullptr, d_out.as<float>()));
             xhCheck(xh_memcpy_d2h(ctx, gallery.data() + n0 * D * D, d_out.p, m * D * D * sizeof(float)));
         }
         d_out.release();
@@ -1364,7 +1360,7 @@ public:
         if (max_sam < 0) max_sam = 2 * sam;
         xh_ctx *ctx = nullptr;
         xhCheck(xh_ctx_create_private(device, &ctx));
-        struct Guard { xh_ctx *c; ~Guard() { if (c) xh_ctx_destroy(c); } } guard{ctx};
+        XhOwner<xh_ctx> ctxOwner(ctx);
         const size_t L = ri.x / 2 + 1;
         std::vector<double> freq(L), frc(L), frc_noise(L), dpr(L, 0.), error_l2(L);
         double rFactor = -1.;

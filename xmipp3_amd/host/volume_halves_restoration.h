@@ -136,11 +136,11 @@ public:
         }
 
         xh_ctx *ctx = nullptr;
-        struct CtxGuard { xh_ctx *&c; ~CtxGuard() { if (c) xh_ctx_destroy(c); } } cg{ctx};
         xhCheck(xh_ctx_create_private(0, &ctx));
+        XhOwner<xh_ctx> ctxOwner(ctx);
         xh_halves *h = nullptr;
         xhCheck(xh_halves_create(ctx, (int)Z, (int)Y, (int)X, &h));
-        struct Guard { xh_halves *&h; ~Guard() { xh_halves_destroy(h); } } hg{h};
+        XhOwner<xh_halves> hOwner(h);
         DeviceBuffer dV1, dV2, dMask, dOut;
         dV1.reserve(ctx, sizeof(double) * N);
         dV2.reserve(ctx, sizeof(double) * N);

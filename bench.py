@@ -19,14 +19,18 @@ buffers, the copy of batch k+1 on its own stream under step k -- is printed besi
 (`--timed streamed` makes it the timed region, as it was in rounds 3-4).  Weak scaling: per-GPU work is
 fixed as N grows.
 
-One JSON line on rank 0 (see the driver contract in the task statement), with
-  roofline      -- the kernel that dominates the timed region, algorithmic work / HIP-event time
+One JSON line on rank 0 (see the driver contract in the task statement).  A plain run does only what the headline needs:
+it sets up, warms up, times the steps, writes `--dump-outputs` and prints the line, with the figures the timed steps
+themselves recorded, among them
+  roofline      -- the kernel that dominates the timed region, algorithmic work / HIP-event time.
+Everything that takes runs of its own comes after the timed region and only with `--full`:
   worst_case    -- the same step with the data-dependent shortcuts of the matcher switched off
   value_streamed -- the same steps + finish with every batch H2D inside the clock
   match_only_leg -- the matching half alone (xh_pm_match + xh_pm_translate), the rate north_star's 2 M / 8 GPUs is stated for
-  noise_gallery / compact_phantom / flexalign -- the data dependence of the headline, and BASELINE config 5
+  noise_gallery / compact_phantom / flexalign / cli -- the data dependence of the headline, BASELINE config 5, the two programs
   cpu_baseline  -- the CPU oracle ("port" of the reference algorithm; Xmipp itself cannot be
-                   built here: xmippCore/FFTW absent) timed on a bounded sample on rank 0.
+                   built here: xmippCore/FFTW absent) timed on a bounded sample on rank 0, with the in-run parity samples.
+In flexalign mode `--full` adds the one-lane leg behind its roofline and stage_ms, the int8 leg and the CPU baseline.
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (fresh child processes, one per
 GPU, rendezvous on 127.0.0.1) and relays rank 0's line; under torchrun it reads RANK / LOCAL_RANK /
@@ -57,7 +61,10 @@ def parse(argv=None):
     ap.add_argument("--box", type=int, default=256, help="particle box D")
     ap.add_argument("--nrefs", type=int, default=1000)
     ap.add_argument("--batch", type=int, default=4096, help="particles per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run what takes runs of its own: the CPU baseline and "
+                    "parity samples, the other timed form, the worst-case / noise-gallery / compact-phantom / match-only / one-stream legs, "
+                    "the FlexAlign and program-level legs (child processes); in flexalign mode the one-lane leg, the int8 leg and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity samples")
     ap.add_argument("--cpu-sample", type=int, default=0, help="particles in the CPU sample (0 = auto)")
     ap.add_argument("--mode", default="full", choices=["full", "match", "grid", "flexalign"],
                     help="full / match / grid: the refine iteration or one half of it; flexalign: BASELINE config 5, one K3 movie per step "
@@ -90,10 +97,10 @@ def parse(argv=None):
     ap.add_argument("--timed", default="resident", choices=["resident", "streamed"],
                     help="what the timed region of `value` feeds on: resident = the batches lie in HBM when the clock starts (the task statement's contract: "
                          "the PCIe-inclusive rate is never `value`); streamed = every batch H2D from page-locked memory inside the timed region (SURVEY.md 8d's "
-                         "metric, `value` of rounds 3-4). The other one is printed beside it (`value_streamed` / `value_resident`)")
-    ap.add_argument("--no-flexalign", action="store_true", help="skip the FlexAlign leg (config 5, a child process) of the default line")
-    ap.add_argument("--no-cli", action="store_true", help="skip the program-level leg (tools/bench_cli.py, a child process) of the default line")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the worst-case and host-streaming legs after the timed region")
+                         "metric, `value` of rounds 3-4). With --full the other one is printed beside it (`value_streamed` / `value_resident`)")
+    ap.add_argument("--no-flexalign", action="store_true", help="with --full: skip the FlexAlign leg (config 5, a child process)")
+    ap.add_argument("--no-cli", action="store_true", help="with --full: skip the program-level leg (tools/bench_cli.py, a child process)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the legs after the timed region but the CPU baseline")
     ap.add_argument("--pipeline", type=int, default=1, help="1: the reconstruction half (shift, CTF, FFT, gridding) of batch k runs on a second "
                     "stream beside the matching of batch k+1")
     ap.add_argument("--stream-test", type=int, default=0, help="diagnosis of the host-traffic cost: 1 no result copies, 2 batches copied device to device, 3 host copies in 16 chunks")
@@ -424,7 +431,7 @@ def main_flexalign(args):
         elapsed = t.item()
     results = [r for ln in lanes for r in ln.results]
     counts_leg = None
-    if args.movie_mode == 2 and not args.no_extra_legs:
+    if args.full and args.movie_mode == 2 and not args.no_extra_legs:
         # the same movies as 8-bit counts (what a K3 writes; MRC mode 0): a quarter of the bytes cross the link, the cast runs on the device
         host8 = []
         for hb in host:
@@ -453,41 +460,27 @@ def main_flexalign(args):
             ln.src = host
         del host8
     stage_overlapped = {k_: float(sum(t.elapsed_ms() for ln in lanes for t in ln.timers[k_])) for k_ in lanes[0].timers}
-    # one lane alone, movies resident in HBM: what the host traffic and the second lane are worth, and the stages' own durations (the
-    # HIP-event times of the timed region include waiting for the other lane's kernels)
-    for ln in lanes:
-        ln.timers = {k_: [] for k_ in ln.timers}
-    nres = max(2, min(args.steps, 3))
-    if not lanes[0].filled[1]:
-        # (no more steps than lanes, warm-up and timed: lane 0 has seen one movie, and its second buffer was never written)
-        lanes[0].dbuf[1].copy_(lanes[0].dbuf[0])
-    barrier()
-    tr0 = time.perf_counter()
-    with torch.cuda.stream(lanes[0].stream):
-        for k in range(nres):
-            lanes[0].align(lanes[0].dbuf[k & 1], True, k & 1)
-    barrier()
-    resident = nres * world / (time.perf_counter() - tr0)
-    timers = lanes[0].timers
+    if args.full:
+        # one lane alone, movies resident in HBM: what the host traffic and the second lane are worth, and the stages' own durations (the
+        # HIP-event times of the timed region include waiting for the other lane's kernels)
+        for ln in lanes:
+            ln.timers = {k_: [] for k_ in ln.timers}
+        nres = max(2, min(args.steps, 3))
+        if not lanes[0].filled[1]:
+            # (no more steps than lanes, warm-up and timed: lane 0 has seen one movie, and its second buffer was never written)
+            lanes[0].dbuf[1].copy_(lanes[0].dbuf[0])
+        barrier()
+        tr0 = time.perf_counter()
+        with torch.cuda.stream(lanes[0].stream):
+            for k in range(nres):
+                lanes[0].align(lanes[0].dbuf[k & 1], True, k & 1)
+        barrier()
+        resident = nres * world / (time.perf_counter() - tr0)
+        timers = lanes[0].timers
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
-    stage = {k_: float(sum(t.elapsed_ms() for t in ts)) for k_, ts in timers.items()}      # of the one-lane resident leg: nres movies
-    # algorithmic bytes per movie of each stage: the global alignment reads every frame once and keeps the low-frequency columns of its
-    # transform (complex, nY x (nX / 2 + 1)); the local alignment reads every patch of every frame and of the two frames averaged with it;
-    # the warp reads a frame and writes (accumulates) a frame per frame
-    nY, nX = fa.new_dims
-    by = {"global_alignment": N * (Y * X * 4 + nY * (nX // 2 + 1) * 8),
-          "local_alignment": patches[0] * patches[1] * psize[0] * psize[1] * N * 3 * 4,
-          "warp_and_sum": N * Y * X * 8}
-    kern = {"global_alignment": "k_fft2d rows/columns of the frame transforms + pair correlations (xh_fa_global_alignment)",
-            "local_alignment": "k_fa_gather + k_fa_gemm_mfma + pair windows (xh_fa_local_alignment)",
-            "warp_and_sum": "k_fa_prefilter + k_fa_warp (xh_fa_apply_bspline, 40 frames)"}
-    dom = max(stage, key=lambda k_: stage[k_])
-    mk = lambda k_: {"kernel": kern[k_], "bound": "hbm", "achieved": nres * by[k_] / (stage[k_] * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                     "frac": nres * by[k_] / (stage[k_] * 1e-3) / 1e9 / 8000.0, "traffic": None, "ms_one_lane_leg": stage[k_], "movies_one_lane_leg": nres,
-                     "avg_ms_per_movie": stage[k_] / nres, "algorithmic_bytes_per_movie": by[k_]}
     # physics check of the timed movies: the drift that was put in comes out of the global alignment
     err = 0.0
     for u, gl in results:
@@ -503,15 +496,32 @@ def main_flexalign(args):
                       "host_traffic": f"every movie ({N * Y * X * host[0].element_size() / 1e9:.2f} GB of {str(raw_dtype).replace('torch.', '')} frames) H2D from page-locked memory inside the timed region (two device buffers, "
                                       "copy stream per lane), the aligned sum D2H", "lanes_per_gpu": nlanes, "HSA_ENABLE_SDMA": os.environ.get("HSA_ENABLE_SDMA", "unset"),
                       "parallelism": f"movie replicas x{world}, no exchange; {nlanes} movies in flight per GPU (host threads, one stream and library handle each)"},
-           "roofline": mk(dom), "roofline_other_kernels": {k_: mk(k_) for k_ in stage if k_ != dom},
-           "stage_ms": {k_: v / nres for k_, v in stage.items()},
-           "stage_ms_note": "per movie, HIP events of one lane alone on movies resident in HBM (the one-lane leg after the timed region); "
-                            "stage_ms_timed_region are the same events inside the timed region, per movie, where they include waiting for the other lanes' kernels",
            "stage_ms_timed_region": {k_: v / args.steps for k_, v in stage_overlapped.items()},
-           "value_resident_one_lane": resident, "global_shift_error_px": err}
+           "global_shift_error_px": err}
+    if args.full:
+        stage = {k_: float(sum(t.elapsed_ms() for t in ts)) for k_, ts in timers.items()}      # of the one-lane resident leg: nres movies
+        # algorithmic bytes per movie of each stage: the global alignment reads every frame once and keeps the low-frequency columns of its
+        # transform (complex, nY x (nX / 2 + 1)); the local alignment reads every patch of every frame and of the two frames averaged with it;
+        # the warp reads a frame and writes (accumulates) a frame per frame
+        nY, nX = fa.new_dims
+        by = {"global_alignment": N * (Y * X * 4 + nY * (nX // 2 + 1) * 8),
+              "local_alignment": patches[0] * patches[1] * psize[0] * psize[1] * N * 3 * 4,
+              "warp_and_sum": N * Y * X * 8}
+        kern = {"global_alignment": "k_fft2d rows/columns of the frame transforms + pair correlations (xh_fa_global_alignment)",
+                "local_alignment": "k_fa_gather + k_fa_gemm_mfma + pair windows (xh_fa_local_alignment)",
+                "warp_and_sum": "k_fa_prefilter + k_fa_warp (xh_fa_apply_bspline, 40 frames)"}
+        dom = max(stage, key=lambda k_: stage[k_])
+        mk = lambda k_: {"kernel": kern[k_], "bound": "hbm", "achieved": nres * by[k_] / (stage[k_] * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                         "frac": nres * by[k_] / (stage[k_] * 1e-3) / 1e9 / 8000.0, "traffic": None, "ms_one_lane_leg": stage[k_], "movies_one_lane_leg": nres,
+                         "avg_ms_per_movie": stage[k_] / nres, "algorithmic_bytes_per_movie": by[k_]}
+        out.update({"roofline": mk(dom), "roofline_other_kernels": {k_: mk(k_) for k_ in stage if k_ != dom},
+                    "stage_ms": {k_: v / nres for k_, v in stage.items()},
+                    "stage_ms_note": "per movie, HIP events of one lane alone on movies resident in HBM (the one-lane leg after the timed region); "
+                                     "stage_ms_timed_region are the same events inside the timed region, per movie, where they include waiting for the other lanes' kernels",
+                    "value_resident_one_lane": resident})
     if counts_leg:
         out["int8_frames_leg"] = counts_leg
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # the oracle's global alignment (ProgMovieAlignmentCorrelation<double>'s arithmetic, one thread) on the first 2 and the first 3 frames
         # of movie 0 at full size: T(n) = n t_frame + n (n - 1) / 2 t_pair, extrapolated to the movie's frames.  The local alignment and
         # the warp are NOT in it (the reference has no CPU form of the patch path): a lower bound of the CPU cost of a movie.
@@ -878,9 +888,9 @@ def main():
     k_ms, k_launches = rf.kernel_ms(reset=False) if rf is not None else (0.0, 0)
     stats_timed = pm.last_stats() if pm is not None else None
 
-    # ---- extra legs, outside the timed region (every rank runs them: same collectives, same barriers)
+    # ---- extra legs, outside the timed region, with --full only (every rank runs them: same collectives, same barriers)
     extra = {}
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         # (1) the same steps + finish fed the other way: what the host traffic costs is value_resident - value_streamed
         nres = max(2, min(args.steps, 4))
         nleg = max(2, args.steps)          # the same number of steps as `value`: both forms amortise the tail alike
@@ -1157,7 +1167,7 @@ def main():
     if pipelined:
         out["stage_ms_note"] = ("HIP-event times of the matcher's stages (prep32 ... translate_s6) and of gridding_insert_images are taken on two streams that "
                                 "share the device: they include WAITING for the other stream's kernels (k_rf_grid holds every CU), not work alone; "
-                                "one_stream_leg.matcher_stage_ms_per_step and one_stream_leg.k_rf_grid_avg_launch_ms are the same stages without a neighbour")
+                                "one_stream_leg.matcher_stage_ms_per_step and one_stream_leg.k_rf_grid_avg_launch_ms (--full) are the same stages without a neighbour")
     out.update(extra)
     if pm is not None:
         out["rescored_fraction"] = stats_timed["rescored_particles"] / float(B)
@@ -1169,7 +1179,7 @@ def main():
         out["s6_repeated_fraction"] = s6_rep[0] / float(max(1, args.steps * B))
 
     # ---- CPU baseline: the oracle on a bounded sample of the same workload, host cores of rank 0
-    if not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N=1 only
+    if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N=1 only
         from oracle import pyoracle as o
         ns = min(B, args.cpu_sample or (256 if D >= 256 else 512))
         ncores = o.lib().xo_num_threads()
@@ -1246,9 +1256,9 @@ def main():
             out["parity_volume_particles"] = nv
             with on_rf_stream():
                 rf.reset()
-    if args.mode == "full" and world == 1 and not args.no_extra_legs and not args.no_flexalign:
+    if args.full and args.mode == "full" and world == 1 and not args.no_extra_legs and not args.no_flexalign:
         out["flexalign"] = flexalign_leg()
-    if args.mode == "full" and world == 1 and not args.no_extra_legs and not args.no_cli:
+    if args.full and args.mode == "full" and world == 1 and not args.no_extra_legs and not args.no_cli:
         out["cli"] = cli_leg(D, nrefs, B)
     print(json.dumps(out))
     if world > 1:
@@ -1286,7 +1296,7 @@ def flexalign_leg():
     in flight) as a CHILD process -- its own runtime, its own contexts; nothing is exec'ed over this process's GPU state -- reduced to the
     figures a reader needs: movies/s and the three stages' times and roofline fractions."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--mode", "flexalign", "--steps", "12", "--warmup", "4", "--no-extra-legs"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--mode", "flexalign", "--steps", "12", "--warmup", "4", "--no-extra-legs"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -1301,7 +1311,7 @@ def flexalign_leg():
                 "stage_roofline_frac": fr,
                 "global_shift_error_px": d.get("global_shift_error_px"), "global_shift_error_bound_px": d.get("global_shift_error_bound_px"),
                 "parity_sample": d.get("parity_sample"), "cpu_baseline": d.get("cpu_baseline"),
-                "what": "`python bench.py --mode flexalign --steps 12 --warmup 4` (four movies in flight) run as a child process after the timed region of the refine iteration"}
+                "what": "`python bench.py --full --mode flexalign --steps 12 --warmup 4` (four movies in flight) run as a child process after the timed region of the refine iteration"}
     except Exception as e:      # the headline must not depend on this leg
         return {"error": repr(e)}
 

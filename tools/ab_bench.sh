@@ -10,7 +10,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do tags+=("$1"); shift; done
 for r in $(seq 1 $rounds); do
   for t in "${tags[@]}"; do
     lib=$root/xmipp3_amd/libxmipp_hip_$t.so; [ "$t" == "base" ] && lib=$root/xmipp3_amd/libxmipp_hip.so
-    XMIPP_HIP_LIB=$lib python3 bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "
+    XMIPP_HIP_LIB=$lib python3 bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 o=d.get('one_stream_leg',{})

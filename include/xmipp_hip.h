@@ -283,7 +283,12 @@ int xh_pm_last_coefficients(const xh_pm *pm, const float **d_coefs, int32_t *fir
 /* particles the last xh_pm_translate repeated in double precision: its first pass is fp32 and a particle whose arg-max
  * or window decision (FIL:1659-1689) comes within a margin of flipping is done again in the reference's arithmetic
  * (xh_pm_set_option "s6_fp32" 0: everything in double; "s6_eps": the margin, relative to the map's maximum -- default 6.4e-6,
- * twenty times the measured error of the fp32 map) */
+ * twenty times the measured error of the fp32 map). That error holds at any scale of particles and references: each image
+ * enters the packed transforms scaled by the power of two that brings its RMS into [0.5, 1), exactly undone on its map, so
+ * the supported range is an RMS within 2^-64 .. 2^64 of 1 for every particle and reference, in any ratio to each other
+ * (tests/test_gpu_pm_scale.py holds 1e-3 .. 1e3 either way). A particle whose pixels are all equal (unmirrored, or zero)
+ * or an all-zero reference gets the reference's shift for a constant map, (0, 0). Repeats are ordered: the same input gives
+ * the same bits from run to run. */
 int xh_pm_translate_stats(const xh_pm *pm, int64_t *repeated);
 /* statistics of the last xh_pm_match call: rows evaluated, particles re-scored in fp64 */
 int xh_pm_last_stats(const xh_pm *pm, int64_t *rows, int64_t *rescored_particles,

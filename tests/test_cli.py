@@ -439,11 +439,23 @@ def test_cli_gallery_then_matching(bins, tmp_path, oracle):
     """volume -> xmipp_angular_project_library (gallery + sampling files) -> xmipp_angular_projection_matching:
     the stack holds the FourierProjector's projections at the sampled directions (oracle parity), and particles
     projected at gallery directions are assigned back to them."""
+    _gallery_then_matching(bins, tmp_path, oracle, 1.0)
+
+
+@pytest.mark.gpu
+def test_cli_gallery_of_a_volume_at_another_scale_then_matching(bins, tmp_path, oracle):
+    """The same with the volume, and so the gallery, scaled by 1e-3 while the particles keep theirs (nothing in either program
+    normalises them): the same assignments, and shifts and maxCC equal to the oracle's on the gallery and particles read back."""
+    _gallery_then_matching(bins, tmp_path, oracle, 1e-3)
+
+
+def _gallery_then_matching(bins, tmp_path, oracle, vol_scale):
     D = 32
     vol = synth.phantom(D, seed=21, nblobs=12).astype(np.float32)
-    xmipp_io.write_volume(str(tmp_path / "in.vol"), vol)
+    xmipp_io.write_volume(str(tmp_path / "in.vol"), (vol * np.float32(vol_scale)).astype(np.float32))
     # experimental images: oracle projections at three sampled directions, rotated in plane
     fp = oracle.FP(vol, 2.0, 0.5, 3)
+    fpg = oracle.FP((vol * np.float32(vol_scale)).astype(np.float32), 2.0, 0.5, 3) if vol_scale != 1.0 else fp
     r = _run([os.path.join(bins, "xmipp_angular_project_library"), "-i", str(tmp_path / "in.vol"), "-o", str(tmp_path / "ref.stk"),
               "--sampling_rate", "20", "--sym", "c1", "--only_create_sampling"])
     assert r.returncode == 0, r.stderr
@@ -462,7 +474,7 @@ def test_cli_gallery_then_matching(bins, tmp_path, oracle):
     gallery = xmipp_io.read_stack(str(tmp_path / "ref.stk"))
     assert gallery.shape == (len(dirs), D, D)
     for k in (0, 1, 9, len(dirs) - 1):
-        exp = fp.project(dirs[k, 0], dirs[k, 1], 0.0)
+        exp = fpg.project(dirs[k, 0], dirs[k, 1], 0.0)
         assert np.abs(gallery[k] - exp).max() <= 3e-7 * np.abs(exp).max()
     r = _run([os.path.join(bins, "xmipp_angular_projection_matching"), "-i", str(tmp_path / "exp.xmd"), "-o", str(tmp_path / "out.xmd"),
               "--ref", str(tmp_path / "ref.stk"), "--max_shift", "3"])
@@ -485,6 +497,16 @@ def test_cli_gallery_then_matching(bins, tmp_path, oracle):
             d = abs(float(rw[oc["anglePsi"]]) - psi) % 360
             assert min(d, 360 - d) <= 360.0 / 90 + 1e-6      # within one step of the in-plane angular grid
         assert float(rw[oc["maxCC"]]) > 0.98
+    if vol_scale != 1.0:
+        # the translational search against the oracle at the program's own assignments
+        pm = oracle.PM(gallery)
+        ref = np.array([int(rw[oc["ref"]]) for rw in orow], np.int32)
+        psi = np.array([int(round(float(rw[oc["anglePsi"]]) / (360.0 / pm.N))) % pm.N for rw in orow], np.int32)
+        flip = np.array([int(rw[oc["flip"]]) for rw in orow], np.uint8)
+        ex, ey, ec = pm.translate(xmipp_io.read_stack(str(tmp_path / "exp.stk")), ref, psi, flip, 3.0)
+        for i, rw in enumerate(orow):
+            assert abs(float(rw[oc["shiftX"]]) - ex[i]) < 1e-3 and abs(float(rw[oc["shiftY"]]) - ey[i]) < 1e-3, (i, rw, ex[i], ey[i])
+            assert abs(float(rw[oc["maxCC"]]) - ec[i]) < 1e-5
 
 
 _CTF_COLS = ["ctfSamplingRate", "ctfVoltage", "ctfDefocusU", "ctfDefocusV", "ctfDefocusAngle", "ctfSphericalAberration", "ctfQ0", "ctfK"]

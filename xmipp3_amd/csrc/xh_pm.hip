@@ -107,10 +107,12 @@ struct xh_pm {
     XhBuf d_chirp, d_vhat;       // Bluestein: chirp[N], vhat[M] (bit-reversed, /M)
     XhBuf d_csN;                 // cos/sin(2 pi j / N) double, for the fp64 re-scorer
     XhBuf d_WD64;                // FFT twiddles W_D^j, j < D (double) for the register-blocked S6 kernels
+    XhBuf d_refScale;            // S6: per reference, int2 {balance exponent, blank} (k_pm_s6_norm)
     XhPlanBufs<double> planD;    // generic length-D line transform (S6 at the other sizes)
     // per-call scratch
     XhBuf d_coef32, d_polar32, d_A32, d_stat32;     // S1<float>
     XhBuf d_trAngles;                               // S6: cos / sin per particle
+    XhBuf d_trScale;                                // S6: int4 per particle (k_pm_s6_scale)
     XhBuf d_cellStart, d_cellSamples, d_cellOrg, d_cellData;    // k_pm_polar_cells: samples per image cell
     int ncells;
     XhBuf d_coef64, d_polar64, d_A64, d_stat64;     // S1<double> (ambiguous particles)
@@ -2123,6 +2125,104 @@ k_pm_idft_dump(const float4 *__restrict__ raw, float *__restrict__ out, const xh
     }
 }
 
+// =========================================================================== S6 balance
+// Two real images share one complex transform twice: z = Mref + i Mimg (forward), and P_a + i P_b (the inverse of two
+// particles' cross-power spectra, k_pm_tr_cols_pair / k_pm_s6f_cols_pair). The rounding of either half follows the size of
+// the larger one, so a map's error relative to its own peak grows with the ratio of a particle's scale to its reference's and
+// to its partner's -- and nothing normalises either (a gallery projected from a volume has the volume's scale): at a ratio
+// of 1e3 the fp32 map is off by ~6e-5 of its peak, ten times s6_eps. Every image therefore enters a transform multiplied by
+// the power of two 2^e that brings its RMS into [0.5, 1), and its map leaves multiplied by 2^-(e_ref + e_img): both steps
+// are exact, so a map is computed as that of unit-scale inputs (both halves of every packing of one size) whatever the
+// scales, and is returned at the scale of the input. z itself (statisticsAdjust, correlationIndex) stays unscaled.
+// Blank: the reference's correlation map of an image whose pixels are all equal, or of an all-zero reference, is constant;
+// statisticsAdjust makes it zero (sd == 0) and bestShift returns (0, 0) -- or, where the rounding of the reference's own sums
+// leaves sd != 0, a one-element window in the map's corner that max_shift (at most D / 2 by default) rejects. On the device
+// the packed partner leaves rounding in such a map and its arg-max lands anywhere, so the shift of a blank pair is (0, 0) by
+// an exact test (max == min) instead of by the map. A mirrored constant particle is not blank (its first column is zero).
+#ifndef XH_S6_EMAX
+#define XH_S6_EMAX 64        // |balance exponent| at most: a unit-RMS fp32 map stays far inside the normal range
+#endif
+__device__ __forceinline__ double d_block_max(double v, double *red)
+{
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wv] = v;
+    __syncthreads();
+    double t = red[0];
+    const int nw = (blockDim.x + 63) >> 6;
+    for (int i = 1; i < nw; ++i) t = fmax(t, red[i]);
+    return t;
+}
+// sum of squares, minimum and maximum of one image (a block); the exponent e with RMS * 2^e in [0.5, 1)
+template <typename T>
+__device__ void d_s6_norm(const T *__restrict__ img, int per, double *red, int &e, double &mn, double &mx)
+{
+    double s2 = 0, lo = 1.0e300, hi = -1.0e300;
+    int t0 = 0;
+    if constexpr (sizeof(T) == 4) {
+        // a particle: float4 loads, four of them in flight per thread (this pass reads every particle once more)
+        if ((per & 3) == 0 && ((uintptr_t)img & 15) == 0) {
+            const float4 *v4 = reinterpret_cast<const float4 *>(img);
+            const int n4 = per >> 2;
+            for (int b = threadIdx.x; b < n4; b += 4 * blockDim.x) {
+                float4 q[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) q[u] = b + u * (int)blockDim.x < n4 ? v4[b + u * blockDim.x] : make_float4(img[0], img[0], img[0], img[0]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (b + u * (int)blockDim.x >= n4) break;
+                    const double a = q[u].x, c = q[u].y, d = q[u].z, e4 = q[u].w;
+                    s2 += a * a + c * c + d * d + e4 * e4;
+                    lo = fmin(lo, fmin(fmin(a, c), fmin(d, e4)));
+                    hi = fmax(hi, fmax(fmax(a, c), fmax(d, e4)));
+                }
+            }
+            t0 = per;
+        }
+    }
+    for (int t = t0 + threadIdx.x; t < per; t += blockDim.x) {
+        const double v = (double)img[t];
+        s2 += v * v; lo = fmin(lo, v); hi = fmax(hi, v);
+    }
+    s2 = d_block_sum(s2, red);
+    mn = -d_block_max(-lo, red);
+    mx = d_block_max(hi, red);
+    const double rms = sqrt(s2 / per);
+    int ex = 0;
+    if (rms > 0 && rms < 1.0e300) frexp(rms, &ex);
+    e = min(max(-ex, -XH_S6_EMAX), XH_S6_EMAX);
+}
+// once per library: {exponent, blank} of every reference's B-spline coefficients (zero exactly when the reference is)
+__global__ void __launch_bounds__(256) k_pm_s6_norm_refs(const double *__restrict__ coef, int per, int2 *__restrict__ out)
+{
+    __shared__ double red[8];
+    int e;
+    double mn, mx;
+    d_s6_norm(coef + (size_t)blockIdx.x * per, per, red, e, mn, mx);
+    if (threadIdx.x == 0) out[blockIdx.x] = make_int2(e, mn == 0 && mx == 0);
+}
+// per batch: {exponent of the reference, exponent of the particle, blank, 0}
+__global__ void __launch_bounds__(256)
+k_pm_s6_scale(const float *__restrict__ parts, const int *__restrict__ refno, const unsigned char *__restrict__ flip,
+              const int2 *__restrict__ refScale, int per, int4 *__restrict__ out)
+{
+    __shared__ double red[8];
+    const int p = blockIdx.x, ref = refno[p];
+    if (ref < 0) {
+        if (threadIdx.x == 0) out[p] = make_int4(0, 0, 0, 0);
+        return;
+    }
+    int e;
+    double mn, mx;
+    d_s6_norm(parts + (size_t)p * per, per, red, e, mn, mx);
+    if (threadIdx.x == 0) {
+        const int2 r = refScale[ref];
+        const bool blank = r.y || (mn == mx && (!flip[p] || mx == 0));
+        out[p] = make_int4(r.x, e, blank ? 1 : 0, 0);
+    }
+}
+
 // =========================================================================== S6 (fp64)
 // Mref = rotate(BSPLINE3, ref, psi, DONT_WRAP) (APM:812); Mimg = mirrored particle (APM:820-828).
 // Packed as z = Mref + i*Mimg for one complex 2-D FFT.
@@ -2162,7 +2262,7 @@ struct XhTrPart { double s1, s2, maxv, secv; int maxi; };     // secv: the large
 // product FFT1 * conj(FFT2) * N from the packed spectrum Z (FFT of Mref + i Mimg), in place.
 // F1[k] = (Z[k] + conj(Z[-k]))/2, F2[k] = (Z[k] - conj(Z[-k]))/(2i); forward FFTs are /N in the
 // reference and the product is multiplied by N (xmippCore correlation_matrix) => net 1/N.
-__global__ void k_pm_crosspower(const xh_cd *__restrict__ Z, xh_cd *__restrict__ Pout, int D)
+__global__ void k_pm_crosspower(const xh_cd *__restrict__ Z, xh_cd *__restrict__ Pout, int D, const int4 *__restrict__ sc)
 {
     const int p = blockIdx.y;
     const int pix = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2175,9 +2275,19 @@ __global__ void k_pm_crosspower(const xh_cd *__restrict__ Z, xh_cd *__restrict__
     const xh_cd f2 = xh_cd{0.5 * (a.y + b.y), -0.5 * (a.x - b.x)};
     const double inv = 1.0 / ((double)D * (double)D);
     xh_cd r = xh_cmulc(f1, f2);
-    r.x *= inv;
-    r.y *= inv;
+    const int e = -(sc[p].x + sc[p].y);              // the balance of k_pm_s6_balance undone (exact)
+    r.x = ldexp(r.x * inv, e);
+    r.y = ldexp(r.y * inv, e);
     Pout[(size_t)p * D * D + pix] = r;
+}
+// w = 2^e_ref Mref + i 2^e_img Mimg: the balanced copy of z that the generic path transforms
+__global__ void k_pm_s6_balance(const xh_cd *__restrict__ z, xh_cd *__restrict__ w, const int4 *__restrict__ sc, int per)
+{
+    const int p = blockIdx.y;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= per) return;
+    const xh_cd v = z[(size_t)p * per + pix];
+    w[(size_t)p * per + pix] = xh_cd{ldexp(v.x, sc[p].x), ldexp(v.y, sc[p].y)};
 }
 
 // bestShift on the centred correlation map (FIL:1593-1719, mask == nullptr, maxShift == -1),
@@ -2190,7 +2300,8 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restrict__ zimg, const int *__restrict__ refno,
                const unsigned char *__restrict__ flip, int D, double maxShift, double *__restrict__ shiftX,
-               double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts)
+               double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts,
+               const int4 *__restrict__ sc)
 {
     __shared__ double red[8];
     __shared__ double sv[256];
@@ -2329,6 +2440,7 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
             if (SC != 0) { ox = XM / SC; oy = YM / SC; }
             if (!(maxShift > 0)) ox = oy = 0.;
             if (ox * ox + oy * oy > maxShift * maxShift) ox = oy = 0.;
+            if (sc[p].z) ox = oy = 0.;                  // blank: the reference's outcome for a constant map (see k_pm_s6_scale)
             sh[0] = ox; sh[1] = oy;
         }
 #undef MC
@@ -2427,7 +2539,7 @@ __global__ void __launch_bounds__(256)
 k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ zimg, const int *__restrict__ refno,
                       const unsigned char *__restrict__ flip, int D, double maxShift, double *__restrict__ shiftX,
                       double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts,
-                      unsigned char *__restrict__ flag, double eps)
+                      unsigned char *__restrict__ flag, double eps, const int4 *__restrict__ sc)
 {
     __shared__ double red[8];
     __shared__ double sv[256];
@@ -2521,6 +2633,7 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
         if (!(maxShift > 0)) ox = oy = 0.;
         if (maxShift > 0 && fabs(sqrt(ox * ox + oy * oy) - (double)maxShift) < 1e-3) f = 1;   // the rejection of APM:841-842 is a decision too
         if (ox * ox + oy * oy > maxShift * maxShift) ox = oy = 0.;
+        if (sc[p].z) { ox = oy = 0.; f = 0; }           // blank: decided exactly, no map involved
         flag[p] = f;
         sh[0] = ox; sh[1] = oy;
     }
@@ -2775,7 +2888,7 @@ template <int R1, int R2, bool PREBUILT = false>
 __global__ void __launch_bounds__(256)
 k_pm_tr_rows(const float *__restrict__ particles, const double *__restrict__ refCoef, const int *__restrict__ refno,
              const int *__restrict__ psi, const unsigned char *__restrict__ flip, xh_cd *__restrict__ z,
-             xh_cd *__restrict__ w, const xh_cd *__restrict__ WD, int N)
+             xh_cd *__restrict__ w, const xh_cd *__restrict__ WD, int N, const int4 *__restrict__ sc)
 {
     typedef TrGeom<R1, R2> G;
     constexpr int D = G::D;
@@ -2793,6 +2906,7 @@ k_pm_tr_rows(const float *__restrict__ particles, const double *__restrict__ ref
     const double minp = -cen, maxp = D - cen - 1;
     const float *img = particles + (size_t)p * D * D;
     const bool fl = flip[p] != 0;
+    const int eR = sc[p].x, eI = sc[p].y;              // the balance (k_pm_s6_scale): z stays unscaled, its transform is balanced
     if (PREBUILT) {              // z comes from k_pm_tr_build; all of the thread's elements in flight before the first store
         constexpr int NE = G::LN * D / 256;
         xh_cd in[NE];
@@ -2801,7 +2915,7 @@ k_pm_tr_rows(const float *__restrict__ particles, const double *__restrict__ ref
 #pragma unroll
         for (int u = 0; u < NE; ++u) {
             const int e = tid + 256 * u, l = e / D, j = e - l * D;
-            s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = in[u];
+            s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = xh_cd{ldexp(in[u].x, eR), ldexp(in[u].y, eI)};
         }
     } else
     for (int e = tid; e < G::LN * D; e += 256) {
@@ -2818,7 +2932,7 @@ k_pm_tr_rows(const float *__restrict__ particles, const double *__restrict__ ref
             } else out.y = (double)img[(size_t)i * D + j];
         }
         z[((size_t)p * D + i) * D + j] = out;
-        s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = out;
+        s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = xh_cd{ldexp(out.x, eR), ldexp(out.y, eI)};
     }
     __syncthreads();
     xh_cd v[G::RM];
@@ -2939,7 +3053,8 @@ k_pm_tr_cols_pair(xh_cd *__restrict__ w, const xh_cd *__restrict__ WD, int m)
 
 template <int R1, int R2>
 __global__ void __launch_bounds__(256)
-k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m)
+k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m,
+              const int4 *__restrict__ sc)
 {
     typedef TrGeom<R1, R2> G;
     constexpr int D = G::D;
@@ -2963,6 +3078,10 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
     if (tid < G::LN * R2) {
         const int l = tid / R2, n2 = tid - l * R2;
         tr_inv1<R1, R2>(v, s + l * G::LS, n2);
+        // the balance undone (exact): the maps at the scale of the input
+        const int ea = -(sc[p].x + sc[p].y), eb = -(sc[p2].x + sc[p2].y);
+#pragma unroll
+        for (int n1 = 0; n1 < R1; ++n1) v[n1] = xh_cd{ldexp(v[n1].x, ea), ldexp(v[n1].y, eb)};
         double *dst = Rout + ((size_t)p * D + row0 + l) * D;
 #pragma unroll
         for (int n1 = 0; n1 < R1; ++n1) dst[n1 * R2 + n2] = v[n1].x;
@@ -3012,7 +3131,7 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
 // fp32 pass of S6 (see xh_pm_translate): forward rows of the prebuilt z
 template <int R1, int R2>
 __global__ void __launch_bounds__(256)
-k_pm_s6f_rows(const xh_cf *__restrict__ z, xh_cf *__restrict__ w, const xh_cd *__restrict__ WD)
+k_pm_s6f_rows(const xh_cf *__restrict__ z, xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, const int4 *__restrict__ sc)
 {
     typedef TrGeom<R1, R2, float> G;
     constexpr int D = G::D;
@@ -3028,10 +3147,11 @@ k_pm_s6f_rows(const xh_cf *__restrict__ z, xh_cf *__restrict__ w, const xh_cd *_
         xh_cf in[NE];
 #pragma unroll
         for (int u = 0; u < NE; ++u) in[u] = z[((size_t)p * D + row0) * D + tid + 256 * u];      // LN consecutive rows: one run
+        const int eR = sc[p].x, eI = sc[p].y;          // the balance (k_pm_s6_scale)
 #pragma unroll
         for (int u = 0; u < NE; ++u) {
             const int e = tid + 256 * u, l = e / D, j = e - l * D;
-            s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = in[u];
+            s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = xh_cf{ldexpf(in[u].x, eR), ldexpf(in[u].y, eI)};
         }
     }
     __syncthreads();
@@ -3148,7 +3268,8 @@ k_pm_s6f_cols_pair(xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, int m)
 
 template <int R1, int R2, bool PAIR = false>
 __global__ void __launch_bounds__(256)
-k_pm_s6f_irows(const xh_cf *__restrict__ w, float *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m)
+k_pm_s6f_irows(const xh_cf *__restrict__ w, float *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m,
+               const int4 *__restrict__ sc)
 {
     typedef TrGeom<R1, R2, float> G;
     constexpr int D = G::D;
@@ -3172,6 +3293,10 @@ k_pm_s6f_irows(const xh_cf *__restrict__ w, float *__restrict__ Rout, const xh_c
     if (tid < G::LN * R2) {
         const int l = tid / R2, n2 = tid - l * R2;
         tr_inv1<R1, R2>(v, s + l * G::LS, n2);
+        // the balance undone (exact): the maps at the scale of the input
+        const int ea = -(sc[p].x + sc[p].y), eb = -(sc[p2].x + sc[p2].y);
+#pragma unroll
+        for (int n1 = 0; n1 < R1; ++n1) v[n1] = xh_cf{ldexpf(v[n1].x, ea), ldexpf(v[n1].y, eb)};
         float *dst = Rout + ((size_t)p * D + row0 + l) * D;
 #pragma unroll
         for (int n1 = 0; n1 < R1; ++n1) dst[n1 * R2 + n2] = v[n1].x;
@@ -3689,6 +3814,10 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
         }
         XH_CHECK(hipMemcpy(pm->d_refSigma.p, sig.data(), sizeof(double) * nrefs, hipMemcpyHostToDevice) == hipSuccess, XH_ERR_HIP,
                  "xh_pm_create: sigma upload failed");
+        // S6's balance exponent and blank test of every reference (k_pm_s6_norm_refs)
+        XH_TRY(xh_buf_alloc(ctx, pm->d_refScale, sizeof(int2) * nrefs));
+        hipLaunchKernelGGL(k_pm_s6_norm_refs, dim3(nrefs), dim3(256), 0, ctx->stream, (const double *)pm->d_refCoef.p, D * D, (int2 *)pm->d_refScale.p);
+        XH_CHECK(hipGetLastError() == hipSuccess, XH_ERR_HIP, "xh_pm_create: reference norms failed");
         {
             const size_t total = (size_t)nrefs * L.ncoef;
             hipLaunchKernelGGL(k_pm_pack_refs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -4270,10 +4399,26 @@ int xh_pm_match(xh_pm *pm, const float *d_particles, int32_t n, const int32_t *h
 // on an assumed 1e-6 --; 1.7 % of the bench's particles, 5.7 % before). Everyone else
 // keeps shifts that differ from the double-precision ones by the rounding of an fp32 sum (1e-5 px against the tolerance of
 // 1e-3 px the tests hold the fp64 path to).
-__global__ void k_pm_s6_list(const unsigned char *__restrict__ flag, int m, int *__restrict__ list, int *__restrict__ count)
+// The flagged particles in ascending order, by a prefix sum over the flags (one block): the repeat pairs the same particles, and
+// so gives the same bits, from run to run.
+__global__ void __launch_bounds__(1024) k_pm_s6_list(const unsigned char *__restrict__ flag, int m, int *__restrict__ list, int *__restrict__ count)
 {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < m && flag[p]) list[atomicAdd(count, 1)] = p;
+    __shared__ int sum[1024];
+    const int t = threadIdx.x, per = (m + 1023) / 1024, b = min(t * per, m), e = min(b + per, m);
+    int c = 0;
+    for (int p = b; p < e; ++p) c += flag[p] != 0;
+    sum[t] = c;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                    // inclusive scan
+        const int v = t >= o ? sum[t - o] : 0;
+        __syncthreads();
+        sum[t] += v;
+        __syncthreads();
+    }
+    int q = sum[t] - c;
+    for (int p = b; p < e; ++p)
+        if (flag[p]) list[q++] = p;
+    if (t == 1023) *count = sum[1023];
 }
 __global__ void __launch_bounds__(256)
 k_pm_s6_gather(const float *__restrict__ parts, const int *__restrict__ refno, const int *__restrict__ psi, const unsigned char *__restrict__ flip,
@@ -4326,12 +4471,15 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         XH_TRY(xh_buf_reserve(ctx, pm->d_t3, sizeof(double) * per * chunk));
         XH_TRY(xh_buf_reserve(ctx, pm->d_trAngles, sizeof(double2) * (size_t)chunk));
         XH_TRY(xh_buf_reserve(ctx, pm->d_trPart, sizeof(XhTrPart) * (size_t)chunk * 64));
+        XH_TRY(xh_buf_reserve(ctx, pm->d_trScale, sizeof(int4) * (size_t)chunk));
+        int4 *sc = (int4 *)pm->d_trScale.p;
         // the chain in double precision over m particles (the reference's arithmetic)
         auto chain64 = [&](const float *parts, const int *refno, const int *psi, const unsigned char *flip, int m, double *sx, double *sy,
                            double *cc) -> int {
             xh_cd *z = (xh_cd *)pm->d_t1.p, *w = (xh_cd *)pm->d_t2.p;
             double *R = (double *)pm->d_t3.p;
             int nparts = 0;
+            hipLaunchKernelGGL(k_pm_s6_scale, dim3(m), dim3(256), 0, ctx->stream, parts, refno, flip, (const int2 *)pm->d_refScale.p, (int)per, sc);
 #define XH_TR(A_, B_)                                                                                                       \
     {                                                                                                                       \
         typedef TrGeom<A_, B_> G;                                                                                           \
@@ -4347,11 +4495,11 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
                            (const double2 *)pm->d_trAngles.p, flip, z, D);                                                  \
         hipLaunchKernelGGL((k_pm_tr_rows<A_, B_, true>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream,                \
                            parts, (const double *)pm->d_refCoef.p, refno, psi,                                              \
-                           flip, z, w, (const xh_cd *)pm->d_WD64.p, L.N);                                                   \
+                           flip, z, w, (const xh_cd *)pm->d_WD64.p, L.N, (const int4 *)sc);                                 \
         hipLaunchKernelGGL((k_pm_tr_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
                            (const xh_cd *)pm->d_WD64.p, m);                                                                 \
         hipLaunchKernelGGL((k_pm_tr_irows<A_, B_>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream,     \
-                           (const xh_cd *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m);                \
+                           (const xh_cd *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m, (const int4 *)sc); \
         nparts = D / G::LN;                                                                                                 \
     }
             if (D == 64) XH_TR(8, 8)
@@ -4360,7 +4508,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
 #undef XH_TR
             XH_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_pm_bestshift<double>, dim3(m), dim3(256), 0, ctx->stream, (const double *)R, 1, (const xh_cd *)z, refno,
-                               flip, D, max_shift, sx, sy, cc, (const XhTrPart *)pm->d_trPart.p, nparts);
+                               flip, D, max_shift, sx, sy, cc, (const XhTrPart *)pm->d_trPart.p, nparts, (const int4 *)sc);
             XH_LAUNCH_CHECK();
             return XH_OK;
         };
@@ -4370,6 +4518,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
             xh_cf *z = (xh_cf *)pm->d_t1.p, *w = (xh_cf *)pm->d_t2.p;
             float *R = (float *)pm->d_t3.p;
             int nparts = 0;
+            hipLaunchKernelGGL(k_pm_s6_scale, dim3(m), dim3(256), 0, ctx->stream, parts, refno, flip, (const int2 *)pm->d_refScale.p, (int)per, sc);
 #define XH_TRF(A_, B_)                                                                                                      \
     {                                                                                                                       \
         typedef TrGeom<A_, B_, float> G;                                                                                    \
@@ -4378,11 +4527,11 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         hipLaunchKernelGGL((k_pm_tr_build<float, float>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream,   \
                            parts, (const float *)pm->d_refCoef32.p, refno, (const double2 *)pm->d_trAngles.p, flip, z, D);  \
         hipLaunchKernelGGL((k_pm_s6f_rows<A_, B_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const xh_cf *)z, w, \
-                           (const xh_cd *)pm->d_WD64.p);                                                                    \
+                           (const xh_cd *)pm->d_WD64.p, (const int4 *)sc);                                                  \
         hipLaunchKernelGGL((k_pm_s6f_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
                            (const xh_cd *)pm->d_WD64.p, m);                                                                 \
         hipLaunchKernelGGL((k_pm_s6f_irows<A_, B_, true>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream,    \
-                           (const xh_cf *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m);                \
+                           (const xh_cf *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m, (const int4 *)sc); \
         nparts = D / G::LN;                                                                                                 \
     }
             if (D == 64) XH_TRF(8, 8)
@@ -4391,7 +4540,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
 #undef XH_TRF
             XH_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const xh_cf *)z, refno, flip, D, max_shift, sx, sy, cc,
-                               (const XhTrPart *)pm->d_trPart.p, nparts, flag, pm->s6_eps);
+                               (const XhTrPart *)pm->d_trPart.p, nparts, flag, pm->s6_eps, (const int4 *)sc);
             XH_LAUNCH_CHECK();
             return XH_OK;
         };
@@ -4418,8 +4567,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
             int *list = (int *)pm->d_s6List.p, *count = list + chunk;
             XH_TRY(chain32(parts, d_refno + p0, d_psi + p0, d_flip + p0, m, d_sx + p0, d_sy + p0, d_cc + p0, flag));
             if (pm->s6_capture == 32) { pm->s6_captured = 32; pm->s6_capturedN = m; continue; }      // the coarse pass alone, no repeats
-            XH_HIP(hipMemsetAsync(count, 0, sizeof(int), ctx->stream));
-            hipLaunchKernelGGL(k_pm_s6_list, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, (const unsigned char *)flag, m, list, count);
+            hipLaunchKernelGGL(k_pm_s6_list, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned char *)flag, m, list, count);
             XH_LAUNCH_CHECK();
             int cnt = 0;
             XH_HIP(hipMemcpyAsync(&cnt, count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -4445,6 +4593,8 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
     }
     const XhPlan<double> &planD = pm->planD.plan;
     const int lpb = xh_plan_lpb(planD, 64 * 1024, 16);
+    XH_TRY(xh_buf_reserve(ctx, pm->d_trScale, sizeof(int4) * (size_t)chunk));
+    const int4 *sc = (const int4 *)pm->d_trScale.p;
     const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << planD.logM;
     for (int p0 = 0; p0 < n; p0 += chunk) {
         const int m = std::min(chunk, n - p0);
@@ -4452,8 +4602,10 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         hipLaunchKernelGGL(k_pm_rot_mirror, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream,
                            d_particles + (size_t)p0 * per, (const double *)pm->d_refCoef.p, d_refno + p0, d_psi + p0,
                            d_flip + p0, z, D, L.N);
+        hipLaunchKernelGGL(k_pm_s6_scale, dim3(m), dim3(256), 0, ctx->stream, d_particles + (size_t)p0 * per, d_refno + p0, d_flip + p0,
+                           (const int2 *)pm->d_refScale.p, (int)per, (int4 *)sc);
+        hipLaunchKernelGGL(k_pm_s6_balance, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream, (const xh_cd *)z, w, sc, (int)per);
         XH_LAUNCH_CHECK();
-        XH_HIP(hipMemcpyAsync(w, z, sizeof(xh_cd) * per * m, hipMemcpyDeviceToDevice, ctx->stream));
         const size_t nlines = (size_t)m * D;
         // forward 2-D FFT of w: rows (contiguous), then columns
         hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream,
@@ -4464,7 +4616,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         XH_LAUNCH_CHECK();
         XH_TRY(xh_buf_reserve(ctx, pm->d_t3, sizeof(xh_cd) * per * chunk));
         xh_cd *pw = (xh_cd *)pm->d_t3.p;
-        hipLaunchKernelGGL(k_pm_crosspower, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream, (const xh_cd *)w, pw, D);
+        hipLaunchKernelGGL(k_pm_crosspower, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream, (const xh_cd *)w, pw, D, sc);
         XH_LAUNCH_CHECK();
         hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream,
                            pw, planD, nlines, (size_t)1, (size_t)D, (size_t)0, (size_t)1, lpb);
@@ -4473,7 +4625,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
                            pw, planD, nlines, (size_t)D, per, (size_t)1, (size_t)D, lpb);
         XH_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_pm_bestshift<double>, dim3(m), dim3(256), 0, ctx->stream, (const double *)pw, 2, (const xh_cd *)z, d_refno + p0,
-                           d_flip + p0, D, max_shift, d_sx + p0, d_sy + p0, d_cc + p0, (const XhTrPart *)nullptr, 0);
+                           d_flip + p0, D, max_shift, d_sx + p0, d_sy + p0, d_cc + p0, (const XhTrPart *)nullptr, 0, sc);
         XH_LAUNCH_CHECK();
     }
     return XH_OK;

@@ -386,6 +386,20 @@ int xh_fft2d_factors(const xh_fft2d *f, int32_t *h_factors);
 int xh_fft2d_exec(xh_fft2d *f, float *d_data /* [ny][nx][2] */, int32_t inverse);
 int xh_fft2d_exec_axis(xh_fft2d *f, float *d_data, int32_t inverse, int32_t axis /* 0: rows only, 1: columns only; un-normalised */);
 
+/* ---- test hooks (used only by tests/ to check the transforms every module builds on, path by path) ----
+ * The LDS line transform of every separable FFT (xh_plan.h), un-normalised, in place on complex<float> (precision 32) or
+ * complex<double> (64): nlines lines of n points, line l starting at (l / inner) * outerStride + (l % inner) * innerStride, its
+ * elements elemStride apart (in complex elements); min(maxLines, 64 KB / line) lines per workgroup like the callers. A line whose
+ * LDS form does not fit 64 KB is refused (XH_ERR_UNSUPPORTED). Synchronous. */
+int xh_debug_fft_lines(xh_ctx *ctx, int32_t precision, int32_t n, void *d_data, size_t nlines, size_t inner, size_t outerStride,
+                       size_t innerStride, size_t elemStride, int32_t maxLines, int32_t inverse);
+/* FlexAlign's row pass of a real Y x X frame, (frame - dark) * gain, on a plan f = xh_fft2d_create(ctx, (Y + 1) / 2, X); dark / gain
+ * nullable. form 0: the packed rows row[2r] + i row[2r + 1] transformed as [(Y + 1) / 2][X] complex, frequency k of a row at
+ * n2 (k % n1) + k / n1; form 1: the nc lowest frequencies of every real row, [Y][nc] complex. h_info[3] = (n1, n2, done): done = 0
+ * when the plan's rows do not take that form (nothing written). Synchronous. */
+int xh_fft2d_debug_real_rows(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int32_t Y, int32_t nc,
+                             int32_t form, float *d_out, int32_t *h_info);
+
 /* ---- ProgRecFourier's own arithmetic: the program behind xmipp_reconstruct_fourier ----------
  * reconstruction/reconstruct_fourier.cpp: double accumulators, image-driven scatter into the FFTW-layout Fourier volume with
  * wrap and, beyond the half, the point-mirrored conjugated slot (RF:571-793), correctWeight with its re-processing passes

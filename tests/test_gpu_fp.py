@@ -16,8 +16,11 @@ def gpu():
     return xa, xa.Context(0), torch
 
 
-@pytest.mark.parametrize("D,padding,maxf", [(32, 2.0, 0.5), (32, 1.0, 0.25), (25, 2.0, 0.3)])
+@pytest.mark.parametrize("D,padding,maxf", [(32, 2.0, 0.5), (32, 1.0, 0.25), (25, 2.0, 0.3), (45, 1.0, 0.5), (49, 1.5, 0.4),
+                                             (96, 2.0, 0.5)])
 def test_coefficients_and_projections_match_the_oracle(gpu, oracle, D, padding, maxf):
+    """45 at padding 1 (odd image, odd padded volume: k_fp_center_split's (k + P/2) % P, no Nyquist row in k_fp_c2r_rows), 49 at
+    padding 1.5 (P = 73) and 96 at padding 2 (P = 192) next to the small boxes."""
     xa, ctx, torch = gpu
     vol = synth.phantom(D, seed=11, nblobs=9).astype(np.float32)
     o = oracle.FP(vol, padding, maxf, 3)
@@ -33,6 +36,22 @@ def test_coefficients_and_projections_match_the_oracle(gpu, oracle, D, padding, 
     for a, g in zip(ang, got):
         exp = o.project(*a)
         assert np.abs(g - exp).max() <= 3e-7 * np.abs(exp).max()        # float32 output
+
+
+def test_project_spanning_two_chunks(gpu):
+    """xh_fp_project cuts a call into chunks of 512 MB of half spectra (1016 projections at D = 256): 1100 projections in one call
+    (two chunks, the second short) are the same bits as the same angles in calls of 100. Every projection is computed alone, so
+    no oracle is needed."""
+    xa, ctx, torch = gpu
+    D = 256
+    g = torch.Generator(device="cuda").manual_seed(3)
+    vol = torch.randn((D, D, D), generator=g, device="cuda")
+    fp = xa.FourierProjector(ctx, vol, 1.0, 0.25, 3)
+    ang = synth.random_angles(1100, np.random.default_rng(7))
+    whole = fp.project(ang)
+    parts = torch.cat([fp.project(ang[i:i + 100]) for i in range(0, len(ang), 100)])
+    assert whole.shape == (1100, D, D) and bool(whole.abs().amax() > 0)
+    assert torch.equal(whole, parts)
 
 
 def test_ctf_multiplier_and_batching(gpu, oracle):

@@ -38,10 +38,14 @@ def test_tables_match_oracle(gpu, oracle):
         assert (rf.P, rf.mv) == (o.P, o.mv)
 
 
-@pytest.mark.parametrize("D,maxres", [(32, 0.5), (64, 0.5), (64, 0.3), (128, 0.5), (50, 0.5), (36, 0.4), (45, 0.5)])
+@pytest.mark.parametrize("D,maxres", [(32, 0.5), (64, 0.5), (64, 0.3), (128, 0.5), (50, 0.5), (36, 0.4), (45, 0.5),
+                                      (512, 0.15), (520, 0.15), (600, 0.15), (1024, 0.1)])
 def test_prepare_images(gpu, oracle, D, maxres):
     """D=64 and 128 take the register-blocked columns-first / rows-last FFT (radix 16 x 8, 16 x 16; 256 px: 16 x 32, in
-    test_gridding_at_full_size_against_the_oracle), D=32 the radix-2 LDS one, 50/36/45 (padded 100/72/90) Bluestein."""
+    test_gridding_at_full_size_against_the_oracle), D=32 the radix-2 LDS one, 50/36/45 (padded 100/72/90) Bluestein.
+    The largest boxes the gridder takes: 512 and 1024 (padded 1024 and 2048, radix 2, 8 and 4 lines per workgroup), 520 and 600
+    (padded 1040 and 1200: Bluestein lines of M = 4096, two per workgroup); a low max_resolution keeps the oracle's volume small,
+    the whole padded transform runs all the same."""
     xa, ctx, torch = gpu
     rng = np.random.default_rng(D)
     imgs = rng.standard_normal((5, D, D)).astype(np.float32)

@@ -157,6 +157,8 @@ SIGNATURES = {
     "xh_fft2d_factors": (C.c_int, [vp, vp]),
     "xh_fft2d_exec": (C.c_int, [vp, vp, i32]),
     "xh_fft2d_exec_axis": (C.c_int, [vp, vp, i32, i32]),
+    "xh_debug_fft_lines": (C.c_int, [vp, i32, i32, vp, sz, sz, sz, sz, sz, i32, i32]),
+    "xh_fft2d_debug_real_rows": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "xh_fp_create": (C.c_int, [vp, vp, i32, C.c_double, C.c_double, i32, pvp]),
     "xh_fp_destroy": (C.c_int, [vp]),
     "xh_fp_info": (C.c_int, [vp, vp, vp, vp]),

@@ -404,11 +404,47 @@ class Fft2D(_Handle):
         check(lib().xh_fft2d_factors(h, _np_ptr(f)))
         self.factors = tuple(int(v) for v in f)
 
-    def __call__(self, data, inverse=False):
+    def __call__(self, data, inverse=False, axis=None):
+        """Both axes (the inverse divided by ny nx), or one: axis 0 transforms the ny rows, axis 1 the nx columns (un-normalised
+        in both directions)."""
         torch = _torch()
         assert data.is_cuda and data.dtype == torch.complex64 and data.is_contiguous() and tuple(data.shape) == (self.ny, self.nx)
-        check(lib().xh_fft2d_exec(self.h, C.c_void_p(data.data_ptr()), int(bool(inverse))))
+        if axis is None:
+            check(lib().xh_fft2d_exec(self.h, C.c_void_p(data.data_ptr()), int(bool(inverse))))
+        else:
+            check(lib().xh_fft2d_exec_axis(self.h, C.c_void_p(data.data_ptr()), int(bool(inverse)), int(axis)))
         return data
+
+    # ---- test hook
+    def debug_real_rows(self, frame, dark=None, gain=None, form=0, nc=0, out=None):
+        """FlexAlign's row pass of a real [Y, X] frame on this plan (ny = (Y + 1) / 2, nx = X): form 0 -> ([ny, nx] complex64 in
+        the four-step order, (n1, n2, done)), form 1 -> ([Y, nc] complex64, (n1, n2, done)). `out`: a complex64 cuda tensor of at
+        least that many elements to write into."""
+        torch = _torch()
+        Y = frame.shape[0]
+        assert all(a is None or tuple(a.shape) == (Y, self.nx) for a in (frame, dark, gain))
+        shape = (self.ny, self.nx) if form == 0 else (Y, int(nc))
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.complex64, device=frame.device)
+        assert out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous() and out.numel() >= shape[0] * shape[1]
+        info = np.zeros(3, np.int32)
+        check(lib().xh_fft2d_debug_real_rows(self.h, _ptr(frame, torch.float32), _ptr(dark, torch.float32), _ptr(gain, torch.float32), int(Y),
+                                             int(nc), int(form), C.c_void_p(out.data_ptr()), _np_ptr(info)))
+        return out, tuple(int(v) for v in info)
+
+
+def debug_fft_lines(ctx, data, n, nlines, inner, outer_stride, inner_stride, elem_stride, max_lines=16, inverse=False):
+    """Test hook: xh_plan.h's line transform in place on a complex64 (fp32) or complex128 (fp64) cuda tensor, strides in complex
+    elements (xh_debug_fft_lines)."""
+    torch = _torch()
+    assert data.is_cuda and data.is_contiguous() and data.dtype in (torch.complex64, torch.complex128)
+    if nlines > 0:        # the last element any line reaches lies inside the tensor
+        last = (nlines - 1) // inner * outer_stride + (min(nlines, inner) - 1) * inner_stride + (n - 1) * elem_stride
+        assert last < data.numel(), "the lines reach beyond the tensor"
+    prec = 32 if data.dtype == torch.complex64 else 64
+    check(lib().xh_debug_fft_lines(ctx.h, prec, int(n), C.c_void_p(data.data_ptr()), int(nlines), int(inner), int(outer_stride),
+                                   int(inner_stride), int(elem_stride), int(max_lines), int(bool(inverse))))
+    return data
 
 
 class FlexAlign(_Handle):

@@ -648,3 +648,62 @@ int xh_fft2d_exec_axis(xh_fft2d *f, float *d_data, int32_t inverse, int32_t axis
 }
 
 }  // extern "C"
+
+// ---- test hooks: the line transform and FlexAlign's row entries on their own (tests/test_gpu_fft.py)
+namespace {
+template <typename T>
+int debug_fft_lines(xh_ctx *ctx, int n, xh_c2<T> *data, size_t nlines, size_t inner, size_t outerStride, size_t innerStride,
+                    size_t elemStride, int maxLines, bool inverse)
+{
+    XhPlanBufs<T> b;
+    XH_TRY(xh_plan_create<T>(ctx, n, b));
+    XH_CHECK((sizeof(xh_c2<T>) << b.plan.logM) <= 64 * 1024, XH_ERR_UNSUPPORTED,
+             "xh_debug_fft_lines: a line of %d points (%d in LDS) does not fit 64 KB", n, 1 << b.plan.logM);
+    if (nlines == 0) return XH_OK;
+    const int lpb = xh_plan_lpb(b.plan, 64 * 1024, maxLines);        // the rule of the callers
+    const size_t smem = ((size_t)lpb * sizeof(xh_c2<T>)) << b.plan.logM;
+    const unsigned grid = (unsigned)((nlines + lpb - 1) / lpb);
+    if (inverse)
+        hipLaunchKernelGGL((xh_k_fft_lines<T, true>), dim3(grid), dim3(256), smem, ctx->stream, data, b.plan, nlines, inner, outerStride,
+                           innerStride, elemStride, lpb);
+    else
+        hipLaunchKernelGGL((xh_k_fft_lines<T, false>), dim3(grid), dim3(256), smem, ctx->stream, data, b.plan, nlines, inner, outerStride,
+                           innerStride, elemStride, lpb);
+    XH_LAUNCH_CHECK();
+    XH_HIP(hipStreamSynchronize(ctx->stream));        // the plan's tables go with b
+    return XH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int xh_debug_fft_lines(xh_ctx *ctx, int32_t precision, int32_t n, void *d_data, size_t nlines, size_t inner, size_t outerStride,
+                       size_t innerStride, size_t elemStride, int32_t maxLines, int32_t inverse)
+{
+    XH_CHECK(ctx && d_data && (precision == 32 || precision == 64) && n >= 1 && inner >= 1 && maxLines >= 1, XH_ERR_ARG,
+             "xh_debug_fft_lines: bad argument");
+    XH_HIP(hipSetDevice(ctx->device));
+    if (precision == 32)
+        return debug_fft_lines<float>(ctx, n, (xh_cf *)d_data, nlines, inner, outerStride, innerStride, elemStride, maxLines, inverse != 0);
+    return debug_fft_lines<double>(ctx, n, (xh_cd *)d_data, nlines, inner, outerStride, innerStride, elemStride, maxLines, inverse != 0);
+}
+
+int xh_fft2d_debug_real_rows(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int32_t Y, int32_t nc, int32_t form,
+                             float *d_out, int32_t *h_info)
+{
+    XH_CHECK(f && h_info && (form == 0 || form == 1), XH_ERR_ARG, "xh_fft2d_debug_real_rows: bad argument");
+    h_info[0] = h_info[1] = h_info[2] = 0;
+    int n1 = 0, n2 = 0, done = 0;
+    if (form == 0) {
+        XH_TRY(xh_fft2d_rows_of_real_pairs(f, d_frame, d_dark, d_gain, Y, d_out, &n1, &n2));
+        done = n1 > 0;
+    } else {
+        XH_TRY(xh_fft2d_rows_of_real_pairs_kept(f, d_frame, d_dark, d_gain, Y, nc, d_out, &done));
+        n1 = f->ax.n1; n2 = f->ax.n2;
+    }
+    XH_HIP(hipStreamSynchronize(f->ctx->stream));
+    h_info[0] = n1; h_info[1] = n2; h_info[2] = done;
+    return XH_OK;
+}
+
+}  // extern "C"

@@ -131,8 +131,7 @@ typedef struct xh_rf xh_rf;
 
 int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out);
 int xh_rf_destroy(xh_rf *rf);
-/* profiling / A-B knobs of the reconstruction handle (defaults are the product path): "unit_z" 4 | 8 (depth of a wave's voxel unit in
- * k_rf_grid), "grid_waves" 0 (= the configuration's default) | 8 | 9 | 12 | 16, "ctf_fast" 1 | 0 (CTFs without envelope terms evaluated
+/* profiling / A-B knobs of the reconstruction handle (defaults are the product path): "ctf_fast" 1 | 0 (CTFs without envelope terms evaluated
  * by the cheap form of preloadCTF's value, or the general double-precision formula for every pixel), "order_spaces" 1 | 0 (the traverse
  * spaces of a launch ordered by plane -- the gridding kernel then shares the voxel queue between projections of one direction -- or in
  * input order; the order permutes the launch's float additions), "shift_bands" 1 | 0 (256-px images shifted band by band out of LDS, or

@@ -220,7 +220,7 @@ def test_iterative_alignment_on_the_reference_tests_population(gpu, oracle, nois
     chain: the SAME pose for every image -- except where a shift step met an arg-max tie: positions of the correlation map whose
     values, as the floats the reference compares (ShiftCorrEstimator<float>), lie within two ulps of the maximum.  Which of them
     wins in the reference is decided by the rounding of its float FFT; device and oracle both transform in double, with different
-    factorisations, and may round such a pair to either side.  For those images (`tools/diag_iterative.py`: 1-3 of 40, always in the
+    factorisations, and may round such a pair to either side.  For those images (`profiles/experiments/r05_diag_iterative.txt`: 1-3 of 40, always in the
     shift -> rotation half, whose first step correlates the still-rotated image) the device's pose must be one of the poses the
     oracle reaches when the ties are resolved either way (`oracle.es_iterative_reachable`)."""
     xa, ctx, torch = gpu

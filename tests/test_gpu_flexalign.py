@@ -317,6 +317,16 @@ def test_errors_are_loud(gpu):
         fa.global_alignment(torch.zeros((3, 256, 256), device="cuda"), 500.0)       # --maxShift beyond the reduced frame
 
 
+def test_retired_options_are_rejected(gpu):
+    """options of experiments that were measured and retired: FlexAlign no longer knows them; its documented options stay"""
+    xa, ctx, torch = gpu
+    from xmipp3_amd._lib import lib
+    fa = xa.FlexAlign(ctx, 256, 256, 1.0, 8.0)
+    assert lib().xh_fa_set_option(fa.h, b"mfma", 1.0) == -1      # XH_ERR_ARG
+    for name, default in [("window", 1), ("pruned_columns", 1), ("rows_kept", 1), ("pairwin_form", 1), ("prefilter_ahead", 0)]:
+        assert lib().xh_fa_set_option(fa.h, name.encode(), float(default)) == 0, name
+
+
 @pytest.mark.parametrize("N,Y,X,patches,psize,cp,avg", [(8, 384, 384, (5, 5), (128, 128), (3, 3, 3), 3), (6, 300, 420, (4, 5), (100, 90), (3, 4, 3), 1),
                                                         (5, 301, 423, (4, 4), (91, 120), (3, 3, 3), 2),
                                                         (6, 1024, 1100, (4, 4), (400, 380), (3, 3, 3), 3)])

@@ -870,6 +870,6 @@ def test_retired_options_are_rejected(gpu):
     xa, ctx, torch = gpu
     from xmipp3_amd._lib import lib
     rf = xa.RecFourier(ctx, 32)
-    for name in ["fft_variant", "records_from_images", "fuse_ctf", "skip_far_cells", "grid_tile_budget"]:
+    for name in ["fft_variant", "records_from_images", "fuse_ctf", "skip_far_cells", "grid_tile_budget", "unit_z", "grid_waves"]:
         assert lib().xh_rf_set_option(rf.h, name.encode(), 1.0) == -1, name      # XH_ERR_ARG
     assert lib().xh_rf_set_option(rf.h, b"order_spaces", 1.0) == 0

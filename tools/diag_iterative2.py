@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Second step of tools/diag_iterative.py: the shift -> rotation half, one round, by hand: where do device and oracle part ways?"""
+"""Where do xh_iterative_alignment and the oracle part ways (profiles/experiments/r05_diag_iterative.txt: only in the shift -> rotation
+half)?  That half, one round, by hand."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

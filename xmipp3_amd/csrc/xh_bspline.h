@@ -78,9 +78,10 @@ __global__ void k_pm_prefilter_cols(T *__restrict__ coefs, int D, int nslots, co
 // The recursive filter (pole z = sqrt(3)-2, half-sample-symmetric boundary; k_pm_prefilter_rows/cols)
 // is, exactly, the convolution of the mirror-extended samples with h[j] = sqrt(3) z^|j|. The recursion is
 // a 2*D-step dependent chain per line (latency-bound: 1.5 us per 256-px image); z^17 < 2e-10 is below
-// fp32 resolution, so the fp32 users (coarse matching pass, image shifts before gridding) use the 33-tap
-// form, every output independent, eight outputs per thread from one 40-sample window. The fp64 paths
-// (reference library, re-scoring) use the 65-tap form below; the gallery projector keeps the recursion.
+// fp32 resolution, so fp32 can use the 33-tap form, every output independent, eight outputs per thread
+// from one 40-sample window (the coarse matching pass and the image shifts before gridding run the tile
+// recursion below instead, FlexAlign's frames under 32 pixels the convolution). The fp64 paths (reference
+// library, re-scoring) use the 65-tap form below; the gallery projector keeps the recursion.
 #define XH_FIR_K 16
 #ifndef XH_FIR_V
 #define XH_FIR_V 8
@@ -252,82 +253,9 @@ static inline XhFir xh_fir_taps()
     return F;
 }
 
-// Both passes in one kernel: a block owns XH_FIR2D_V rows x XH_FIR_TW columns of an image. Its threads first filter down the
-// columns (thread <-> column, 40-row window, coalesced; the 16 columns either side of the tile too, mirrored at the image
-// border) into an LDS tile, then along the rows out of LDS (thread <-> 8 outputs of one row). The image is read once and
-// written once; the two-kernel form above wrote and re-read the row-filtered intermediate.
-#define XH_FIR_TW 256
-#ifndef XH_FIR2D_V
-#define XH_FIR2D_V 32        // tile rows of the two-pass kernel: 64 rows read per 32 written (8: 40 per 8; prep32 4.5 -> 4.2 ms per 4096 particles)
-#endif
-template <int TW>
-__global__ void __launch_bounds__(256)
-k_pm_prefilter_fir2d(const float *__restrict__ in, float *__restrict__ out, int D, int tilesX, XhFir F)
-{
-    __shared__ __align__(16) float tile[XH_FIR2D_V][XH_FIR_TW + 2 * XH_FIR_K];
-    const int ty = blockIdx.x / tilesX, tx = blockIdx.x - ty * tilesX;
-    const int x0 = tx * XH_FIR_TW, y0 = ty * XH_FIR2D_V;
-    const size_t base = (size_t)blockIdx.y * D * D;
-    const float *src = in + base;
-    for (int xx = threadIdx.x; xx < XH_FIR_TW + 2 * XH_FIR_K; xx += 256) {
-        int p = x0 + xx - XH_FIR_K;
-        if (p >= D + XH_FIR_K) break;                   // beyond the halo of the last, partial tile
-        // half-sample-symmetric extension: -1-i <-> i, D+i <-> D-1-i (repeated for tiny images)
-        while (p < 0 || p >= D) p = p < 0 ? -1 - p : 2 * D - 1 - p;
-        float w[XH_FIR2D_V + 2 * XH_FIR_K];
-#pragma unroll
-        for (int i = 0; i < XH_FIR2D_V + 2 * XH_FIR_K; ++i) {
-            int q = y0 + i - XH_FIR_K;
-            while (q < 0 || q >= D) q = q < 0 ? -1 - q : 2 * D - 1 - q;
-            w[i] = src[(size_t)q * D + p];
-        }
-#pragma unroll
-        for (int o = 0; o < XH_FIR2D_V; ++o) {
-            float acc = F.h[0] * w[o + XH_FIR_K];
-#pragma unroll
-            for (int j = 1; j <= XH_FIR_K; ++j) acc += F.h[j] * (w[o + XH_FIR_K - j] + w[o + XH_FIR_K + j]);
-            tile[o][xx] = acc;
-        }
-    }
-    __syncthreads();
-    // rows: 256 threads cover 256 / (TW / 8) = 8 tile rows at a time
-    constexpr int RPP = 256 / (XH_FIR_TW / 8);
-    const int seg = threadIdx.x % (XH_FIR_TW / 8);
-    const int xo = x0 + seg * 8;
-    if (xo >= D) return;
-#pragma unroll
-    for (int r = threadIdx.x / (XH_FIR_TW / 8); r < XH_FIR2D_V; r += RPP) {
-        const int y = y0 + r;
-        if (y >= D) break;
-        float w[8 + 2 * XH_FIR_K];
-        const float4 *t4 = reinterpret_cast<const float4 *>(&tile[r][seg * 8]);
-#pragma unroll
-        for (int i = 0; i < (8 + 2 * XH_FIR_K) / 4; ++i) {
-            const float4 q = t4[i];
-            w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
-        }
-        float res[8];
-#pragma unroll
-        for (int o = 0; o < 8; ++o) {
-            float acc = F.h[0] * w[o + XH_FIR_K];
-#pragma unroll
-            for (int j = 1; j <= XH_FIR_K; ++j) acc += F.h[j] * (w[o + XH_FIR_K - j] + w[o + XH_FIR_K + j]);
-            res[o] = acc;
-        }
-        float *dst = out + base + (size_t)y * D + xo;
-        if ((D & 3) == 0 && xo + 8 <= D) {
-            reinterpret_cast<float4 *>(dst)[0] = make_float4(res[0], res[1], res[2], res[3]);
-            reinterpret_cast<float4 *>(dst)[1] = make_float4(res[4], res[5], res[6], res[7]);
-        } else
-#pragma unroll
-            for (int o = 0; o < 8; ++o)
-                if (xo + o < D) dst[o] = res[o];
-    }
-}
-
 // ---- the same filter in its recursive form, tile by tile ---------------------------------------------------------------
-// The 33-tap convolution costs 33 operations per output and axis (k_pm_prefilter_fir2d: 66 vector instructions per pixel, its
-// row pass reading LDS with 32-byte lane strides). The recursion costs three -- c+[k] = s[k] + z c+[k-1] forwards,
+// The 33-tap convolution costs 33 operations per output and axis (both passes in one kernel through an LDS tile: 66 vector
+// instructions per pixel, its row pass reading LDS with 32-byte lane strides). The recursion costs three -- c+[k] = s[k] + z c+[k-1] forwards,
 // c[k] = z (c[k+1] - c+[k]) backwards -- and a thread may enter it anywhere: whatever it starts from is forgotten as z^k
 // (0.268^14 = 1e-8, below fp32 resolution), so XH_REC_K = 14 warm-up samples either side of a run of 32 outputs give
 // (32 + 28) + 2 (32 + 14) + 32 = 184 operations per 32 outputs, 5.8 per pixel and axis, on the same mirror-extended samples
@@ -338,6 +266,7 @@ k_pm_prefilter_fir2d(const float *__restrict__ in, float *__restrict__ out, int 
 #define XH_REC_K 14
 #define XH_REC_V 32
 #define XH_REC_S 324
+#define XH_FIR_TW 256
 template <int TW>
 __global__ void __launch_bounds__(256)
 k_pm_prefilter_rec2d(const float *__restrict__ in, float *__restrict__ out, int D, int tilesX)
@@ -533,32 +462,14 @@ k_pm_prefilter_rec64_2d(const TIN *__restrict__ in, double *__restrict__ out, in
     }
 }
 
-// which form xh_prefilter_fir_launch runs: 1 the recursion tile by tile (k_pm_prefilter_rec2d), 0 the 33-tap convolution
-// (k_pm_prefilter_fir2d); XH_PREFILTER_FORM in the environment picks for A/B runs
-static inline int xh_prefilter_form()
-{
-    static const int form = [] { const char *e = xh_debug_env("XH_PREFILTER_FORM"); return e ? atoi(e) : 1; }();
-    return form;
-}
-
 // n images [n][D][D]: in -> out (must not alias)
 static inline void xh_prefilter_fir_launch(hipStream_t stream, const float *in, float *out, int D, size_t n)
 {
-    if (xh_prefilter_form() == 1) {
-        const int tilesX = (D + XH_FIR_TW - 1) / XH_FIR_TW, tilesY = (D + XH_REC_V - 1) / XH_REC_V;
-        const size_t img = (size_t)D * D;
-        for (size_t i0 = 0; i0 < n; i0 += 65535) {
-            const unsigned m = (unsigned)std::min<size_t>(65535, n - i0);
-            hipLaunchKernelGGL((k_pm_prefilter_rec2d<XH_FIR_TW>), dim3(tilesX * tilesY, m), dim3(256), 0, stream, in + i0 * img, out + i0 * img, D, tilesX);
-        }
-        return;
-    }
-    const XhFir F = xh_fir_taps();
-    const int tilesX = (D + XH_FIR_TW - 1) / XH_FIR_TW, tilesY = (D + XH_FIR2D_V - 1) / XH_FIR2D_V;
+    const int tilesX = (D + XH_FIR_TW - 1) / XH_FIR_TW, tilesY = (D + XH_REC_V - 1) / XH_REC_V;
     const size_t img = (size_t)D * D;
     for (size_t i0 = 0; i0 < n; i0 += 65535) {
         const unsigned m = (unsigned)std::min<size_t>(65535, n - i0);
-        hipLaunchKernelGGL((k_pm_prefilter_fir2d<XH_FIR_TW>), dim3(tilesX * tilesY, m), dim3(256), 0, stream, in + i0 * img, out + i0 * img, D, tilesX, F);
+        hipLaunchKernelGGL((k_pm_prefilter_rec2d<XH_FIR_TW>), dim3(tilesX * tilesY, m), dim3(256), 0, stream, in + i0 * img, out + i0 * img, D, tilesX);
     }
 }
 

@@ -352,11 +352,8 @@ int xh_iterative_alignment(xh_ctx *ctx, const float *d_ref, const float *d_other
         return r2;
     };
     std::vector<float> pRS, mRS, pSR, mSR;
-    // test hook (tools/diag_iterative.py): XH_ES_ORDER=RS / SR returns that half of compute() alone
-    const char *only = xh_debug_env("XH_ES_ORDER");
-    XH_TRY(pass(!(only && !strcmp(only, "SR")), pRS, mRS));
-    if (only) { pSR = pRS; mSR = mRS; }
-    else XH_TRY(pass(false, pSR, mSR));
+    XH_TRY(pass(true, pRS, mRS));
+    XH_TRY(pass(false, pSR, mSR));
     for (int j = 0; j < n; ++j) {
         const bool sr = mRS[j] < mSR[j];
         h_merit[j] = sr ? mSR[j] : mRS[j];

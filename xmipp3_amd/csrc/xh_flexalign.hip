@@ -24,7 +24,6 @@
 #include <map>
 #include <string>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -491,30 +490,20 @@ __global__ void __launch_bounds__(256) k_fa_pairwin_b(const fa_cf *__restrict__ 
 }
 
 // ---- local (patch) alignment: computeLocalAlignment, movie_alignment_correlation_gpu.cpp:288-430 ------------------------------
-// One patch position at a time, all N frames of it:
-//   k_fa_gather      the patch window of every frame at the frame's rounded global shift, dark / gain applied (getPatchData, :166-202)
-//   k_fa_gemm        the part of the patch spectrum the correlation keeps, as two pruned DFTs written as matrix products:
+// A batch of patch positions at a time, all N frames of each:
+//   k_fa_gemm_mfma   the part of the patch spectrum the correlation keeps, as two pruned DFTs written as matrix products:
 //                    along x for the cxh = C/2+1 kept columns, along y for the C kept rows (performFFTAndScale /
 //                    scaleFFT2DKernel, cuda_flexalign_scale.cpp:58-77 + cuda_gpu_movie_alignment_correlation_kernels.cu, take an
-//                    FFT of P x P and drop all but C x cxh values: 58 x 114 of 251 x 500 at the defaults)
+//                    FFT of P x P and drop all but C x cxh values: 58 x 114 of 251 x 500 at the defaults); the x pass reads the
+//                    patch window of every frame at the frame's rounded global shift, dark / gain applied, where it lies in the
+//                    frame (getPatchData, :166-202)
 //   k_fa_patch_sum   the patchesAvg frames around t summed (the transform is linear: getPatchData sums the pixels), low-pass
 //   k_fa_patch_corr  per frame pair: S_a conj(S_b) (-1)^(x+y), inverse transform of the window the maximum is searched in only
 //                    (2 maxDist + 3 rows and columns about the centre, not all C x C), first maximum within maxDist, centre of
 //                    mass of the 3 x 3 values around it (computeCorrelations / sFindMax2DAroundCenter / refineLocation)
-__global__ void __launch_bounds__(256) k_fa_gather(const float *__restrict__ frames, const float *__restrict__ dark, const float *__restrict__ gain,
-                                                   const int *__restrict__ offs, float *__restrict__ out, int N, int nFrames, int Y, int X, int PY, int PX)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (size_t)N * PY * PX) return;
-    const int x = (int)(t % PX), y = (int)((t / PX) % PY), f = (int)(t / ((size_t)PX * PY));          // f: (patch of the batch, frame)
-    const size_t src = (size_t)(offs[2 * f + 1] + y) * X + offs[2 * f] + x;
-    float v = frames[(size_t)(f % nFrames) * Y * X + src];
-    if (dark) v -= dark[src];
-    if (gain) v *= gain[src];
-    out[t] = v;
-}
 
 // C[b][m][n] = sum_k A[b][m][k] B[b][k][n], B and C complex, A real or complex; 64 x 32 tiles of C per block, 4 x 2 per thread
+// (the products of xh_fa_correlate)
 template <bool ACPLX>
 __global__ void __launch_bounds__(256) k_fa_gemm(const float *__restrict__ A, size_t lda, size_t sA, const fa_cf *__restrict__ B, size_t ldb, size_t sB,
                                                  fa_cf *__restrict__ C, size_t ldc, size_t sC, int M, int Nc, int K)
@@ -583,8 +572,8 @@ __global__ void __launch_bounds__(256) k_fa_gemm(const float *__restrict__ A, si
 // 64 x 64 (2 x 2 MFMA tiles), K in steps of 16 through LDS.
 typedef float fa_f32x16 __attribute__((ext_vector_type(16)));
 // GATHER (real A only): A is the movie itself -- row m = (patch frame f = m / PY, patch row y = m % PY) of the product is the window of
-// frame f % nFrames at the frame's rounded global shift, (frame - dark) * gain like k_fa_gather, read where it lies: the patch copy
-// (k_fa_gather: 4.3 GB written and read back per K3 movie) disappears.
+// frame f % nFrames at the frame's rounded global shift, (frame - dark) * gain, read where it lies: no patch copy (4.3 GB written and
+// read back per K3 movie).
 struct FaGather { const float *dark, *gain; const int *offs; int nFrames, Y, X, PY; };
 // a second batch level: blockIdx.z = z1 Z0 + z0, matrices at s z0 + s1 z1 (Z0 = 0: one level, blockIdx.z = z0)
 struct FaBatch2 { int Z0; size_t sA1, sB1, sC1; };
@@ -910,7 +899,7 @@ __global__ void __launch_bounds__(256) k_fa_patch_corr2(const fa_cf *__restrict_
 
 // ---- B-spline warp: applyBSplineTransform(3, ...) (cuda_gpu_geo_transformer.cpp:186-239) ---------------------------------------
 // cubic B-spline prefilter of the (dark / gain corrected) frame as a convolution (xh_bspline.h: exactly the recursion with the
-// half-sample mirror, 33 taps in fp32), both passes in one kernel like k_pm_prefilter_fir2d, for frames that are not square:
+// half-sample mirror, 33 taps in fp32), both passes in one kernel, for frames that are not square:
 // a block owns XH_FIR_V rows x 256 columns, filters down the columns (thread <-> column, the 16 either side too, the correction
 // applied as the samples are read) into an LDS tile and along the rows out of it. plain += the corrected samples (initialMic).
 __global__ void __launch_bounds__(256) k_fa_prefilter(const float *__restrict__ in, const float *__restrict__ dark, const float *__restrict__ gain,
@@ -1052,10 +1041,10 @@ __global__ void __launch_bounds__(256) k_fa_prefilter_rec(const float *__restric
         else { dst[0] = q.x; if (x + 1 < X) dst[1] = q.y; if (x + 2 < X) dst[2] = q.z; if (x + 3 < X) dst[3] = q.w; }
     }
 }
-// which form the frames' prefilter takes: the recursion (default) or the 33-tap convolution (XH_PREFILTER_FORM=0, A/B)
+// the frames' prefilter: the recursion, or the 33-tap convolution for frames under 32 pixels
 static void fa_prefilter_launch(hipStream_t stream, const float *in, const float *dark, const float *gain, float *out, float *plain, int Y, int X)
 {
-    if (xh_prefilter_form() == 1 && Y >= 32 && X >= 32) {
+    if (Y >= 32 && X >= 32) {
         const int tilesX = (X + XH_FA_REC_TW - 1) / XH_FA_REC_TW, tilesY = (Y + XH_REC_V - 1) / XH_REC_V;
         hipLaunchKernelGGL(k_fa_prefilter_rec, dim3((unsigned)(tilesX * tilesY)), dim3(256), 0, stream, in, dark, gain, out, plain, Y, X, tilesX);
         return;
@@ -1074,26 +1063,18 @@ __device__ __forceinline__ float d_fa_b3(float x)
     return 0.f;
 }
 
-#ifndef XH_FA_B3_TAPS
-#define XH_FA_B3_TAPS 1             // d_fa_b3_taps without d_fa_b3's branches (0: d_fa_b3 per weight, A/B)
-#endif
 // The four weights d_fa_b3(t0 - i), i = 0 .. 3, of a position whose taps start one control point / pixel before it: t0 lies in [1, 2],
 // so the arguments fall into (1, 2], (0, 1], (-1, 0], (-2, -1] and each weight's polynomial is known beforehand -- the outer two take
 // the cubic tail, the inner two the central piece (at |x| = 1 the two pieces meet: 1/6 from either, to a rounding).  Same expressions
 // as d_fa_b3, without its two compares and selects per weight (12 -> 4-5 vector instructions; twenty weights per pixel of the warp).
 __device__ __forceinline__ void d_fa_b3_taps(float t0, float (&w)[4])
 {
-#if XH_FA_B3_TAPS
     float a0 = fabsf(t0) - 2.f, a3 = fabsf(t0 - 3.f) - 2.f;
     const float a1 = fabsf(t0 - 1.f), a2 = fabsf(t0 - 2.f);
     w[0] = a0 * a0 * a0 * (-1.f / 6.f);
     w[1] = a1 * a1 * (a1 - 2.f) * 0.5f + (2.f / 3.f);
     w[2] = a2 * a2 * (a2 - 2.f) * 0.5f + (2.f / 3.f);
     w[3] = a3 * a3 * a3 * (-1.f / 6.f);
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = d_fa_b3(t0 - i);
-#endif
 }
 
 // applyLocalShiftGeometryKernelMorePixels<T, 3> (cuda_gpu_geo_transformer.cu:193-254): the shift of every pixel from the control
@@ -1173,12 +1154,6 @@ __global__ void __launch_bounds__(256) k_fa_warp(const float *__restrict__ coef,
 // wave share the cell almost always: a broadcast) instead of eight ds_read_b32, and the 1e-4 cut multiplies a dropped term by zero
 // instead of branching around it (sx + C * 0 = sx).  Same terms, same order (layer, column, row), same products bY (bX bT).
 #define XH_FA_WARP_RG 8
-#ifndef XH_FA_WARP_INSIDE
-#define XH_FA_WARP_INSIDE 1         // the mirrored-border index loops only in the waves that touch a border (0: in every wave, A/B)
-#endif
-#ifndef XH_FA_WARP_WAVE
-#define XH_FA_WARP_WAVE 1           // the 64 terms of the shift once per wave where its pixels share a control cell (0: per lane always, A/B)
-#endif
 __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__ coef, const float *__restrict__ cX, const float *__restrict__ cY, int lX, int lY, int lT,
                                                        float hX, float hY, float tPos, int Y, int X, float *__restrict__ out, float *__restrict__ sum)
 {
@@ -1210,7 +1185,6 @@ __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__
     d_fa_b3_taps(yPos - (yi - 1), bY);
     fa_v2 sxy = fa_v2{0.f, 0.f};
     const unsigned long long lanesOn = __builtin_amdgcn_read_exec();
-#if XH_FA_WARP_WAVE
     // A wave is 64 neighbouring pixels of one row: they share the frame's layers, the control row and -- unless a control column ends
     // inside them -- the control column, i.e. all 64 control points and the products bY bT; only bX differs from lane to lane, and
     // within a control cell each bX[b] runs monotonically from the first lane to the last.  So the 64 terms are formed ONCE per wave,
@@ -1236,11 +1210,7 @@ __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__
         const float hib = tb == 0 ? bmax[0] : tb == 1 ? bmax[1] : tb == 2 ? bmax[2] : bmax[3];
         const float wyt = bYc * bTa;
         const bool valid = ta < nT;
-#ifdef XH_FA_WARP_DEBUG
-        const bool kept = false, mixed = valid && wyt * hib > delta;
-#else
         const bool kept = valid && wyt * lob > delta, mixed = valid && !kept && wyt * hib > delta;
-#endif
         fa_v2 C = fa_v2{0.f, 0.f};
         if (valid) {
             const float *rec = reinterpret_cast<const float *>(sq + 2 * (ta * nq + (yi + tc) * qx + xi0));
@@ -1271,7 +1241,6 @@ __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__
             if (tmp > delta) { sxy.x = __builtin_fmaf(cx, tmp, sxy.x); sxy.y = __builtin_fmaf(cy, tmp, sxy.y); }
         }
     } else
-#endif
     // The 1e-4 cut as an execution mask: v_cmpx switches the lanes whose term is dropped off for the one packed multiply-add that follows
     // (compare + select + multiply-add were three vector instructions per term, 192 of a pixel's 540; this is two and a scalar move).
 #pragma unroll
@@ -1309,7 +1278,7 @@ __global__ void __launch_bounds__(256) k_fa_warp_quads(const float *__restrict__
     d_fa_b3_taps(yd, wy);
     // the mirrored borders concern the waves at the frame's edges: where the sixteen taps of every lane lie inside the frame (one ballot)
     // the indices are l1 + i, m1 + i as they stand
-    const bool inside = XH_FA_WARP_INSIDE && __builtin_amdgcn_ballot_w64(l1 < 0 || l1 + 3 >= X || m1 < 0 || m1 + 3 >= Y) == 0ull;
+    const bool inside = __builtin_amdgcn_ballot_w64(l1 < 0 || l1 + 3 >= X || m1 < 0 || m1 + 3 >= Y) == 0ull;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int l = l1 + i;
@@ -1479,7 +1448,6 @@ struct xh_fa {
     xh_fft2d *rows = nullptr, *cols = nullptr, *small = nullptr;        // rows: (Y+1)/2 packed rows of X points; cols: the nc kept columns of Y points; small: a pair map
     int nc;                               // columns of the frame transform the reduced frame keeps (nX/2 + 1)
     int lastFull = 0;                     // pairs of the last global alignment that went through the full transform
-    int use_mfma = 1;                     // the pruned-DFT products of the local alignment on the matrix cores (0: the vector-ALU kernel)
     int use_window = 1;                   // pair correlations inside the search window only (0: every pair through the full transform)
     XhBuf work, spectra, lpf, pair, part, res, warpC;
     std::vector<float> warpCHost;         // the spline coefficients the device holds (uploaded once per set, not once per frame)
@@ -1575,7 +1543,6 @@ int xh_fa_set_option(xh_fa *h, const char *name, double value)
 {
     XH_CHECK(h && name, XH_ERR_ARG, "xh_fa_set_option: bad argument");
     if (!strcmp(name, "window")) h->use_window = value != 0;
-    else if (!strcmp(name, "mfma")) h->use_mfma = value != 0;
     else if (!strcmp(name, "pairwin_form")) h->pairwin_form = (int)value;
     else if (!strcmp(name, "rows_kept")) h->rows_kept = value != 0;
     else if (!strcmp(name, "pruned_columns")) { h->pruned_cols = (int)value; h->cKey.clear(); }
@@ -1964,9 +1931,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     const float actualScale = (float)CX / (float)PX;
     const int maxDist = (int)(max_shift_px * actualScale);
     XH_CHECK(maxDist >= 0, XH_ERR_ARG, "xh_fa_local_alignment: negative --maxShift");
-    const bool timing = getenv("XH_FA_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tA = now();
     const int nP = patchesX * patchesY, rows = N * (N - 1) / 2;
     std::vector<double> tl;
     fa_patch_layout(N, Y, X, h_gShiftX, h_gShiftY, patchesX, patchesY, PX, PY, tl, h_centers);
@@ -1986,7 +1950,7 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     const int y0 = std::max(0, yHalf - maxDist - 1), y1 = std::min(CY - 1, yHalf + maxDist + 1), wy = y1 - y0 + 1;
     const int x0 = std::max(0, xHalf - maxDist - 1), x1 = std::min(CX - 1, xHalf + maxDist + 1), wx = x1 - x0 + 1;
     const size_t E = (size_t)CY * cxh;
-    XhBuf *pOffs = nullptr, *pWx = nullptr, *pWy = nullptr, *pTabY = nullptr, *pTabX = nullptr, *pFilter = nullptr, *pPatch = nullptr, *pT = nullptr, *pSingle = nullptr, *pS = nullptr,
+    XhBuf *pOffs = nullptr, *pWx = nullptr, *pWy = nullptr, *pTabY = nullptr, *pTabX = nullptr, *pFilter = nullptr, *pT = nullptr, *pSingle = nullptr, *pS = nullptr,
           *pU = nullptr, *pW = nullptr, *pRes = nullptr;
     char key[160];
     snprintf(key, sizeof(key), "%d %d %d %d %d %d %d %d %.9g %.9g", PX, PY, CX, CY, y0, wy, x0, wx, (double)(h->Ts / actualScale), (double)h->maxRes);
@@ -2021,7 +1985,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
         XH_TRY(fa_table(h, "l_filter", filter.data(), sizeof(float) * filter.size(), &pFilter));
         h->lKey = key;
     }
-    const double tB = now();
     XH_TRY(fa_scratch(h, "l_Wx", 0, &pWx));
     XH_TRY(fa_scratch(h, "l_Wy", 0, &pWy));
     XH_TRY(fa_scratch(h, "l_tabY", 0, &pTabY));
@@ -2031,47 +1994,26 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     // PB patches at a time: the pair kernel has one wave per frame pair, the second product one workgroup per patch frame -- a single patch (780
     // waves, 40 workgroups for 40 frames) leaves most of the device idle; 36 (three launches for the 108 patches of a K3 movie) against
     // 16: local alignment 18.5 -> 17.5 ms per movie
-    static const int pbEnv = xh_debug_env("XH_FA_PB") ? atoi(xh_debug_env("XH_FA_PB")) : 0;        // A/B runs
-    const int PB = std::min(nP, pbEnv > 0 ? pbEnv : 36);
-    static const bool copyPatchesEnv = xh_debug_env("XH_FA_COPY_PATCHES") != nullptr;
-    XH_TRY(fa_scratch(h, "l_patch", (h->use_mfma && !copyPatchesEnv) ? 16 : sizeof(float) * (size_t)PB * N * PY * PX, &pPatch));      // the fused product reads the frames
+    const int PB = std::min(nP, 36);
     XH_TRY(fa_scratch(h, "l_T", sizeof(fa_cf) * (size_t)PB * N * PY * cxh, &pT));
     XH_TRY(fa_scratch(h, "l_single", sizeof(fa_cf) * (size_t)PB * N * E, &pSingle));
     XH_TRY(fa_scratch(h, "l_S", sizeof(fa_cf) * (size_t)PB * N * E, &pS));
     XH_TRY(fa_scratch(h, "l_U", sizeof(fa_cf) * (size_t)PB * rows * wy * cxh, &pU));
     XH_TRY(fa_scratch(h, "l_W", sizeof(float) * (size_t)PB * rows * wy * wx, &pW));
     XH_TRY(fa_scratch(h, "l_res", sizeof(double) * 2 * (size_t)rows * nP, &pRes));
-    XhBuf &bOffs = *pOffs, &bWx = *pWx, &bWy = *pWy, &bTabY = *pTabY, &bTabX = *pTabX, &bFilter = *pFilter, &bPatch = *pPatch, &bT = *pT, &bSingle = *pSingle, &bS = *pS, &bU = *pU,
+    XhBuf &bOffs = *pOffs, &bWx = *pWx, &bWy = *pWy, &bTabY = *pTabY, &bTabX = *pTabX, &bFilter = *pFilter, &bT = *pT, &bSingle = *pSingle, &bS = *pS, &bU = *pU,
           &bW = *pW, &bRes = *pRes;
     int rc = XH_OK;
-    const double tC = now();
     for (int p0 = 0; p0 < nP && rc == XH_OK; p0 += PB) {
         const int pb = std::min(PB, nP - p0), nf = pb * N;
-        const size_t tot = (size_t)nf * PY * PX;
-        static const bool copyPatches = xh_debug_env("XH_FA_COPY_PATCHES") != nullptr;        // A/B runs
-        const bool fused = h->use_mfma && !copyPatches;
-        if (!fused)
-            hipLaunchKernelGGL(k_fa_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, d_frames, d_dark, d_gain, (const int *)bOffs.p + (size_t)p0 * N * 2,
-                               (float *)bPatch.p, nf, N, Y, X, PY, PX);
         // along x, all frames of all patches of the batch at once: [pb N PY][PX] x [PX][cxh]; the matrix-core product reads the patches
         // out of the frames
-        if (fused) {
-            FaGather G{d_dark, d_gain, (const int *)bOffs.p + (size_t)p0 * N * 2, N, Y, X, PY};
-            hipLaunchKernelGGL((k_fa_gemm_mfma<false, true>), dim3((2 * cxh + 127) / 128, (unsigned)(((size_t)nf * PY + 127) / 128), 1), dim3(256), 0, ctx->stream, d_frames,
-                               (size_t)PX, (size_t)0, (const fa_cf *)bWx.p, (size_t)cxh, (size_t)0, (fa_cf *)bT.p, (size_t)cxh, (size_t)0, nf * PY, cxh, PX, G);
-        } else if (h->use_mfma)
-            hipLaunchKernelGGL((k_fa_gemm_mfma<false>), dim3((2 * cxh + 127) / 128, (unsigned)(((size_t)nf * PY + 127) / 128), 1), dim3(256), 0, ctx->stream, (const float *)bPatch.p,
-                               (size_t)PX, (size_t)0, (const fa_cf *)bWx.p, (size_t)cxh, (size_t)0, (fa_cf *)bT.p, (size_t)cxh, (size_t)0, nf * PY, cxh, PX, FaGather{});
-        else
-        hipLaunchKernelGGL((k_fa_gemm<false>), dim3((cxh + 31) / 32, (unsigned)(((size_t)nf * PY + 63) / 64), 1), dim3(256), 0, ctx->stream, (const float *)bPatch.p, (size_t)PX,
-                           (size_t)0, (const fa_cf *)bWx.p, (size_t)cxh, (size_t)0, (fa_cf *)bT.p, (size_t)cxh, (size_t)0, nf * PY, cxh, PX);
+        FaGather G{d_dark, d_gain, (const int *)bOffs.p + (size_t)p0 * N * 2, N, Y, X, PY};
+        hipLaunchKernelGGL((k_fa_gemm_mfma<false, true>), dim3((2 * cxh + 127) / 128, (unsigned)(((size_t)nf * PY + 127) / 128), 1), dim3(256), 0, ctx->stream, d_frames,
+                           (size_t)PX, (size_t)0, (const fa_cf *)bWx.p, (size_t)cxh, (size_t)0, (fa_cf *)bT.p, (size_t)cxh, (size_t)0, nf * PY, cxh, PX, G);
         // along y, frame by frame: [CY][PY] x [PY][cxh]
-        if (h->use_mfma)
-            hipLaunchKernelGGL((k_fa_gemm_mfma<true>), dim3((2 * cxh + 127) / 128, (CY + 127) / 128, nf), dim3(256), 0, ctx->stream, (const float *)bWy.p, (size_t)PY, (size_t)0,
-                               (const fa_cf *)bT.p, (size_t)cxh, (size_t)PY * cxh, (fa_cf *)bSingle.p, (size_t)cxh, E, CY, cxh, PY, FaGather{});
-        else
-        hipLaunchKernelGGL((k_fa_gemm<true>), dim3((cxh + 31) / 32, (CY + 63) / 64, nf), dim3(256), 0, ctx->stream, (const float *)bWy.p, (size_t)PY, (size_t)0,
-                           (const fa_cf *)bT.p, (size_t)cxh, (size_t)PY * cxh, (fa_cf *)bSingle.p, (size_t)cxh, E, CY, cxh, PY);
+        hipLaunchKernelGGL((k_fa_gemm_mfma<true>), dim3((2 * cxh + 127) / 128, (CY + 127) / 128, nf), dim3(256), 0, ctx->stream, (const float *)bWy.p, (size_t)PY, (size_t)0,
+                           (const fa_cf *)bT.p, (size_t)cxh, (size_t)PY * cxh, (fa_cf *)bSingle.p, (size_t)cxh, E, CY, cxh, PY, FaGather{});
         hipLaunchKernelGGL(k_fa_patch_sum, dim3((unsigned)(((size_t)nf * E + 255) / 256)), dim3(256), 0, ctx->stream, (const fa_cf *)bSingle.p, (fa_cf *)bS.p,
                            (const float *)bFilter.p, nf, N, E, patchesAvg);
         const size_t ldsU = sizeof(fa_cf) * (size_t)wy * cxh;
@@ -2103,7 +2045,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
     std::vector<double> res(2 * (size_t)rows * nP);
     if (rc == XH_OK && hipMemcpyAsync(res.data(), bRes.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
     if (rc == XH_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = XH_ERR_HIP;
-    const double tD = now();
     h->aheadBase = nullptr;
     if (rc == XH_OK && h->prefilter_ahead) {
         // the warp's prefilter of every frame, behind the results' copy: runs while the host solves below
@@ -2117,7 +2058,6 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
             else { h->aheadBase = d_frames; h->aheadDark = d_dark; h->aheadGain = d_gain; h->aheadN = N; }
         }
     }
-    const double tE = now();
     if (rc != XH_OK) { if (rc == XH_ERR_HIP) xh_set_error("xh_fa_local_alignment: device error"); return rc; }
     // computeAlignment (:776-797) per patch: deduct the centre, scale to the movie's pixels, solve, add the rounded global shift
     auto solvePatches = [&](int pBegin, int pEnd) {
@@ -2142,11 +2082,7 @@ int xh_fa_local_alignment(xh_fa *h, const float *d_frames, int32_t N, const floa
         for (int t = 0; t < nthr; ++t) pool.emplace_back(solvePatches, (int)((long long)nP * t / nthr), (int)((long long)nP * (t + 1) / nthr));
         for (auto &th : pool) th.join();
     }
-    const double tF = now();
     if (h_coeffsX && h_coeffsY) fa_fit_bspline(N, Y, X, nP, h_centers, h_patchShifts, lX, lY, lT, h_coeffsX, h_coeffsY);
-    if (timing)
-        fprintf(stderr, "xh_fa_local_alignment: tables %.1f ms, buffers %.1f ms, device %.1f ms, free %.1f ms, patch solves %.1f ms, spline fit %.1f ms\n", 1e3 * (tB - tA),
-                1e3 * (tC - tB), 1e3 * (tD - tC), 1e3 * (tE - tD), 1e3 * (tF - tE), 1e3 * (now() - tF));
     return XH_OK;
 }
 
@@ -2243,12 +2179,11 @@ int xh_fa_apply_bspline(xh_fa *h, const float *d_frame, const float *d_dark, con
         // hX, hY, tPos in float on the host like applyBSplineTransform (cuda_gpu_geo_transformer.cpp:206-210)
         const float hX = (lX == 3) ? (float)X : (X / (float)(lX - 3)), hY = (lY == 3) ? (float)Y : (Y / (float)(lY - 3)), hT = (lT == 3) ? (float)N : (N / (float)(lT - 3));
         const float tPos = n / hT;
-        static const bool plain = xh_debug_env("XH_FA_WARP_PLAIN") != nullptr;        // A/B runs
         // dynamic LDS of the two forms: four layers of quads (16 bytes per control row and first column, both fields) or of plain control
         // points; a control grid whose quads do not fit 64 KB takes the plain kernel, one that fits neither is refused
         const size_t ldsQuads = sizeof(float4) * 2 * 4 * (size_t)(lX - 3) * lY, ldsPlain = sizeof(float) * 2 * 4 * (size_t)lX * lY;
         XH_CHECK(ldsPlain <= 64 * 1024, XH_ERR_UNSUPPORTED, "xh_fa_apply_bspline: %d x %d control points per layer exceed the 64 KB of LDS the warp kernel stages them in", lX, lY);
-        if (lX >= 4 && lY >= 4 && !plain && ldsQuads <= 64 * 1024)
+        if (lX >= 4 && lY >= 4 && ldsQuads <= 64 * 1024)
             hipLaunchKernelGGL(k_fa_warp_quads, dim3((X + 63) / 64, (Y + 4 * XH_FA_WARP_RG - 1) / (4 * XH_FA_WARP_RG)), dim3(256), ldsQuads, ctx->stream, (const float *)coef,
                                (const float *)h->warpC.p, (const float *)h->warpC.p + Cc, lX, lY, lT, hX, hY, tPos, Y, X, d_out, d_sum);
         else

@@ -239,7 +239,7 @@ struct xh_rf {
     XhBuf d_shiftCoef, d_shiftXY;   // xh_rf_shift_images scratch
     XhBuf d_tileCounter;            // ints [32,41): class offsets of the tile list, [128,384): the stream counters
     XhBuf d_cull, d_pack, d_superList, d_superCount, d_superVec;
-    XhBuf d_gtiles[2], d_grecs, d_gweights, d_spectra;   // d_spectra: scratch of xh_rf_insert_images   // k_rf_grid: tile list (16 x 16 x 8 tiles), records, per-image weights
+    XhBuf d_gtiles, d_grecs, d_gweights, d_spectra;   // d_spectra: scratch of xh_rf_insert_images   // k_rf_grid: tile list (16 x 16 x 8 tiles), records, per-image weights
     // pinned staging of the small host arrays (records, shifts, CTF parameters): uploads never wait for the stream
     // pinned staging area of the small per-call host arrays: two halves used in turn, an event per half (recorded after the half's last
     // copy).  Entering a half waits for ITS event -- recorded a whole half ago -- so the host never waits for the copy it has just
@@ -260,8 +260,6 @@ struct xh_rf {
     int64_t kernelLaunches;
     double meanFactor2;   // cached mean of sinc^2 over the output window (< 0: not computed yet)
     bool cropped;
-    int unit_z = 4;       // depth of a gridding unit (8 x 8 x unit_z voxels per wave): 4 or 8
-    int grid_waves = 0;   // waves per CU of the gridding kernel; 0: the default of the unit depth
     XhBuf d_finSpec, d_finVol, d_finFbt;   // the finaliser's expanded spectrum, output volume and Fourier blob table
     int shift_bands = 1;  // 256-px images shifted band by band out of LDS (k_rf_shift_band; 0: k_rf_shift, for A/B)
     int fftSkipR2 = 0x7fffffff;   // set by xh_rf_insert_images* around its own projection FFT: spectra cells beyond that radius are not stored
@@ -1300,14 +1298,14 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
     XH_TRY(xh_plan_create<float>(ctx, rf->P, rf->planP32));
     XH_TRY(xh_plan_create<double>(ctx, rf->P, rf->planP64));
     XH_TRY(xh_buf_alloc(ctx, rf->d_tileCounter, sizeof(int) * 512));
-    // k_rf_grid: tiles of 2 x 2 x 2 units (16 x 16 x 8 voxels for units 4 deep, 16^3 for units 8 deep) that a projection can
-    // reach (sphere of radius sizeX + blob), in raster order (z, y, x) cut into 8 contiguous z-slabs of equal estimated work, one
-    // per XCD (block b runs on XCD b % 8: a projection's patch is pulled into one or two L2s instead of all eight). A tile at
-    // distance rho from the centre is crossed by a fraction ~1/rho of all central planes: that is its weight. Inside a class
-    // Morton order (the waves of the chip work on a narrow band of consecutive tiles, and a compact band shares more of the
-    // projections' patches in the L2 than a row of the raster). Class offsets at d_tileCounter + 32 (units 4 deep) and + 48 (8).
-    for (int v = 0; v < 2; ++v) {
-        const int tzs = v ? 16 : 8;                            // voxels per tile in z
+    // k_rf_grid: tiles of 2 x 2 x 2 units (16 x 16 x 8 voxels) that a projection can reach (sphere of radius sizeX + blob), in raster
+    // order (z, y, x) cut into 8 contiguous z-slabs of equal estimated work, one per XCD (block b runs on XCD b % 8: a projection's
+    // patch is pulled into one or two L2s instead of all eight). A tile at distance rho from the centre is crossed by a fraction ~1/rho
+    // of all central planes: that is its weight. Inside a class Morton order (the waves of the chip work on a narrow band of
+    // consecutive tiles, and a compact band shares more of the projections' patches in the L2 than a row of the raster). Class
+    // offsets at d_tileCounter + 32.
+    {
+        const int tzs = 8;                                     // voxels per tile in z
         const int tpx = (rf->mv + 1 + 15) / 16, tpz = (rf->mv + 1 + tzs - 1) / tzs;
         const double hz = 0.5 * tzs - 0.5;
         const double R = rf->sizeX + p->blob_radius + std::sqrt(2 * 7.5 * 7.5 + hz * hz) + 1.0;
@@ -1327,16 +1325,15 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
             classOff[c] = (int)(std::lower_bound(wsum.begin(), wsum.end(), acc * c / 8.0) - wsum.begin());
         classOff[8] = (int)packed.size();
         auto spread = [](unsigned v) { unsigned long long x = v & 0x3ff; x = (x | x << 16) & 0x30000ffULL; x = (x | x << 8) & 0x300f00fULL; x = (x | x << 4) & 0x30c30c3ULL; x = (x | x << 2) & 0x9249249ULL; return x; };
-        // Morton order; tiles of 4-deep units are half as tall as wide: on (x, y, z / 2) with the low bit of z last
+        // Morton order; tiles are half as tall as wide: on (x, y, z / 2) with the low bit of z last
         auto key = [&](unsigned t) {
-            if (tzs == 16) return spread(t & 0x3ff) | spread((t >> 10) & 0x3ff) << 1 | spread((t >> 20) & 0x3ff) << 2;
             return (spread(t & 0x3ff) | spread((t >> 10) & 0x3ff) << 1 | spread((t >> 21) & 0x1ff) << 2) << 1 | ((t >> 20) & 1);
         };
         for (int c = 0; c < 8; ++c)
             std::sort(packed.begin() + classOff[c], packed.begin() + classOff[c + 1], [&](unsigned u, unsigned w) { return key(u) < key(w); });
-        XH_TRY(xh_buf_alloc(ctx, rf->d_gtiles[v], sizeof(unsigned) * std::max<size_t>(1, packed.size())));
-        if (hipMemcpy(rf->d_gtiles[v].p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
-        if (hipMemcpy((int *)rf->d_tileCounter.p + 32 + 16 * v, classOff, sizeof(classOff), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+        XH_TRY(xh_buf_alloc(ctx, rf->d_gtiles, sizeof(unsigned) * std::max<size_t>(1, packed.size())));
+        if (hipMemcpy(rf->d_gtiles.p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+        if (hipMemcpy((int *)rf->d_tileCounter.p + 32, classOff, sizeof(classOff), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
     }
     *out = rf.release();
     return XH_OK;
@@ -1361,12 +1358,7 @@ int xh_rf_kernel_ms(xh_rf *rf, double *h_ms, int64_t *h_launches, int32_t reset)
 int xh_rf_set_option(xh_rf *rf, const char *name, double value)
 {
     XH_CHECK(rf && name, XH_ERR_ARG, "null argument");
-    if (!strcmp(name, "unit_z")) {
-        XH_CHECK((int)value == 4 || (int)value == 8, XH_ERR_ARG, "xh_rf_set_option: unit_z is 4 or 8");
-        rf->unit_z = (int)value;
-    }
-    else if (!strcmp(name, "grid_waves")) rf->grid_waves = (int)value;
-    else if (!strcmp(name, "ctf_fast")) rf->ctf_fast = (int)value;
+    if (!strcmp(name, "ctf_fast")) rf->ctf_fast = (int)value;
     else if (!strcmp(name, "order_spaces")) rf->order_spaces = (int)value;
     else if (!strcmp(name, "shift_bands")) rf->shift_bands = (int)value;
     else if (!strcmp(name, "tile_max_spaces")) rf->tile_max_spaces = (int)value;
@@ -1749,34 +1741,17 @@ static int grid_run(xh_rf *rf, int ns, const float *d_fft, const float *d_ctf, c
                            (int *)rf->d_superList.p, (int *)rf->d_superCount.p, superN, superX);
         XH_LAUNCH_CHECK();
         if (ev0 && ev1) XH_HIP(hipEventRecord(ev0, ctx->stream));    // the events bracket the gridding kernel alone
-        // unit depth and waves per CU: 8-deep units halve the visits (and the patch bytes they fetch) for the price of a larger
-        // accumulator block per wave, which the LDS holds for nine waves instead of twelve
-        const int uz = rf->unit_z, tl = uz == 8 ? 1 : 0;
-        const int nw = rf->grid_waves ? rf->grid_waves : (uz == 8 ? (br < 2.0 || fast ? 9 : 8) : 12);      // (6 x 6 footprints: larger patches)
         // persistent workgroups: one per CU, multiples of eight (XCD classes)
         const unsigned gridBlocks = 8u * (unsigned)std::max(1, ctx->num_cus / 8);
-#ifndef XG_ABL
-#define XG_ABL 0
-#endif
-#define XH_GRID(W_, F_, Z_, N_)                                                                                                  \
-    hipLaunchKernelGGL((k_rf_grid<W_, F_, Z_, N_, XG_ABL>), dim3(gridBlocks), dim3(64 * N_), 0, ctx->stream, \
+#define XH_GRID(W_, F_)                                                                                                          \
+    hipLaunchKernelGGL((k_rf_grid<W_, F_>), dim3(gridBlocks), dim3(64 * XgCfg<W_>::NW), 0, ctx->stream,                          \
                        (const XgRec *)rf->d_grecs.p + s0, (const XgCell *)rf->d_pack.p, (const float *)rf->d_blob.p, tempV, tempW, \
-                       rf->mv, rf->iDeltaSqrt, br, (const unsigned *)rf->d_gtiles[tl].p, (const int *)rf->d_tileCounter.p + 32 + 16 * tl, \
+                       rf->mv, rf->iDeltaSqrt, br, (const unsigned *)rf->d_gtiles.p, (const int *)rf->d_tileCounter.p + 32,        \
                        (int *)rf->d_tileCounter.p + 128, (const int *)rf->d_superList.p, (const int *)rf->d_superCount.p,         \
                        superDim, m, (const float4 *)superN, (const float4 *)superX, reach)
-#define XH_GRID_WF(W_, F_)                                                                                                       \
-    do {                                                                                                                         \
-        if (uz == 8 && nw == 9 && W_ == 4) XH_GRID(4, F_, 8, 9);                                                                 \
-        else if (uz == 8 && nw == 8) XH_GRID(W_, F_, 8, 8);                                                                      \
-        else if (uz == 4 && nw == 12) XH_GRID(W_, F_, 4, 12);                                                                    \
-        else if (uz == 4 && nw == 16 && W_ == 4) XH_GRID(4, F_, 4, 16);                                                          \
-        else if (uz == 4 && nw == 8) XH_GRID(W_, F_, 4, 8);                                                                      \
-        else { xh_set_error("xh_rf_insert: no gridding kernel for unit_z %d with %d waves", uz, nw); return XH_ERR_UNSUPPORTED; } \
-    } while (0)
-        if (fast) XH_GRID_WF(4, true);
-        else if (br < 2.0) XH_GRID_WF(4, false);
-        else XH_GRID_WF(6, false);
-#undef XH_GRID_WF
+        if (fast) XH_GRID(4, true);
+        else if (br < 2.0) XH_GRID(4, false);
+        else XH_GRID(6, false);
 #undef XH_GRID
         XH_LAUNCH_CHECK();
         if (ev0 && ev1) XH_HIP(hipEventRecord(ev1, ctx->stream));

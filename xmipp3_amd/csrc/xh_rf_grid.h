@@ -27,54 +27,31 @@
 #ifndef XH_RF_GRID_H
 #define XH_RF_GRID_H
 
-#ifndef XG_ACC_ATOMIC
-#define XG_ACC_ATOMIC 0         // 1: the unit's sums updated by LDS additions without a return (A/B: tools/build_variant.sh)
-#endif
-#ifndef XG_TAPMASK
-#define XG_TAPMASK 0            // 1: taps beyond the blob switched off with an execution mask instead of a select (A/B: tools/build_variant.sh)
-#endif
 #ifndef XG_PAD
 #define XG_PAD 6                // zero cells around a packed record: a 6 x 6 footprint (blob radius < 3) starts at ceil(-2 r) >= -5
 #endif
 
 #include "xh_rf_cell.h"
 
-// Compile-time shape of a kernel instance. A unit is 8 x 8 x ZD voxels (ZD = 4 or 8); NW waves share a CU.
+// Compile-time shape of the kernel. A unit is 8 x 8 x ZD voxels; NW waves share a CU.
 //   PN   pixels per patch row / column a footprint can reach: the image extent of a unit is at most its diagonal
-//        (10.4 / 12.2 pixels), so first footprint pixels lie 0..11 / 0..13 behind the patch origin, and a footprint is W wide
+//        (10.4 pixels), so first footprint pixels lie 0..11 behind the patch origin, and a footprint is W wide
 //   PW   patch row stride in pixels: > PN and not a multiple of 16 (64 banks of 4 bytes): consecutive rows are skewed
 //   NDMA LDS-DMA instructions per patch (64 pixels each)
 //   KCAP surviving projections listed per cull phase, three words each (index + flag, patch cell, patch origin)
-// With 14 or more waves the LDS has no room for skew columns or for the slots behind the last row: the patch is PN x PN pixels
-// exactly (an odd row stride: rows are skewed anyway), the last copy instruction runs with the lanes beyond the patch switched
-// off, and the cull phase lists 32 projections at a time.
-template <int W, int ZD, int NW> struct XgCfg {
-    static constexpr int PN = (ZD == 8 ? 14 : 12) + W - 1;
-    static constexpr bool TIGHT = NW >= 14;
-#ifdef XG_PW_OVERRIDE
-    static constexpr int PW = (W == 4 && ZD == 4 && NW == 12) ? XG_PW_OVERRIDE : (TIGHT ? PN : (PN <= 17 ? 18 : 20));      // A/B builds (tools/build_variant.sh)
-#else
+template <int W> struct XgCfg {
+    static constexpr int ZD = 4, NW = 12;
+    static constexpr int PN = 12 + W - 1;
     // (15 rows of 21 pixels fill the five copy instructions of the 4 x 4 footprint's patch; a record is four banks wide, so the
     // sixteen lanes a ds_read_b128 serves per cycle collide when their (row, column) differ by a multiple of sixteen in
     // 21 row + column -- (1, -5), (3, 1), (2, 6) ... -- where a stride of 18 had (1, -2): measured 3 % of the kernel)
-    static constexpr int PW = TIGHT ? PN : (PN == 15 ? 21 : (PN <= 17 ? 18 : 20));
-#endif
+    static constexpr int PW = PN == 15 ? 21 : 18;
     static constexpr int NDMA = (PN * PW + 63) / 64;
-    static constexpr int PATCH_BYTES = TIGHT ? PN * PW * 16 : NDMA * 1024;
-    static constexpr int KCAP = TIGHT ? 32 : 64;
-    // The 4 x 4 footprint in one go, two rows at a time (registers: fourteen waves and more) or -- the product's twelve waves -- row by
-    // row with the records and table entries of the next row requested before this row's multiply-adds (PIPE: two register sets; 133
-    // registers instead of 167 and 1.4 % off the launch, round 6: profiles/experiments/r06_ab_grid_pipeline.txt)
-#ifdef XG_HALVES
-    static constexpr int HALVES = XG_HALVES;               // A/B builds (tools/build_variant.sh)
-#else
-    static constexpr int HALVES = (W == 4 && NW == 12) ? 4 : (TIGHT ? 2 : 1);
-#endif
-#ifdef XG_PIPE
-    static constexpr bool PIPE = XG_PIPE != 0 && HALVES >= 2;
-#else
-    static constexpr bool PIPE = HALVES == 4;
-#endif
+    static constexpr int PATCH_BYTES = NDMA * 1024;
+    static constexpr int KCAP = 64;
+    // The 4 x 4 footprint row by row, with the records and table entries of the next row requested before this row's multiply-adds
+    // (two register sets; 133 registers instead of 167 and 1.4 % off the launch, round 6: profiles/experiments/r06_ab_grid_pipeline.txt)
+    static constexpr int HALVES = 4;
     static constexpr int NVOX = 64 * ZD;
     static constexpr int LDS_PATCH = 0;                                  // [NW][PATCH_BYTES]; first, so that LDS-DMA bases stay below 64 KB
     static constexpr int LDS_BLOB = NW * PATCH_BYTES;                    // float[XH_BLOB_TABLE + 4]; entry XH_BLOB_TABLE is 0
@@ -98,15 +75,12 @@ struct XgRec { float4 r0, r1, r2, h0, h1, h2, da, db, dc; };
 // (base, ldsBase wave-uniform). M0 carries the LDS address. M0 is a reserved register of the AMDGPU back end: it never holds a
 // value across instructions (the compiler writes it right before every use it generates), and naming it as a clobber is
 // rejected as undefined behaviour (-Winline-asm), so the clobber list names memory and SCC only.
-template <int NDMA, int SLOTS>
-__device__ __forceinline__ void xg_dma_patch(const void *base, const unsigned (&off)[NDMA], unsigned ldsBase, int lane)
+template <int NDMA>
+__device__ __forceinline__ void xg_dma_patch(const void *base, const unsigned (&off)[NDMA], unsigned ldsBase)
 {
 #pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-        // (SLOTS < 64 NDMA: the lanes of the last instruction that would write behind the patch stay out of it)
-        if (64 * (i + 1) <= SLOTS || 64 * i + lane < SLOTS)
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off[i]), "s"(base), "s"(ldsBase + 1024u * i) : "memory");
-    }
+    for (int i = 0; i < NDMA; ++i)
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(off[i]), "s"(base), "s"(ldsBase + 1024u * i) : "memory");
 }
 __device__ __forceinline__ void xg_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 typedef float xg_v2f __attribute__((ext_vector_type(2)));
@@ -335,23 +309,19 @@ __global__ void __launch_bounds__(64) k_rf_spaces(const double *__restrict__ ang
 }
 
 // W: footprint width (4 for a blob radius below 2, 6 below 3). FAST: processVoxel (RFA:595-625), nearest pixel, one voxel per row.
-// ZD: depth of a unit in z (4 or 8); NW: waves per workgroup (= per CU: the LDS budget admits one workgroup).
-// ABL: ablation switch for profiling builds (tools/ab_grid.sh); 0 in the product: 1 no wait for the patch copy, 2 no dense pass,
-// 3 no patch copy, 5 histogram of items per visit into tempV, 6 = 2 + 3, 7 = 6 without the sparse pass, 8 every patch copied
-// from the first megabyte of the records (the copy instructions without their HBM traffic), 9 every tap reads the patch's first
-// record, 10 every tap reads the table's first entry, 11 = 9 + 10 (the LDS reads without their bank conflicts).
-template <int W, bool FAST, int ZD, int NW, int ABL>
-__global__ void __launch_bounds__(64 * NW, (NW + 3) / 4)
+// One workgroup of XgCfg<W>::NW = 12 waves per CU (the LDS budget admits one workgroup), three per SIMD.
+template <int W, bool FAST>
+__global__ void __launch_bounds__(768, 3)
 k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const float *__restrict__ blobTable,
           float *__restrict__ tempV, float *__restrict__ tempW, int mv, float iDeltaSqrt, double blobRadius,
           const unsigned *__restrict__ tileList, const int *__restrict__ classOff, int *__restrict__ counter,
           const int *__restrict__ superList, const int *__restrict__ superCount, int superDim, int superCap,
           const float4 *__restrict__ superN, const float4 *__restrict__ superX, float4 reach)
 {
-    using C = XgCfg<W, ZD, NW>;
-    constexpr int PW = C::PW, PN = C::PN, NDMA = C::NDMA, NVOX = C::NVOX, KCAP = C::KCAP;
+    using C = XgCfg<W>;
+    constexpr int PW = C::PW, PN = C::PN, NDMA = C::NDMA, NVOX = C::NVOX, KCAP = C::KCAP, ZD = C::ZD, NW = C::NW;
     constexpr float HZ = 0.5f * ZD - 0.5f;                   // half extent of a unit's voxel centres in z
-    constexpr float HSPH = ZD == 8 ? 6.1f : 5.2f;            // ... never wider than the sphere around them
+    constexpr float HSPH = 5.2f;                             // ... never wider than the sphere around them
     __shared__ __align__(16) unsigned char lds[C::LDS_TOTAL];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -500,11 +470,7 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                     const float ex0 = ex - fr, ey0 = ey - fr;
                     const bool inReach = (cix - ex0 >= reach.x) && (cix + ex0 <= reach.y) && (ciy - ey0 >= reach.z) && (ciy + ey0 <= reach.w);
                     const int at = nk + __popcll(bal & below);
-#ifdef XG_NO_INTERIOR
-                    sKept[at] = sIdx | ((a1 || a2) ? (int)0x80000000 : 0) | ((inBox && inReach && mv < 0) ? 0x40000000 : 0);      // A/B builds
-#else
                     sKept[at] = sIdx | ((a1 || a2) ? (int)0x80000000 : 0) | ((inBox && inReach) ? 0x40000000 : 0);
-#endif
                     sKept[KCAP + at] = (int)cell;
                     sKept[2 * KCAP + at] = (ox & 0xffff) | (oy << 16);
                 }
@@ -575,7 +541,7 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                 }
                 // ---- the patch copy (origin found in the cull phase). The patch buffer is free: the previous dense pass has
                 // consumed its reads.
-                if constexpr (ABL != 3 && ABL != 6 && ABL != 7) xg_dma_patch<NDMA, C::PATCH_BYTES / 16>(pk + (ABL == 8 ? (cell & 0xffffu) : cell), dOff, patchBase, lane);
+                xg_dma_patch<NDMA>(pk + cell, dOff, patchBase);
                 // ---- sparse pass (RFA:631-653 and the reach of the footprint), two z at a time
                 const int yy = __float_as_int(R1.w), zz = __float_as_int(R2.w);
                 const bool yok = !(y < (yy & 0xffff) || y > (yy >> 16));
@@ -583,7 +549,6 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                 const bool sameQueue = interior && prevInterior && (R2.x == pNx && R2.y == pNy && R2.z == pNz);
                 pNx = R2.x; pNy = R2.y; pNz = R2.z; prevInterior = interior;
                 if (!sameQueue) qn = 0;
-                if constexpr (ABL != 7) {
                 if (sameQueue) {
                 } else if (interior) {
                     // the slab test alone (the sphere bit stays: the unit may straddle the sphere the reference keeps)
@@ -622,14 +587,12 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                         qn += __popcll(pb);
                     }
                 }
-                }
-                if constexpr (ABL == 5) { if (lane == 0) atomicAdd(reinterpret_cast<int *>(tempV) + min(qn, NVOX), 1); }   // profiling: items per visit
                 // ---- the patch of this visit has landed
-                if constexpr (ABL != 1) xg_wait_vm0();
+                xg_wait_vm0();
                 // ---- dense pass
                 const xg_v2f r01x = {R0.x, R1.x}, r01y = {R0.y, R1.y}, r01z = {R0.z, R1.z};
                 const float uLo = 0.5f - H2.x, uHi = 0.5f + H2.x, tLo = 0.5f - H2.y, tHi = 0.5f + H2.y;
-                if constexpr (ABL != 2 && ABL != 6 && ABL != 7) for (int b0 = 0; b0 < qn; b0 += 64) {
+                for (int b0 = 0; b0 < qn; b0 += 64) {
                     if (b0 + lane < qn) {
                         const int ai = sQueue[b0 + lane];
                         const float qx = fx0 + (float)(ai & 7), qy = fy0 + (float)((ai >> 3) & 7), qz = fz0 + (float)(ai >> 6);
@@ -666,9 +629,7 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                         xg_v2f accRI = {0.f, 0.f};
                         float accW = 0.f;
                         // the voxel's sums so far: requested now, needed at the very end
-#if !XG_ACC_ATOMIC
                         const float oW = sAcc[ai], oR = sAcc[NVOX + ai], oI = sAcc[2 * NVOX + ai];
-#endif
                         if constexpr (W == 4) {
                             // distances to the footprint's columns and rows as the reference forms them, i - (float)j (RFA:663,673)
                             const xg_v2f ix2 = {ixy.x, ixy.x}, iy2 = {ixy.y, ixy.y}, fbx2 = {fbx, fbx}, fby2 = {fby, fby};
@@ -679,115 +640,16 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                             const xg_v2f yz01 = ya * ya + z2, yz23 = yb * yb + z2;
                             const float yz[4] = {yz01.x, yz01.y, yz23.x, yz23.y};
                             constexpr int NT = 16 / C::HALVES, NR = 4 / C::HALVES;     // taps and footprint rows per go
-                            if constexpr (C::PIPE) {
                             // NR footprint rows at a time, the records and table entries of the next go requested before this go's
                             // multiply-adds (two register sets)
-#ifndef XG_PIPE_DEPTH
-#define XG_PIPE_DEPTH 1                                     // goes requested ahead of the multiply-adds (A/B: 2 = three register sets)
-#endif
-                            constexpr int PD = XG_PIPE_DEPTH, NS = PD + 1;
+                            constexpr int PD = 1, NS = PD + 1;                 // goes requested ahead of the multiply-adds
                             xg_v4f qq[NS][NT];
-#if XG_TAPMASK
-                            typedef xg_v2f xg_wt;           // a table entry in the low half of a register pair: the packed multiply-add's operand as it is
-#else
-                            typedef float xg_wt;
-#endif
-                            xg_wt ww[NS][NT];
-#if XG_TAPMASK
-                            // A tap beyond the blob (d > r^2, RFA:679) is switched off instead of being sent to the table's zero entry: its
-                            // distance stays in a register until the multiply-adds, where v_cmpx takes its lane out of EXEC for the two of
-                            // them (compare + select + 2 multiply-adds -> compare + 2 multiply-adds; what a dead lane read from the table
-                            // -- its index is not clamped any more, the LDS returns zero or whatever lies there -- is never used)
-                            float dd[NS][NT];
-                            const unsigned long long lanesOn = __builtin_amdgcn_read_exec();
-#endif
+                            float ww[NS][NT];
                             auto loadq = [&](int h, xg_v4f (&q_)[NT]) {
 #pragma unroll
                                 for (int t = 0; t < NT; ++t) q_[t] = tap[(h * NR + t / 4) * PW + (t & 3)];
                             };
-                            auto loadw = [&](int h, xg_wt (&w_)[NT], float *d_) {
-                                int aux[NT];
-#pragma unroll
-                                for (int a = 0; a < NR; ++a) {
-                                    const xg_v2f ya2 = {yz[h * NR + a], yz[h * NR + a]};
-                                    const xg_v2f d01 = xs01 + ya2, d23 = xs23 + ya2;
-                                    const xg_v2f t01 = d01 * idel2 + half2, t23 = d23 * idel2 + half2;
-#if XG_TAPMASK
-                                    d_[a * 4 + 0] = d01.x; d_[a * 4 + 1] = d01.y; d_[a * 4 + 2] = d23.x; d_[a * 4 + 3] = d23.y;
-                                    aux[a * 4 + 0] = (int)t01.x; aux[a * 4 + 1] = (int)t01.y; aux[a * 4 + 2] = (int)t23.x; aux[a * 4 + 3] = (int)t23.y;
-#else
-                                    aux[a * 4 + 0] = (int)(d01.x > radiusSqr ? limf : t01.x);
-                                    aux[a * 4 + 1] = (int)(d01.y > radiusSqr ? limf : t01.y);
-                                    aux[a * 4 + 2] = (int)(d23.x > radiusSqr ? limf : t23.x);
-                                    aux[a * 4 + 3] = (int)(d23.y > radiusSqr ? limf : t23.y);
-#endif
-                                }
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) {
-#if XG_TAPMASK
-                                    w_[t].x = sBlob[aux[t]];                    // (.y stays undefined on purpose: never read, op_sel_hi 0)
-#else
-                                    w_[t] = sBlob[aux[t]];
-#endif
-                                }
-                            };
-                            auto fmas = [&](xg_v4f (&q_)[NT], xg_wt (&w_)[NT], const float *d_) {
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) {
-#if XG_TAPMASK
-                                    const xg_v2f w2 = w_[t];                    // (the packed instruction reads the low half for both products: op_sel_hi 0)
-                                    const xg_v2f qxy = {q_[t].x, q_[t].y};
-                                    // !(d > r^2), the reference's test with the reference's operands: v_cmpx_nlt r^2, d
-                                    asm volatile("v_cmpx_nlt_f32_e32 vcc, %[r2], %[d]\n\t"
-                                                 "v_pk_fma_f32 %[ri], %[w2], %[qxy], %[ri] op_sel_hi:[0,1,1]\n\t"
-                                                 "v_fmac_f32_e32 %[aw], %[w], %[qz]\n\t"
-                                                 "s_mov_b64 exec, %[on]"
-                                                 : [ri] "+v"(accRI), [aw] "+v"(accW)
-                                                 : [r2] "s"(radiusSqr), [d] "v"(d_[t]), [w2] "v"(w2), [qxy] "v"(qxy), [w] "v"(w2.x), [qz] "v"(q_[t].z), [on] "s"(lanesOn)
-                                                 : "vcc");
-#else
-                                    const xg_v2f w2 = {w_[t], w_[t]};
-                                    accRI = __builtin_elementwise_fma(w2, (xg_v2f){q_[t].x, q_[t].y}, accRI);
-                                    accW = __builtin_fmaf(w_[t], q_[t].z, accW);
-#endif
-                                    asm volatile("" :: "v"(q_[t].w));
-                                }
-                            };
-#if XG_TAPMASK
-#define XG_DD(i) dd[i]
-#else
-#define XG_DD(i) nullptr
-#endif
-#pragma unroll
-                            for (int h = 0; h < PD && h < C::HALVES; ++h) {
-                                loadq(h, qq[h % NS]);
-                                if (h == 0) __builtin_amdgcn_sched_barrier(0);
-                                loadw(h, ww[h % NS], XG_DD(h % NS));
-                            }
-#pragma unroll
-                            for (int h = 0; h < C::HALVES; ++h) {
-                                if (h + PD < C::HALVES) { loadq(h + PD, qq[(h + PD) % NS]); loadw(h + PD, ww[(h + PD) % NS], XG_DD((h + PD) % NS)); }
-                                __builtin_amdgcn_sched_barrier(0);
-                                fmas(qq[h % NS], ww[h % NS], XG_DD(h % NS));
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-#undef XG_DD
-                            } else
-#pragma unroll
-                            for (int h = 0; h < C::HALVES; ++h) {
-                                // the records are requested before the index arithmetic of the weights, which they do not depend
-                                // on: their latency passes under it (the scheduler, left alone, clusters them behind the table
-                                // reads and the wave then waits for all of them)
-                                xg_v4f q[NT];
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) {
-                                    if constexpr (ABL == 9 || ABL == 11) {      // profiling: every lane reads the patch's first record
-                                        asm volatile("" :: "v"(tap));
-                                        q[t] = ((const __attribute__((address_space(3))) xg_v4f *)(uintptr_t)patchBase)[0];
-                                    } else
-                                    q[t] = tap[(h * NR + (t >> 2)) * PW + (t & 3)];
-                                }
-                                __builtin_amdgcn_sched_barrier(0);
+                            auto loadw = [&](int h, float (&w_)[NT]) {
                                 // table entry (int)(d2 * iDelta + 0.5) (RFA:682); a tap beyond the blob (d2 > r^2, RFA:679) reads a zero entry
                                 int aux[NT];
 #pragma unroll
@@ -800,22 +662,32 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                                     aux[a * 4 + 2] = (int)(d23.x > radiusSqr ? limf : t23.x);
                                     aux[a * 4 + 3] = (int)(d23.y > radiusSqr ? limf : t23.y);
                                 }
-                                float wB[NT];
+#pragma unroll
+                                for (int t = 0; t < NT; ++t) w_[t] = sBlob[aux[t]];
+                            };
+                            auto fmas = [&](xg_v4f (&q_)[NT], float (&w_)[NT]) {
 #pragma unroll
                                 for (int t = 0; t < NT; ++t) {
-                                    if constexpr (ABL == 10 || ABL == 11) { asm volatile("" :: "v"(aux[t])); wB[t] = sBlob[0]; }      // profiling: one table entry
-                                    else
-                                    wB[t] = sBlob[aux[t]];
-                                }
-#pragma unroll
-                                for (int t = 0; t < NT; ++t) {
-                                    const xg_v2f w2 = {wB[t], wB[t]};
-                                    accRI = __builtin_elementwise_fma(w2, (xg_v2f){q[t].x, q[t].y}, accRI);
-                                    accW = __builtin_fmaf(wB[t], q[t].z, accW);
+                                    const xg_v2f w2 = {w_[t], w_[t]};
+                                    accRI = __builtin_elementwise_fma(w2, (xg_v2f){q_[t].x, q_[t].y}, accRI);
+                                    accW = __builtin_fmaf(w_[t], q_[t].z, accW);
                                     // the unused fourth component stays allocated up to here: handed out again earlier, its
                                     // register makes the index arithmetic wait for the record reads (write after write)
-                                    asm volatile("" :: "v"(q[t].w));
+                                    asm volatile("" :: "v"(q_[t].w));
                                 }
+                            };
+#pragma unroll
+                            for (int h = 0; h < PD && h < C::HALVES; ++h) {
+                                loadq(h, qq[h % NS]);
+                                if (h == 0) __builtin_amdgcn_sched_barrier(0);
+                                loadw(h, ww[h % NS]);
+                            }
+#pragma unroll
+                            for (int h = 0; h < C::HALVES; ++h) {
+                                if (h + PD < C::HALVES) { loadq(h + PD, qq[(h + PD) % NS]); loadw(h + PD, ww[(h + PD) % NS]); }
+                                __builtin_amdgcn_sched_barrier(0);
+                                fmas(qq[h % NS], ww[h % NS]);
+                                __builtin_amdgcn_sched_barrier(0);
                             }
                         } else {
                             // wider blobs: the same taps row by row
@@ -842,16 +714,9 @@ k_rf_grid(const XgRec *__restrict__ recs, const XgCell *__restrict__ pk, const f
                                 }
                             }
                         }
-#if XG_ACC_ATOMIC
-                        // A/B build: three LDS additions without a return instead of three reads, three adds and three writes
-                        __builtin_amdgcn_ds_faddf((__attribute__((address_space(3))) float *)(sAcc + ai), accW, 0, 0, false);
-                        __builtin_amdgcn_ds_faddf((__attribute__((address_space(3))) float *)(sAcc + NVOX + ai), accRI.x, 0, 0, false);
-                        __builtin_amdgcn_ds_faddf((__attribute__((address_space(3))) float *)(sAcc + 2 * NVOX + ai), accRI.y, 0, 0, false);
-#else
                         sAcc[ai] = oW + accW;
                         sAcc[NVOX + ai] = oR + accRI.x;
                         sAcc[2 * NVOX + ai] = oI + accRI.y;
-#endif
                     }
                 }
                 __builtin_amdgcn_wave_barrier();

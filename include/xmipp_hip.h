@@ -658,6 +658,80 @@ int xh_halves_binary_mask(const float *h_values, size_t n, int32_t *h_mask);
 typedef double (*xh_cost_fn)(double *x, void *user);
 int xh_powell_minimize(int32_t n, double *p, const double *steps, double ftol, xh_cost_fn f, void *user, double *fret, int32_t *iter);
 
+/* Many Powell searches in lockstep (xmipp3_amd/host/powell_batch.h; host only, no device needed): problem q minimises over its n[q]
+ * variables p[q * nmax .. q * nmax + n[q] - 1] with the steps at the same places. Each search is xh_powell_minimize's own code paused at
+ * every cost call; at each step the live searches' vectors (at most `capacity` of them, never a finished problem's) go to f in one call:
+ * row r is problem[r] with its variables 0-based at x[r * nmax ..]; f writes cost[r] and returns 0 (anything else ends the run and is
+ * returned). A finished search gives its slot to the next problem. Every problem's minimum, cost and iteration count are bit for bit
+ * what xh_powell_minimize gives for it alone; evals (nullable) receives the number of cost calls of each. */
+typedef int32_t (*xh_batch_cost_fn)(int32_t m, const int32_t *problem, const double *x, double *cost, void *user);
+int xh_powell_minimize_batch(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
+                             xh_batch_cost_fn f, void *user, double *fret, int32_t *iter, int64_t *evals);
+
+/* ---- xmipp_angular_continuous_assign2 (reconstruction/angular_continuous_assign2.cpp; CUDA twin
+ * reconstruction_adapt_cuda/angular_continuous_assign2_gpu.cpp) ----
+ * Continuous refinement of each particle's pose against projections of a volume: Powell's method over continuous2cost (L348-395).
+ * The searches of all particles advance in lockstep, one cost evaluation of every live search per device step (xh_ca2.hip).
+ * The 13 variables of a row are the reference's p(0..12): a, b (grey I' = a I + b), shift x, y (added to the input shift), scale x, y,
+ * scale angle, change of rot, tilt, psi, change of defocus U, V, defocus angle.
+ * A particle with a CTF has its projections multiplied by generateCTF's image at K = 1 (updateCTFImage L225-247: the CTF with its damping
+ * envelope; its absolute value when phase_flipped) and its spectrum by the envelope image (L447-460); the CTF's noise model is not read.
+ * Refused with XH_ERR_UNSUPPORTED: particles of another size than the volume (scaleToSize, L574-578). */
+typedef struct xh_ca2 xh_ca2;
+typedef struct {
+    double max_shift, max_scale, max_angular_change, max_defocus_change, max_resolution, max_gray_scale, max_gray_shift, sampling, Rmax,
+        padding;                                                                                     /* readParams L52-62 */
+    int32_t optimize_gray, optimize_shift, optimize_scale, optimize_angles, optimize_defocus, phase_flipped, same_defocus;
+} xh_ca2_params;
+/* one particle's input row (processImage L421-445): the caller resolves the continuous* columns (continuousX / Y / Flip replace
+ * shiftX / Y / flip when continuousScaleX is present) */
+typedef struct {
+    double rot, tilt, psi, shift_x, shift_y, scale_x, scale_y, scale_angle, gray_a, gray_b;
+    int32_t flip, has_ctf;
+    xh_ctf_params ctf;      /* read when has_ctf: the row's CTF (readFromMdRow); phase_shift in degrees; K is taken as 1 (updateCTFImage) */
+} xh_ca2_row;
+/* the program's defaults (defineParams L121-140) */
+void xh_ca2_defaults(xh_ca2_params *p);
+/* preProcess (L157-222): the projector FourierProjector(V, padding, sampling / max_resolution, BSPLINE3) through xh_fp_create, the binary
+ * circular mask of radius Rmax (< 0: D / 2), the cost type (L1 when grey values are optimised, else minus the masked correlation).
+ * The random covariance of L189-201 feeds nothing and is not built. capacity: evaluations per device step. */
+int xh_ca2_create(xh_ctx *ctx, const float *d_vol, int32_t D, const xh_ca2_params *prm, int32_t capacity, xh_ca2 **out);
+int xh_ca2_destroy(xh_ca2 *h);
+/* processImage L414-478 for n particles h_images [n][ydim][xdim] (host): Istddev, Ifiltered = the raised-cosine low pass at
+ * sampling / max_resolution, raised_w 0.02 (fourier_filter.cpp:423-432, 710-716), times the CTF envelope where the particle has a CTF
+ * (generateEnvelope, ctf.h:1271-1290), resident as doubles; replaces what was loaded */
+int xh_ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_ca2_row *rows);
+/* continuous2cost + tranformImage (L251-395) of m rows: particle h_particle[r] at the 13 variables h_vars[r][13] -> h_cost[r]. A row
+ * outside the bounds of L364-375, or with a non-finite variable, costs 1e38 and no device work. Where a variance under the mask is 0 the correlation is 0.
+ * A row's cost does not depend on the rows it is evaluated with. Synchronous. */
+int xh_ca2_cost(xh_ca2 *h, int32_t m, const int32_t *h_particle, const double *h_vars, double *h_cost);
+/* P (the projection), E (the residual) and Ifilteredp (the transformed particle, 0 outside the mask) [D][D] doubles of device row `row`
+ * of the last evaluation (the in-bound rows of the last xh_ca2_cost chunk, in order); null pointers are skipped.
+ * Deviation: the reference writes these from whatever Powell evaluated last, which is generally not the minimum it returns; here the
+ * caller evaluates once more at the returned variables (xh_ca2_cost) and reads them then. */
+int xh_ca2_last_images(xh_ca2 *h, int32_t row, double *d_P, double *d_E, double *d_Ifilteredp);
+/* the similarity measures of processImage (L543-547) between P and Ifilteredp of device row `row` of the last evaluation -> h_out[3]:
+ * corrIdx (correlationIndex without mask), corrMask (correlationMasked, filters.cpp:1397-1452; 0 where the reference divides 0 by 0),
+ * imed (imedDistance, filters.cpp:1269-1318, its 7 x 7 weights exp(-(x^2 + y^2) / 2) / sqrt(2 pi) from the formula). Computed on the host
+ * from the two images (once per particle, sequential sums in the reference's order). corrWeight (correlationWeighted, which needs
+ * alignImages) is not computed. */
+int xh_ca2_measures(xh_ca2 *h, int32_t row, double *h_out);
+/* the final transform of processImage (L571-613) for every loaded particle: h_images [n][D][D] (host; the --applyTo images, in the order
+ * loaded) through applyGeometry(BSPLINE3, ., A, IS_NOT_INV, DONT_WRAP) with A of L579-598 at h_vars [n][13], then (I - b) / a inside the
+ * mask and 0 outside when grey values were optimised (L600-612) -> h_out [n][D][D] float. Synchronous. */
+int xh_ca2_apply(xh_ca2 *h, const float *h_images, const double *h_vars, float *h_out);
+/* Ifiltered [D][D] (host, nullable) and Istddev (nullable) of a loaded particle */
+int xh_ca2_filtered(xh_ca2 *h, int32_t particle, double *h_out, double *h_stddev);
+/* the search of processImage (L488-540) for every loaded particle, ftol 0.01: h_vars [n][13], h_cost [n] (Powell's minimum: minus the
+ * correlation, or the L1 cost), h_iter [n], h_evals [n] (cost calls, those the bounds decided included), h_enabled [n] (1, or -1: the
+ * input scale out of bounds L489-491, where cost is -1 and nothing is searched; a search ending on the 1e38 barrier or at a positive
+ * correlation cost L523-540, where the variables return to their input values).
+ * Only the variables whose step is non-zero are searched (the reference hands Powell all 13, the frozen ones with step 0, and spends
+ * line searches on flat directions): results agree with the reference within ftol, not bit for bit. */
+int xh_ca2_refine(xh_ca2 *h, double *h_vars, double *h_cost, int32_t *h_iter, int64_t *h_evals, int32_t *h_enabled);
+/* of the last refine: device steps, rows evaluated, seconds inside device steps (upload to the wait's end), seconds in all */
+int xh_ca2_stats(const xh_ca2 *h, double *h_stats);
+
 #ifdef __cplusplus
 }
 #endif

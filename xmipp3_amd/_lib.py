@@ -28,11 +28,25 @@ class CtfParams(C.Structure):
         "DeltaF", "DeltaR", "Q0", "K", "envR0", "envR1", "envR2", "phase_shift", "VPP_radius")]
 
 
+class Ca2Params(C.Structure):
+    _fields_ = [(n, C.c_double) for n in (
+        "max_shift", "max_scale", "max_angular_change", "max_defocus_change", "max_resolution", "max_gray_scale", "max_gray_shift",
+        "sampling", "Rmax", "padding")] + [(n, C.c_int32) for n in (
+            "optimize_gray", "optimize_shift", "optimize_scale", "optimize_angles", "optimize_defocus", "phase_flipped", "same_defocus")]
+
+
+class Ca2Row(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("rot", "tilt", "psi", "shift_x", "shift_y", "scale_x", "scale_y", "scale_angle", "gray_a",
+                                          "gray_b")] + [("flip", C.c_int32), ("has_ctf", C.c_int32), ("ctf", CtfParams)]
+
+
 # every symbol include/xmipp_hip.h declares: name -> (restype, argtypes)
 vp, i32, i64, d, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 pvp = C.POINTER(C.c_void_p)
 # xh_cost_fn: double (*)(double *x, void *user), x read 1-based
 COST_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
+# xh_batch_cost_fn: int32 (*)(int32 m, const int32 *problem, const double *x, double *cost, void *user)
+BATCH_COST_FN = C.CFUNCTYPE(C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 SIGNATURES = {
     "xh_last_error": (C.c_char_p, []),
     "xh_version": (C.c_char_p, []),
@@ -133,6 +147,18 @@ SIGNATURES = {
     "xh_halves_circular_mask": (C.c_int, [i32, i32, i32, d, d, d, d, vp]),
     "xh_halves_binary_mask": (C.c_int, [vp, sz, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
+    "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),
+    "xh_ca2_create": (C.c_int, [vp, vp, i32, C.POINTER(Ca2Params), i32, pvp]),
+    "xh_ca2_destroy": (C.c_int, [vp]),
+    "xh_ca2_load": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "xh_ca2_cost": (C.c_int, [vp, i32, vp, vp, vp]),
+    "xh_ca2_last_images": (C.c_int, [vp, i32, vp, vp, vp]),
+    "xh_ca2_measures": (C.c_int, [vp, i32, vp]),
+    "xh_ca2_apply": (C.c_int, [vp, vp, vp, vp]),
+    "xh_ca2_filtered": (C.c_int, [vp, i32, vp, C.POINTER(C.c_double)]),
+    "xh_ca2_refine": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "xh_ca2_stats": (C.c_int, [vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

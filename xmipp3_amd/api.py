@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import CtfParams, RfParams, XhError, check, lib
+from ._lib import Ca2Params, Ca2Row, CtfParams, RfParams, XhError, check, lib
 
 
 def _torch():
@@ -829,6 +829,44 @@ def powell_minimize(f, p, steps=None, ftol=0.01):
     return p, fret.value, it.value
 
 
+def powell_minimize_batch(f, problems, steps=None, ftol=0.01, capacity=64):
+    """Many Powell searches in lockstep (xh_powell_minimize_batch, host only). problems: a list of starting vectors (any mix of
+    lengths); f(idx, X) takes the problem indices of the rows and the list of their variable lists and returns their costs, one call per
+    step over at most `capacity` live searches. Returns (list of minima, costs, iterations, cost calls): problem by problem what
+    powell_minimize returns for it alone."""
+    from ._lib import BATCH_COST_FN
+    nprob = len(problems)
+    n = np.asarray([len(q) for q in problems], np.int32)
+    nmax = max(1, int(n.max())) if nprob else 1
+    p = np.zeros((nprob, nmax))
+    st = np.ones((nprob, nmax))
+    for q in range(nprob):
+        p[q, :n[q]] = problems[q]
+        if steps is not None:
+            st[q, :n[q]] = steps[q]
+    failure = []
+
+    def cb(m, problem, x, cost, _user):
+        try:
+            idx = [problem[r] for r in range(m)]
+            rows = [[x[r * nmax + j] for j in range(n[idx[r]])] for r in range(m)]
+            out = f(idx, rows)
+            for r in range(m):
+                cost[r] = float(out[r])
+            return 0
+        except BaseException as e:      # an exception must not cross the C frames: end the run and raise it afterwards
+            failure.append(e)
+            return 1
+    cfn = BATCH_COST_FN(cb)
+    fret, it, ev = np.zeros(nprob), np.zeros(nprob, np.int32), np.zeros(nprob, np.int64)
+    rc = lib().xh_powell_minimize_batch(nprob, _np_ptr(n), nmax, _np_ptr(p), _np_ptr(st), float(ftol), int(capacity), cfn, None, _np_ptr(fret),
+                                        _np_ptr(it), _np_ptr(ev))
+    if failure:
+        raise failure[0]
+    check(rc)
+    return [p[q, :n[q]].copy() for q in range(nprob)], fret, it, ev
+
+
 def movie_binned_size(Y, X, binning):
     """AProgMovieAlignmentCorrelation::getMovieSize (movie_alignment_correlation_base.cpp:356-370): float arithmetic, truncated"""
     f = np.float32
@@ -939,6 +977,103 @@ class FourierProjector(_Handle):
         out = torch.empty((n, self.D, self.D), dtype=torch.float32, device=self.ctx.torch_device)
         check(lib().xh_fp_project(self.h, _np_ptr(ang), n, None if ctf is None else _ptr(ctf, torch.float64), _ptr(out)))
         return out
+
+
+class ContinuousAssign2(_Handle):
+    """Device side of ProgAngularContinuousAssign2 (reconstruction/angular_continuous_assign2.cpp): Powell refinement of every
+    particle's grey values, shift, scale and angles against projections of `vol` ([z][y][x] float32, cuda), all searches in lockstep.
+    Keyword arguments are the fields of xh_ca2_params (the program's options); capacity = evaluations per device step."""
+
+    _destroy = "xh_ca2_destroy"
+    VARIABLES = ("a", "b", "shiftX", "shiftY", "scaleX", "scaleY", "scaleAngle", "rot", "tilt", "psi", "defocusU", "defocusV",
+                 "defocusAngle")
+
+    def __init__(self, ctx, vol, capacity=4096, **params):
+        torch = _torch()
+        assert vol.is_cuda and vol.dtype == torch.float32 and vol.is_contiguous() and vol.dim() == 3
+        self.D = vol.shape[0]
+        self.params = Ca2Params()
+        lib().xh_ca2_defaults(C.byref(self.params))
+        for k, v in params.items():
+            if not hasattr(self.params, k):
+                raise XhError(f"ContinuousAssign2: unknown parameter {k}")
+            setattr(self.params, k, v)
+        self.capacity = int(capacity)
+        self.n = 0
+        h = C.c_void_p()
+        check(lib().xh_ca2_create(ctx.h, _ptr(vol), self.D, C.byref(self.params), self.capacity, C.byref(h)))
+        super().__init__(ctx, h)
+
+    def load(self, images, rows=None):
+        """images: [n, D, D] float32 (host); rows: per particle a dict with any of rot, tilt, psi, shift_x, shift_y, flip, scale_x,
+        scale_y, scale_angle, gray_a, gray_b, ctf (a CtfParams: the particle has a CTF) (defaults: 0, gray_a 1, no CTF)"""
+        img = np.ascontiguousarray(images, np.float32)
+        assert img.ndim == 3
+        n = img.shape[0]
+        arr = (Ca2Row * n)()
+        for i in range(n):
+            arr[i].gray_a = 1.0
+            for k, v in (rows[i] if rows is not None else {}).items():
+                if not hasattr(arr[i], k) or k == "has_ctf":
+                    raise XhError(f"ContinuousAssign2.load: unknown column {k}")
+                if k == "ctf":
+                    if v is not None:
+                        arr[i].ctf, arr[i].has_ctf = v, 1
+                else:
+                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
+        check(lib().xh_ca2_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
+        self.n = n
+
+    def cost(self, particles, variables):
+        """particles: [m] indices; variables: [m, 13] -> costs [m] (1e38 for a row out of bounds)"""
+        idx = np.ascontiguousarray(particles, np.int32).reshape(-1)
+        x = np.ascontiguousarray(variables, np.float64).reshape(-1, 13)
+        assert x.shape[0] == idx.shape[0]
+        out = np.zeros(idx.shape[0])
+        check(lib().xh_ca2_cost(self.h, idx.shape[0], _np_ptr(idx), _np_ptr(x), _np_ptr(out)))
+        return out
+
+    def last_images(self, row=0):
+        """(P, E, Ifilteredp) [D, D] float64 cuda tensors of one row of the last evaluation"""
+        torch = _torch()
+        out = [torch.empty((self.D, self.D), dtype=torch.float64, device=self.ctx.torch_device) for _ in range(3)]
+        check(lib().xh_ca2_last_images(self.h, int(row), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return out
+
+    def measures(self, row=0):
+        """(corrIdx, corrMask, imed) between P and Ifilteredp of one row of the last evaluation"""
+        out = np.zeros(3)
+        check(lib().xh_ca2_measures(self.h, int(row), _np_ptr(out)))
+        return tuple(out)
+
+    def apply(self, images, variables):
+        """the final transform of every loaded particle: images [n, D, D] float32 (host), variables [n, 13] -> [n, D, D] float32"""
+        img = np.ascontiguousarray(images, np.float32)
+        x = np.ascontiguousarray(variables, np.float64).reshape(-1, 13)
+        assert img.shape == (self.n, self.D, self.D) and x.shape[0] == self.n
+        out = np.empty_like(img)
+        check(lib().xh_ca2_apply(self.h, _np_ptr(img), _np_ptr(x), _np_ptr(out)))
+        return out
+
+    def filtered(self, particle):
+        """(Ifiltered [D, D] float64 numpy, Istddev) of a loaded particle"""
+        out = np.empty((self.D, self.D))
+        sd = C.c_double()
+        check(lib().xh_ca2_filtered(self.h, int(particle), _np_ptr(out), C.byref(sd)))
+        return out, sd.value
+
+    def refine(self):
+        """-> (variables [n, 13], cost [n], iterations [n], cost calls [n], enabled [n]) of every loaded particle"""
+        n = self.n
+        x, cost = np.zeros((n, 13)), np.zeros(n)
+        it, ev, en = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        check(lib().xh_ca2_refine(self.h, _np_ptr(x), _np_ptr(cost), _np_ptr(it), _np_ptr(ev), _np_ptr(en)))
+        return x, cost, it, ev, en
+
+    def stats(self):
+        s = np.zeros(4)
+        check(lib().xh_ca2_stats(self.h, _np_ptr(s)))
+        return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
 
 
 class ProjectionMatcher(_Handle):

@@ -83,6 +83,18 @@ int xh_fft2d_user_scratch(xh_fft2d *f, size_t bytes, void **p);
 int xh_fft2d_rows_of_real_pairs(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int Y, float *d_work, int *n1, int *n2);
 int xh_fft2d_rows_of_real_pairs_kept(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int Y, int nc, float *d_C, int *done);
 
+// the Fourier projector's internals shared with xh_ca2: Euler_angles2matrix -> A [9], and n projections from device Euler matrices
+// (eul_stride doubles apart on the device) as doubles that stay on the device, d_out [n][D][D]; projection p is multiplied by the CTF image [D][D/2+1] at
+// d_ctf + p * ctf_stride (d_ctf null: none). Asynchronous on the context's stream.
+void xh_fp_euler(double rot, double tilt, double psi, double *A);
+int xh_fp_project_f64(xh_fp *fp, const double *d_eul, int32_t eul_stride, int32_t n, const double *d_ctf, size_t ctf_stride, double *d_out);
+
+// lockstep Powell (host/powell_batch.h; defined in xh_halves.hip next to xh_powell_minimize). pre (nullable) decides a cost on the
+// host: it returns 1 and sets *cost, and that evaluation never reaches f
+typedef int32_t (*xh_lockstep_pre_fn)(int32_t problem, const double *x, double *cost, void *user);
+int xh_powell_lockstep(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
+                       xh_batch_cost_fn f, xh_lockstep_pre_fn pre, void *user, double *fret, int32_t *iter, int64_t *evals);
+
 static inline int xh_ilog2(int n)
 {
     int l = 0;

@@ -71,10 +71,11 @@ __global__ void k_fp_crop(const double *__restrict__ in, double *__restrict__ ou
     out[idx] = in[((size_t)(k + po) * P + (i + po)) * P + (j + po)];
 }
 
-// project (L91-245), cubic B-spline branch; one thread per (projection, i, j) of the half spectrum
+// project (L91-245), cubic B-spline branch; one thread per (projection, i, j) of the half spectrum. Projection p reads its Euler
+// matrix at eul + p * eulStride and multiplies by the CTF image at ctf + p * ctfStride (stride 0: one image for all)
 __global__ void __launch_bounds__(256)
-k_fp_slice(const double *__restrict__ R, const double *__restrict__ I, const double *__restrict__ eul, const double *__restrict__ ctf,
-           xh_cd *__restrict__ pf, int n, int D, int P, int c, int st, double maxFreq2)
+k_fp_slice(const double *__restrict__ R, const double *__restrict__ I, const double *__restrict__ eul, int eulStride, const double *__restrict__ ctf,
+           size_t ctfStride, xh_cd *__restrict__ pf, int n, int D, int P, int c, int st, double maxFreq2)
 {
     const int xh = D / 2 + 1;
     const size_t per = (size_t)D * xh;
@@ -83,7 +84,7 @@ k_fp_slice(const double *__restrict__ R, const double *__restrict__ I, const dou
     const int p = idx / per;
     const int rem = idx - (size_t)p * per;
     const int i = rem / xh, j = rem - i * xh;
-    const double *E = eul + 9 * p;
+    const double *E = eul + (size_t)eulStride * p;
     const double freqy = (double)(i <= D / 2 ? i : i - D) / (double)D;       // FFT_IDX2DIGFREQ
     const double freqx = (double)j / (double)D;                               // j <= D/2
     xh_cd out = xh_cd{0., 0.};
@@ -126,16 +127,17 @@ k_fp_slice(const double *__restrict__ R, const double *__restrict__ I, const dou
         const double xxshift = -2.0 * 3.14159265358979323846 * (double)(D / 2) / (double)D;
         const double dotp = (double)j * xxshift + (double)i * xxshift;
         double a = cos(dotp), b = sin(dotp);
-        if (ctf) { const double cv = ctf[rem]; a *= cv; b *= cv; }
+        if (ctf) { const double cv = ctf[(size_t)p * ctfStride + rem]; a *= cv; b *= cv; }
         const double ac = a * cc, bd = b * dd, ab_cd = (a + b) * (cc + dd);
         out = xh_cd{ac - bd, ab_cd - ac - bd};
     }
     pf[idx] = out;
 }
 
-// last pass of the c2r inverse: Hermitian-extend a row of the half spectrum, inverse FFT, real part -> float
+// last pass of the c2r inverse: Hermitian-extend a row of the half spectrum, inverse FFT, real part -> float (the gallery) or double
+template <typename TOUT>
 __global__ void __launch_bounds__(256)
-k_fp_c2r_rows(const xh_cd *__restrict__ pf, XhPlan<double> plan, float *__restrict__ out, int D, size_t nrows, int lpb)
+k_fp_c2r_rows(const xh_cd *__restrict__ pf, XhPlan<double> plan, TOUT *__restrict__ out, int D, size_t nrows, int lpb)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     xh_cd *s = reinterpret_cast<xh_cd *>(smem);
@@ -157,11 +159,13 @@ k_fp_c2r_rows(const xh_cd *__restrict__ pf, XhPlan<double> plan, float *__restri
     xh_plan_exec<double, true>(s, plan, lpb, tid, nth);
     for (int i = tid; i < nl * D; i += nth) {
         const int l = i / D, e = i - l * D;
-        out[(row0 + l) * D + e] = (float)s[l * M + e].x;
+        out[(row0 + l) * D + e] = (TOUT)s[l * M + e].x;
     }
 }
 
-void h_euler(double rot, double tilt, double psi, double *A)
+}  // namespace
+
+void xh_fp_euler(double rot, double tilt, double psi, double *A)
 {
     // Euler_angles2matrix, closed form (function_tests/test_geometry_main.cpp:46-65)
     const double a = rot * kPI / 180., b = tilt * kPI / 180., g = psi * kPI / 180.;
@@ -171,7 +175,6 @@ void h_euler(double rot, double tilt, double psi, double *A)
     A[3] = -sg * cc - cg * sa; A[4] = -sg * cs + cg * ca; A[5] = sg * sb;
     A[6] = sc; A[7] = ss; A[8] = cb;
 }
-}  // namespace
 
 struct xh_fp {
     xh_ctx *ctx;
@@ -186,6 +189,39 @@ struct xh_fp {
         (void)hipStreamSynchronize(ctx->stream);
     }
 };
+
+// m projections from the Euler matrices on the device (eul_stride doubles apart): slice, inverse along y, c2r rows -> out [m][D][D]
+template <typename TOUT>
+static int fp_launch(xh_fp *fp, const double *d_eul, int eul_stride, int m, const double *d_ctf, size_t ctf_stride, TOUT *d_out)
+{
+    xh_ctx *ctx = fp->ctx;
+    const int D = fp->D, xh = D / 2 + 1;
+    const size_t per = (size_t)D * xh;
+    const XhPlan<double> &plan = fp->planD.plan;
+    const int lpb = xh_plan_lpb(plan, 64 * 1024, 16);
+    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << plan.logM;
+    hipLaunchKernelGGL(k_fp_slice, dim3((unsigned)((per * m + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)fp->d_re.p,
+                       (const double *)fp->d_im.p, d_eul, eul_stride, d_ctf, ctf_stride, (xh_cd *)fp->d_pf.p, m, D, fp->P, fp->cdim, fp->cstart,
+                       fp->maxFreq * fp->maxFreq);
+    XH_LAUNCH_CHECK();
+    // inverse along y: lines (p, j): offset p*per + j, element stride xh
+    const size_t ncol = (size_t)m * xh;
+    hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((ncol + lpb - 1) / lpb)), dim3(256), smem, ctx->stream,
+                       (xh_cd *)fp->d_pf.p, plan, ncol, (size_t)xh, per, (size_t)1, (size_t)xh, lpb);
+    XH_LAUNCH_CHECK();
+    const size_t nrows = (size_t)m * D;
+    hipLaunchKernelGGL((k_fp_c2r_rows<TOUT>), dim3((unsigned)((nrows + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, (const xh_cd *)fp->d_pf.p,
+                       plan, d_out, D, nrows, lpb);
+    XH_LAUNCH_CHECK();
+    return XH_OK;
+}
+
+int xh_fp_project_f64(xh_fp *fp, const double *d_eul, int32_t eul_stride, int32_t n, const double *d_ctf, size_t ctf_stride, double *d_out)
+{
+    if (n == 0) return XH_OK;
+    XH_TRY(xh_buf_reserve(fp->ctx, fp->d_pf, sizeof(xh_cd) * (size_t)fp->D * (fp->D / 2 + 1) * n));
+    return fp_launch<double>(fp, d_eul, eul_stride, n, d_ctf, ctf_stride, d_out);
+}
 
 extern "C" {
 
@@ -282,33 +318,18 @@ int xh_fp_project(xh_fp *fp, const double *h_angles, int32_t n, const double *d_
     XH_HIP(hipSetDevice(fp->ctx->device));
     if (n == 0) return XH_OK;
     xh_ctx *ctx = fp->ctx;
-    const int D = fp->D, xh = D / 2 + 1;
-    const size_t per = (size_t)D * xh;
+    const int D = fp->D;
+    const size_t per = (size_t)D * (D / 2 + 1);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)512 << 20) / (per * sizeof(xh_cd))));
     XH_TRY(xh_buf_reserve(ctx, fp->d_pf, sizeof(xh_cd) * per * chunk));
     XH_TRY(xh_buf_reserve(ctx, fp->d_eul, sizeof(double) * 9 * chunk));
-    const XhPlan<double> &plan = fp->planD.plan;
-    const int lpb = xh_plan_lpb(plan, 64 * 1024, 16);
-    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << plan.logM;
     std::vector<double> E(9 * (size_t)chunk);
     for (int p0 = 0; p0 < n; p0 += chunk) {
         const int m = std::min(chunk, n - p0);
-        for (int p = 0; p < m; ++p) h_euler(h_angles[3 * (p0 + p)], h_angles[3 * (p0 + p) + 1], h_angles[3 * (p0 + p) + 2], &E[9 * (size_t)p]);
+        for (int p = 0; p < m; ++p) xh_fp_euler(h_angles[3 * (p0 + p)], h_angles[3 * (p0 + p) + 1], h_angles[3 * (p0 + p) + 2], &E[9 * (size_t)p]);
         XH_HIP(hipMemcpyAsync(fp->d_eul.p, E.data(), sizeof(double) * 9 * m, hipMemcpyHostToDevice, ctx->stream));
         XH_HIP(hipStreamSynchronize(ctx->stream));
-        hipLaunchKernelGGL(k_fp_slice, dim3((unsigned)((per * m + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)fp->d_re.p,
-                           (const double *)fp->d_im.p, (const double *)fp->d_eul.p, d_ctf, (xh_cd *)fp->d_pf.p, m, D, fp->P, fp->cdim,
-                           fp->cstart, fp->maxFreq * fp->maxFreq);
-        XH_LAUNCH_CHECK();
-        // inverse along y: lines (p, j): offset p*per + j, element stride xh
-        const size_t ncol = (size_t)m * xh;
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((ncol + lpb - 1) / lpb)), dim3(256), smem, ctx->stream,
-                           (xh_cd *)fp->d_pf.p, plan, ncol, (size_t)xh, per, (size_t)1, (size_t)xh, lpb);
-        XH_LAUNCH_CHECK();
-        const size_t nrows = (size_t)m * D;
-        hipLaunchKernelGGL(k_fp_c2r_rows, dim3((unsigned)((nrows + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, (const xh_cd *)fp->d_pf.p,
-                           plan, d_out + (size_t)p0 * D * D, D, nrows, lpb);
-        XH_LAUNCH_CHECK();
+        XH_TRY(fp_launch<float>(fp, (const double *)fp->d_eul.p, 9, m, d_ctf, (size_t)0, d_out + (size_t)p0 * D * D));
     }
     return XH_OK;
 }

@@ -29,6 +29,7 @@
 // The reference's power(double, int) truncates weightPower to an integer before pow; so does this file.
 #include "xh_fft3d.h"
 #include "../host/powell.h"
+#include "../host/powell_batch.h"
 #include <cmath>
 
 namespace {
@@ -817,4 +818,26 @@ int xh_powell_minimize(int32_t n, double *p, const double *steps, double ftol, x
     return XH_OK;
 }
 
+int xh_powell_minimize_batch(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
+                             xh_batch_cost_fn f, void *user, double *fret, int32_t *iter, int64_t *evals)
+{
+    XH_CHECK(nprob >= 0 && n && nmax >= 1 && p && steps && capacity >= 1 && f && fret && iter, XH_ERR_ARG, "xh_powell_minimize_batch: bad argument");
+    return xh_powell_lockstep(nprob, n, nmax, p, steps, ftol, capacity, f, nullptr, user, fret, iter, evals);
+}
+
 }  // extern "C"
+
+// the scheduler behind xh_powell_minimize_batch and xh_ca2_refine; it lives in this translation unit so that every search runs the
+// one compiled powellOptimizer that xh_powell_minimize runs (same code, same floating-point contraction setting, same bits)
+int xh_powell_lockstep(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
+                       xh_batch_cost_fn f, xh_lockstep_pre_fn pre, void *user, double *fret, int32_t *iter, int64_t *evals)
+{
+    for (int q = 0; q < nprob; ++q)
+        XH_CHECK(n[q] >= 1 && n[q] <= nmax, XH_ERR_ARG, "xh_powell_minimize_batch: problem %d has %d variables, outside 1..%d", q, n[q], nmax);
+    if (nprob == 0) return XH_OK;
+    xh_powell::Lockstep L;
+    const int rc = L.run(nprob, n, nmax, p, steps, ftol, capacity, f, pre, user, fret, iter, evals);
+    XH_CHECK(rc != xh_powell::Lockstep::kNoStacks, XH_ERR_NOMEM, "xh_powell_minimize_batch: out of host memory for %d coroutine stacks", capacity);
+    if (rc > 0 || rc < XH_ERR_UNSUPPORTED) xh_set_error("xh_powell_minimize_batch: the cost callback returned %d", rc);
+    return rc;
+}

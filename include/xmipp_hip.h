@@ -732,6 +732,51 @@ int xh_ca2_refine(xh_ca2 *h, double *h_vars, double *h_cost, int32_t *h_iter, in
 /* of the last refine: device steps, rows evaluated, seconds inside device steps (upload to the wait's end), seconds in all */
 int xh_ca2_stats(const xh_ca2 *h, double *h_stats);
 
+/* ---- xmipp_volume_deform_sph (reconstruction/volume_deform_sph.cpp; CUDA twin reconstruction_adapt_cuda/volume_deform_sph_gpu.cpp,
+ * reconstruction_cuda/cuda_volume_deform_sph.cu) ----
+ * The Zernike3D deformation that fits an input volume to a reference: g(p) = sum_idx c_idx Z_idx(p / Rmax) inside the ball r < Rmax about
+ * the Xmipp origin (index - size / 2), 0 outside, fitted by Powell's method over
+ *   cost = sqrt(diff2 / count) + lambda (sqrt(modg / count) + |sumVI - sumVD| / sumVI)
+ * with, over every voxel of every (input I_p, reference R_p) pair, vI = I_p sampled trilinearly at p + g(p) (0 outside the volume),
+ * diff2 = sum (R_p - vI)^2, sumVD = sum of the vI >= 0, modg = sum |g|^2, count = pairs Z Y X, sumVI = sum of the input voxels >= 0.
+ * Everything is fp64; the volumes stay on the device. Volumes and results of these calls are host arrays [Z][Y][X].
+ * The variables x [3 nterms] are cx, then cy, then cz of every term, in the order of xh_vds_terms.
+ * Supported degrees: l1 <= 5, l2 <= 4 (the polynomial forms); anything beyond is XH_ERR_UNSUPPORTED. Deviations from the reference
+ * (details in xh_vds.hip): the displacement is the CUDA twin's (the CPU loop drops a term whose x coefficient is 0); the search moves
+ * only the variables whose step is 1; normalize_Robust follows stated readings of xmippCore primitives. */
+typedef struct xh_vds xh_vds;
+/* host only, no device needed. Terms of degrees (L1, L2) (numCoefficients): for h = 0 .. L2, l = h, h + 2, ... <= L1, m = -h .. h the term
+ * (l1 = l, n = h, l2 = h, m), written to out [n][4] (fillVectorTerms) */
+int xh_vds_num_terms(int32_t L1, int32_t L2, int32_t *n);
+int xh_vds_terms(int32_t L1, int32_t L2, int32_t *out);
+/* host only: one basis term, R_l1^n(r) S_l2^m(xr, yr, zr) (ZernikeSphericalHarmonics), by the function the kernels run */
+int xh_vds_zsh(int32_t l1, int32_t n, int32_t l2, int32_t m, double xr, double yr, double zr, double r, double *out);
+/* host only: normalize_Robust with a zero background mask, in place: (v - median of the background) / (99th percentile of the
+ * foreground) with the two split by EntropySegmentation, clipped to +-clip when clip > 0 (the program: 1.3284). A constant volume, an
+ * empty foreground or background and a percentile <= 0 are XH_ERR_ARG. */
+int xh_vds_normalize_robust(double *v, size_t n, double clip);
+/* Rmax < 0: X / 2 */
+int xh_vds_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t L1, int32_t L2, double Rmax, double lambda, xh_vds **out);
+int xh_vds_destroy(xh_vds *h);
+/* Rmax as resolved, the number of terms, sumVI of the loaded pairs; null pointers are skipped */
+int xh_vds_info(const xh_vds *h, double *Rmax, int32_t *nterms, double *sumVI);
+/* REALGAUSSIAN low pass exp(-pi^2 w^2 sigma^2), w the digital frequency (FourierFilter::applyMaskSpace). Synchronous. */
+int xh_vds_gauss(xh_vds *h, double sigma, const double *h_in, double *h_out);
+/* the pairs h_I, h_R [npairs][Z][Y][X] (already normalised), copied to the device; computes sumVI and the share of diff2 and sumVD of
+ * the voxels with r >= Rmax, which no coefficient changes */
+int xh_vds_set_pairs(xh_vds *h, int32_t npairs, const double *h_I, const double *h_R);
+/* one evaluation at h_x [3 nterms] -> h_out[4] = cost, diff2, sumVD, modg. The same h_x gives the same bits on every call. Synchronous. */
+int xh_vds_cost(xh_vds *h, const double *h_x, double *h_out);
+/* one stage of the program's loop: Powell (xh_powell_minimize, ftol 0.01) from h_x over the first numCoefficients(L1, l2_stage) entries
+ * of each third of h_x, step 1; the others stay. fret is the cost at the returned h_x; evals (nullable) the number of evaluations. */
+int xh_vds_refine_stage(xh_vds *h, int32_t l2_stage, double *h_x, double *fret, int32_t *iter, int64_t *evals);
+/* h_VO = h_raw sampled at p + g(p); h_G (nullable) [3][Z][Y][X] = gx, gy, gz, exactly 0 where r >= Rmax. Synchronous. */
+int xh_vds_apply(xh_vds *h, const double *h_raw, const double *h_x, double *h_VO, double *h_G);
+/* computeStrain: h_G [3][Z][Y][X] is low-passed (REALGAUSSIAN, sigma 2) in place; over the interior (2 voxels in from every face), with
+ * U = grad g by the five-point stencil (1, -8, 8, -1) / 12, h_LS = |det(sym U)| and h_LR = 180 / pi sqrt(h01^2 + h02^2 + h12^2) of the
+ * antisymmetric part (the modulus of its imaginary eigenvalues) where that exceeds 1e-6, else 0; both are 0 on the border. Synchronous. */
+int xh_vds_strain(xh_vds *h, double *h_G, double *h_LS, double *h_LR);
+
 #ifdef __cplusplus
 }
 #endif

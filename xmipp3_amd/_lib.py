@@ -159,6 +159,19 @@ SIGNATURES = {
     "xh_ca2_filtered": (C.c_int, [vp, i32, vp, C.POINTER(C.c_double)]),
     "xh_ca2_refine": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "xh_ca2_stats": (C.c_int, [vp, vp]),
+    "xh_vds_num_terms": (C.c_int, [i32, i32, C.POINTER(i32)]),
+    "xh_vds_terms": (C.c_int, [i32, i32, vp]),
+    "xh_vds_zsh": (C.c_int, [i32, i32, i32, i32, d, d, d, d, C.POINTER(C.c_double)]),
+    "xh_vds_normalize_robust": (C.c_int, [vp, sz, d]),
+    "xh_vds_create": (C.c_int, [vp, i32, i32, i32, i32, i32, d, d, pvp]),
+    "xh_vds_destroy": (C.c_int, [vp]),
+    "xh_vds_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double)]),
+    "xh_vds_gauss": (C.c_int, [vp, d, vp, vp]),
+    "xh_vds_set_pairs": (C.c_int, [vp, i32, vp, vp]),
+    "xh_vds_cost": (C.c_int, [vp, vp, vp]),
+    "xh_vds_refine_stage": (C.c_int, [vp, i32, vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i64)]),
+    "xh_vds_apply": (C.c_int, [vp, vp, vp, vp, vp]),
+    "xh_vds_strain": (C.c_int, [vp, vp, vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

@@ -814,6 +814,120 @@ def halves_binary_mask(values):
     check(lib().xh_halves_binary_mask(_np_ptr(v), v.size, _np_ptr(m)))
     return m
 
+def vds_num_terms(L1, L2):
+    """terms of the Zernike3D basis of degrees (L1, L2) (host only)"""
+    n = C.c_int32()
+    check(lib().xh_vds_num_terms(int(L1), int(L2), C.byref(n)))
+    return n.value
+
+
+def vds_terms(L1, L2):
+    """the basis terms (l1, n, l2, m) of degrees (L1, L2), int32 [n, 4] (host only)"""
+    out = np.zeros((vds_num_terms(L1, L2), 4), np.int32)
+    check(lib().xh_vds_terms(int(L1), int(L2), _np_ptr(out)))
+    return out
+
+
+def vds_zsh(l1, n, l2, m, xr, yr, zr, r):
+    """one basis term at one point, by the function the kernels run (host only)"""
+    v = C.c_double()
+    check(lib().xh_vds_zsh(int(l1), int(n), int(l2), int(m), float(xr), float(yr), float(zr), float(r), C.byref(v)))
+    return v.value
+
+
+def vds_normalize_robust(v, clip=1.3284):
+    """normalize_Robust of a float64 array with a zero background mask; returns a new array (host only)"""
+    out = np.ascontiguousarray(v, np.float64).copy()
+    check(lib().xh_vds_normalize_robust(_np_ptr(out), out.size, float(clip)))
+    return out
+
+
+class VolumeDeformSph(_Handle):
+    """The device side of xmipp_volume_deform_sph: the Zernike3D deformation of degrees (L1, L2) that fits an input volume to a
+    reference. Volumes are numpy float64 [Z, Y, X] on the host (they stay on the device once set); the variables x are
+    [3 * nterms]: cx, then cy, then cz."""
+
+    _destroy = "xh_vds_destroy"
+
+    def __init__(self, ctx, shape, L1=3, L2=2, Rmax=-1.0, lam=0.00025):
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        self.L1, self.L2 = int(L1), int(L2)
+        h = C.c_void_p()
+        check(lib().xh_vds_create(ctx.h, *self.shape, self.L1, self.L2, float(Rmax), float(lam), C.byref(h)))
+        super().__init__(ctx, h)
+        r, n = C.c_double(), C.c_int32()
+        check(lib().xh_vds_info(self.h, C.byref(r), C.byref(n), None))
+        self.Rmax, self.nterms = r.value, n.value
+
+    def _vols(self, v, lead=()):
+        v = np.ascontiguousarray(v, np.float64)
+        assert tuple(v.shape) == tuple(lead) + self.shape, v.shape
+        return v
+
+    def _x(self, x):
+        x = np.ascontiguousarray(x, np.float64)
+        assert x.shape == (3 * self.nterms,), x.shape
+        return x
+
+    def gauss(self, v, sigma):
+        """the REALGAUSSIAN low pass exp(-pi^2 w^2 sigma^2) of a volume"""
+        v = self._vols(v)
+        out = np.empty_like(v)
+        check(lib().xh_vds_gauss(self.h, float(sigma), _np_ptr(v), _np_ptr(out)))
+        return out
+
+    def set_pairs(self, I, R):
+        """the (input, reference) pairs [npairs, Z, Y, X], already normalised"""
+        I = np.ascontiguousarray(I, np.float64)
+        I = self._vols(I, (I.shape[0],))
+        R = self._vols(R, (I.shape[0],))
+        check(lib().xh_vds_set_pairs(self.h, I.shape[0], _np_ptr(I), _np_ptr(R)))
+
+    @property
+    def sumVI(self):
+        s = C.c_double()
+        check(lib().xh_vds_info(self.h, None, None, C.byref(s)))
+        return s.value
+
+    def cost(self, x):
+        """(cost, diff2, sumVD, modg) at x, float64 [4]"""
+        out = np.zeros(4)
+        check(lib().xh_vds_cost(self.h, _np_ptr(self._x(x)), _np_ptr(out)))
+        return out
+
+    def refine_stage(self, stage, x):
+        """one stage of the search from x: (x, cost, iterations, evaluations)"""
+        x = self._x(x).copy()
+        fret, it, ev = C.c_double(), C.c_int32(), C.c_int64()
+        check(lib().xh_vds_refine_stage(self.h, int(stage), _np_ptr(x), C.byref(fret), C.byref(it), C.byref(ev)))
+        return x, fret.value, it.value, ev.value
+
+    def refine(self, x=None):
+        """the program's loop, stages 0 .. L2: (x, cost, total evaluations)"""
+        x = np.zeros(3 * self.nterms) if x is None else self._x(x)
+        cost, evals = None, 0
+        for stage in range(self.L2 + 1):
+            x, cost, _, ev = self.refine_stage(stage, x)
+            evals += ev
+        return x, cost, evals
+
+    def apply(self, raw, x, field=False):
+        """raw sampled at the displaced positions; with field, also g [3, Z, Y, X]"""
+        raw = self._vols(raw)
+        VO = np.empty_like(raw)
+        G = np.empty((3,) + self.shape) if field else None
+        check(lib().xh_vds_apply(self.h, _np_ptr(raw), _np_ptr(self._x(x)), _np_ptr(VO), _np_ptr(G)))
+        return (VO, G) if field else VO
+
+    def strain(self, G):
+        """(the field low-passed at sigma 2, local strain, local rotation in degrees) of a field [3, Z, Y, X]"""
+        G = self._vols(G, (3,)).copy()
+        LS, LR = np.empty(self.shape), np.empty(self.shape)
+        check(lib().xh_vds_strain(self.h, _np_ptr(G), _np_ptr(LS), _np_ptr(LR)))
+        return G, LS, LR
+
+
 def powell_minimize(f, p, steps=None, ftol=0.01):
     """Powell's method of xmipp3_amd/host/powell.h (host only): f(x) takes the list of variables; returns (p, fmin, iterations)"""
     from ._lib import COST_FN

@@ -13,7 +13,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 mkdir -p build/variants
 # build.sh's flags (files that must round like the reference's scalar code: no FMA contraction)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-function -Wno-unused-result"
-case $SRC in xh_rf|xh_fsc|xh_halves) FLAGS="$FLAGS -ffp-contract=off";; esac
+case $SRC in xh_rf|xh_fsc|xh_halves|xh_powell) FLAGS="$FLAGS -ffp-contract=off";; esac
 # The file is compiled a second time without the extra flags to compare against.  hipcc gives every compilation a new unit id, which
 # changes the object; with the same -cuid the two objects are equal byte for byte unless the flags changed the code.
 obj=build/variants/${SRC}_$tag.o

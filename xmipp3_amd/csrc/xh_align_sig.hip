@@ -200,7 +200,7 @@ struct xh_align_sig {
     xh_ctx *ctx = nullptr;
     int D = 0, maxRefs = 0, batch = 0, maxShift = 0, iters = 0, R = 0;
     EsRotation rot;                   // ring table and the per-batch buffers of the rotation estimator
-    EsFft2d64 fft;
+    XhFft2d64 fft;
     XhBuf Fref, refSpec, refs;        // per reference: polar ring DFT, shift spectrum, pixels (for the merit)
     XhBuf dest, work, map, pos, pose, A, meritSR;
     ~xh_align_sig()
@@ -239,11 +239,11 @@ static int as_step_shift(xh_align_sig *h, long long g0, int n, int m, const floa
     const int D = h->D;
     const size_t per = (size_t)D * D, total = per * m;
     xh_cd *w = (xh_cd *)h->work.p;
-    hipLaunchKernelGGL(k_es_to_complex64, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, (const float *)h->dest.p, w, total);
-    XH_TRY(es_fft2d64(ctx, h->fft, w, m, false));
+    hipLaunchKernelGGL(xh_k_to_complex64<float>, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, (const float *)h->dest.p, w, total);
+    XH_TRY(xh_fft2d64(ctx, h->fft, w, m, false));
     hipLaunchKernelGGL(k_as_correlate64, dim3(as_blocks(per), m), dim3(256), 0, ctx->stream, w, (const xh_cd *)h->refSpec.p, D, g0, n);
-    XH_TRY(es_fft2d64(ctx, h->fft, w, m, true));
-    hipLaunchKernelGGL(k_es_real64, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, (const xh_cd *)w, (float *)h->map.p, total);
+    XH_TRY(xh_fft2d64(ctx, h->fft, w, m, true));
+    hipLaunchKernelGGL(xh_k_real64<float>, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, (const xh_cd *)w, (float *)h->map.p, total);
     XH_LAUNCH_CHECK();
     hipLaunchKernelGGL((k_es_extrema<false>), dim3(m), dim3(256), 0, ctx->stream, (const float *)h->map.p, per, D, D, 1, h->maxShift, 0, (float *)h->pos.p, (float *)nullptr);
     XH_LAUNCH_CHECK();
@@ -302,7 +302,7 @@ int xh_align_sig_create(xh_ctx *ctx, int32_t D, int32_t max_refs, int32_t batch_
     h->ctx = ctx; h->D = D; h->maxRefs = max_refs; h->batch = batch_pairs; h->maxShift = max_shift; h->iters = iters;
     const size_t per = (size_t)D * D, B = (size_t)batch_pairs;
     XH_TRY(es_rotation_plan(ctx, D, first_ring, last_ring, h->rot));
-    XH_TRY(es_fft2d64_create(ctx, D, D, h->fft, "xh_align_sig_create"));
+    XH_TRY(xh_fft2d64_create(ctx, D, D, h->fft, "xh_align_sig_create"));
     EsRotation &R = h->rot;
     XH_TRY(xh_buf_alloc(ctx, h->Fref, sizeof(double2) * (size_t)R.ncoefs * max_refs));
     XH_TRY(xh_buf_alloc(ctx, h->refSpec, sizeof(xh_cd) * per * max_refs));
@@ -332,9 +332,9 @@ int xh_align_sig_load_references(xh_align_sig *h, const float *d_refs, int32_t R
     const size_t per = (size_t)h->D * h->D, total = per * R;
     XH_TRY(es_rotation_transform(h->rot, d_refs, R, 0, (double2 *)h->Fref.p));
     XH_HIP(hipMemcpyAsync(h->refs.p, d_refs, sizeof(float) * total, hipMemcpyDeviceToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_es_to_complex64, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, d_refs, (xh_cd *)h->refSpec.p, total);
+    hipLaunchKernelGGL(xh_k_to_complex64<float>, dim3(as_blocks(total)), dim3(256), 0, ctx->stream, d_refs, (xh_cd *)h->refSpec.p, total);
     XH_LAUNCH_CHECK();
-    XH_TRY(es_fft2d64(ctx, h->fft, (xh_cd *)h->refSpec.p, R, false));
+    XH_TRY(xh_fft2d64(ctx, h->fft, (xh_cd *)h->refSpec.p, R, false));
     XH_HIP(hipStreamSynchronize(ctx->stream));
     h->R = R;
     return XH_OK;

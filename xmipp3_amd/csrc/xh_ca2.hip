@@ -20,6 +20,7 @@
 #include "xh_common.h"
 #include "xh_fft.h"
 #include "xh_plan.h"
+#include "xh_reduce.h"
 #include "xh_ctf.h"
 #include "xh_bspline.h"
 #include <chrono>
@@ -35,13 +36,6 @@ static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evalu
 const double kAcc = 1e-6;       // XMIPP_EQUAL_ACCURACY
 const double kBarrier = 1e38;   // continuous2cost's cost of a vector out of bounds
 
-// image (float) -> complex doubles
-__global__ void k_ca2_to_complex(const float *__restrict__ in, xh_cd *__restrict__ out, size_t total)
-{
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < total) out[idx] = xh_cd{(double)in[idx], 0.};
-}
-
 // FourierFilter LOWPASS / RAISED_COSINE (fourier_filter.cpp:423-432) on the full spectrum, the 1/D^2 of the inverse folded in; where the
 // image has a CTF (rows: one evaluation-style row per image, nullable) also the envelope image of generateEnvelope (ctf.h:1271-1290)
 // that processImage multiplies into the spectrum (L447-460). Both filters are real and even, so one pass over the full spectrum of the
@@ -51,7 +45,7 @@ __global__ void k_ca2_lowpass(xh_cd *__restrict__ F, size_t total, int D, double
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int j = idx % D, i = (idx / D) % D;
-    const double fy = (double)(i <= D / 2 ? i : i - D) / (double)D, fx = (double)(j <= D / 2 ? j : j - D) / (double)D;   // FFT_IDX2DIGFREQ
+    const double fy = d_digfreq(i, D), fx = d_digfreq(j, D);
     const double absw = sqrt(fx * fx + fy * fy);
     double m;
     if (absw < w1) m = 1;
@@ -71,12 +65,6 @@ __global__ void k_ca2_lowpass(xh_cd *__restrict__ F, size_t total, int D, double
     }
     xh_cd v = F[idx];
     F[idx] = xh_cd{v.x * m, v.y * m};
-}
-
-__global__ void k_ca2_take_real(const xh_cd *__restrict__ F, double *__restrict__ out, size_t total)
-{
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < total) out[idx] = F[idx].x;
 }
 
 // updateCTFImage (L225-247) for the rows of one evaluation: generateCTF with K = 1 on the half spectrum [D][D/2+1] (the part the projector
@@ -132,20 +120,6 @@ __device__ __forceinline__ double d_ca2_linear(const double *__restrict__ V1, in
     return tmp;
 }
 
-// sum over the workgroup's 256 threads in a fixed order; every thread returns the total
-__device__ __forceinline__ double d_ca2_reduce(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // tranformImage (L275-317): one workgroup per evaluation. Writes Ifilteredp (0 outside the mask), E, and the cost.
 // l1: CONTCOST_L1 = mean over the mask of |a P + b - Ifilteredp|; else CONTCOST_CORR = -correlationIndex(Ifilteredp, P, mask), where a
 // sigma below XMIPP_EQUAL_ACCURACY gives correlation 0.
@@ -153,7 +127,7 @@ __global__ void __launch_bounds__(256)
 k_ca2_cost(const double *__restrict__ ev, const double *__restrict__ Ifiltered, const double *__restrict__ P, const int *__restrict__ mask,
            double *__restrict__ Ifp, double *__restrict__ E, double *__restrict__ cost, int D, int l1, double nmask)
 {
-    __shared__ double red[256];
+    __shared__ double red[1][256];
     const int e = blockIdx.x, tid = threadIdx.x, DD = D * D;
     const double *q = ev + (size_t)kEv * e;
     double A[6];
@@ -182,14 +156,14 @@ k_ca2_cost(const double *__restrict__ ev, const double *__restrict__ Ifiltered, 
         Ie[n] = val;
         Ee[n] = err;
     }
-    s0 = d_ca2_reduce(s0, red);
+    s0 = xh_block_sum(s0, red);
     if (l1) {
         if (tid == 0) cost[e] = s0 * (1.0 / nmask);      // cost *= iMask2Dsum (L314)
         return;
     }
-    s1 = d_ca2_reduce(s1, red);
-    s2 = d_ca2_reduce(s2, red);
-    s3 = d_ca2_reduce(s3, red);
+    s1 = xh_block_sum(s1, red);
+    s2 = xh_block_sum(s2, red);
+    s3 = xh_block_sum(s3, red);
     const double mx = s0 / nmask, my = s1 / nmask;
     const double sx = sqrt(fabs(s2 / nmask - mx * mx)), sy = sqrt(fabs(s3 / nmask - my * my));
     if (fabs(sx) < kAcc || fabs(sy) < kAcc) {      // uniform over the workgroup: every thread holds the same sums
@@ -199,7 +173,7 @@ k_ca2_cost(const double *__restrict__ ev, const double *__restrict__ Ifiltered, 
     double r = 0;
     for (int n = tid; n < DD; n += 256)
         if (mask[n]) r += (Ie[n] - mx) * (Pe[n] - my);      // Ie[n] was written by this thread
-    r = d_ca2_reduce(r, red);
+    r = xh_block_sum(r, red);
     if (tid == 0) cost[e] = -(r / ((sx * sy) * nmask));
 }
 
@@ -253,7 +227,7 @@ struct xh_ca2 {
     XhBuf d_mask, d_If, d_ev, d_P, d_Ifp, d_E, d_cost;
     XhBuf d_ctfRow, d_ctfPart;                      // [capacity] and [particles] CTF images [D][D/2+1]; allocated when a particle has a CTF
     bool anyCTF = false;
-    XhPlanBufs<double> planD;
+    XhFft2d64 fft;                                  // the load's transforms
     double *h_ev = nullptr, *h_cost = nullptr;      // pinned
     std::vector<Particle> parts;
     std::vector<int> active;                        // the searched variables' indices into the 13
@@ -431,7 +405,7 @@ int xh_ca2_create(xh_ctx *ctx, const float *d_vol, int32_t D, const xh_ca2_param
     h->l1 = prm->optimize_gray ? 1 : 0;         // contCost (L218-221)
     // the projector of preProcess (L203-207): the coefficient cubes are xh_fp_create's own
     XH_TRY(xh_fp_create(ctx, d_vol, D, prm->padding, prm->sampling / prm->max_resolution, 3, &h->fp));
-    XH_TRY(xh_plan_create<double>(ctx, D, h->planD));
+    XH_TRY(xh_fft2d64_create(ctx, D, D, h->fft, "xh_ca2_create"));
     // BINARY_CIRCULAR_MASK, INNER_MASK, R1 = Rmax about the Xmipp origin (L179-187)
     const double R = prm->Rmax < 0 ? (double)(D / 2) : prm->Rmax;
     std::vector<int32_t> mask((size_t)D * D);
@@ -536,39 +510,22 @@ static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, i
             }
         }
     }
-    const XhPlan<double> &plan = h->planD.plan;
-    const int lpb = xh_plan_lpb(plan, 64 * 1024, 16);
-    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << plan.logM;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)256 << 20) / (DD * sizeof(xh_cd))));
     XhBuf d_img, d_F;
     XH_TRY(xh_buf_alloc(ctx, d_img, sizeof(float) * DD * chunk));
     XH_TRY(xh_buf_alloc(ctx, d_F, sizeof(xh_cd) * DD * chunk));
+    xh_cd *F = (xh_cd *)d_F.p;
     const double w1 = h->prm.sampling / h->prm.max_resolution;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
-        const size_t total = DD * m, nl = (size_t)m * D;
-        const unsigned g = (unsigned)((total + 255) / 256), gl = (unsigned)((nl + lpb - 1) / lpb);
+        const size_t total = DD * m;
+        const unsigned g = (unsigned)((total + 255) / 256);
         XH_HIP(hipMemcpyAsync(d_img.p, h_images + DD * i0, sizeof(float) * total, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_ca2_to_complex, dim3(g), dim3(256), 0, ctx->stream, (const float *)d_img.p, (xh_cd *)d_F.p, total);
-        XH_LAUNCH_CHECK();
-        // rows: line l at l * D, stride 1; columns: line (image, j) at image * D^2 + j, stride D
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)d_F.p, plan, nl, (size_t)1, (size_t)D,
-                           (size_t)0, (size_t)1, lpb);
-        XH_LAUNCH_CHECK();
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)d_F.p, plan, nl, (size_t)D, DD,
-                           (size_t)1, (size_t)D, lpb);
-        XH_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ca2_lowpass, dim3(g), dim3(256), 0, ctx->stream, (xh_cd *)d_F.p, total, D, w1, 0.02,
-                           h->anyCTF ? (const double *)d_rows.p + (size_t)kEv * i0 : (const double *)nullptr, iTs);
-        XH_LAUNCH_CHECK();
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)d_F.p, plan, nl, (size_t)D, DD,
-                           (size_t)1, (size_t)D, lpb);
-        XH_LAUNCH_CHECK();
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3(gl), dim3(256), smem, ctx->stream, (xh_cd *)d_F.p, plan, nl, (size_t)1, (size_t)D,
-                           (size_t)0, (size_t)1, lpb);
-        XH_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ca2_take_real, dim3(g), dim3(256), 0, ctx->stream, (const xh_cd *)d_F.p, (double *)h->d_If.p + DD * i0, total);
-        XH_LAUNCH_CHECK();
+        XH_LAUNCH256(ctx, xh_k_to_complex64<float>, g, (const float *)d_img.p, F, total);
+        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, false));
+        XH_LAUNCH256(ctx, k_ca2_lowpass, g, F, total, D, w1, 0.02, h->anyCTF ? (const double *)d_rows.p + (size_t)kEv * i0 : (const double *)nullptr, iTs);
+        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, true));
+        XH_LAUNCH256(ctx, xh_k_real64<double>, g, (const xh_cd *)F, (double *)h->d_If.p + DD * i0, total);
         XH_HIP(hipStreamSynchronize(ctx->stream));
     }
     for (int i = 0; i < n; ++i) {

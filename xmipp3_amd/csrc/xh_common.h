@@ -38,6 +38,13 @@ void xh_set_error(const char *fmt, ...);
 
 #define XH_LAUNCH_CHECK() XH_HIP(hipGetLastError())
 
+// a kernel of 256-thread workgroups on the context's stream
+#define XH_LAUNCH256(ctx, kern, grid, ...)                                                       \
+    do {                                                                                         \
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, (ctx)->stream, __VA_ARGS__);          \
+        XH_LAUNCH_CHECK();                                                                       \
+    } while (0)
+
 struct xh_ctx {
     int device;
     hipStream_t stream;
@@ -89,8 +96,8 @@ int xh_fft2d_rows_of_real_pairs_kept(xh_fft2d *f, const float *d_frame, const fl
 void xh_fp_euler(double rot, double tilt, double psi, double *A);
 int xh_fp_project_f64(xh_fp *fp, const double *d_eul, int32_t eul_stride, int32_t n, const double *d_ctf, size_t ctf_stride, double *d_out);
 
-// lockstep Powell (host/powell_batch.h; defined in xh_halves.hip next to xh_powell_minimize). pre (nullable) decides a cost on the
-// host: it returns 1 and sets *cost, and that evaluation never reaches f
+// lockstep Powell (host/powell_batch.h, xh_powell.hip). pre (nullable) decides a cost on the host: it returns 1 and sets *cost, and
+// that evaluation never reaches f
 typedef int32_t (*xh_lockstep_pre_fn)(int32_t problem, const double *x, double *cost, void *user);
 int xh_powell_lockstep(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
                        xh_batch_cost_fn f, xh_lockstep_pre_fn pre, void *user, double *fret, int32_t *iter, int64_t *evals);
@@ -102,5 +109,9 @@ static inline int xh_ilog2(int n)
     return l;
 }
 static inline bool xh_is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+
+// FFT_IDX2DIGFREQ (xmippCore xmipp_fft.h; in-tree copy cuda_gpu_reconstruct_fourier.cpp:381-385): the digital frequency, in
+// [-0.5, 0.5], of index idx of a transform of `size` points
+__device__ __forceinline__ double d_digfreq(int idx, int size) { return size <= 1 ? 0.0 : (double)(idx <= (size >> 1) ? idx : idx - size) / (double)size; }
 
 #endif

@@ -76,9 +76,6 @@ __device__ __forceinline__ double d_ctf_at(const CtfSide &s, double X, double Y,
     return -s.K * (s.Ksin * sine_part - s.Kcos * cosine_part) * E;
 }
 
-// FFT_IDX2DIGFREQ (xmippCore xmipp_fft.h; in-tree copy cuda_gpu_reconstruct_fourier.cpp:381-385)
-__device__ __forceinline__ double d_digfreq(int idx, int size) { return size <= 1 ? 0.0 : (double)(idx <= size / 2 ? idx : idx - size) / (double)size; }
-
 // the damping envelope alone, E of getValueDampingAt (ctf.h:424-449) clamped at 0: generateEnvelope's -getValueDampingAt() for K = 1
 __device__ __forceinline__ double d_ctf_envelope(const CtfSide &s, double X, double Y)
 {

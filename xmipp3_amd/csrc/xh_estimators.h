@@ -11,6 +11,7 @@
 #include "xh_common.h"
 #include "xh_bspline.h"
 #include "xh_plan.h"
+#include "xh_reduce.h"
 
 namespace {
 typedef float2 es_cf;
@@ -62,18 +63,6 @@ __global__ void __launch_bounds__(256) k_es_extrema(const float *__restrict__ da
     }
 }
 
-__global__ void __launch_bounds__(256) k_es_to_complex64(const float *__restrict__ in, xh_cd *__restrict__ out, size_t tot)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < tot) out[t] = xh_cd{(double)in[t], 0.0};
-}
-
-__global__ void __launch_bounds__(256) k_es_real64(const xh_cd *__restrict__ in, float *__restrict__ out, size_t tot)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < tot) out[t] = (float)in[t].x;
-}
-
 // element (x, y) of the centred correlation of the shift estimator: ref conj(other) (-1)^(x+y), double precision
 __device__ __forceinline__ xh_cd es_correlate64_at(xh_cd r, xh_cd o, int x, int y)
 {
@@ -122,13 +111,8 @@ __device__ __forceinline__ float es_corr_index_block(const float *__restrict__ r
     __shared__ double red[5][256];
     double mx = 0, my = 0, sx = 0, sy = 0, sxy = 0;
     for (size_t i = threadIdx.x; i < N; i += 256) { const double a = ref[i], b = y[i]; mx += a; my += b; sx += a * a; sy += b * b; sxy += a * b; }
-    red[0][threadIdx.x] = mx; red[1][threadIdx.x] = my; red[2][threadIdx.x] = sx; red[3][threadIdx.x] = sy; red[4][threadIdx.x] = sxy;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int q = 0; q < 5; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + o];
-        __syncthreads();
-    }
+    const double v[5] = {mx, my, sx, sy, sxy};
+    xh_tree256(red, v);
     if (threadIdx.x != 0) return 0.f;
     const double n = (double)N;
     mx = red[0][0] / n; my = red[1][0] / n;
@@ -333,40 +317,6 @@ static int es_rotation_create(xh_ctx *ctx, const float *d_ref, int32_t D, int32_
 {
     XH_TRY(es_rotation_plan(ctx, D, first_ring, last_ring, R));
     return es_rotation_transform(R, d_ref, 1, 0, (double2 *)R.Fref.p);                // load2DReferenceOneToN: not conjugated
-}
-
-// the shift estimator's line plans, double precision (xh_plan.h)
-struct EsFft2d64 {
-    int x = 0, y = 0;
-    XhPlanBufs<double> planX, planY;
-};
-
-static int es_fft2d64_create(xh_ctx *ctx, int x, int y, EsFft2d64 &P, const char *who)
-{
-    P.x = x; P.y = y;
-    XH_TRY(xh_plan_create<double>(ctx, x, P.planX));
-    XH_TRY(xh_plan_create<double>(ctx, y, P.planY));
-    XH_CHECK((sizeof(xh_cd) << P.planX.plan.logM) <= 64 * 1024 && (sizeof(xh_cd) << P.planY.plan.logM) <= 64 * 1024, XH_ERR_UNSUPPORTED,
-             "%s: a line of %d x %d does not fit the LDS of the double-precision transform", who, x, y);
-    return XH_OK;
-}
-
-// 2-D complex transform of n images [n][y][x] (double) in place, un-normalised: rows then columns
-static int es_fft2d64(xh_ctx *ctx, EsFft2d64 &P, xh_cd *d, int n, bool inverse)
-{
-    const size_t budget = 64 * 1024;
-    const int lx = xh_plan_lpb(P.planX.plan, budget, 16), ly = xh_plan_lpb(P.planY.plan, budget, 16);
-    const size_t rows = (size_t)n * P.y, cols = (size_t)n * P.x;
-    const size_t smx = ((size_t)lx * sizeof(xh_cd)) << P.planX.plan.logM, smy = ((size_t)ly * sizeof(xh_cd)) << P.planY.plan.logM;
-    if (!inverse) {
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((rows + lx - 1) / lx)), dim3(256), smx, ctx->stream, d, P.planX.plan, rows, rows, (size_t)0, (size_t)P.x, (size_t)1, lx);
-        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((cols + ly - 1) / ly)), dim3(256), smy, ctx->stream, d, P.planY.plan, cols, (size_t)P.x, (size_t)P.x * P.y, (size_t)1, (size_t)P.x, ly);
-    } else {
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((cols + ly - 1) / ly)), dim3(256), smy, ctx->stream, d, P.planY.plan, cols, (size_t)P.x, (size_t)P.x * P.y, (size_t)1, (size_t)P.x, ly);
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((rows + lx - 1) / lx)), dim3(256), smx, ctx->stream, d, P.planX.plan, rows, rows, (size_t)0, (size_t)P.x, (size_t)1, lx);
-    }
-    XH_LAUNCH_CHECK();
-    return XH_OK;
 }
 
 #endif

@@ -104,7 +104,7 @@ static int es_rotation_run(EsRotation &R, const float *d_others, int n, float *h
 struct xh_shiftcorr {
     xh_ctx *ctx;
     int x, y, maxShift;
-    EsFft2d64 fft;                        // line transforms of any length (xh_plan.h), double precision
+    XhFft2d64 fft;                        // line transforms of any length (xh_plan.h), double precision
     XhBuf ref, work, map, pos;
     bool refLoaded;
     ~xh_shiftcorr()
@@ -114,7 +114,6 @@ struct xh_shiftcorr {
     }
 };
 
-static int es_fft2d64(xh_shiftcorr *h, xh_cd *d, int n, bool inverse) { return es_fft2d64(h->ctx, h->fft, d, n, inverse); }
 
 extern "C" {
 
@@ -167,7 +166,7 @@ int xh_shiftcorr_create(xh_ctx *ctx, int32_t xdim, int32_t ydim, int32_t max_shi
     // The reference's ShiftCorrEstimator<float> transforms with fftwf; its test images (one-pixel lines) give correlation maps full of
     // exact ties, which single-precision rounding breaks at random.  The device transforms in double and compares the map as floats,
     // so that the first maximum in raster order is the one exact arithmetic has.
-    XH_TRY(es_fft2d64_create(ctx, xdim, ydim, h->fft, "xh_shiftcorr_create"));
+    XH_TRY(xh_fft2d64_create(ctx, xdim, ydim, h->fft, "xh_shiftcorr_create"));
     XH_TRY(xh_buf_alloc(ctx, h->ref, sizeof(xh_cd) * (size_t)xdim * ydim));
     *out = h.release();
     return XH_OK;
@@ -180,9 +179,9 @@ int xh_shiftcorr_load_reference(xh_shiftcorr *h, const float *d_ref)
     xh_ctx *ctx = h->ctx;
     XH_HIP(hipSetDevice(ctx->device));
     const size_t tot = (size_t)h->x * h->y;
-    hipLaunchKernelGGL(k_es_to_complex64, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, d_ref, (xh_cd *)h->ref.p, tot);
+    hipLaunchKernelGGL(xh_k_to_complex64<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, d_ref, (xh_cd *)h->ref.p, tot);
     XH_LAUNCH_CHECK();
-    XH_TRY(es_fft2d64(h, (xh_cd *)h->ref.p, 1, false));
+    XH_TRY(xh_fft2d64(ctx, h->fft, (xh_cd *)h->ref.p, 1, false));
     h->refLoaded = true;
     return XH_OK;
 }
@@ -217,11 +216,11 @@ int xh_shiftcorr_compute_shifts(xh_shiftcorr *h, const float *d_others, int32_t 
         const size_t total = tot * (size_t)m;
         const unsigned grid = (unsigned)((total + 255) / 256);
         xh_cd *w = (xh_cd *)h->work.p;
-        hipLaunchKernelGGL(k_es_to_complex64, dim3(grid), dim3(256), 0, ctx->stream, d_others + (size_t)i0 * tot, w, total);
-        XH_TRY(es_fft2d64(h, w, m, false));
+        hipLaunchKernelGGL(xh_k_to_complex64<float>, dim3(grid), dim3(256), 0, ctx->stream, d_others + (size_t)i0 * tot, w, total);
+        XH_TRY(xh_fft2d64(ctx, h->fft, w, m, false));
         hipLaunchKernelGGL(k_es_correlate64, dim3(grid), dim3(256), 0, ctx->stream, w, (const xh_cd *)h->ref.p, tot, h->x, total);
-        XH_TRY(es_fft2d64(h, w, m, true));
-        hipLaunchKernelGGL(k_es_real64, dim3(grid), dim3(256), 0, ctx->stream, (const xh_cd *)w, (float *)h->map.p + (size_t)i0 * tot, total);
+        XH_TRY(xh_fft2d64(ctx, h->fft, w, m, true));
+        hipLaunchKernelGGL(xh_k_real64<float>, dim3(grid), dim3(256), 0, ctx->stream, (const xh_cd *)w, (float *)h->map.p + (size_t)i0 * tot, total);
         XH_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL((k_es_extrema<false>), dim3(n), dim3(256), 0, ctx->stream, (const float *)h->map.p, tot, h->y, h->x, 1, h->maxShift, 0, (float *)h->pos.p, (float *)nullptr);

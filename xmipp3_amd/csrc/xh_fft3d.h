@@ -1,7 +1,7 @@
 // xh_fft3d.h -- fp64 3-D real transforms of any size (line FFTs of xh_plan.h) in FFTW layout: real [Z][Y][X] <-> half spectrum
 // [Z][Y][X/2+1]. Both directions are un-normalised, as FFTW's and cuFFT's plans are; a caller that wants the 1/N of an inverse passes it
 // as `scale`, which multiplies each result once, the same single rounding as a separate pass over the output.
-// Used by xh_fsc.hip (forward) and xh_halves.hip (both).
+// Used by xh_fsc.hip (forward), xh_halves.hip and xh_vds.hip (both).
 #ifndef XH_FFT3D_H
 #define XH_FFT3D_H
 #include "xh_common.h"
@@ -82,29 +82,42 @@ int fft3d_yz(xh_ctx *ctx, xh_cd *F, int Z, int Y, int xh, const XhPlan<double> &
     return XH_OK;
 }
 
-// forward: d_in [Z][Y][X] (each value times scale) -> F [Z][Y][X/2+1]
-int fft3d_r2c(xh_ctx *ctx, const double *d_in, xh_cd *F, int Z, int Y, int X, const XhPlan<double> &px, const XhPlan<double> &py,
-              const XhPlan<double> &pz, double scale = 1.0)
-{
-    const int xh = X / 2 + 1;
-    const int lpb = xh_plan_lpb(px, 64 * 1024, 8);
-    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.logM, nlines = (size_t)Z * Y;
-    hipLaunchKernelGGL(k_fft3d_rows_r2c, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, d_in, F, px, nlines, X, xh, lpb, scale);
-    XH_LAUNCH_CHECK();
-    return fft3d_yz<false>(ctx, F, Z, Y, xh, py, pz);
-}
+// the plans of one volume size. The tables belong to the struct, so it lives with the handle (or the call) that transforms
+struct XhFft3d {
+    xh_ctx *ctx = nullptr;
+    int Z = 0, Y = 0, X = 0, xh = 0;
+    XhPlanBufs<double> px, py, pz;
 
-// inverse: F [Z][Y][X/2+1] (overwritten) -> d_out [Z][Y][X], each value times scale
-int fft3d_c2r(xh_ctx *ctx, xh_cd *F, double *d_out, int Z, int Y, int X, const XhPlan<double> &px, const XhPlan<double> &py,
-              const XhPlan<double> &pz, double scale)
+    // forward: d_in [Z][Y][X] (each value times scale) -> F [Z][Y][X/2+1]
+    int r2c(const double *d_in, xh_cd *F, double scale = 1.0) const
+    {
+        const int lpb = xh_plan_lpb(px.plan, 64 * 1024, 8);
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.plan.logM, nlines = (size_t)Z * Y;
+        hipLaunchKernelGGL(k_fft3d_rows_r2c, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, d_in, F, px.plan, nlines, X, xh, lpb,
+                           scale);
+        XH_LAUNCH_CHECK();
+        return fft3d_yz<false>(ctx, F, Z, Y, xh, py.plan, pz.plan);
+    }
+
+    // inverse: F [Z][Y][X/2+1] (overwritten) -> d_out [Z][Y][X], each value times scale
+    int c2r(xh_cd *F, double *d_out, double scale) const
+    {
+        XH_TRY(fft3d_yz<true>(ctx, F, Z, Y, xh, py.plan, pz.plan));
+        const int lpb = xh_plan_lpb(px.plan, 64 * 1024, 8);
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.plan.logM, nlines = (size_t)Z * Y;
+        hipLaunchKernelGGL(k_fft3d_rows_c2r, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, d_out, px.plan, nlines, X, xh, lpb,
+                           scale);
+        XH_LAUNCH_CHECK();
+        return XH_OK;
+    }
+};
+
+int xh_fft3d_create(xh_ctx *ctx, int Z, int Y, int X, XhFft3d &f)
 {
-    const int xh = X / 2 + 1;
-    XH_TRY(fft3d_yz<true>(ctx, F, Z, Y, xh, py, pz));
-    const int lpb = xh_plan_lpb(px, 64 * 1024, 8);
-    const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << px.logM, nlines = (size_t)Z * Y;
-    hipLaunchKernelGGL(k_fft3d_rows_c2r, dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, d_out, px, nlines, X, xh, lpb, scale);
-    XH_LAUNCH_CHECK();
-    return XH_OK;
+    f.ctx = ctx; f.Z = Z; f.Y = Y; f.X = X; f.xh = X / 2 + 1;
+    XH_TRY(xh_plan_create<double>(ctx, X, f.px));
+    XH_TRY(xh_plan_create<double>(ctx, Y, f.py));
+    return xh_plan_create<double>(ctx, Z, f.pz);
 }
 
 }  // namespace

@@ -85,7 +85,7 @@ k_fp_slice(const double *__restrict__ R, const double *__restrict__ I, const dou
     const int rem = idx - (size_t)p * per;
     const int i = rem / xh, j = rem - i * xh;
     const double *E = eul + (size_t)eulStride * p;
-    const double freqy = (double)(i <= D / 2 ? i : i - D) / (double)D;       // FFT_IDX2DIGFREQ
+    const double freqy = d_digfreq(i, D);
     const double freqx = (double)j / (double)D;                               // j <= D/2
     xh_cd out = xh_cd{0., 0.};
     if (!((freqy * freqy + freqx * freqx) > maxFreq2)) {

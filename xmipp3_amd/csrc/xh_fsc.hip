@@ -14,9 +14,6 @@
 
 namespace {
 
-// FFT_IDX2DIGFREQ_FAST (xmippCore xmipp_fft.h)
-__device__ __forceinline__ double digfreq(int idx, int size) { return (double)(idx <= size / 2 ? idx : idx - size) / (double)size; }
-
 // realWRAP (xmippCore xmipp_macros.h)
 __device__ __forceinline__ double real_wrap(double x, double x0, double xF)
 {
@@ -43,7 +40,7 @@ k_fsc_shells(const xh_cd *__restrict__ F1, const xh_cd *__restrict__ F2, int Z, 
         const int j = (int)(e % xh);
         const size_t r = e / xh;
         const int i = (int)(r % Y), k = (int)(r / Y);
-        const double fz = digfreq(k, Z), fy = digfreq(i, Y), fx = digfreq(j, X);
+        const double fz = d_digfreq(k, Z), fy = d_digfreq(i, Y), fx = d_digfreq(j, X);
         const double R2 = fz * fz + fy * fy + fx * fx;
         xh_cd z1 = F1[e], z2 = F2[e];
         z1.x *= inv; z1.y *= inv; z2.x *= inv; z2.y *= inv;
@@ -89,17 +86,15 @@ extern "C" int xh_frc_dpr(xh_ctx *ctx, const double *d_m1, const double *d_m2, i
     XH_HIP(hipSetDevice(ctx->device));
     const int xh = X / 2 + 1, L = X / 2 + 1, nt = S_NSUMS * L + 2;
     const size_t total = (size_t)Z * Y * xh;
-    XhPlanBufs<double> px, py, pz;
+    XhFft3d fft;
     XhBuf F1, F2, sums;
-    XH_TRY(xh_plan_create<double>(ctx, X, px));
-    XH_TRY(xh_plan_create<double>(ctx, Y, py));
-    XH_TRY(xh_plan_create<double>(ctx, Z, pz));
+    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, fft));
     XH_TRY(xh_buf_alloc(ctx, F1, sizeof(xh_cd) * total));
     XH_TRY(xh_buf_alloc(ctx, F2, sizeof(xh_cd) * total));
     XH_TRY(xh_buf_alloc(ctx, sums, sizeof(double) * nt));
     std::vector<double> h((size_t)nt, 0.0);
-    XH_TRY(fft3d_r2c(ctx, d_m1, (xh_cd *)F1.p, Z, Y, X, px.plan, py.plan, pz.plan));
-    XH_TRY(fft3d_r2c(ctx, d_m2, (xh_cd *)F2.p, Z, Y, X, px.plan, py.plan, pz.plan));
+    XH_TRY(fft.r2c(d_m1, (xh_cd *)F1.p));
+    XH_TRY(fft.r2c(d_m2, (xh_cd *)F2.p));
     hipError_t e = hipMemsetAsync(sums.p, 0, sums.bytes, ctx->stream);
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->num_cus * 8);

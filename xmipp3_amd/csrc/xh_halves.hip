@@ -28,8 +28,7 @@
 //    forever).
 // The reference's power(double, int) truncates weightPower to an integer before pow; so does this file.
 #include "xh_fft3d.h"
-#include "../host/powell.h"
-#include "../host/powell_batch.h"
+#include "xh_reduce.h"
 #include <cmath>
 
 namespace {
@@ -50,15 +49,13 @@ struct CdfDev {
     double tab[2][HV_NR];              // [min, x_0 .. x_199, max] of two CDFs
 };
 
-__device__ __forceinline__ double hv_digfreq(int idx, int size) { return size <= 1 ? 0.0 : (double)(idx <= (size >> 1) ? idx : idx - size) / (double)size; }
-
 // R2 of half-spectrum element e of [Z][Y][xh] (initializeFilter)
 __device__ __forceinline__ double hv_r2(size_t e, int Y, int X, int Z, int xh)
 {
     const int j = (int)(e % xh);
     const size_t r = e / xh;
     const int i = (int)(r % Y), k = (int)(r / Y);
-    const double fz = hv_digfreq(k, Z), fy = hv_digfreq(i, Y), fx = hv_digfreq(j, X);
+    const double fz = d_digfreq(k, Z), fy = d_digfreq(i, Y), fx = d_digfreq(j, X);
     return fx * fx + fy * fy + fz * fz;
 }
 
@@ -340,38 +337,7 @@ k_difference(double *__restrict__ V1, double *__restrict__ V2, const double *__r
     }
 }
 
-// ---------------------------------------------------------------- reductions: partials [NC][gridDim.x], then one workgroup
-template <int NC> __device__ __forceinline__ void hv_block_partials(double (&v)[NC], double *__restrict__ partials)
-{
-    __shared__ double red[NC][256];
-    for (int c = 0; c < NC; ++c) red[c][threadIdx.x] = v[c];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int c = 0; c < NC; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        for (int c = 0; c < NC; ++c) partials[(size_t)c * gridDim.x + blockIdx.x] = red[c][0];
-}
-
-__global__ void __launch_bounds__(256) k_reduce_final(const double *__restrict__ partials, int G, int NC, double *__restrict__ out)
-{
-    __shared__ double red[256];
-    for (int c = 0; c < NC; ++c) {
-        double v = 0;
-        for (int i = threadIdx.x; i < G; i += 256) v += partials[(size_t)c * G + i];
-        red[threadIdx.x] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[c] = red[0];
-        __syncthreads();
-    }
-}
-
+// ---------------------------------------------------------------- reductions (xh_reduce.h): partials [NC][gridDim.x], then one workgroup
 // restorationSigmaCostError
 __global__ void __launch_bounds__(256)
 k_sigma_cost(const xh_cd *__restrict__ fVol, const xh_cd *__restrict__ fV1, const xh_cd *__restrict__ fV2, double K1, double K2, double inv_size,
@@ -388,7 +354,7 @@ k_sigma_cost(const xh_cd *__restrict__ fVol, const xh_cd *__restrict__ fV1, cons
             acc[0] += sqrt(d1x * d1x + d1y * d1y) + sqrt(d2x * d2x + d2y * d2y);
         }
     }
-    hv_block_partials<1>(acc, partials);
+    xh_block_partials(acc, partials);
 }
 
 // computeDiffAndAverage, with the sums of D and D^2 (over the mask, if any) of computeAvgStd[WithMask] riding along
@@ -403,14 +369,14 @@ k_diff_avg(const double *__restrict__ V1, const double *__restrict__ V2, double 
         S[n] = (a + b) * 0.5;
         if (!mask || mask[n]) { acc[0] += d; acc[1] += d * d; }
     }
-    if (partials) hv_block_partials<2>(acc, partials);
+    if (partials) xh_block_partials(acc, partials);
 }
 
 __global__ void __launch_bounds__(256) k_mask_count(const int *__restrict__ mask, size_t N, double *__restrict__ partials)
 {
     double acc[1] = {0.0};
     HV_LOOP(n, N) acc[0] += mask[n] != 0 ? 1.0 : 0.0;
-    hv_block_partials<1>(acc, partials);
+    xh_block_partials(acc, partials);
 }
 
 }  // namespace
@@ -420,11 +386,10 @@ enum { HV_OUT_RESTORED1 = 0, HV_OUT_RESTORED2, HV_OUT_FILTERBANK, HV_OUT_DECONVO
 
 struct xh_halves {
     xh_ctx *ctx = nullptr;
-    int Z = 0, Y = 0, X = 0, xh = 0;
     size_t N = 0, NF = 0;
     unsigned grid = 0;                       // per-voxel kernels and reductions
     unsigned gridPass = 0;                   // CDF histogram passes (53 KB of LDS each)
-    XhPlanBufs<double> px, py, pz;
+    XhFft3d fft;
     XhBuf V1, V2, S, B2, B3, keys, C1, C2, C3, cdf, partials, result;
     XhBuf out[4];                            // filter bank, deconvolved, convolved, average difference
     bool loaded = false, has[HV_NOUT] = {};
@@ -446,35 +411,14 @@ double *dp(XhBuf &b) { return (double *)b.p; }
 xh_cd *cp(XhBuf &b) { return (xh_cd *)b.p; }
 CdfDev *cdfp(xh_halves *h) { return (CdfDev *)h->cdf.p; }
 
-int hv_r2c(xh_halves *h, const double *in, XhBuf &F, double scale = 1.0)
-{
-    return fft3d_r2c(h->ctx, in, cp(F), h->Z, h->Y, h->X, h->px.plan, h->py.plan, h->pz.plan, scale);
-}
-int hv_c2r(xh_halves *h, XhBuf &F, double *out, double scale)
-{
-    return fft3d_c2r(h->ctx, cp(F), out, h->Z, h->Y, h->X, h->px.plan, h->py.plan, h->pz.plan, scale);
-}
-
-#define HV_LAUNCH(kern, grid, ...)                                                               \
-    do {                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->ctx->stream, __VA_ARGS__);         \
-        XH_LAUNCH_CHECK();                                                                       \
-    } while (0)
-
 // sum of NC partial rows -> NC doubles on the host (synchronous)
-int hv_finish_reduce(xh_halves *h, int NC, double *out)
-{
-    HV_LAUNCH(k_reduce_final, 1, (const double *)h->partials.p, (int)h->grid, NC, dp(h->result));
-    XH_HIP(hipMemcpyAsync(out, h->result.p, sizeof(double) * NC, hipMemcpyDeviceToHost, h->ctx->stream));
-    XH_HIP(hipStreamSynchronize(h->ctx->stream));
-    return XH_OK;
-}
+int hv_sums(xh_halves *h, int NC, double *out) { return xh_reduce_finish(h->ctx, dp(h->partials), (int)h->grid, NC, dp(h->result), out); }
 
 int hv_mask_count(xh_halves *h, const int *d_mask, size_t *count)
 {
-    HV_LAUNCH(k_mask_count, h->grid, d_mask, h->N, dp(h->partials));
+    XH_LAUNCH256(h->ctx, k_mask_count, h->grid, d_mask, h->N, dp(h->partials));
     double c = 0;
-    XH_TRY(hv_finish_reduce(h, 1, &c));
+    XH_TRY(hv_sums(h, 1, &c));
     *count = (size_t)c;
     XH_CHECK(*count > 0, XH_ERR_ARG, "xh_halves: the mask is empty");
     return XH_OK;
@@ -484,28 +428,28 @@ int hv_mask_count(xh_halves *h, const int *d_mask, size_t *count)
 int hv_cdf(xh_halves *h, const double *a, const double *b, const int *mask, double mult, size_t n, int slot)
 {
     CdfDev *cd = cdfp(h);
-    HV_LAUNCH(k_cdf_init, 1, cd, (unsigned long long)n);
+    XH_LAUNCH256(h->ctx, k_cdf_init, 1, cd, (unsigned long long)n);
     unsigned long long *keys = (unsigned long long *)h->keys.p;
-    if (b) HV_LAUNCH(k_cdf_first<1>, h->grid, a, b, mask, mult, keys, h->N, cd);
-    else HV_LAUNCH(k_cdf_first<0>, h->grid, a, b, mask, mult, keys, h->N, cd);
-    HV_LAUNCH(k_cdf_select, 1, cd, HV_W0);
+    if (b) XH_LAUNCH256(h->ctx, k_cdf_first<1>, h->grid, a, b, mask, mult, keys, h->N, cd);
+    else XH_LAUNCH256(h->ctx, k_cdf_first<0>, h->grid, a, b, mask, mult, keys, h->N, cd);
+    XH_LAUNCH256(h->ctx, k_cdf_select, 1, cd, HV_W0);
     for (int bits = 1 + HV_W0; bits < 64;) {
         const int w = std::min(HV_W, 64 - bits);
-        HV_LAUNCH(k_cdf_pass, h->gridPass, (const unsigned long long *)keys, h->N, bits, w, cd);
-        HV_LAUNCH(k_cdf_select, 1, cd, w);
+        XH_LAUNCH256(h->ctx, k_cdf_pass, h->gridPass, (const unsigned long long *)keys, h->N, bits, w, cd);
+        XH_LAUNCH256(h->ctx, k_cdf_select, 1, cd, w);
         bits += w;
     }
-    HV_LAUNCH(k_cdf_finish, 1, cd, slot);
+    XH_LAUNCH256(h->ctx, k_cdf_finish, 1, cd, slot);
     return XH_OK;
 }
 
 // estimateS + normalizeForFFT: S = ifft(filterS(fft(averagePositivity(V1, V2)))) / N
 int hv_estimate_s(xh_halves *h, const int *mask)
 {
-    HV_LAUNCH(k_avg_positivity, h->grid, dp(h->V1), dp(h->V2), mask, dp(h->S), h->N);
-    XH_TRY(hv_r2c(h, dp(h->S), h->C1));
-    HV_LAUNCH(k_filter_s, h->grid, cp(h->C1), h->Z, h->Y, h->X, h->xh);
-    return hv_c2r(h, h->C1, dp(h->S), 1.0 / (double)h->N);
+    XH_LAUNCH256(h->ctx, k_avg_positivity, h->grid, dp(h->V1), dp(h->V2), mask, dp(h->S), h->N);
+    XH_TRY(h->fft.r2c(dp(h->S), cp(h->C1)));
+    XH_LAUNCH256(h->ctx, k_filter_s, h->grid, cp(h->C1), h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh);
+    return h->fft.c2r(cp(h->C1), dp(h->S), 1.0 / (double)h->N);
 }
 
 double hv_sigma_cost_cb(double *x, void *prm)
@@ -529,15 +473,13 @@ int xh_halves_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_halves **o
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_halves_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
     XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_halves> h(new xh_halves);
-    h->ctx = ctx; h->Z = Z; h->Y = Y; h->X = X; h->xh = X / 2 + 1;
+    h->ctx = ctx;
+    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
     h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->xh;
+    h->NF = (size_t)Z * Y * h->fft.xh;
     h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->NF + 255) / 256, (size_t)ctx->num_cus * 4));
     h->gridPass = (unsigned)std::max<size_t>(1, std::min<size_t>((h->N + 255) / 256, (size_t)ctx->num_cus * 2));
     const size_t vb = sizeof(double) * h->N, fb = sizeof(xh_cd) * h->NF;
-    XH_TRY(xh_plan_create<double>(ctx, X, h->px));
-    XH_TRY(xh_plan_create<double>(ctx, Y, h->py));
-    XH_TRY(xh_plan_create<double>(ctx, Z, h->pz));
     for (XhBuf *b : {&h->V1, &h->V2, &h->S, &h->B2, &h->B3, &h->keys, &h->out[0], &h->out[1], &h->out[2], &h->out[3]}) XH_TRY(xh_buf_alloc(ctx, *b, vb));
     for (XhBuf *b : {&h->C1, &h->C2, &h->C3}) XH_TRY(xh_buf_alloc(ctx, *b, fb));
     XH_TRY(xh_buf_alloc(ctx, h->cdf, sizeof(CdfDev)));
@@ -585,7 +527,7 @@ int xh_halves_denoise(xh_halves *h, int32_t iters, const int32_t *d_mask)
         XH_TRY(hv_cdf(h, dp(h->S), nullptr, d_mask, 1.0, nS, 0));
         for (XhBuf *V : {&h->V1, &h->V2}) {
             XH_TRY(hv_cdf(h, dp(*V), dp(h->S), nullptr, 1.0, h->N, 1));
-            HV_LAUNCH(k_mask_noise, h->grid, dp(*V), (const CdfDev *)h->cdf.p, h->N);
+            XH_LAUNCH256(h->ctx, k_mask_noise, h->grid, dp(*V), (const CdfDev *)h->cdf.p, h->N);
         }
     }
     return XH_OK;
@@ -597,9 +539,9 @@ int xh_halves_deconv_spectra(xh_halves *h)
     XH_CHECK(h->loaded, XH_ERR_STATE, "xh_halves_deconv_spectra: no volumes loaded");
     XH_HIP(hipSetDevice(h->ctx->device));
     XH_TRY(hv_estimate_s(h, nullptr));
-    XH_TRY(hv_r2c(h, dp(h->S), h->C1));
-    XH_TRY(hv_r2c(h, dp(h->V1), h->C2));
-    return hv_r2c(h, dp(h->V2), h->C3);
+    XH_TRY(h->fft.r2c(dp(h->S), cp(h->C1)));
+    XH_TRY(h->fft.r2c(dp(h->V1), cp(h->C2)));
+    return h->fft.r2c(dp(h->V2), cp(h->C3));
 }
 
 int xh_halves_sigma_cost(xh_halves *h, double sigma1, double sigma2, double *h_cost)
@@ -608,9 +550,9 @@ int xh_halves_sigma_cost(xh_halves *h, double sigma1, double sigma2, double *h_c
     XH_HIP(hipSetDevice(h->ctx->device));
     const double K1 = -0.5 / (sigma1 * sigma1), K2 = -0.5 / (sigma2 * sigma2);
     const double inv_size = 1.0 / (2 * (double)h->NF);
-    HV_LAUNCH(k_sigma_cost, h->grid, (const xh_cd *)h->C1.p, (const xh_cd *)h->C2.p, (const xh_cd *)h->C3.p, K1, K2, inv_size, h->Z, h->Y, h->X, h->xh,
+    XH_LAUNCH256(h->ctx, k_sigma_cost, h->grid, (const xh_cd *)h->C1.p, (const xh_cd *)h->C2.p, (const xh_cd *)h->C3.p, K1, K2, inv_size, h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh,
               dp(h->partials));
-    return hv_finish_reduce(h, 1, h_cost);
+    return hv_sums(h, 1, h_cost);
 }
 
 int xh_halves_deconvolve(xh_halves *h, int32_t iters, double sigma0, double lambda, double *h_sigmas)
@@ -623,23 +565,23 @@ int xh_halves_deconvolve(xh_halves *h, int32_t iters, double sigma0, double lamb
     double sigmaConv1 = sigma0, sigmaConv2 = sigma0;
     for (int it = 0; it < iters; ++it) {
         XH_TRY(xh_halves_deconv_spectra(h));
-        std::vector<double> p = {sigmaConv1, sigmaConv2}, steps = {1.0, 1.0};
-        double cost;
-        int iter;
+        double p[2] = {sigmaConv1, sigmaConv2}, cost;
+        const double steps[2] = {1.0, 1.0};
+        int32_t iter;
         h->costRc = XH_OK;
-        powellOptimizer(p, 1, 2, hv_sigma_cost_cb, h, 0.01, cost, iter, steps);
+        XH_TRY(xh_powell_minimize(2, p, steps, 0.01, hv_sigma_cost_cb, h, &cost, &iter));
         XH_TRY(h->costRc);
         sigmaConv1 = p[0]; sigmaConv2 = p[1];
         if (h_sigmas) { h_sigmas[2 * it] = sigmaConv1; h_sigmas[2 * it + 1] = sigmaConv2; }
         const double K1 = -0.5 / (sigmaConv1 * sigmaConv1), K2 = -0.5 / (sigmaConv2 * sigmaConv2);
-        HV_LAUNCH(k_deconvolve, h->grid, cp(h->C1), cp(h->C2), cp(h->C3), K1, K2, lambda, h->Z, h->Y, h->X, h->xh);
-        XH_TRY(hv_c2r(h, h->C2, dp(h->V1), inv));
-        XH_TRY(hv_c2r(h, h->C3, dp(h->V2), inv));
+        XH_LAUNCH256(h->ctx, k_deconvolve, h->grid, cp(h->C1), cp(h->C2), cp(h->C3), K1, K2, lambda, h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh);
+        XH_TRY(h->fft.c2r(cp(h->C2), dp(h->V1), inv));
+        XH_TRY(h->fft.c2r(cp(h->C3), dp(h->V2), inv));
     }
     XH_HIP(hipMemcpyAsync(h->out[HV_OUT_DECONVOLVED - 2].p, h->S.p, h->S.bytes, hipMemcpyDeviceToDevice, h->ctx->stream));
     const double sigmaConv = (sigmaConv1 + sigmaConv2) / 2;
-    HV_LAUNCH(k_convolve, h->grid, cp(h->C1), -0.5 / (sigmaConv * sigmaConv), h->Z, h->Y, h->X, h->xh);
-    XH_TRY(hv_c2r(h, h->C1, dp(h->out[HV_OUT_CONVOLVED - 2]), inv));
+    XH_LAUNCH256(h->ctx, k_convolve, h->grid, cp(h->C1), -0.5 / (sigmaConv * sigmaConv), h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh);
+    XH_TRY(h->fft.c2r(cp(h->C1), dp(h->out[HV_OUT_CONVOLVED - 2]), inv));
     h->has[HV_OUT_DECONVOLVED] = h->has[HV_OUT_CONVOLVED] = true;
     return XH_OK;
 }
@@ -655,8 +597,8 @@ int xh_halves_filter_bank(xh_halves *h, double step, double overlap, int32_t wei
     XH_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
     const double inv = 1.0 / (double)h->N;
-    XH_TRY(hv_r2c(h, dp(h->V1), h->C1, inv));
-    XH_TRY(hv_r2c(h, dp(h->V2), h->C2, inv));
+    XH_TRY(h->fft.r2c(dp(h->V1), cp(h->C1), inv));
+    XH_TRY(h->fft.r2c(dp(h->V2), cp(h->C2), inv));
     double *S = dp(h->out[HV_OUT_FILTERBANK - 2]);
     XH_HIP(hipMemsetAsync(h->V1.p, 0, h->V1.bytes, st));
     XH_HIP(hipMemsetAsync(h->V2.p, 0, h->V2.bytes, st));
@@ -666,14 +608,14 @@ int xh_halves_filter_bank(xh_halves *h, double step, double overlap, int32_t wei
     for (double w = 0; w < 0.5; w += filterStep) {
         const double w2 = w * w, w2Step = (w + step) * (w + step);
         if (h->timing) XH_HIP(hipEventRecord(h->ev[0], st));
-        HV_LAUNCH(k_band, h->grid, (const xh_cd *)h->C1.p, cp(h->C3), w2, w2Step, h->Z, h->Y, h->X, h->xh);
-        XH_TRY(hv_c2r(h, h->C3, dp(h->B2), 1.0));
-        HV_LAUNCH(k_band, h->grid, (const xh_cd *)h->C2.p, cp(h->C3), w2, w2Step, h->Z, h->Y, h->X, h->xh);
-        XH_TRY(hv_c2r(h, h->C3, dp(h->B3), 1.0));
+        XH_LAUNCH256(h->ctx, k_band, h->grid, (const xh_cd *)h->C1.p, cp(h->C3), w2, w2Step, h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh);
+        XH_TRY(h->fft.c2r(cp(h->C3), dp(h->B2), 1.0));
+        XH_LAUNCH256(h->ctx, k_band, h->grid, (const xh_cd *)h->C2.p, cp(h->C3), w2, w2Step, h->fft.Z, h->fft.Y, h->fft.X, h->fft.xh);
+        XH_TRY(h->fft.c2r(cp(h->C3), dp(h->B3), 1.0));
         if (h->timing) XH_HIP(hipEventRecord(h->ev[1], st));
         XH_TRY(hv_cdf(h, dp(h->B2), dp(h->B3), nullptr, 0.5, h->N, 0));
         if (h->timing) XH_HIP(hipEventRecord(h->ev[2], st));
-        HV_LAUNCH(k_weights, h->grid, dp(h->B2), dp(h->B3), dp(h->V1), dp(h->V2), S, (const CdfDev *)h->cdf.p, weightPower, (int)weightFun, h->N);
+        XH_LAUNCH256(h->ctx, k_weights, h->grid, dp(h->B2), dp(h->B3), dp(h->V1), dp(h->V2), S, (const CdfDev *)h->cdf.p, weightPower, (int)weightFun, h->N);
         if (h->timing) {
             XH_HIP(hipEventRecord(h->ev[3], st));
             XH_HIP(hipEventSynchronize(h->ev[3]));
@@ -685,7 +627,7 @@ int xh_halves_filter_bank(xh_halves *h, double step, double overlap, int32_t wei
         }
         ++h->bands;
     }
-    HV_LAUNCH(k_scale3, h->grid, S, dp(h->V1), dp(h->V2), 1 - overlap, h->N);
+    XH_LAUNCH256(h->ctx, k_scale3, h->grid, S, dp(h->V1), dp(h->V2), 1 - overlap, h->N);
     h->has[HV_OUT_FILTERBANK] = true;
     return XH_OK;
 }
@@ -699,9 +641,9 @@ int xh_halves_difference(xh_halves *h, int32_t iters, double K, const int32_t *d
     size_t size = h->N;
     if (d_mask) XH_TRY(hv_mask_count(h, d_mask, &size));
     for (int it = 0; it < iters; ++it) {
-        HV_LAUNCH(k_diff_avg, h->grid, dp(h->V1), dp(h->V2), dp(h->S), dp(h->B2), d_mask, h->N, dp(h->partials));
+        XH_LAUNCH256(h->ctx, k_diff_avg, h->grid, dp(h->V1), dp(h->V2), dp(h->S), dp(h->B2), d_mask, h->N, dp(h->partials));
         double sums[2];
-        XH_TRY(hv_finish_reduce(h, 2, sums));
+        XH_TRY(hv_sums(h, 2, sums));
         // normAvgStd
         double avg = sums[0] / size, std = sums[1];
         if (size > 1) {
@@ -710,9 +652,9 @@ int xh_halves_difference(xh_halves *h, int32_t iters, double K, const int32_t *d
             std = sqrt(fabs(std));
         } else std = 0;
         std *= K;
-        HV_LAUNCH(k_difference, h->grid, dp(h->V1), dp(h->V2), dp(h->S), dp(h->B2), -0.5 / (std * std), h->N);
+        XH_LAUNCH256(h->ctx, k_difference, h->grid, dp(h->V1), dp(h->V2), dp(h->S), dp(h->B2), -0.5 / (std * std), h->N);
     }
-    HV_LAUNCH(k_diff_avg, h->grid, dp(h->V1), dp(h->V2), dp(h->out[HV_OUT_AVGDIFF - 2]), dp(h->B2), nullptr, h->N, nullptr);
+    XH_LAUNCH256(h->ctx, k_diff_avg, h->grid, dp(h->V1), dp(h->V2), dp(h->out[HV_OUT_AVGDIFF - 2]), dp(h->B2), nullptr, h->N, nullptr);
     h->has[HV_OUT_AVGDIFF] = true;
     return XH_OK;
 }
@@ -732,7 +674,7 @@ int xh_halves_fft_r2c(xh_halves *h, const double *d_in, void *d_out)
 {
     XH_CHECK(h && d_in && d_out, XH_ERR_ARG, "xh_halves_fft_r2c: null argument");
     XH_HIP(hipSetDevice(h->ctx->device));
-    return fft3d_r2c(h->ctx, d_in, (xh_cd *)d_out, h->Z, h->Y, h->X, h->px.plan, h->py.plan, h->pz.plan);
+    return h->fft.r2c(d_in, (xh_cd *)d_out);
 }
 
 int xh_halves_fft_c2r(xh_halves *h, const void *d_in, double *d_out, double scale)
@@ -740,7 +682,7 @@ int xh_halves_fft_c2r(xh_halves *h, const void *d_in, double *d_out, double scal
     XH_CHECK(h && d_in && d_out, XH_ERR_ARG, "xh_halves_fft_c2r: null argument");
     XH_HIP(hipSetDevice(h->ctx->device));
     XH_HIP(hipMemcpyAsync(h->C3.p, d_in, h->C3.bytes, hipMemcpyDeviceToDevice, h->ctx->stream));
-    return hv_c2r(h, h->C3, d_out, scale);
+    return h->fft.c2r(cp(h->C3), d_out, scale);
 }
 
 int xh_halves_cdf(xh_halves *h, const double *d_a, const double *d_b, const int32_t *d_mask, double mult, double *h_table)
@@ -799,45 +741,4 @@ int xh_halves_binary_mask(const float *h_values, size_t n, int32_t *h_mask)
     return XH_OK;
 }
 
-struct HvPowellUser { xh_cost_fn f; void *user; };
-static double hv_powell_tramp(double *x, void *prm)
-{
-    HvPowellUser *u = (HvPowellUser *)prm;
-    return u->f(x, u->user);
-}
-
-int xh_powell_minimize(int32_t n, double *p, const double *steps, double ftol, xh_cost_fn f, void *user, double *fret, int32_t *iter)
-{
-    XH_CHECK(n >= 1 && p && steps && f && fret && iter, XH_ERR_ARG, "xh_powell_minimize: bad argument");
-    std::vector<double> pv(p, p + n), sv(steps, steps + n);
-    HvPowellUser u{f, user};
-    int it = 0;
-    powellOptimizer(pv, 1, n, hv_powell_tramp, &u, ftol, *fret, it, sv);
-    for (int j = 0; j < n; ++j) p[j] = pv[j];
-    *iter = it;
-    return XH_OK;
-}
-
-int xh_powell_minimize_batch(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
-                             xh_batch_cost_fn f, void *user, double *fret, int32_t *iter, int64_t *evals)
-{
-    XH_CHECK(nprob >= 0 && n && nmax >= 1 && p && steps && capacity >= 1 && f && fret && iter, XH_ERR_ARG, "xh_powell_minimize_batch: bad argument");
-    return xh_powell_lockstep(nprob, n, nmax, p, steps, ftol, capacity, f, nullptr, user, fret, iter, evals);
-}
-
 }  // extern "C"
-
-// the scheduler behind xh_powell_minimize_batch and xh_ca2_refine; it lives in this translation unit so that every search runs the
-// one compiled powellOptimizer that xh_powell_minimize runs (same code, same floating-point contraction setting, same bits)
-int xh_powell_lockstep(int32_t nprob, const int32_t *n, int32_t nmax, double *p, const double *steps, double ftol, int32_t capacity,
-                       xh_batch_cost_fn f, xh_lockstep_pre_fn pre, void *user, double *fret, int32_t *iter, int64_t *evals)
-{
-    for (int q = 0; q < nprob; ++q)
-        XH_CHECK(n[q] >= 1 && n[q] <= nmax, XH_ERR_ARG, "xh_powell_minimize_batch: problem %d has %d variables, outside 1..%d", q, n[q], nmax);
-    if (nprob == 0) return XH_OK;
-    xh_powell::Lockstep L;
-    const int rc = L.run(nprob, n, nmax, p, steps, ftol, capacity, f, pre, user, fret, iter, evals);
-    XH_CHECK(rc != xh_powell::Lockstep::kNoStacks, XH_ERR_NOMEM, "xh_powell_minimize_batch: out of host memory for %d coroutine stacks", capacity);
-    if (rc > 0 || rc < XH_ERR_UNSUPPORTED) xh_set_error("xh_powell_minimize_batch: the cost callback returned %d", rc);
-    return rc;
-}

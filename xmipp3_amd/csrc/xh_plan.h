@@ -183,4 +183,51 @@ template <typename T> static int xh_plan_lpb(const XhPlan<T> &p, size_t budget, 
     return (int)std::max<size_t>(1, std::min<size_t>((size_t)maxLines, budget / line));
 }
 
+// ---- 2-D complex transform of images [n][y][x] in double precision, out of the line transforms above
+struct XhFft2d64 {
+    int x = 0, y = 0;
+    XhPlanBufs<double> planX, planY;
+};
+
+static int xh_fft2d64_create(xh_ctx *ctx, int x, int y, XhFft2d64 &P, const char *who)
+{
+    P.x = x; P.y = y;
+    XH_TRY(xh_plan_create<double>(ctx, x, P.planX));
+    XH_TRY(xh_plan_create<double>(ctx, y, P.planY));
+    XH_CHECK((sizeof(xh_cd) << P.planX.plan.logM) <= 64 * 1024 && (sizeof(xh_cd) << P.planY.plan.logM) <= 64 * 1024, XH_ERR_UNSUPPORTED,
+             "%s: a line of %d x %d does not fit the LDS of the double-precision transform", who, x, y);
+    return XH_OK;
+}
+
+// n images in place, un-normalised: rows then columns forward, columns then rows inverse
+static int xh_fft2d64(xh_ctx *ctx, const XhFft2d64 &P, xh_cd *d, int n, bool inverse)
+{
+    const size_t budget = 64 * 1024;
+    const int lx = xh_plan_lpb(P.planX.plan, budget, 16), ly = xh_plan_lpb(P.planY.plan, budget, 16);
+    const size_t rows = (size_t)n * P.y, cols = (size_t)n * P.x;
+    const size_t smx = ((size_t)lx * sizeof(xh_cd)) << P.planX.plan.logM, smy = ((size_t)ly * sizeof(xh_cd)) << P.planY.plan.logM;
+    if (!inverse) {
+        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((rows + lx - 1) / lx)), dim3(256), smx, ctx->stream, d, P.planX.plan, rows, rows, (size_t)0, (size_t)P.x, (size_t)1, lx);
+        hipLaunchKernelGGL((xh_k_fft_lines<double, false>), dim3((unsigned)((cols + ly - 1) / ly)), dim3(256), smy, ctx->stream, d, P.planY.plan, cols, (size_t)P.x, (size_t)P.x * P.y, (size_t)1, (size_t)P.x, ly);
+    } else {
+        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((cols + ly - 1) / ly)), dim3(256), smy, ctx->stream, d, P.planY.plan, cols, (size_t)P.x, (size_t)P.x * P.y, (size_t)1, (size_t)P.x, ly);
+        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((rows + lx - 1) / lx)), dim3(256), smx, ctx->stream, d, P.planX.plan, rows, rows, (size_t)0, (size_t)P.x, (size_t)1, lx);
+    }
+    XH_LAUNCH_CHECK();
+    return XH_OK;
+}
+
+// real images -> the transform's complex doubles, and the real part back. Templates, so that only the files that launch them hold them
+template <typename TI> __global__ void __launch_bounds__(256) xh_k_to_complex64(const TI *__restrict__ in, xh_cd *__restrict__ out, size_t tot)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < tot) out[t] = xh_cd{(double)in[t], 0.0};
+}
+
+template <typename TO> __global__ void __launch_bounds__(256) xh_k_real64(const xh_cd *__restrict__ in, TO *__restrict__ out, size_t tot)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < tot) out[t] = (TO)in[t].x;
+}
+
 #endif

@@ -27,7 +27,7 @@
 // r^2 >= Rmax^2 have g = 0 and sample exactly I[k, i, j]: their share of diff2 and sumVD is a constant of the loaded pairs, summed once
 // on the host by xh_vds_set_pairs, and their share of modg is 0.
 // Reduction: every thread sums its voxels in index order, a workgroup adds its 256 sums in a fixed tree in LDS, one workgroup adds the
-// per-workgroup partials in a fixed order. No floating-point atomics, and the grid depends on the handle's geometry alone: the same
+// per-workgroup partials in a fixed order (xh_reduce.h). No floating-point atomics, and the grid depends on the handle's geometry alone: the same
 // coefficients give the same bits on every call. Three doubles come back per evaluation, into page-locked memory.
 //
 // Deviations from the reference, each where it reads what it never wrote, or where its two versions disagree:
@@ -43,6 +43,7 @@
 //  - normalize_Robust rests on xmippCore primitives whose source is not in the reference tree (compute_hist, index2val, binarize, the
 //    median within a mask); the readings used are stated at xh_vds_normalize_robust and in SURVEY Appendix B.
 #include "xh_fft3d.h"
+#include "xh_reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -202,21 +203,6 @@ __device__ __forceinline__ double vds_sample(const double *__restrict__ V, const
     return vds_lin(az, vds_lin(ay, dx00, dx10), vds_lin(ay, dx01, dx11));
 }
 
-// 256 sums of 3 values -> partials [3][gridDim.x], fixed tree
-__device__ __forceinline__ void vds_block_partials(double (&v)[3], double *__restrict__ partials)
-{
-    __shared__ double red[3][256];
-    for (int c = 0; c < 3; ++c) red[c][threadIdx.x] = v[c];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        for (int c = 0; c < 3; ++c) partials[(size_t)c * gridDim.x + blockIdx.x] = red[c][0];
-}
-
 // diff2, sumVD, modg over the voxels of the box with r^2 < Rmax^2
 template <int L1, int L2>
 __global__ void __launch_bounds__(256)
@@ -245,25 +231,7 @@ k_vds_cost(const double *__restrict__ I, const double *__restrict__ R, const Vds
         }
         acc[2] += (double)g.npairs * (gx * gx + gy * gy + gz * gz);
     }
-    vds_block_partials(acc, partials);
-}
-
-// partials [3][G] -> out [3], one workgroup, fixed order
-__global__ void __launch_bounds__(256) k_vds_reduce(const double *__restrict__ partials, int G, double *__restrict__ out)
-{
-    __shared__ double red[256];
-    for (int c = 0; c < 3; ++c) {
-        double v = 0;
-        for (int i = threadIdx.x; i < G; i += 256) v += partials[(size_t)c * G + i];
-        red[threadIdx.x] = v;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[c] = red[0];
-        __syncthreads();
-    }
+    xh_block_partials(acc, partials);
 }
 
 // the output volume and the field: every voxel of the volume. G (nullable) [3][N]
@@ -283,8 +251,6 @@ k_vds_apply(const double *__restrict__ raw, const VdsGeom g, const VdsCoef C, in
     }
 }
 
-__device__ __forceinline__ double vds_digfreq(int idx, int size) { return size <= 1 ? 0.0 : (double)(idx <= (size >> 1) ? idx : idx - size) / (double)size; }
-
 // REALGAUSSIAN low pass exp(-pi^2 w^2 sigma^2) of a half spectrum [Z][Y][xh], times scale
 __global__ void __launch_bounds__(256) k_vds_gauss(xh_cd *__restrict__ F, int Z, int Y, int X, int xh, double sigma, double scale)
 {
@@ -292,7 +258,7 @@ __global__ void __launch_bounds__(256) k_vds_gauss(xh_cd *__restrict__ F, int Z,
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < NF; e += (size_t)gridDim.x * 256) {
         const int j = (int)(e % xh);
         const size_t r = e / xh;
-        const double fx = vds_digfreq(j, X), fy = vds_digfreq((int)(r % Y), Y), fz = vds_digfreq((int)(r / Y), Z);
+        const double fx = d_digfreq(j, X), fy = d_digfreq((int)(r % Y), Y), fz = d_digfreq((int)(r / Y), Z);
         const double w = scale * exp(-VDS_PI * VDS_PI * (fx * fx + fy * fy + fz * fz) * sigma * sigma);
         F[e] = xh_cd{F[e].x * w, F[e].y * w};
     }
@@ -334,10 +300,10 @@ k_vds_strain(const double *__restrict__ G, int Z, int Y, int X, double *__restri
 struct xh_vds {
     xh_ctx *ctx = nullptr;
     VdsGeom g = {};
-    int L1 = 0, L2 = 0, vecSize = 0, xh = 0;
+    int L1 = 0, L2 = 0, vecSize = 0;
     double Rmax = 0, lambda = 0;
     unsigned grid = 0, gridVol = 0;
-    XhPlanBufs<double> px, py, pz;
+    XhFft3d fft;
     XhBuf I, R;                    // the pairs [npairs][N]
     XhBuf B[2];                    // scratch volumes: raw and VO, LS and LR
     XhBuf C, partials, result;
@@ -379,12 +345,6 @@ void vds_pack(const xh_vds *h, const double *x, VdsCoef &C, int *l2eff)
     *l2eff = e;
 }
 
-#define VDS_LAUNCH(kern, grid, ...)                                                              \
-    do {                                                                                         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->ctx->stream, __VA_ARGS__);         \
-        XH_LAUNCH_CHECK();                                                                       \
-    } while (0)
-
 int vds_launch_cost(xh_vds *h, const VdsCoef &C, int l2)
 {
     const double *I = (const double *)h->I.p, *R = (const double *)h->R.p;
@@ -392,7 +352,7 @@ int vds_launch_cost(xh_vds *h, const VdsCoef &C, int l2)
     const int l1 = h->L1;
 #define VDS_CASE(A, B)                                                                  \
     if (l1 == A && l2 == B) {                                                           \
-        VDS_LAUNCH((k_vds_cost<A, B>), h->grid, I, R, h->g, C, l1, l2, part);           \
+        XH_LAUNCH256(h->ctx, (k_vds_cost<A, B>), h->grid, I, R, h->g, C, l1, l2, part); \
         return XH_OK;                                                                   \
     }
     VDS_CASE(1, 0) VDS_CASE(1, 1)
@@ -401,15 +361,16 @@ int vds_launch_cost(xh_vds *h, const VdsCoef &C, int l2)
     VDS_CASE(4, 0) VDS_CASE(4, 1) VDS_CASE(4, 2) VDS_CASE(4, 3) VDS_CASE(4, 4)
     VDS_CASE(5, 0) VDS_CASE(5, 1) VDS_CASE(5, 2) VDS_CASE(5, 3) VDS_CASE(5, 4)
 #undef VDS_CASE
-    VDS_LAUNCH((k_vds_cost<-1, -1>), h->grid, I, R, h->g, C, l1, l2, part);
+    XH_LAUNCH256(h->ctx, (k_vds_cost<-1, -1>), h->grid, I, R, h->g, C, l1, l2, part);
     return XH_OK;
 }
 
 int vds_gauss_dev(xh_vds *h, double *d_v, double sigma)
 {
-    XH_TRY(fft3d_r2c(h->ctx, d_v, (xh_cd *)h->C.p, h->g.Z, h->g.Y, h->g.X, h->px.plan, h->py.plan, h->pz.plan));
-    VDS_LAUNCH(k_vds_gauss, h->gridVol, (xh_cd *)h->C.p, h->g.Z, h->g.Y, h->g.X, h->xh, sigma, 1.0 / (double)h->g.N);
-    return fft3d_c2r(h->ctx, (xh_cd *)h->C.p, d_v, h->g.Z, h->g.Y, h->g.X, h->px.plan, h->py.plan, h->pz.plan, 1.0);
+    xh_cd *F = (xh_cd *)h->C.p;
+    XH_TRY(h->fft.r2c(d_v, F));
+    XH_LAUNCH256(h->ctx, k_vds_gauss, h->gridVol, F, h->g.Z, h->g.Y, h->g.X, h->fft.xh, sigma, 1.0 / (double)h->g.N);
+    return h->fft.c2r(F, d_v, 1.0);
 }
 
 struct VdsStage { xh_vds *h; std::vector<double> x; std::vector<int> active; };
@@ -537,7 +498,7 @@ int xh_vds_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t L1, int3
     std::unique_ptr<xh_vds> h(new xh_vds);
     h->ctx = ctx; h->L1 = L1; h->L2 = L2; h->Rmax = Rmax; h->lambda = lambda;
     h->vecSize = vds_num_terms(L1, L2);
-    h->xh = X / 2 + 1;
+    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
     VdsGeom &g = h->g;
     g.Z = Z; g.Y = Y; g.X = X; g.N = (size_t)Z * Y * X; g.npairs = 0;
     g.Rmax2 = Rmax * Rmax; g.iRmax = 1.0 / Rmax;
@@ -550,12 +511,9 @@ int xh_vds_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t L1, int3
         lo[a] = first; n[a] = last - first + 1;
     }
     g.z0 = lo[0]; g.y0 = lo[1]; g.x0 = lo[2]; g.bz = n[0]; g.by = n[1]; g.bx = n[2];
-    const size_t nbox = (size_t)g.bz * g.by * g.bx, NF = (size_t)Z * Y * h->xh;
+    const size_t nbox = (size_t)g.bz * g.by * g.bx, NF = (size_t)Z * Y * h->fft.xh;
     h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nbox + 255) / 256, (size_t)ctx->num_cus * 8));
     h->gridVol = (unsigned)std::max<size_t>(1, std::min<size_t>((g.N + 255) / 256, (size_t)ctx->num_cus * 8));
-    XH_TRY(xh_plan_create<double>(ctx, X, h->px));
-    XH_TRY(xh_plan_create<double>(ctx, Y, h->py));
-    XH_TRY(xh_plan_create<double>(ctx, Z, h->pz));
     for (XhBuf &b : h->B) XH_TRY(xh_buf_alloc(ctx, b, sizeof(double) * g.N));
     XH_TRY(xh_buf_alloc(ctx, h->C, sizeof(xh_cd) * NF));
     XH_TRY(xh_buf_alloc(ctx, h->partials, sizeof(double) * 3 * h->grid));
@@ -635,9 +593,7 @@ int xh_vds_cost(xh_vds *h, const double *h_x, double *h_out)
     int l2;
     vds_pack(h, h_x, C, &l2);
     XH_TRY(vds_launch_cost(h, C, l2));
-    VDS_LAUNCH(k_vds_reduce, 1, (const double *)h->partials.p, (int)h->grid, (double *)h->result.p);
-    XH_HIP(hipMemcpyAsync(h->pinned, h->result.p, sizeof(double) * 3, hipMemcpyDeviceToHost, h->ctx->stream));
-    XH_HIP(hipStreamSynchronize(h->ctx->stream));
+    XH_TRY(xh_reduce_finish(h->ctx, (const double *)h->partials.p, (int)h->grid, 3, (double *)h->result.p, h->pinned));
     const double count = (double)h->g.npairs * (double)h->g.N;
     const double diff2 = h->pinned[0] + h->outDiff2, sumVD = h->pinned[1] + h->outSumVD, modg = h->pinned[2];
     const double deformation = std::sqrt(modg / count);
@@ -685,7 +641,7 @@ int xh_vds_apply(xh_vds *h, const double *h_raw, const double *h_x, double *h_VO
         XH_TRY(xh_buf_reserve(h->ctx, h->G, 3 * vb));
         G = (double *)h->G.p;
     }
-    VDS_LAUNCH(k_vds_apply, h->gridVol, (const double *)h->B[0].p, h->g, C, h->L1, h->L2, (double *)h->B[1].p, G);
+    XH_LAUNCH256(h->ctx, k_vds_apply, h->gridVol, (const double *)h->B[0].p, h->g, C, h->L1, h->L2, (double *)h->B[1].p, G);
     XH_HIP(hipMemcpyAsync(h_VO, h->B[1].p, vb, hipMemcpyDeviceToHost, st));
     if (h_G) XH_HIP(hipMemcpyAsync(h_G, G, 3 * vb, hipMemcpyDeviceToHost, st));
     XH_HIP(hipStreamSynchronize(st));
@@ -704,7 +660,7 @@ int xh_vds_strain(xh_vds *h, double *h_G, double *h_LS, double *h_LR)
     for (int c = 0; c < 3; ++c) XH_TRY(vds_gauss_dev(h, G + (size_t)c * N, 2.0));
     XH_HIP(hipMemsetAsync(h->B[0].p, 0, vb, st));
     XH_HIP(hipMemsetAsync(h->B[1].p, 0, vb, st));
-    VDS_LAUNCH(k_vds_strain, h->gridVol, (const double *)G, h->g.Z, h->g.Y, h->g.X, (double *)h->B[0].p, (double *)h->B[1].p);
+    XH_LAUNCH256(h->ctx, k_vds_strain, h->gridVol, (const double *)G, h->g.Z, h->g.Y, h->g.X, (double *)h->B[0].p, (double *)h->B[1].p);
     XH_HIP(hipMemcpyAsync(h_G, G, 3 * vb, hipMemcpyDeviceToHost, st));
     XH_HIP(hipMemcpyAsync(h_LS, h->B[0].p, vb, hipMemcpyDeviceToHost, st));
     XH_HIP(hipMemcpyAsync(h_LR, h->B[1].p, vb, hipMemcpyDeviceToHost, st));

@@ -548,6 +548,93 @@ def test_outputs_at_the_final_variables(gpu, oracle, l1):
     h.close()
 
 
+# ------------------------------------------------------------------ check 6b: every chunk seam of load and apply
+def _seam_row(i):
+    """a row whose every number is a function of the particle's index: neighbours differ, and so do particles one chunk (16 384,
+    32 768) apart. Shifts on a quarter-pixel grid, so that the variables that cancel them are exact."""
+    ctf = dict(CTF, DeltafU=12000.0 + (i * 7919) % 6000, azimuthal_angle=float((i * 37) % 180), Ca=0.015 + 0.001 * (i % 11), espr=0.8 + 0.05 * (i % 9),
+               ispr=5e-10 * (i % 5), alpha=2e-5 * (1 + i % 4), DeltaF=10.0 + i % 13, DeltaR=0.1 + 0.05 * (i % 7))
+    ctf["DeltafV"] = ctf["DeltafU"] + 100.0 + i % 300
+    return dict(rot=float((i * 17) % 360), tilt=float((i * 29) % 180), psi=float((i * 41) % 360), shift_x=0.25 * ((i * 13) % 9 - 4),
+                shift_y=0.25 * ((i * 7) % 11 - 5), flip=i % 2, ctf=ctf)
+
+
+def _identity_variables(row):
+    """the variables at which the final transform is the identity: they cancel the row's shift, and a flipped row's mirror by a scale
+    of -2 along x (A[0][0] = -(1 + scaleX)); every entry of A comes out exact"""
+    x = np.zeros(VARS)
+    x[0] = 1
+    x[2], x[3] = -row["shift_x"], -row["shift_y"]
+    if row["flip"]:
+        x[4] = -2.0
+    return x
+
+
+def test_every_chunk_seam_of_load_and_apply(gpu, oracle):
+    """32 772 particles of 32 x 32 in one load: the load transforms them in chunks of 256 MB / (D^2 16 B) = 16 384 images and evaluates
+    their CTF images in launches of 32 768 rows; apply works in chunks of 32 768. At the particles next to every seam the resident
+    filtered image, the resident CTF image (a cost that leaves the defocus alone reads it), a cost that evaluates the CTF in its row, and
+    the applied image are held to the bounds of test_cost_parity and test_outputs_at_the_final_variables; everywhere else apply
+    gets the identity, which copies: one comparison of the whole output finds an image that went to another particle's place.
+    Measured on an MI355X: filtered image 4.7e-16 of its largest value, its standard deviation 1.4e-15 relative, costs 3.3e-15 and
+    3.4e-15, applied images 4.4e-8 of the largest value."""
+    xa, ctx, torch = gpu
+    D, n = 32, 32772
+    seams = [0, 1, 16383, 16384, 16385, 32767, 32768, 32771]
+    assert (256 << 20) // (D * D * 16) == 16384 and min(32768, (256 << 20) // (D * D * 8)) == 32768 and n > 32768 + 1
+    prm = dict(PRM, max_shift=4.0)
+    vol = synth.phantom(D, seed=11, nblobs=9).astype(np.float32)
+    res = Restated(oracle, vol, prm, False)
+    imgs = np.random.default_rng(n).standard_normal((n, D, D), dtype=np.float32)
+    rows = [_seam_row(i) for i in range(n)]
+    h = xa.ContinuousAssign2(ctx, torch.from_numpy(vol).cuda(), capacity=8, optimize_shift=1, optimize_angles=1, optimize_defocus=1, **prm)
+    h.load(imgs, _device_rows(rows))
+    # the resident filtered images
+    prep = {i: res.prepare(imgs[i], rows[i]) for i in seams}
+    err_If = err_sd = 0.0
+    got_If = {i: h.filtered(i) for i in seams}
+    for i in seams:
+        err_If = max(err_If, np.abs(got_If[i][0] - prep[i][0]).max() / np.abs(prep[i][0]).max())
+        err_sd = max(err_sd, abs(got_If[i][1] - prep[i][1]) / prep[i][1])
+    print(f"seams: filtered image max {err_If:.3e} of its largest value (bound 1e-11), standard deviation {err_sd:.3e} relative (bound 1e-12)")
+    for i in seams:
+        assert np.abs(got_If[i][0] - prep[i][0]).max() <= 1e-11 * np.abs(prep[i][0]).max(), i
+        assert abs(got_If[i][1] - prep[i][1]) <= 1e-12 * prep[i][1], i
+    # costs: the particle's resident CTF image, then the CTF evaluated in the row
+    x = np.zeros(VARS)
+    x[0] = 1
+    x[2:4] = 0.6, -0.35
+    x[7:10] = 1.5, -0.8, 2.1
+    moved = x.copy()
+    moved[10:13] = 120.0, -80.0, 5.0
+    for what, xs in (("resident CTF", x), ("CTF in the row", moved)):
+        got = h.cost(seams, np.tile(xs, (len(seams), 1)))
+        exp = np.array([res.cost(prep[i][0], prep[i][1], rows[i], xs) for i in seams])
+        print(f"seams: cost with the {what}: device {got} max |device - restatement| = {np.abs(got - exp).max():.3e} (bound 1e-9)")
+        assert np.all(np.abs(exp) < 1e30) and len(set(np.round(exp, 6))) == len(seams)      # every particle has a cost of its own
+        assert np.abs(got - exp).max() <= 1e-9
+    # apply: a transform at the seams, the identity everywhere else
+    X = np.stack([_identity_variables(r) for r in rows])
+    eye = np.eye(3)
+    assert all(np.array_equal(res.matrix(rows[i], X[i]), eye) for i in range(n))
+    for i in seams:
+        X[i] = [1, 0, 0.7, -0.4, 0.01, -0.005, 0.4, 0, 0, 0, 0, 0, 0]
+    out = h.apply(imgs, X)
+    err = 0.0
+    expected = {i: oracle.apply_geometry2d(imgs[i].astype(np.float64), res.matrix(rows[i], X[i]), 3, False, False) for i in seams}
+    for i in seams:
+        err = max(err, np.abs(out[i] - expected[i]).max() / np.abs(expected[i]).max())
+    print(f"seams: applied images max {err:.3e} of the largest value (bound 3e-7)")
+    for i in seams:
+        assert np.abs(out[i] - expected[i]).max() <= 3e-7 * np.abs(expected[i]).max(), i
+        assert np.abs(out[i] - imgs[i]).max() > 0.1
+    others = np.ones(n, bool)
+    others[seams] = False
+    same = (out == imgs).all(axis=(1, 2))
+    assert same[others].all(), f"particles whose identity transform is no copy: {np.nonzero(~same & others)[0][:20]}"
+    h.close()
+
+
 # ------------------------------------------------------------------ check 7: the program end to end
 def _run_program(tmp, name, batch, extra):
     r = subprocess.run([PROG, "-i", str(tmp / "in.xmd"), "-o", str(tmp / f"{name}.stk"), "--ref", str(tmp / "ref.vol"), "--oresiduals",

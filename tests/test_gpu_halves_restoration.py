@@ -403,6 +403,109 @@ def test_difference_of_equal_halves(gpu):
         assert np.array_equal(got, (V + V) * 0.5)
 
 
+# ---------------------------------------------------------------- stages past the grid cap
+# Every per-voxel kernel and reduction runs on min(ceil(NF / 256), 4 CUs) workgroups of 256 and walks the rest in a grid-stride loop.
+# (81, 80, 82): NF = 81 * 80 * 42 = 272 160 half-spectrum elements and N = 531 360 voxels, between one and two passes of 1024 threads
+# per CU on 256 CUs, non-cubic with an odd dimension: the loops over the half spectrum take a second, partial pass (those over the
+# voxels, on the same grid, a third; they already took a second in the shapes above).
+# The restatements, the data and the tolerances are those of the per-stage tests above.
+BIG = (81, 80, 82)
+
+
+@pytest.fixture(scope="module")
+def big(gpu):
+    xa, ctx, torch = gpu
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    NF = BIG[0] * BIG[1] * (BIG[2] // 2 + 1)
+    print(f"{BIG}: {NF} half-spectrum elements on {cus} CUs, grid cap {256 * 4 * cus} threads")
+    assert NF > 256 * 4 * cus, f"{NF} half-spectrum elements do not exceed the grid cap of {256 * 4 * cus} threads on {cus} CUs"
+    return halves(BIG)
+
+
+def _report(what, got, exp):
+    got, exp = np.asarray(got), np.asarray(exp)
+    print(f"{BIG} {what}: max |device - numpy| = {np.abs(got - exp).max() / np.abs(exp).max():.3e} of the largest value")
+
+
+def test_sigma_cost_grid_past_the_cap(gpu, big):
+    """test_sigma_cost_grid's sigmas to its 1e-12 relative; and the same arguments twice give the same bits: 1024 partial sums on 256
+    CUs, four per thread of the final workgroup, added in a fixed order. Measured on an MI355X: at most 5.6e-16 relative."""
+    V1, V2 = big
+    h = _handle(gpu, V1, V2)
+    h.deconv_spectra()
+    _, fVol, fV1, fV2 = spectra(V1, V2)
+    worst = 0.0
+    for s1 in (0.05, 0.2, 0.7, 1.9):
+        for s2 in (0.1, 0.5, 1.3):
+            exp = sigma_cost(fVol, fV1, fV2, s1, s2, BIG)
+            got = h.sigma_cost(s1, s2)
+            worst = max(worst, abs(got - exp) / abs(exp))
+            print(f"{BIG} sigma_cost({s1}, {s2}): device {got!r} numpy {exp!r} relative {abs(got - exp) / abs(exp):.3e}")
+            assert np.float64(h.sigma_cost(s1, s2)).tobytes() == np.float64(got).tobytes()
+            assert abs(got - exp) <= 1e-12 * abs(exp)
+    print(f"{BIG} sigma_cost: largest relative error {worst:.3e} (bound 1e-12)")
+
+
+def test_deconvolve_past_the_cap(gpu, big):
+    """test_deconvolve at its 1e-9 of the largest value. Measured on an MI355X: at most 1.6e-15."""
+    V1, V2 = big
+    h = _handle(gpu, V1, V2)
+    sig = h.deconvolve(2, 0.2, 0.001)
+    assert sig.shape == (2, 2) and np.all((sig >= 0) & (sig <= 2))
+    e1, e2, eS, eC = deconvolve(V1, V2, [tuple(s) for s in sig], 0.001)
+    pairs = [(name, _np(h.output(name)), e) for name, e in (("restored1", e1), ("restored2", e2), ("deconvolved", eS), ("convolved", eC))]
+    for name, got, e in pairs:
+        _report("deconvolve " + name, got, e)
+    for name, got, e in pairs:
+        _close(got, e)
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_denoise_past_the_cap(gpu, big, masked):
+    """test_denoise at its 1e-9 of the largest value. Measured on an MI355X: at most 1.5e-16."""
+    xa, ctx, torch = gpu
+    V1, V2 = big
+    mask = xa.halves_circular_mask(BIG, -min(BIG) / 3) if masked else None
+    h = _handle(gpu, V1, V2)
+    h.denoise(2, None if mask is None else torch.from_numpy(mask).cuda())
+    e1, e2 = denoise(V1, V2, 2, mask)
+    g1, g2 = _np(h.output("restored1")), _np(h.output("restored2"))
+    _report(f"denoise masked={masked} restored1", g1, e1)
+    _report(f"denoise masked={masked} restored2", g2, e2)
+    _close(g1, e1)
+    _close(g2, e2)
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_difference_past_the_cap(gpu, big, masked):
+    """test_difference at its 1e-9 of the largest value. Measured on an MI355X: at most 1.5e-16."""
+    xa, ctx, torch = gpu
+    V1, V2 = big
+    mask = xa.halves_circular_mask(BIG, min(BIG) / 4) if masked else None
+    h = _handle(gpu, V1, V2)
+    h.difference(2, 1.5, None if mask is None else torch.from_numpy(mask).cuda())
+    exp = difference(V1, V2, 2, 1.5, mask)
+    got = [_np(h.output(name)) for name in ("restored1", "restored2", "avgDiff")]
+    for name, g, e in zip(("restored1", "restored2", "avgDiff"), got, exp):
+        _report(f"difference masked={masked} {name}", g, e)
+    for g, e in zip(got, exp):
+        _close(g, e)
+
+
+def test_filter_bank_past_the_cap(gpu, big):
+    """test_filter_bank with weight function 1 and a step of 0.125 (8 bands at overlap 0.5) at its 1e-9 of the largest value.
+    Measured on an MI355X: at most 9.1e-16."""
+    V1, V2 = big
+    h = _handle(gpu, V1, V2)
+    h.filter_bank(0.125, 0.5, 1, 3.7)
+    exp = filter_bank(V1, V2, 0.125, 0.5, 1, 3.7)
+    got = [_np(h.output(name)) for name in ("filterBank", "restored1", "restored2")]
+    for name, g, e in zip(("filterBank", "restored1", "restored2"), got, exp):
+        _report("filter_bank " + name, g, e)
+    for g, e in zip(got, exp):
+        _close(g, e)
+
+
 @pytest.mark.parametrize("shape", SHAPES)
 def test_chain(gpu, shape):
     xa, ctx, torch = gpu

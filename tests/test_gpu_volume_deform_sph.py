@@ -276,6 +276,145 @@ def test_strain(gpu):
     assert np.all(np.abs(LR - eLR) <= 1e-10 * np.abs(eLR) + 1e-12)
 
 
+# ---------------------------------------------------------------- past the grid caps
+# k_vds_cost runs on min(ceil(nbox / 256), 8 CUs) workgroups of 256 and k_vds_apply / k_vds_gauss / k_vds_strain on as many for the N
+# voxels; each walks the rest in a grid-stride loop. (81, 84, 82): N = 557 928, and the box of the ball of Rmax = -1 (41 voxels) is
+# 81^3 = 531 441, both between one and two passes of 2048 threads per CU on 256 CUs: a second, partial pass, on a non-cubic volume
+# with an odd dimension. The cost's 3 rows of 2048 partial sums take the final reduction through its strided loop (8 per thread).
+# With Rmax = -1 the second pass of the cost holds the last 7153 voxels of the box, of which only the ball's pole (k = 40, about 250
+# voxels) counts; with an Rmax that holds the whole volume every voxel of it does. k_vds_gauss loops over the half spectrum
+# (285 768 elements) on the grid sized for N: that one still fits a single pass at this shape.
+BIG = (81, 84, 82)
+BIG_ALL = 80.0       # an Rmax that holds the whole volume: r^2 <= 40^2 + 42^2 + 41^2 = 5045 < 6400
+
+
+def _past_caps(count):
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print(f"{BIG}: {count} elements on {cus} CUs, grid cap {256 * 8 * cus} threads")
+    assert count > 256 * 8 * cus, f"{count} elements do not exceed the grid cap of {256 * 8 * cus} threads on {cus} CUs"
+    return cus
+
+
+@pytest.mark.parametrize("Rmax", [-1.0, BIG_ALL])
+@pytest.mark.parametrize("degrees", [(3, 2), (0, 0)])      # a compile-time instantiation, and the kernel with run-time degrees
+def test_cost_parity_past_the_cap(gpu, degrees, Rmax):
+    """test_cost_parity at (81, 84, 82), to its 1e-9 relative. The bound restated for this size: the sums have at most 3 * 557 928,
+    about 1.7 M, non-negative terms, so their worst-case linear rounding bound is 1.7e6 * 1.1e-16 = 2e-10, whatever the order. A
+    sample errs by about 3e-13 as there: sumVD by at most 1.7e6 * 3e-13 = 5e-7 against 1e4 (5e-11), diff2, whose terms d^2 have an
+    rms d of about 0.02, by at most 1.7e6 * 2 * 0.02 * 3e-13 = 2e-8 against 300 to 900 (7e-11). The two add up to under 3e-10: 1e-9
+    holds with a margin of 3 over the worst case.
+    Measured on an MI355X: at most 9.7e-15 over the 16 cases."""
+    xa, ctx = gpu
+    L1, L2 = degrees
+    N = int(np.prod(BIG))
+    nbox = 81 ** 3 if Rmax < 0 else N
+    _past_caps(N)
+    _past_caps(nbox)
+    Zm = basis(BIG, L1, L2, Rmax)
+    k, i, j = logical(BIG)
+    inside = (k * k + i * i + j * j) < (41.0 if Rmax < 0 else Rmax) ** 2
+    assert np.all(Zm[0][inside] != 0) and np.all(Zm[0][~inside] == 0)
+    assert inside.all() == (Rmax == BIG_ALL)
+    # the box the kernel loops over is the bounding box of the ball, clipped to the volume
+    span = [int(np.ptp(np.nonzero(inside.any(axis=tuple(a for a in range(3) if a != ax)))[0])) + 1 for ax in range(3)]
+    assert span[0] * span[1] * span[2] == nbox
+    h = xa.VolumeDeformSph(ctx, BIG, L1, L2, Rmax, LAMBDA)
+    assert h.nterms == Zm.shape[0]
+    worst = 0.0
+    for npairs in (1, 3):
+        I, R = pairs(BIG)
+        I, R = I[:npairs], R[:npairs]
+        h.set_pairs(I, R)
+        assert h.sumVI == pytest.approx(np.sum(I[I >= 0]), rel=1e-12)
+        for x in (random_x(Zm, seed=5), np.zeros(3 * Zm.shape[0])):
+            got, want = h.cost(x), cost_ref(I, R, x, Zm)
+            rel = np.abs(got - want) / np.where(want != 0, np.abs(want), 1.0)
+            worst = max(worst, rel.max())
+            print(f"shape {BIG} degrees {degrees} Rmax {Rmax} pairs {npairs} |x|max {np.abs(x).max():.3g}: got {got} rel.err {rel}")
+            assert np.all(np.abs(got - want) <= 1e-9 * np.abs(want)), (got, want)
+    print(f"shape {BIG} degrees {degrees} Rmax {Rmax}: largest relative error {worst:.3e} (bound 1e-9)")
+
+
+def test_determinism_past_the_cap(gpu):
+    """the same coefficients twice give the same bits with 2048 partial sums in each of 3 rows: the final reduction's strided loop
+    (more than 256 partials per row needs more than 32 CUs) and the grid-stride loop's second pass"""
+    xa, ctx = gpu
+    cus = _past_caps(81 ** 3)
+    assert 8 * cus > 256, f"{8 * cus} partial sums per row do not take the final reduction past its first 256"
+    Zm = basis(BIG, 3, 2, -1.0)
+    I, R = pairs(BIG)
+    h = xa.VolumeDeformSph(ctx, BIG, 3, 2)
+    h.set_pairs(I, R)
+    xa_, xb = random_x(Zm, seed=1), random_x(Zm, seed=2, reach=0.5)
+    first = h.cost(xa_)
+    other = h.cost(xb)
+    again = h.cost(xa_)
+    assert not np.array_equal(first, other)
+    assert np.array_equal(first.view(np.uint64), again.view(np.uint64))
+
+
+def test_apply_past_the_cap(gpu):
+    """test_apply's bounds (1e-10 absolute on clipped-scale data; g exactly 0 outside Rmax) with Rmax = -1, the ball of 41 voxels.
+    Measured on an MI355X: VO 1.4e-15, g 1.4e-15."""
+    xa, ctx = gpu
+    _past_caps(int(np.prod(BIG)))
+    Zm = basis(BIG, 3, 2, -1.0)
+    raw = pairs(BIG)[0][0]
+    h = xa.VolumeDeformSph(ctx, BIG, 3, 2)
+    x = random_x(Zm, seed=4)
+    VO, G = h.apply(raw, x, field=True)
+    gx, gy, gz = field(x, Zm)
+    k, i, j = logical(BIG)
+    want = sample(raw, j + gx, i + gy, k + gz)
+    print(f"{BIG} apply: max |VO - numpy| {np.abs(VO - want).max():.3e}, max |g - numpy| {max(np.abs(got - w).max() for got, w in zip(G, (gx, gy, gz))):.3e}")
+    assert np.abs(VO - want).max() <= 1e-10
+    for got, w in zip(G, (gx, gy, gz)):
+        assert np.abs(got - w).max() <= 1e-10
+    assert np.abs(VO - raw).max() > 0.01       # the deformation moved something
+    outside = (k * k + i * i + j * j) >= 41 * 41
+    assert outside.any() and np.all(G[:, outside] == 0)
+    assert np.array_equal(h.apply(raw, x), VO)
+
+
+def test_gauss_past_the_cap(gpu):
+    """test_gauss's 1e-12 of the largest value. Measured on an MI355X: 8.1e-16."""
+    xa, ctx = gpu
+    _past_caps(int(np.prod(BIG)))
+    v = blobs(BIG, seed=21)
+    h = xa.VolumeDeformSph(ctx, BIG, 1, 0)
+    want = gauss_ref(v, 1.5)
+    got = h.gauss(v, 1.5)
+    print(f"{BIG} gauss: max |device - numpy| = {np.abs(got - want).max() / np.abs(want).max():.3e} of the largest value")
+    assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
+
+
+def test_strain_past_the_cap(gpu):
+    """test_strain's field and bounds on the whole of (81, 84, 82). Measured on an MI355X: filtered field 1.9e-15 of its largest
+    value, LS and LR equal to the restatement bit for bit."""
+    xa, ctx = gpu
+    _past_caps(int(np.prod(BIG)))
+    Zm = basis(BIG, 3, 2, BIG_ALL)
+    k, i, j = logical(BIG)
+    g = field(random_x(Zm, seed=6, reach=0.5), Zm)
+    G = np.array([g[0] - 0.05 * i, g[1] + 0.05 * j, g[2]])
+    h = xa.VolumeDeformSph(ctx, BIG, 3, 2, BIG_ALL)
+    Gf, LS, LR = h.strain(G)
+    want = np.array([gauss_ref(G[c], 2.0) for c in range(3)])
+    eLS, eLR, w = strain_ref(Gf)
+    assert np.abs(w - 1e-6).min() > 1e-3       # nowhere near the threshold: checked on the numpy side first
+    border = np.ones(BIG, bool)
+    border[2:-2, 2:-2, 2:-2] = False
+    with np.errstate(all="ignore"):
+        print(f"{BIG} strain: filtered field {np.abs(Gf - want).max() / np.abs(want).max():.3e} of the largest value, "
+              f"LS {np.nanmax(np.abs(LS - eLS)[~border] / np.abs(eLS)[~border]):.3e}, LR {np.nanmax(np.abs(LR - eLR)[~border] / np.abs(eLR)[~border]):.3e} relative")
+    assert np.abs(Gf - want).max() <= 1e-12 * np.abs(want).max()
+    assert np.all(LS[border] == 0) and np.all(LR[border] == 0)
+    assert np.all(LR[~border] > 0)
+    assert np.all(np.abs(LS - eLS) <= 1e-10 * np.abs(eLS) + 1e-12)
+    assert np.all(np.abs(LR - eLR) <= 1e-10 * np.abs(eLR) + 1e-12)
+
+
 # ---------------------------------------------------------------- search
 def test_stage_discipline(gpu):
     xa, ctx = gpu

@@ -777,6 +777,61 @@ int xh_vds_apply(xh_vds *h, const double *h_raw, const double *h_x, double *h_VO
  * antisymmetric part (the modulus of its imaginary eigenvalues) where that exceeds 1e-6, else 0; both are 0 on the border. Synchronous. */
 int xh_vds_strain(xh_vds *h, double *h_G, double *h_LS, double *h_LR);
 
+/* ---- xmipp_angular_sph_alignment (reconstruction/angular_sph_alignment.cpp; CUDA twin
+ * reconstruction_adapt_cuda/angular_sph_alignment_gpu.cpp, reconstruction_cuda/cuda_angular_sph_alignment.cu) ----
+ * For every particle a pose and a Zernike3D deformation of the reference volume, fitted by Powell's method over
+ *   cost = -correlationIndex(Ifilteredp, P, mask2D) + lambda (sqrt(modg / count) + |sumV - sumVd| / sumV)
+ * with P the projection along z of the volume sampled at R^-1 p + g(R^-1 p), R = Euler(rot, tilt, psi), over the voxels with r < RDef
+ * whose displaced position falls on a mask voxel equal to 1 (deformVol L530-609), then multiplied by the particle's CTF and low-passed.
+ * The nvars = 3 vecSize + 8 variables of a row are the reference's p: cx, cy, cz of every term (the order of xh_vds_terms), then the change
+ * of shift x, y, of rot, tilt, psi, of defocus U, V and of the defocus angle. Everything is fp64; the searches of all loaded particles
+ * advance in lockstep, one evaluation of every live search per device step. A row's results never depend on the rows evaluated with it.
+ * Deviations from the reference are listed at the head of xmipp3_amd/csrc/xh_asa.hip. */
+typedef struct xh_asa xh_asa;
+typedef struct {
+    double max_shift, max_angular_change, max_resolution, sampling, Rmax, RDef, lambda;      /* readParams L52-64; lambda: --regularization */
+    int32_t l1, l2, optimize_alignment, optimize_deformation, optimize_defocus, phase_flipped;
+} xh_asa_params;
+/* one particle's input row (processImage L304-325) */
+typedef struct {
+    double rot, tilt, psi, shift_x, shift_y;
+    int32_t flip, has_ctf;
+    xh_ctf_params ctf;      /* read when has_ctf (readFromMdRow); phase_shift in degrees; K is taken as 1 (updateCTFImage L521-528) */
+} xh_asa_row;
+/* the program's defaults (defineParams L104-120) */
+void xh_asa_defaults(xh_asa_params *p);
+/* the flags of xh_asa_stage_active: --optimizeDeformation, --optimizeAlignment, --optimizeDefocus */
+enum { XH_ASA_OPT_DEFORMATION = 1, XH_ASA_OPT_ALIGNMENT = 2, XH_ASA_OPT_DEFOCUS = 4 };
+/* host only, no device needed: the indices (ascending, into the nvars variables of degrees (L1, L2)) of the variables that stage `stage`
+ * (0 .. L2; the program runs 1 .. L2) frees: minimizepos (L472-482) and the steps of processImage (L351-358). out holds up to nvars. */
+int xh_asa_stage_active(int32_t L1, int32_t L2, int32_t stage, int32_t flags, int32_t *out, int32_t *n);
+/* preProcess (L125-188): d_vol [D][D][D] float (device) is kept as doubles; h_mask [D][D][D] int32 (host; null: the sphere of radius RDef);
+ * sumV = the sum of the volume where the mask is 1 (0 or non-finite: XH_ERR_ARG); mask2D of radius Rmax; RDef, Rmax < 0: D / 2.
+ * Degrees above l1 = 5, l2 = 4 are XH_ERR_UNSUPPORTED. capacity: evaluations per device step. */
+int xh_asa_create(xh_ctx *ctx, const float *d_vol, int32_t D, const int32_t *h_mask, const xh_asa_params *prm, int32_t capacity, xh_asa **out);
+int xh_asa_destroy(xh_asa *h);
+/* RDef and Rmax as resolved, vecSize, the number of variables, sumV; null pointers are skipped */
+int xh_asa_info(const xh_asa *h, double *RDef, double *Rmax, int32_t *vecSize, int32_t *nvars, double *sumV);
+/* processImage L304-333 for n particles h_images [n][ydim][xdim] (host): Ifiltered = the raised-cosine low pass at sampling / max_resolution,
+ * raised_w 0.02, resident as doubles; replaces what was loaded. Particles of another size than the volume: XH_ERR_UNSUPPORTED. */
+int xh_asa_load(xh_asa *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_asa_row *rows);
+/* continuousSphCost + tranformImageSph (L196-289) of m rows: particle h_particle[r] at the variables h_vars[r][nvars] -> h_cost[r]. A row
+ * outside the bounds of L275-278, or with a non-finite variable, costs 1e38 and no device work; so does a row whose count is 0.
+ * Synchronous. */
+int xh_asa_cost(xh_asa *h, int32_t m, const int32_t *h_particle, const double *h_vars, double *h_cost);
+/* of device row `row` of the last evaluation (the in-bound rows of the last chunk, in order): the projection before (d_P_raw) and after
+ * (d_P) the CTF and the low pass, the transformed particle (d_Ifilteredp, 0 outside mask2D), [D][D] doubles on the device, and
+ * h_sums[4] = sumVd, modg, count, corr (host); null pointers are skipped */
+int xh_asa_last(xh_asa *h, int32_t row, double *d_P_raw, double *d_P, double *d_Ifilteredp, double *h_sums);
+/* the search of processImage (L335-415) for every loaded particle: stages h = 1 .. l2, each Powell (ftol 0.01, step 1) over the variables
+ * xh_asa_stage_active names, from the variables the stage before left; a stage that ends at a positive cost disables the particle and
+ * zeroes its variables (L369-373). h_vars [n][nvars], h_cost [n] (the last stage's minimum: minus the correlation written), h_enabled [n]
+ * (1 or -1), h_deformation [n] (sqrt(modg / count) of one more evaluation at the returned variables; 0 when that row is out of bounds),
+ * h_iter [n] and h_evals [n] (iterations and cost calls over all stages). */
+int xh_asa_refine(xh_asa *h, double *h_vars, double *h_cost, int32_t *h_enabled, double *h_deformation, int32_t *h_iter, int64_t *h_evals);
+/* of the last xh_asa_cost or xh_asa_refine: device steps, rows evaluated on the device, seconds inside device steps, seconds in all */
+int xh_asa_stats(const xh_asa *h, double *h_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,16 @@ class Ca2Row(C.Structure):
                                           "gray_b")] + [("flip", C.c_int32), ("has_ctf", C.c_int32), ("ctf", CtfParams)]
 
 
+class AsaParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("max_shift", "max_angular_change", "max_resolution", "sampling", "Rmax", "RDef", "lambda_")] + [
+        (n, C.c_int32) for n in ("l1", "l2", "optimize_alignment", "optimize_deformation", "optimize_defocus", "phase_flipped")]
+
+
+class AsaRow(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("rot", "tilt", "psi", "shift_x", "shift_y")] + [("flip", C.c_int32), ("has_ctf", C.c_int32),
+                                                                                          ("ctf", CtfParams)]
+
+
 # every symbol include/xmipp_hip.h declares: name -> (restype, argtypes)
 vp, i32, i64, d, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 pvp = C.POINTER(C.c_void_p)
@@ -172,6 +182,16 @@ SIGNATURES = {
     "xh_vds_refine_stage": (C.c_int, [vp, i32, vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i64)]),
     "xh_vds_apply": (C.c_int, [vp, vp, vp, vp, vp]),
     "xh_vds_strain": (C.c_int, [vp, vp, vp, vp]),
+    "xh_asa_defaults": (None, [C.POINTER(AsaParams)]),
+    "xh_asa_stage_active": (C.c_int, [i32, i32, i32, i32, vp, C.POINTER(i32)]),
+    "xh_asa_create": (C.c_int, [vp, vp, i32, vp, C.POINTER(AsaParams), i32, pvp]),
+    "xh_asa_destroy": (C.c_int, [vp]),
+    "xh_asa_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]),
+    "xh_asa_load": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "xh_asa_cost": (C.c_int, [vp, i32, vp, vp, vp]),
+    "xh_asa_last": (C.c_int, [vp, i32, vp, vp, vp, vp]),
+    "xh_asa_refine": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "xh_asa_stats": (C.c_int, [vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

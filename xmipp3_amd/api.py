@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import Ca2Params, Ca2Row, CtfParams, RfParams, XhError, check, lib
+from ._lib import AsaParams, AsaRow, Ca2Params, Ca2Row, CtfParams, RfParams, XhError, check, lib
 
 
 def _torch():
@@ -1187,6 +1187,103 @@ class ContinuousAssign2(_Handle):
     def stats(self):
         s = np.zeros(4)
         check(lib().xh_ca2_stats(self.h, _np_ptr(s)))
+        return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
+
+
+def asa_stage_active(L1, L2, stage, deformation=True, alignment=False, defocus=False):
+    """the indices of the variables that stage `stage` of xmipp_angular_sph_alignment frees, among the 3 vecSize + 8 of degrees (L1, L2)
+    (host only)"""
+    flags = (1 if deformation else 0) | (2 if alignment else 0) | (4 if defocus else 0)
+    out = np.zeros(3 * 45 + 8, np.int32)
+    n = C.c_int32()
+    check(lib().xh_asa_stage_active(int(L1), int(L2), int(stage), flags, _np_ptr(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+class AngularSphAlignment(_Handle):
+    """Device side of ProgAngularSphAlignment (reconstruction/angular_sph_alignment.cpp): for every particle a pose and a Zernike3D
+    deformation of `vol` ([z][y][x] float32, cuda, a cube), fitted by Powell's method, all searches in lockstep. mask: int32 [D, D, D]
+    (numpy; None: the sphere of radius RDef). Keyword arguments are the fields of xh_asa_params (the program's options; lam is
+    --regularization); capacity = evaluations per device step. The variables of a row are [3 vecSize + 8]: cx, cy, cz of every term,
+    then the change of shift x, y, rot, tilt, psi, defocus U, V, defocus angle."""
+
+    _destroy = "xh_asa_destroy"
+    POSE = ("shiftX", "shiftY", "rot", "tilt", "psi", "defocusU", "defocusV", "defocusAngle")
+
+    def __init__(self, ctx, vol, mask=None, capacity=64, **params):
+        torch = _torch()
+        assert vol.is_cuda and vol.dtype == torch.float32 and vol.is_contiguous() and vol.dim() == 3
+        if not (vol.shape[0] == vol.shape[1] == vol.shape[2]):
+            raise XhError(f"AngularSphAlignment: the volume must be a cube, got {tuple(vol.shape)} (not supported)")
+        self.D = vol.shape[0]
+        self.params = AsaParams()
+        lib().xh_asa_defaults(C.byref(self.params))
+        for k, v in params.items():
+            k = "lambda_" if k in ("lam", "lambda_") else k
+            if not hasattr(self.params, k):
+                raise XhError(f"AngularSphAlignment: unknown parameter {k}")
+            setattr(self.params, k, v)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32)
+            if mask.shape != (self.D,) * 3:
+                raise XhError(f"AngularSphAlignment: a mask of shape {mask.shape} against a volume of size {self.D} (not supported)")
+        self.capacity = int(capacity)
+        self.n = 0
+        h = C.c_void_p()
+        check(lib().xh_asa_create(ctx.h, _ptr(vol), self.D, _np_ptr(mask), C.byref(self.params), self.capacity, C.byref(h)))
+        super().__init__(ctx, h)
+        rd, rm, vs, nv, sv = C.c_double(), C.c_double(), C.c_int32(), C.c_int32(), C.c_double()
+        check(lib().xh_asa_info(self.h, C.byref(rd), C.byref(rm), C.byref(vs), C.byref(nv), C.byref(sv)))
+        self.RDef, self.Rmax, self.vecSize, self.nvars, self.sumV = rd.value, rm.value, vs.value, nv.value, sv.value
+
+    def load(self, images, rows=None):
+        """images: [n, D, D] float32 (host); rows: per particle a dict with any of rot, tilt, psi, shift_x, shift_y, flip, ctf (a
+        CtfParams: the particle has a CTF) (defaults: 0, no CTF)"""
+        img = np.ascontiguousarray(images, np.float32)
+        assert img.ndim == 3
+        n = img.shape[0]
+        arr = (AsaRow * n)()
+        for i in range(n):
+            for k, v in (rows[i] if rows is not None else {}).items():
+                if not hasattr(arr[i], k) or k == "has_ctf":
+                    raise XhError(f"AngularSphAlignment.load: unknown column {k}")
+                if k == "ctf":
+                    if v is not None:
+                        arr[i].ctf, arr[i].has_ctf = v, 1
+                else:
+                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
+        check(lib().xh_asa_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
+        self.n = n
+
+    def cost(self, particles, variables):
+        """particles: [m] indices; variables: [m, nvars] -> costs [m] (1e38 for a row out of bounds, and for one whose count is 0)"""
+        idx = np.ascontiguousarray(particles, np.int32).reshape(-1)
+        x = np.ascontiguousarray(variables, np.float64).reshape(-1, self.nvars)
+        assert x.shape[0] == idx.shape[0]
+        out = np.zeros(idx.shape[0])
+        check(lib().xh_asa_cost(self.h, idx.shape[0], _np_ptr(idx), _np_ptr(x), _np_ptr(out)))
+        return out
+
+    def last(self, row=0):
+        """(P_raw, P, Ifilteredp) [D, D] float64 cuda tensors and (sumVd, modg, count, corr) float64 [4] of one device row of the last
+        evaluation"""
+        torch = _torch()
+        out = [torch.empty((self.D, self.D), dtype=torch.float64, device=self.ctx.torch_device) for _ in range(3)]
+        sums = np.zeros(4)
+        check(lib().xh_asa_last(self.h, int(row), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _np_ptr(sums)))
+        return out[0], out[1], out[2], sums
+
+    def refine(self):
+        """-> (variables [n, nvars], cost [n], enabled [n], deformation [n], iterations [n], cost calls [n]) of every loaded particle"""
+        n = self.n
+        x, cost, de = np.zeros((n, self.nvars)), np.zeros(n), np.zeros(n)
+        en, it, ev = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        check(lib().xh_asa_refine(self.h, _np_ptr(x), _np_ptr(cost), _np_ptr(en), _np_ptr(de), _np_ptr(it), _np_ptr(ev)))
+        return x, cost, en, de, it, ev
+
+    def stats(self):
+        s = np.zeros(4)
+        check(lib().xh_asa_stats(self.h, _np_ptr(s)))
         return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
 
 

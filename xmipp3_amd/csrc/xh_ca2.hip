@@ -23,6 +23,7 @@
 #include "xh_reduce.h"
 #include "xh_ctf.h"
 #include "xh_bspline.h"
+#include "xh_image2d.h"
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -33,7 +34,6 @@ namespace {
 // 2 computed from the CtfSide that follows), CtfSide[18], pad
 const int kEv = 40, kEvCtf = 19, kEvSide = 20;
 static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evaluation row as 18 doubles");
-const double kAcc = 1e-6;       // XMIPP_EQUAL_ACCURACY
 const double kBarrier = 1e38;   // continuous2cost's cost of a vector out of bounds
 
 // FourierFilter LOWPASS / RAISED_COSINE (fourier_filter.cpp:423-432) on the full spectrum, the 1/D^2 of the inverse folded in; where the
@@ -47,10 +47,7 @@ __global__ void k_ca2_lowpass(xh_cd *__restrict__ F, size_t total, int D, double
     const int j = idx % D, i = (idx / D) % D;
     const double fy = d_digfreq(i, D), fx = d_digfreq(j, D);
     const double absw = sqrt(fx * fx + fy * fy);
-    double m;
-    if (absw < w1) m = 1;
-    else if (absw < w1 + raised_w) m = (1 + cos(3.14159265358979323846 / raised_w * (absw - w1))) / 2;
-    else m = 0;
+    double m = d_lowpass_raised_cosine(absw, w1, raised_w);
     m /= (double)D * (double)D;
     if (rows) {
         const double *q = rows + (size_t)kEv * (idx / ((size_t)D * D));
@@ -89,35 +86,6 @@ k_ca2_ctf_rows(const double *__restrict__ ev, const double *__restrict__ ctfPart
         if (phaseFlipped) v = fabs(v);
     }
     out[(size_t)e * per + t] = v;
-}
-
-// applyGeometry's 2-D LINEAR branch at one output pixel (i, j), DONT_WRAP, outside 0; A is the matrix already inverted (rows 0 and 1).
-// The same interpolation as xh_apply_geometry2d's, in doubles.
-__device__ __forceinline__ double d_ca2_linear(const double *__restrict__ V1, int D, const double *A, int i, int j)
-{
-    const int cen = D / 2;
-    const double minp = -cen - kAcc, maxp = (D - cen - 1) + kAcc;
-    const double x = (double)(j - cen), y = (double)(i - cen);
-    const double xp = x * A[0] + y * A[1] + A[2], yp = x * A[3] + y * A[4] + A[5];
-    if (!(xp >= minp && xp <= maxp && yp >= minp && yp <= maxp)) return 0.0;      // a NaN coordinate is outside, too
-    double wx = xp + cen;
-    const int m1 = (int)wx;
-    wx = wx - m1;
-    const int m2 = m1 + 1;
-    double wy = yp + cen;
-    const int n1 = (int)wy;
-    wy = wy - n1;
-    const int n2 = n1 + 1;
-    const double wx_1 = 1 - wx, wy_1 = 1 - wy;
-    double aux2 = wy_1 * wx_1;
-    double tmp = aux2 * V1[(size_t)n1 * D + m1];
-    if (wx != 0 && m2 < D) tmp += (wy_1 - aux2) * V1[(size_t)n1 * D + m2];
-    if (wy != 0 && n2 < D) {
-        aux2 = wy * wx_1;
-        tmp += aux2 * V1[(size_t)n2 * D + m1];
-        if (wx != 0 && m2 < D) tmp += (wy - aux2) * V1[(size_t)n2 * D + m2];
-    }
-    return tmp;
 }
 
 // tranformImage (L275-317): one workgroup per evaluation. Writes Ifilteredp (0 outside the mask), E, and the cost.

@@ -19,5 +19,6 @@ $CXX $FLAGS align_significant_main.cpp -o ../bin/xmipp_align_significant $LINK &
 $CXX $FLAGS volume_halves_restoration_main.cpp -o ../bin/xmipp_volume_halves_restoration $LINK &
 $CXX $FLAGS angular_continuous_assign2_main.cpp -o ../bin/xmipp_angular_continuous_assign2 $LINK &
 $CXX $FLAGS volume_deform_sph_main.cpp -o ../bin/xmipp_volume_deform_sph $LINK &
+$CXX $FLAGS angular_sph_alignment_main.cpp -o ../bin/xmipp_angular_sph_alignment $LINK &
 wait
-echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph}"
+echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph,angular_sph_alignment}"

@@ -1093,12 +1093,55 @@ class FourierProjector(_Handle):
         return out
 
 
-class ContinuousAssign2(_Handle):
+class _LockstepRows(_Handle):
+    """What the per-particle Powell programs share: load's rows, cost and stats. A subclass names its ABI prefix (_abi) and its row
+    struct (_Row, with _row_defaults), and sets nvars before the first cost."""
+
+    _row_defaults = {}
+
+    def _fn(self, name):
+        return getattr(lib(), f"xh_{self._abi}_{name}")
+
+    def _load(self, images, rows):
+        img = np.ascontiguousarray(images, np.float32)
+        assert img.ndim == 3
+        n = img.shape[0]
+        arr = (self._Row * n)()
+        for i in range(n):
+            for k, v in self._row_defaults.items():
+                setattr(arr[i], k, v)
+            for k, v in (rows[i] if rows is not None else {}).items():
+                if not hasattr(arr[i], k) or k == "has_ctf":
+                    raise XhError(f"{type(self).__name__}.load: unknown column {k}")
+                if k == "ctf":
+                    if v is not None:
+                        arr[i].ctf, arr[i].has_ctf = v, 1
+                else:
+                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
+        check(self._fn("load")(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
+        self.n = n
+
+    def _cost(self, particles, variables):
+        idx = np.ascontiguousarray(particles, np.int32).reshape(-1)
+        x = np.ascontiguousarray(variables, np.float64).reshape(-1, self.nvars)
+        assert x.shape[0] == idx.shape[0]
+        out = np.zeros(idx.shape[0])
+        check(self._fn("cost")(self.h, idx.shape[0], _np_ptr(idx), _np_ptr(x), _np_ptr(out)))
+        return out
+
+    def stats(self):
+        s = np.zeros(4)
+        check(self._fn("stats")(self.h, _np_ptr(s)))
+        return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
+
+
+class ContinuousAssign2(_LockstepRows):
     """Device side of ProgAngularContinuousAssign2 (reconstruction/angular_continuous_assign2.cpp): Powell refinement of every
     particle's grey values, shift, scale and angles against projections of `vol` ([z][y][x] float32, cuda), all searches in lockstep.
     Keyword arguments are the fields of xh_ca2_params (the program's options); capacity = evaluations per device step."""
 
     _destroy = "xh_ca2_destroy"
+    _abi, _Row, _row_defaults, nvars = "ca2", Ca2Row, {"gray_a": 1.0}, 13
     VARIABLES = ("a", "b", "shiftX", "shiftY", "scaleX", "scaleY", "scaleAngle", "rot", "tilt", "psi", "defocusU", "defocusV",
                  "defocusAngle")
 
@@ -1121,31 +1164,11 @@ class ContinuousAssign2(_Handle):
     def load(self, images, rows=None):
         """images: [n, D, D] float32 (host); rows: per particle a dict with any of rot, tilt, psi, shift_x, shift_y, flip, scale_x,
         scale_y, scale_angle, gray_a, gray_b, ctf (a CtfParams: the particle has a CTF) (defaults: 0, gray_a 1, no CTF)"""
-        img = np.ascontiguousarray(images, np.float32)
-        assert img.ndim == 3
-        n = img.shape[0]
-        arr = (Ca2Row * n)()
-        for i in range(n):
-            arr[i].gray_a = 1.0
-            for k, v in (rows[i] if rows is not None else {}).items():
-                if not hasattr(arr[i], k) or k == "has_ctf":
-                    raise XhError(f"ContinuousAssign2.load: unknown column {k}")
-                if k == "ctf":
-                    if v is not None:
-                        arr[i].ctf, arr[i].has_ctf = v, 1
-                else:
-                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
-        check(lib().xh_ca2_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
-        self.n = n
+        self._load(images, rows)
 
     def cost(self, particles, variables):
         """particles: [m] indices; variables: [m, 13] -> costs [m] (1e38 for a row out of bounds)"""
-        idx = np.ascontiguousarray(particles, np.int32).reshape(-1)
-        x = np.ascontiguousarray(variables, np.float64).reshape(-1, 13)
-        assert x.shape[0] == idx.shape[0]
-        out = np.zeros(idx.shape[0])
-        check(lib().xh_ca2_cost(self.h, idx.shape[0], _np_ptr(idx), _np_ptr(x), _np_ptr(out)))
-        return out
+        return self._cost(particles, variables)
 
     def last_images(self, row=0):
         """(P, E, Ifilteredp) [D, D] float64 cuda tensors of one row of the last evaluation"""
@@ -1184,11 +1207,6 @@ class ContinuousAssign2(_Handle):
         check(lib().xh_ca2_refine(self.h, _np_ptr(x), _np_ptr(cost), _np_ptr(it), _np_ptr(ev), _np_ptr(en)))
         return x, cost, it, ev, en
 
-    def stats(self):
-        s = np.zeros(4)
-        check(lib().xh_ca2_stats(self.h, _np_ptr(s)))
-        return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
-
 
 def asa_stage_active(L1, L2, stage, deformation=True, alignment=False, defocus=False):
     """the indices of the variables that stage `stage` of xmipp_angular_sph_alignment frees, among the 3 vecSize + 8 of degrees (L1, L2)
@@ -1200,7 +1218,7 @@ def asa_stage_active(L1, L2, stage, deformation=True, alignment=False, defocus=F
     return out[:n.value].copy()
 
 
-class AngularSphAlignment(_Handle):
+class AngularSphAlignment(_LockstepRows):
     """Device side of ProgAngularSphAlignment (reconstruction/angular_sph_alignment.cpp): for every particle a pose and a Zernike3D
     deformation of `vol` ([z][y][x] float32, cuda, a cube), fitted by Powell's method, all searches in lockstep. mask: int32 [D, D, D]
     (numpy; None: the sphere of radius RDef). Keyword arguments are the fields of xh_asa_params (the program's options; lam is
@@ -1208,6 +1226,7 @@ class AngularSphAlignment(_Handle):
     then the change of shift x, y, rot, tilt, psi, defocus U, V, defocus angle."""
 
     _destroy = "xh_asa_destroy"
+    _abi, _Row = "asa", AsaRow
     POSE = ("shiftX", "shiftY", "rot", "tilt", "psi", "defocusU", "defocusV", "defocusAngle")
 
     def __init__(self, ctx, vol, mask=None, capacity=64, **params):
@@ -1239,30 +1258,11 @@ class AngularSphAlignment(_Handle):
     def load(self, images, rows=None):
         """images: [n, D, D] float32 (host); rows: per particle a dict with any of rot, tilt, psi, shift_x, shift_y, flip, ctf (a
         CtfParams: the particle has a CTF) (defaults: 0, no CTF)"""
-        img = np.ascontiguousarray(images, np.float32)
-        assert img.ndim == 3
-        n = img.shape[0]
-        arr = (AsaRow * n)()
-        for i in range(n):
-            for k, v in (rows[i] if rows is not None else {}).items():
-                if not hasattr(arr[i], k) or k == "has_ctf":
-                    raise XhError(f"AngularSphAlignment.load: unknown column {k}")
-                if k == "ctf":
-                    if v is not None:
-                        arr[i].ctf, arr[i].has_ctf = v, 1
-                else:
-                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
-        check(lib().xh_asa_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
-        self.n = n
+        self._load(images, rows)
 
     def cost(self, particles, variables):
         """particles: [m] indices; variables: [m, nvars] -> costs [m] (1e38 for a row out of bounds, and for one whose count is 0)"""
-        idx = np.ascontiguousarray(particles, np.int32).reshape(-1)
-        x = np.ascontiguousarray(variables, np.float64).reshape(-1, self.nvars)
-        assert x.shape[0] == idx.shape[0]
-        out = np.zeros(idx.shape[0])
-        check(lib().xh_asa_cost(self.h, idx.shape[0], _np_ptr(idx), _np_ptr(x), _np_ptr(out)))
-        return out
+        return self._cost(particles, variables)
 
     def last(self, row=0):
         """(P_raw, P, Ifilteredp) [D, D] float64 cuda tensors and (sumVd, modg, count, corr) float64 [4] of one device row of the last
@@ -1280,11 +1280,6 @@ class AngularSphAlignment(_Handle):
         en, it, ev = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
         check(lib().xh_asa_refine(self.h, _np_ptr(x), _np_ptr(cost), _np_ptr(en), _np_ptr(de), _np_ptr(it), _np_ptr(ev)))
         return x, cost, en, de, it, ev
-
-    def stats(self):
-        s = np.zeros(4)
-        check(lib().xh_asa_stats(self.h, _np_ptr(s)))
-        return {"steps": int(s[0]), "rows": int(s[1]), "device_s": s[2], "total_s": s[3]}
 
 
 class ProjectionMatcher(_Handle):

@@ -9,7 +9,9 @@
 // with float atomics; here
 //
 //   the unit of device work is ONE EVALUATION FOR EACH OF MANY (particle, variables) ROWS, as in xh_ca2.hip: the rows go up through one
-//   pinned buffer, a fixed sequence of launches evaluates all of them, four sums per row come back in one copy behind one stream wait.
+//   pinned buffer, a fixed sequence of launches evaluates all of them, four sums per row come back in one copy behind one stream wait
+//   (XhRowEval of xh_lockstep.h, shared with xh_ca2.hip, as are the particle load, the filter kernel, the 2-D mask and the correlation
+//   index of xh_image2d.h; the host side of the Zernike3D basis is xh_zernike.h's, shared with xh_vds.hip).
 //
 //   k_asa_project : grid (tiles of 256 projection columns, row). A thread owns one column (i, j), lanes along j, and walks k upwards:
 //                   pos = R (j, i, k), g = sum c Z(pos / RDef) (vds_disp of xh_zernike.h), the mask at the truncated pos + g, the trilinear
@@ -21,11 +23,10 @@
 //                   batch, the other rows' workgroups leave at once), so a row's bits never depend on what shares its batch.
 //                   k is not split into segments: a split would change the order of the additions from the reference's, and a batch
 //                   fills the device without it (D = 128: 64 workgroups per row); the grid depends on D alone.
-//   FFT           : forward 2-D transforms of the planes (XhFft2d64), one multiply by the raised-cosine low pass times the row's CTF,
-//                   inverse transforms.
+//   FFT           : forward 2-D transforms of the planes (XhFft2d64), one multiply by the raised-cosine low pass times the row's CTF
+//                   (xh_k_lowpass_ctf<XH_FACTOR_CTF>: FilterCTF's mask of applyCTFImage L506-519), inverse transforms.
 //   k_asa_cost    : one workgroup per row: the partials' totals, then every pixel of mask2D takes Ifiltered at the inverse of A (LINEAR,
-//                   DONT_WRAP, outside 0) and the correlation sums go through the fixed tree of xh_reduce.h. The cost is assembled on the
-//                   host in doubles.
+//                   DONT_WRAP, outside 0), then d_masked_correlation. The cost is assembled on the host in doubles.
 //
 // Deviations from the reference:
 //  - r^2 is k^2 + i^2 + j^2 of the integer coordinates, not |R p|^2 of the rotated ones: a rotation keeps the norm, and the rounded
@@ -49,7 +50,7 @@
 #include "xh_ctf.h"
 #include "xh_image2d.h"
 #include "xh_zernike.h"
-#include <chrono>
+#include "xh_lockstep.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -59,9 +60,7 @@ namespace {
 // identity, CTF (0 none, 1 computed from the CtfSide that follows), CtfSide[18], the instantiation's l2
 const int kRowCoef = 9, kRowA = kRowCoef + 3 * VDS_MAXT, kRowPart = kRowA + 6, kRowIdent = kRowPart + 1, kRowCtf = kRowIdent + 1,
           kRowSide = kRowCtf + 1, kRowL2 = kRowSide + 18, kRow = kRowL2 + 1;
-static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evaluation row as 18 doubles");
 static_assert(sizeof(VdsCoef) == 3 * VDS_MAXT * sizeof(double), "VdsCoef rides in an evaluation row");
-const double kBarrier = 1e38;   // continuousSphCost's cost of a vector out of bounds
 
 struct AsaGeom : ZkDims {    // Z, Y, X: the volume (a cube of side D)
     int D, DD, tiles;        // tiles: workgroups of 256 columns per row
@@ -109,43 +108,6 @@ k_asa_project(const double *__restrict__ V, const int *__restrict__ M, const dou
     xh_block_partials(acc, partials + (size_t)e * 3 * g.tiles);
 }
 
-// the planes as complex doubles
-__global__ void __launch_bounds__(256) k_asa_to_complex(const double *__restrict__ in, xh_cd *__restrict__ out, size_t tot)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < tot) out[t] = xh_cd{in[t], 0.0};
-}
-
-// FourierFilter LOWPASS / RAISED_COSINE on the full spectrum with the 1 / D^2 of the inverse folded in, times, where the row has a CTF,
-// FilterCTF's mask (applyCTFImage L506-519: generateCTF at K = 1 without the noise model, its absolute value after correctPhase). Both
-// are real and even: the CTF is taken at the half-spectrum index of (i, j), so the product keeps the spectrum Hermitian.
-// ev null: the low pass alone (the particles).
-__global__ void __launch_bounds__(256)
-k_asa_filter(xh_cd *__restrict__ F, size_t total, int D, double w1, double raised_w, const double *__restrict__ ev, double iTs, int phaseFlipped)
-{
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int j = idx % D, i = (idx / D) % D;
-    const double fy = d_digfreq(i, D), fx = d_digfreq(j, D);
-    double m = d_lowpass_raised_cosine(sqrt(fx * fx + fy * fy), w1, raised_w);
-    m /= (double)D * (double)D;
-    if (ev && m != 0.0) {
-        const double *q = ev + (size_t)kRow * (idx / ((size_t)D * D));
-        if (q[kRowCtf] != 0.0) {
-            CtfSide s;
-            double *sp = reinterpret_cast<double *>(&s);
-            for (int k = 0; k < 18; ++k) sp[k] = q[kRowSide + k];
-            int ih = i, jh = j;
-            if (jh > D / 2) { jh = D - jh; ih = (D - ih) % D; }
-            double v = d_ctf_at(s, d_digfreq(jh, D) * iTs, d_digfreq(ih, D) * iTs, true);
-            if (phaseFlipped) v = fabs(v);
-            m *= v;
-        }
-    }
-    const xh_cd v = F[idx];
-    F[idx] = xh_cd{v.x * m, v.y * m};
-}
-
 // tranformImageSph (L218-224) for one row per workgroup: the totals of the projection's partials, P = the real part of the filtered plane,
 // Ifilteredp (0 outside mask2D), correlationIndex(Ifilteredp, P, mask2D) (0 where a sigma is below XMIPP_EQUAL_ACCURACY).
 // out [m][4] = sumVd, modg, count, corr
@@ -183,20 +145,7 @@ k_asa_cost(const double *__restrict__ ev, const double *__restrict__ Ifiltered, 
         Pe[n] = p;
         Ie[n] = val;
     }
-    s0 = xh_block_sum(s0, red);
-    s1 = xh_block_sum(s1, red);
-    s2 = xh_block_sum(s2, red);
-    s3 = xh_block_sum(s3, red);
-    const double mx = s0 / nmask, my = s1 / nmask;
-    const double sx = sqrt(fabs(s2 / nmask - mx * mx)), sy = sqrt(fabs(s3 / nmask - my * my));
-    double corr = 0.0;
-    if (!(fabs(sx) < kAcc || fabs(sy) < kAcc)) {      // uniform over the workgroup: every thread holds the same sums
-        double r = 0;
-        for (int n = tid; n < DD; n += 256)
-            if (mask[n]) r += (Ie[n] - mx) * (Pe[n] - my);      // both were written by this thread
-        r = xh_block_sum(r, red);
-        corr = r / ((sx * sy) * nmask);
-    }
+    const double corr = d_masked_correlation(s0, s1, s2, s3, mask, Ie, Pe, DD, nmask, red);
     if (tid == 0) {
         out[4 * (size_t)e] = tot[0];
         out[4 * (size_t)e + 1] = tot[1];
@@ -210,39 +159,26 @@ struct AsaParticle {
     int flip, hasCTF;
     xh_ctf_params ctf;
 };
-
-int asa_check_degrees(const char *who, int L1, int L2)
-{
-    XH_CHECK(L1 >= 0 && L2 >= 0, XH_ERR_ARG, "%s: negative degree (l1 %d, l2 %d)", who, L1, L2);
-    XH_CHECK(L1 <= VDS_MAX_L1 && L2 <= VDS_MAX_L2, XH_ERR_UNSUPPORTED, "%s: degrees l1 = %d, l2 = %d are not supported (l1 <= %d, l2 <= %d)", who, L1, L2,
-             VDS_MAX_L1, VDS_MAX_L2);
-    return XH_OK;
-}
 }  // namespace
 
 struct xh_asa {
     xh_ctx *ctx = nullptr;
     xh_asa_params prm;
     AsaGeom g = {};
-    int D = 0, capacity = 0, nmask = 0, L1 = 0, L2 = 0, vecSize = 0, nvars = 0;
+    int D = 0, nmask = 0, L1 = 0, L2 = 0, vecSize = 0, nvars = 0;
     double RDef = 0, Rmax = 0, sumV = 0;
-    XhBuf d_vol, d_mask3, d_mask2, d_If, d_ev, d_Praw, d_F, d_P, d_Ifp, d_partials, d_out;
+    XhRowEval ev;                                  // rows of kRow doubles up; sumVd, modg, count, corr per row down
+    XhBuf d_vol, d_mask3, d_mask2, d_If, d_Praw, d_F, d_P, d_Ifp, d_partials;
     XhFft2d64 fft;
-    double *h_ev = nullptr, *h_out = nullptr;      // pinned
     std::vector<AsaParticle> parts;
-    int last_rows = 0;
     // refine's bookkeeping
     std::vector<int> active;
     std::vector<double> cur;                       // [particles][nvars]: the stage's frozen variables
-    double t_device = 0, t_total = 0;
-    int64_t steps = 0, rows = 0;
     ~xh_asa()
     {
         if (!ctx) return;
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
-        if (h_ev) (void)hipHostFree(h_ev);
-        if (h_out) (void)hipHostFree(h_out);
     }
 };
 
@@ -271,17 +207,7 @@ void asa_fill_row(const xh_asa *h, int part, const double *x, double *row)
     xh_fp_euler(pt.rot + t[2], pt.tilt + t[3], pt.psi + t[4], E);
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) row[r * 3 + c] = E[c * 3 + r];      // R^-1: the transpose
-    int last = -1;
-    for (int k = 0; k < 3 * VDS_MAXT; ++k) row[kRowCoef + k] = 0.0;
-    for (int idx = 0; idx < vs; ++idx)
-        for (int d = 0; d < 3; ++d) {
-            const double v = x[(size_t)d * vs + idx];
-            row[kRowCoef + 3 * idx + d] = v;
-            if (v != 0.0) last = idx;
-        }
-    int l2 = 0;
-    while (l2 < h->L2 && vds_num_terms(h->L1, l2) <= last) ++l2;
-    row[kRowL2] = (double)l2;
+    row[kRowL2] = (double)zk_pack(h->L1, h->L2, vs, x, row + kRowCoef);
     // A (L280-285, L211-216): the identity with the translation, its whole first row negated by the flip; inverted for IS_NOT_INV
     const double f = pt.flip ? -1.0 : 1.0, tx = pt.shiftX + t[0], ty = pt.shiftY + t[1];
     double *A = row + kRowA;
@@ -305,61 +231,49 @@ void asa_fill_row(const xh_asa *h, int part, const double *x, double *row)
 
 int asa_launch_project(xh_asa *h, int m, int l2)
 {
-    const double *V = (const double *)h->d_vol.p, *ev = (const double *)h->d_ev.p;
+    const double *V = (const double *)h->d_vol.p, *ev = h->ev.dev_rows();
     const int *M = (const int *)h->d_mask3.p;
     double *Praw = (double *)h->d_Praw.p, *part = (double *)h->d_partials.p;
     const int l1 = h->L1;
     const dim3 grid((unsigned)h->g.tiles, (unsigned)m);
-#define ASA_CASE(A, B)                                                                                                         \
-    if (l1 == A && l2 == B) {                                                                                                  \
-        hipLaunchKernelGGL((k_asa_project<A, B>), grid, dim3(256), 0, h->ctx->stream, V, M, ev, h->g, l1, l2, Praw, part);      \
-        XH_LAUNCH_CHECK();                                                                                                     \
-        return XH_OK;                                                                                                          \
-    }
-    ASA_CASE(1, 0) ASA_CASE(1, 1)
-    ASA_CASE(2, 0) ASA_CASE(2, 1) ASA_CASE(2, 2)
-    ASA_CASE(3, 0) ASA_CASE(3, 1) ASA_CASE(3, 2) ASA_CASE(3, 3)
-    ASA_CASE(4, 0) ASA_CASE(4, 1) ASA_CASE(4, 2) ASA_CASE(4, 3) ASA_CASE(4, 4)
-    ASA_CASE(5, 0) ASA_CASE(5, 1) ASA_CASE(5, 2) ASA_CASE(5, 3) ASA_CASE(5, 4)
-#undef ASA_CASE
-    hipLaunchKernelGGL((k_asa_project<-1, -1>), grid, dim3(256), 0, h->ctx->stream, V, M, ev, h->g, l1, l2, Praw, part);
-    XH_LAUNCH_CHECK();
+#define ASA_LAUNCH(A, B)                                                                                                   \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL((k_asa_project<A, B>), grid, dim3(256), 0, h->ctx->stream, V, M, ev, h->g, l1, l2, Praw, part);  \
+        XH_LAUNCH_CHECK();                                                                                                 \
+    } while (0)
+    ZK_DISPATCH(l1, l2, ASA_LAUNCH);
+#undef ASA_LAUNCH
     return XH_OK;
 }
 
-// m <= capacity rows already in h->h_ev: upload, project, filter, cost, download; one stream wait
+// m <= capacity rows already in h->ev: upload, project, filter, cost, download; one stream wait
 int asa_eval(xh_asa *h, int m)
 {
     xh_ctx *ctx = h->ctx;
-    const auto t1 = std::chrono::steady_clock::now();
-    XH_HIP(hipMemcpyAsync(h->d_ev.p, h->h_ev, sizeof(double) * kRow * m, hipMemcpyHostToDevice, ctx->stream));
+    const auto t1 = XhRowEval::now();
+    XH_TRY(h->ev.upload(m));
     bool seen[VDS_MAX_L2 + 1] = {};
-    for (int r = 0; r < m; ++r) seen[(int)h->h_ev[(size_t)kRow * r + kRowL2]] = true;
+    for (int r = 0; r < m; ++r) seen[(int)h->ev.row(r)[kRowL2]] = true;
     for (int l2 = 0; l2 <= VDS_MAX_L2; ++l2)
         if (seen[l2]) XH_TRY(asa_launch_project(h, m, l2));
     const size_t total = (size_t)h->g.DD * m;
     const unsigned g = (unsigned)((total + 255) / 256);
     xh_cd *F = (xh_cd *)h->d_F.p;
-    XH_LAUNCH256(ctx, k_asa_to_complex, g, (const double *)h->d_Praw.p, F, total);
+    XH_LAUNCH256(ctx, xh_k_to_complex64<double>, g, (const double *)h->d_Praw.p, F, total);
     XH_TRY(xh_fft2d64(ctx, h->fft, F, m, false));
-    XH_LAUNCH256(ctx, k_asa_filter, g, F, total, h->D, h->prm.sampling / h->prm.max_resolution, 0.02, (const double *)h->d_ev.p, 1.0 / h->prm.sampling,
-                 (int)h->prm.phase_flipped);
+    XH_LAUNCH256(ctx, xh_k_lowpass_ctf<XH_FACTOR_CTF>, g, F, total, h->D, h->prm.sampling / h->prm.max_resolution, 0.02, h->ev.dev_rows(), kRow, kRowCtf,
+                 1.0 / h->prm.sampling, (int)h->prm.phase_flipped);
     XH_TRY(xh_fft2d64(ctx, h->fft, F, m, true));
-    XH_LAUNCH256(ctx, k_asa_cost, m, (const double *)h->d_ev.p, (const double *)h->d_If.p, (const xh_cd *)F, (const int *)h->d_mask2.p,
-                 (const double *)h->d_partials.p, h->g.tiles, (double *)h->d_P.p, (double *)h->d_Ifp.p, (double *)h->d_out.p, h->D, (double)h->nmask);
-    XH_HIP(hipMemcpyAsync(h->h_out, h->d_out.p, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, ctx->stream));
-    XH_HIP(hipStreamSynchronize(ctx->stream));
-    h->last_rows = m;
-    h->t_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    ++h->steps;
-    h->rows += m;
+    XH_LAUNCH256(ctx, k_asa_cost, m, h->ev.dev_rows(), (const double *)h->d_If.p, (const xh_cd *)F, (const int *)h->d_mask2.p,
+                 (const double *)h->d_partials.p, h->g.tiles, (double *)h->d_P.p, (double *)h->d_Ifp.p, (double *)h->ev.d_res.p, h->D, (double)h->nmask);
+    XH_TRY(h->ev.download(m));
+    h->ev.count(m, t1);      // every evaluation counts, a single cost call's too: xh_asa_stats reports the last cost or refine
     return XH_OK;
 }
 
-// tranformImageSph's return value (L256-257) from device row r's sums
-double asa_row_cost(const xh_asa *h, int r)
+// tranformImageSph's return value (L256-257) from a row's sums s = sumVd, modg, count, corr
+double asa_row_cost(const xh_asa *h, const double *s)
 {
-    const double *s = h->h_out + 4 * (size_t)r;
     if (!(s[2] > 0)) return kBarrier;      // count = 0: the reference takes sqrt(0 / 0)
     return -s[3] + h->prm.lambda * (std::sqrt(s[1] / s[2]) + std::fabs(h->sumV - s[0]) / h->sumV);
 }
@@ -367,33 +281,19 @@ double asa_row_cost(const xh_asa *h, int r)
 // m rows (any m): costs, and (nullable) each row's deformation sqrt(modg / count), 0 for a row that never reached the device
 int asa_cost_rows(xh_asa *h, int m, const int32_t *particle, const double *vars, double *cost, double *deformation)
 {
-    int r = 0;
-    std::vector<int> dest((size_t)h->capacity);
-    while (r < m) {
-        int k = 0;
-        for (; r < m && k < h->capacity; ++r) {
-            const double *x = vars + (size_t)h->nvars * r;
-            if (deformation) deformation[r] = 0.0;
-            if (asa_out_of_bounds(h, x)) { cost[r] = kBarrier; continue; }      // no device work (L275-278)
-            asa_fill_row(h, particle[r], x, h->h_ev + (size_t)kRow * k);
-            dest[k++] = r;
-        }
-        if (k == 0) continue;
-        XH_TRY(asa_eval(h, k));
-        for (int j = 0; j < k; ++j) {
-            cost[dest[j]] = asa_row_cost(h, j);
-            const double *s = h->h_out + 4 * (size_t)j;
-            if (deformation && s[2] > 0) deformation[dest[j]] = std::sqrt(s[1] / s[2]);
-        }
-    }
-    return XH_OK;
+    return h->ev.cost_rows(
+        m, [&](int r) { return asa_out_of_bounds(h, vars + (size_t)h->nvars * r); },      // no device work (L275-278)
+        [&](int r, double *row) { asa_fill_row(h, particle[r], vars + (size_t)h->nvars * r, row); return XH_OK; }, [&](int k) { return asa_eval(h, k); },
+        [&](int r, const double *s) {
+            cost[r] = s ? asa_row_cost(h, s) : kBarrier;
+            if (deformation) deformation[r] = s && s[2] > 0 ? std::sqrt(s[1] / s[2]) : 0.0;
+        });
 }
 
 // the compact vector of a stage's search -> all the variables (the frozen ones keep the stage's starting values)
 void asa_expand(const xh_asa *h, int part, const double *xc, double *x)
 {
-    std::memcpy(x, &h->cur[(size_t)part * h->nvars], sizeof(double) * h->nvars);
-    for (size_t k = 0; k < h->active.size(); ++k) x[h->active[k]] = xc[k];
+    xh_lockstep_expand(h->active, &h->cur[(size_t)part * h->nvars], h->nvars, xc, x);
 }
 
 int32_t asa_pre(int32_t problem, const double *xc, double *cost, void *user)
@@ -413,10 +313,10 @@ int32_t asa_batch(int32_t m, const int32_t *problem, const double *xc, double *c
     std::vector<double> x((size_t)h->nvars);
     for (int r = 0; r < m; ++r) {
         asa_expand(h, problem[r], xc + (size_t)r * nact, x.data());
-        asa_fill_row(h, problem[r], x.data(), h->h_ev + (size_t)kRow * r);
+        asa_fill_row(h, problem[r], x.data(), h->ev.row(r));
     }
     XH_TRY(asa_eval(h, m));
-    for (int r = 0; r < m; ++r) cost[r] = asa_row_cost(h, r);
+    for (int r = 0; r < m; ++r) cost[r] = asa_row_cost(h, h->ev.res(r));
     return 0;
 }
 
@@ -455,7 +355,7 @@ void xh_asa_defaults(xh_asa_params *p)
 int xh_asa_stage_active(int32_t L1, int32_t L2, int32_t stage, int32_t flags, int32_t *out, int32_t *n)
 {
     XH_CHECK(out && n, XH_ERR_ARG, "xh_asa_stage_active: null argument");
-    XH_TRY(asa_check_degrees("xh_asa_stage_active", L1, L2));
+    XH_TRY(zk_check_degrees("xh_asa_stage_active", L1, L2));
     XH_CHECK(stage >= 0 && stage <= L2, XH_ERR_ARG, "xh_asa_stage_active: stage %d outside 0 .. %d", stage, L2);
     XH_CHECK((flags & ~7) == 0, XH_ERR_ARG, "xh_asa_stage_active: unknown flags %d", flags);
     std::vector<int> a;
@@ -470,14 +370,14 @@ int xh_asa_create(xh_ctx *ctx, const float *d_vol, int32_t D, const int32_t *h_m
     XH_CHECK(ctx && d_vol && prm && out && D >= 4 && capacity >= 1, XH_ERR_ARG, "xh_asa_create: bad argument");
     XH_CHECK(D <= 1024, XH_ERR_UNSUPPORTED, "xh_asa_create: sizes above 1024 are not supported (%d)", D);
     XH_CHECK(capacity <= 65535, XH_ERR_ARG, "xh_asa_create: capacity %d exceeds 65535 evaluations per step", capacity);
-    XH_TRY(asa_check_degrees("xh_asa_create", prm->l1, prm->l2));
+    XH_TRY(zk_check_degrees("xh_asa_create", prm->l1, prm->l2));
     XH_CHECK(prm->sampling > 0 && prm->max_resolution > 0, XH_ERR_ARG, "xh_asa_create: sampling %g / max_resolution %g must be positive", prm->sampling,
              prm->max_resolution);
     XH_CHECK(std::isfinite(prm->lambda) && std::isfinite(prm->RDef) && std::isfinite(prm->Rmax), XH_ERR_ARG, "xh_asa_create: lambda %g, RDef %g, Rmax %g",
              prm->lambda, prm->RDef, prm->Rmax);
     XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_asa> h(new xh_asa);
-    h->ctx = ctx; h->prm = *prm; h->D = D; h->capacity = capacity; h->L1 = prm->l1; h->L2 = prm->l2;
+    h->ctx = ctx; h->prm = *prm; h->D = D; h->L1 = prm->l1; h->L2 = prm->l2;
     h->vecSize = vds_num_terms(h->L1, h->L2);
     h->nvars = 3 * h->vecSize + 8;
     h->RDef = prm->RDef < 0 ? (double)(D / 2) : prm->RDef;      // preProcess L135-136
@@ -499,12 +399,7 @@ int xh_asa_create(xh_ctx *ctx, const float *d_vol, int32_t D, const int32_t *h_m
     XH_TRY(xh_buf_upload(ctx, h->d_vol, vd.data(), sizeof(double) * N));
     XH_TRY(xh_buf_upload(ctx, h->d_mask3, mask3.data(), sizeof(int32_t) * N));
     // mask2D: BINARY_CIRCULAR_MASK, INNER_MASK, R1 = Rmax (L166-168)
-    std::vector<int32_t> mask2(DD);
-    XH_TRY(xh_halves_circular_mask(1, D, D, -h->Rmax, 0, 0, 0, mask2.data()));
-    if (h->Rmax == 0) for (auto &v : mask2) v = 0;
-    for (int32_t v : mask2) h->nmask += v;
-    XH_CHECK(h->nmask > 0, XH_ERR_ARG, "xh_asa_create: the mask of radius %g is empty", h->Rmax);
-    XH_TRY(xh_buf_upload(ctx, h->d_mask2, mask2.data(), sizeof(int32_t) * DD));
+    XH_TRY(xh_circular_mask2d(ctx, "xh_asa_create", D, h->Rmax, h->d_mask2, &h->nmask));
     AsaGeom &g = h->g;
     g.Z = g.Y = g.X = D; g.D = D; g.DD = (int)DD; g.tiles = (int)((DD + 255) / 256);
     g.RDef2 = h->RDef * h->RDef; g.iRDef = 1.0 / h->RDef;
@@ -512,15 +407,12 @@ int xh_asa_create(xh_ctx *ctx, const float *d_vol, int32_t D, const int32_t *h_m
     const int B = (int)std::min(2048.0, std::ceil(h->RDef)) - 1;
     g.kmin = std::max(-(D / 2), -B); g.kmax = std::min(D - 1 - D / 2, B);
     XH_TRY(xh_fft2d64_create(ctx, D, D, h->fft, "xh_asa_create"));
-    XH_TRY(xh_buf_alloc(ctx, h->d_ev, sizeof(double) * kRow * capacity));
+    XH_TRY(h->ev.create(ctx, capacity, kRow, 4));
     XH_TRY(xh_buf_alloc(ctx, h->d_Praw, sizeof(double) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_F, sizeof(xh_cd) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_P, sizeof(double) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_Ifp, sizeof(double) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_partials, sizeof(double) * 3 * g.tiles * capacity));
-    XH_TRY(xh_buf_alloc(ctx, h->d_out, sizeof(double) * 4 * capacity));
-    XH_HIP(hipHostMalloc((void **)&h->h_ev, sizeof(double) * kRow * capacity, hipHostMallocDefault));
-    XH_HIP(hipHostMalloc((void **)&h->h_out, sizeof(double) * 4 * capacity, hipHostMallocDefault));
     *out = h.release();
     return XH_OK;
 }
@@ -566,31 +458,14 @@ static int asa_load(xh_asa *h, const float *h_images, int32_t n, int32_t ydim, i
     }
     // Ifiltered = the low pass of I (processImage L332-333), resident as doubles
     XH_TRY(xh_buf_alloc(ctx, h->d_If, sizeof(double) * DD * n));
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)256 << 20) / (DD * sizeof(xh_cd))));
-    XhBuf d_img, d_F;
-    XH_TRY(xh_buf_alloc(ctx, d_img, sizeof(float) * DD * chunk));
-    XH_TRY(xh_buf_alloc(ctx, d_F, sizeof(xh_cd) * DD * chunk));
-    xh_cd *F = (xh_cd *)d_F.p;
-    const double w1 = h->prm.sampling / h->prm.max_resolution;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        const size_t total = DD * m;
-        const unsigned g = (unsigned)((total + 255) / 256);
-        XH_HIP(hipMemcpyAsync(d_img.p, h_images + DD * i0, sizeof(float) * total, hipMemcpyHostToDevice, ctx->stream));
-        XH_LAUNCH256(ctx, xh_k_to_complex64<float>, g, (const float *)d_img.p, F, total);
-        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, false));
-        XH_LAUNCH256(ctx, k_asa_filter, g, F, total, D, w1, 0.02, (const double *)nullptr, 1.0 / h->prm.sampling, 0);
-        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, true));
-        XH_LAUNCH256(ctx, xh_k_real64<double>, g, (const xh_cd *)F, (double *)h->d_If.p + DD * i0, total);
-        XH_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return XH_OK;
+    return xh_lowpass_images(ctx, h->fft, h_images, n, D, h->prm.sampling / h->prm.max_resolution, 1.0 / h->prm.sampling, nullptr, 0, 0,
+                             (double *)h->d_If.p);
 }
 
 int xh_asa_load(xh_asa *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_asa_row *rows)
 {
     XH_CHECK(h && h_images && rows && n >= 1, XH_ERR_ARG, "xh_asa_load: bad argument");
-    h->last_rows = 0;       // the images of the last evaluation belong to the particles that are being replaced
+    h->ev.last_rows = 0;    // the images of the last evaluation belong to the particles that are being replaced
     const int rc = asa_load(h, h_images, n, ydim, xdim, rows);
     if (rc != XH_OK) h->parts.clear();      // a load that fails leaves no particles, not half-filled ones
     return rc;
@@ -602,17 +477,17 @@ int xh_asa_cost(xh_asa *h, int32_t m, const int32_t *h_particle, const double *h
     XH_HIP(hipSetDevice(h->ctx->device));
     const int np = (int)h->parts.size();
     for (int r = 0; r < m; ++r) XH_CHECK(h_particle[r] >= 0 && h_particle[r] < np, XH_ERR_ARG, "xh_asa_cost: row %d names particle %d of %d", r, h_particle[r], np);
-    const auto t0 = std::chrono::steady_clock::now();
-    h->t_device = 0; h->steps = 0; h->rows = 0;
+    const auto t0 = XhRowEval::now();
+    h->ev.reset();
     XH_TRY(asa_cost_rows(h, m, h_particle, h_vars, h_cost, nullptr));
-    h->t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    h->ev.t_total = XhRowEval::since(t0);
     return XH_OK;
 }
 
 int xh_asa_last(xh_asa *h, int32_t row, double *d_P_raw, double *d_P, double *d_Ifilteredp, double *h_sums)
 {
     XH_CHECK(h, XH_ERR_ARG, "xh_asa_last: null handle");
-    XH_CHECK(row >= 0 && row < h->last_rows, XH_ERR_STATE, "xh_asa_last: row %d of the %d the last evaluation held", row, h->last_rows);
+    XH_CHECK(row >= 0 && row < h->ev.last_rows, XH_ERR_STATE, "xh_asa_last: row %d of the %d the last evaluation held", row, h->ev.last_rows);
     XH_HIP(hipSetDevice(h->ctx->device));
     const size_t bytes = sizeof(double) * h->D * h->D;
     hipStream_t st = h->ctx->stream;
@@ -621,7 +496,7 @@ int xh_asa_last(xh_asa *h, int32_t row, double *d_P_raw, double *d_P, double *d_
     if (d_Ifilteredp) XH_HIP(hipMemcpyAsync(d_Ifilteredp, (const char *)h->d_Ifp.p + bytes * row, bytes, hipMemcpyDeviceToDevice, st));
     XH_HIP(hipStreamSynchronize(st));
     if (h_sums)
-        for (int k = 0; k < 4; ++k) h_sums[k] = h->h_out[4 * (size_t)row + k];
+        for (int k = 0; k < 4; ++k) h_sums[k] = h->ev.res(row)[k];
     return XH_OK;
 }
 
@@ -633,11 +508,11 @@ int xh_asa_refine(xh_asa *h, double *h_vars, double *h_cost, int32_t *h_enabled,
     const int flags = asa_flags(h->prm);
     XH_CHECK(flags != 0, XH_ERR_ARG, "xh_asa_refine: no --optimize* flag is set, there is nothing to search");
     XH_HIP(hipSetDevice(h->ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = XhRowEval::now();
     const int np = (int)h->parts.size(), nv = h->nvars;
     h->cur.assign((size_t)np * nv, 0.0);      // p.initZeros (L297)
     for (int i = 0; i < np; ++i) { h_enabled[i] = 1; h_iter[i] = 0; h_evals[i] = 0; h_cost[i] = 0; }
-    h->t_device = 0; h->steps = 0; h->rows = 0;
+    h->ev.reset();
     for (int stage = 1; stage <= h->L2; ++stage) {      // L335-415
         asa_stage(h->L1, h->vecSize, stage, flags, h->active);
         const int nact = (int)h->active.size();
@@ -646,7 +521,7 @@ int xh_asa_refine(xh_asa *h, double *h_vars, double *h_cost, int32_t *h_enabled,
         std::vector<int64_t> ev((size_t)np, 0);
         for (int q = 0; q < np; ++q)
             for (int k = 0; k < nact; ++k) p[(size_t)q * nact + k] = h->cur[(size_t)q * nv + h->active[k]];
-        XH_TRY(xh_powell_lockstep(np, n.data(), nact, p.data(), steps.data(), 0.01, h->capacity, asa_batch, asa_pre, h, fret.data(), it.data(), ev.data()));
+        XH_TRY(xh_powell_lockstep(np, n.data(), nact, p.data(), steps.data(), 0.01, h->ev.capacity, asa_batch, asa_pre, h, fret.data(), it.data(), ev.data()));
         for (int q = 0; q < np; ++q) {
             double *x = &h->cur[(size_t)q * nv];
             if (fret[q] > 0) {      // L369-373: disabled, p.initZeros(); the next stage still runs, from zero
@@ -665,14 +540,14 @@ int xh_asa_refine(xh_asa *h, double *h_vars, double *h_cost, int32_t *h_enabled,
     std::vector<double> c((size_t)np);
     for (int i = 0; i < np; ++i) idx[i] = i;
     XH_TRY(asa_cost_rows(h, np, idx.data(), h_vars, c.data(), h_deformation));
-    h->t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    h->ev.t_total = XhRowEval::since(t0);
     return XH_OK;
 }
 
 int xh_asa_stats(const xh_asa *h, double *h_stats)
 {
     XH_CHECK(h && h_stats, XH_ERR_ARG, "xh_asa_stats: null argument");
-    h_stats[0] = (double)h->steps; h_stats[1] = (double)h->rows; h_stats[2] = h->t_device; h_stats[3] = h->t_total;
+    h->ev.stats(h_stats);
     return XH_OK;
 }
 

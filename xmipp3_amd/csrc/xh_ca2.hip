@@ -10,12 +10,16 @@
 //   one copy behind one stream wait.
 //
 //   load  : particles -> fp64, 2-D FFT (xh_plan.h line transforms), raised-cosine low pass w1 = Ts/maxResol, raised_w = 0.02
-//           (fourier_filter.cpp:423-432, 710-716), inverse -> Ifiltered, resident as doubles
+//           (fourier_filter.cpp:423-432, 710-716) times, where the particle has a CTF, the envelope image of generateEnvelope
+//           (ctf.h:1271-1290) that processImage multiplies into the spectrum (L447-460), inverse -> Ifiltered, resident as doubles:
+//           xh_lowpass_images and xh_k_lowpass_ctf<XH_FACTOR_ENVELOPE> of xh_image2d.h, shared with xh_asa.hip
 //   cost  : (1) central slices of the projector's coefficient cubes at each row's own Euler matrix, (2) inverse along y, (3) c2r rows
 //           -> P as doubles that never leave the device: these three are the projector's own kernels (xh_fp.hip, shared, not copied);
 //           (4) k_ca2_cost, one workgroup per evaluation: every masked pixel takes Ifiltered at the inverse of A (LINEAR, DONT_WRAP,
 //           outside 0), accumulates the sums of the cost, and the workgroup reduces them in a fixed order (strided partial sums, LDS
 //           tree; no floating-point atomics), so a row's cost does not depend on what shares its batch.
+//           Its correlation index is d_masked_correlation of xh_image2d.h.
+// The row buffers, the chunked cost loop and the counters behind xh_ca2_stats are XhRowEval of xh_lockstep.h, shared with xh_asa.hip.
 // All arithmetic is fp64, like the reference and xh_fp.hip.
 #include "xh_common.h"
 #include "xh_fft.h"
@@ -24,7 +28,7 @@
 #include "xh_ctf.h"
 #include "xh_bspline.h"
 #include "xh_image2d.h"
-#include <chrono>
+#include "xh_lockstep.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -33,36 +37,6 @@ namespace {
 // doubles per evaluation row on the device: E[9], Ainv[6], a, b, particle, identity, CTF mode (0 none, 1 the particle's resident image,
 // 2 computed from the CtfSide that follows), CtfSide[18], pad
 const int kEv = 40, kEvCtf = 19, kEvSide = 20;
-static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evaluation row as 18 doubles");
-const double kBarrier = 1e38;   // continuous2cost's cost of a vector out of bounds
-
-// FourierFilter LOWPASS / RAISED_COSINE (fourier_filter.cpp:423-432) on the full spectrum, the 1/D^2 of the inverse folded in; where the
-// image has a CTF (rows: one evaluation-style row per image, nullable) also the envelope image of generateEnvelope (ctf.h:1271-1290)
-// that processImage multiplies into the spectrum (L447-460). Both filters are real and even, so one pass over the full spectrum of the
-// real image is the reference's two passes over the half spectrum; the envelope is taken at the half-spectrum index of (i, j).
-__global__ void k_ca2_lowpass(xh_cd *__restrict__ F, size_t total, int D, double w1, double raised_w, const double *__restrict__ rows, double iTs)
-{
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    const int j = idx % D, i = (idx / D) % D;
-    const double fy = d_digfreq(i, D), fx = d_digfreq(j, D);
-    const double absw = sqrt(fx * fx + fy * fy);
-    double m = d_lowpass_raised_cosine(absw, w1, raised_w);
-    m /= (double)D * (double)D;
-    if (rows) {
-        const double *q = rows + (size_t)kEv * (idx / ((size_t)D * D));
-        if (q[kEvCtf] != 0.0) {
-            CtfSide s;
-            double *sp = reinterpret_cast<double *>(&s);
-            for (int k = 0; k < 18; ++k) sp[k] = q[kEvSide + k];
-            int ih = i, jh = j;
-            if (jh > D / 2) { jh = D - jh; ih = (D - ih) % D; }
-            m *= d_ctf_envelope(s, d_digfreq(jh, D) * iTs, d_digfreq(ih, D) * iTs);
-        }
-    }
-    xh_cd v = F[idx];
-    F[idx] = xh_cd{v.x * m, v.y * m};
-}
 
 // updateCTFImage (L225-247) for the rows of one evaluation: generateCTF with K = 1 on the half spectrum [D][D/2+1] (the part the projector
 // reads), |.| when the particles were phase flipped. Mode 1 copies the image the particle keeps for its input defocus (the same function
@@ -78,9 +52,7 @@ k_ca2_ctf_rows(const double *__restrict__ ev, const double *__restrict__ ctfPart
     double v = 1.0;
     if (mode == 1) v = ctfPart[(size_t)q[17] * per + t];
     else if (mode == 2) {
-        CtfSide s;
-        double *sp = reinterpret_cast<double *>(&s);
-        for (int k = 0; k < 18; ++k) sp[k] = q[kEvSide + k];
+        D_CTF_SIDE_FROM_ROW(s, q + kEvSide)
         const int i = t / xh, j = t - i * xh;
         v = d_ctf_at(s, d_digfreq(j, D) * iTs, d_digfreq(i, D) * iTs, true);
         if (phaseFlipped) v = fabs(v);
@@ -124,25 +96,13 @@ k_ca2_cost(const double *__restrict__ ev, const double *__restrict__ Ifiltered, 
         Ie[n] = val;
         Ee[n] = err;
     }
-    s0 = xh_block_sum(s0, red);
     if (l1) {
+        s0 = xh_block_sum(s0, red);
         if (tid == 0) cost[e] = s0 * (1.0 / nmask);      // cost *= iMask2Dsum (L314)
         return;
     }
-    s1 = xh_block_sum(s1, red);
-    s2 = xh_block_sum(s2, red);
-    s3 = xh_block_sum(s3, red);
-    const double mx = s0 / nmask, my = s1 / nmask;
-    const double sx = sqrt(fabs(s2 / nmask - mx * mx)), sy = sqrt(fabs(s3 / nmask - my * my));
-    if (fabs(sx) < kAcc || fabs(sy) < kAcc) {      // uniform over the workgroup: every thread holds the same sums
-        if (tid == 0) cost[e] = -0.0;
-        return;
-    }
-    double r = 0;
-    for (int n = tid; n < DD; n += 256)
-        if (mask[n]) r += (Ie[n] - mx) * (Pe[n] - my);      // Ie[n] was written by this thread
-    r = xh_block_sum(r, red);
-    if (tid == 0) cost[e] = -(r / ((sx * sy) * nmask));
+    const double corr = d_masked_correlation(s0, s1, s2, s3, mask, Ie, Pe, DD, nmask, red);
+    if (tid == 0) cost[e] = -corr;
 }
 
 // the final transform of processImage (L599-612): applyGeometry(BSPLINE3, ., A, IS_NOT_INV, DONT_WRAP) from the B-spline coefficients
@@ -190,28 +150,22 @@ bool inv3(const double *A, double *B)
 struct xh_ca2 {
     xh_ctx *ctx = nullptr;
     xh_ca2_params prm;
-    int D = 0, capacity = 0, nmask = 0, l1 = 0;
+    int D = 0, nmask = 0, l1 = 0;
     xh_fp *fp = nullptr;
-    XhBuf d_mask, d_If, d_ev, d_P, d_Ifp, d_E, d_cost;
+    XhRowEval ev;                                   // rows of kEv doubles up, one cost per row down
+    XhBuf d_mask, d_If, d_P, d_Ifp, d_E;
     XhBuf d_ctfRow, d_ctfPart;                      // [capacity] and [particles] CTF images [D][D/2+1]; allocated when a particle has a CTF
     bool anyCTF = false;
     XhFft2d64 fft;                                  // the load's transforms
-    double *h_ev = nullptr, *h_cost = nullptr;      // pinned
     std::vector<Particle> parts;
     std::vector<int> active;                        // the searched variables' indices into the 13
-    int last_rows = 0;
-    // refine's bookkeeping
-    std::vector<int> prob2part;
-    double t_device = 0, t_total = 0;
-    int64_t steps = 0, rows = 0;
+    std::vector<int> prob2part;                     // refine's problems: the particles that are not skipped
     ~xh_ca2()
     {
         if (!ctx) return;
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
         if (fp) xh_fp_destroy(fp);
-        if (h_ev) (void)hipHostFree(h_ev);
-        if (h_cost) (void)hipHostFree(h_cost);
     }
 };
 
@@ -288,35 +242,31 @@ int ca2_fill_row(const xh_ca2 *h, int part, const double *x, double *row)
     return XH_OK;
 }
 
-// m <= capacity rows already in h->h_ev: upload, project, cost, download; one stream wait
+// m <= capacity rows already in h->ev: upload, project, cost, download; one stream wait
 int ca2_eval(xh_ca2 *h, int m)
 {
     xh_ctx *ctx = h->ctx;
-    XH_HIP(hipMemcpyAsync(h->d_ev.p, h->h_ev, sizeof(double) * kEv * m, hipMemcpyHostToDevice, ctx->stream));
+    const double *d_ev = h->ev.dev_rows();
+    XH_TRY(h->ev.upload(m));
     // the Euler matrix is the first 9 of a row's kEv doubles
     const size_t per = (size_t)h->D * (h->D / 2 + 1);
     if (h->anyCTF) {
-        hipLaunchKernelGGL(k_ca2_ctf_rows, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream, (const double *)h->d_ev.p,
+        hipLaunchKernelGGL(k_ca2_ctf_rows, dim3((unsigned)((per + 255) / 256), m), dim3(256), 0, ctx->stream, d_ev,
                            (const double *)h->d_ctfPart.p, (double *)h->d_ctfRow.p, h->D, 1.0 / h->prm.sampling, h->prm.phase_flipped);
         XH_LAUNCH_CHECK();
     }
-    XH_TRY(xh_fp_project_f64(h->fp, (const double *)h->d_ev.p, kEv, m, h->anyCTF ? (const double *)h->d_ctfRow.p : nullptr, per, (double *)h->d_P.p));
-    hipLaunchKernelGGL(k_ca2_cost, dim3(m), dim3(256), 0, ctx->stream, (const double *)h->d_ev.p, (const double *)h->d_If.p,
-                       (const double *)h->d_P.p, (const int *)h->d_mask.p, (double *)h->d_Ifp.p, (double *)h->d_E.p, (double *)h->d_cost.p,
+    XH_TRY(xh_fp_project_f64(h->fp, d_ev, kEv, m, h->anyCTF ? (const double *)h->d_ctfRow.p : nullptr, per, (double *)h->d_P.p));
+    hipLaunchKernelGGL(k_ca2_cost, dim3(m), dim3(256), 0, ctx->stream, d_ev, (const double *)h->d_If.p,
+                       (const double *)h->d_P.p, (const int *)h->d_mask.p, (double *)h->d_Ifp.p, (double *)h->d_E.p, (double *)h->ev.d_res.p,
                        h->D, h->l1, (double)h->nmask);
     XH_LAUNCH_CHECK();
-    XH_HIP(hipMemcpyAsync(h->h_cost, h->d_cost.p, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    XH_HIP(hipStreamSynchronize(ctx->stream));
-    h->last_rows = m;
-    return XH_OK;
+    return h->ev.download(m);
 }
 
 // the compact vector of a search -> the reference's 13 (frozen variables keep their starting values)
 void ca2_expand(const xh_ca2 *h, int part, const double *xc, double *x13)
 {
-    const Particle &pt = h->parts[part];
-    for (int k = 0; k < 13; ++k) x13[k] = pt.p0[k];
-    for (size_t k = 0; k < h->active.size(); ++k) x13[h->active[k]] = xc[k];
+    xh_lockstep_expand(h->active, h->parts[part].p0, 13, xc, x13);
 }
 
 int32_t ca2_pre(int32_t problem, const double *xc, double *cost, void *user)
@@ -338,14 +288,12 @@ int32_t ca2_batch(int32_t m, const int32_t *problem, const double *xc, double *c
         const int part = h->prob2part[problem[r]];
         double x[13];
         ca2_expand(h, part, xc + (size_t)r * nact, x);
-        XH_TRY(ca2_fill_row(h, part, x, h->h_ev + (size_t)kEv * r));
+        XH_TRY(ca2_fill_row(h, part, x, h->ev.row(r)));
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    const auto t1 = XhRowEval::now();
     XH_TRY(ca2_eval(h, m));
-    for (int r = 0; r < m; ++r) cost[r] = h->h_cost[r];
-    h->t_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    ++h->steps;
-    h->rows += m;
+    for (int r = 0; r < m; ++r) cost[r] = *h->ev.res(r);
+    h->ev.count(m, t1);
     return 0;
 }
 }  // namespace
@@ -369,30 +317,22 @@ int xh_ca2_create(xh_ctx *ctx, const float *d_vol, int32_t D, const xh_ca2_param
              prm->sampling, prm->max_resolution);
     XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_ca2> h(new xh_ca2);
-    h->ctx = ctx; h->prm = *prm; h->D = D; h->capacity = capacity;
+    h->ctx = ctx; h->prm = *prm; h->D = D;
     h->l1 = prm->optimize_gray ? 1 : 0;         // contCost (L218-221)
     // the projector of preProcess (L203-207): the coefficient cubes are xh_fp_create's own
     XH_TRY(xh_fp_create(ctx, d_vol, D, prm->padding, prm->sampling / prm->max_resolution, 3, &h->fp));
     XH_TRY(xh_fft2d64_create(ctx, D, D, h->fft, "xh_ca2_create"));
     // BINARY_CIRCULAR_MASK, INNER_MASK, R1 = Rmax about the Xmipp origin (L179-187)
     const double R = prm->Rmax < 0 ? (double)(D / 2) : prm->Rmax;
-    std::vector<int32_t> mask((size_t)D * D);
-    XH_TRY(xh_halves_circular_mask(1, D, D, -R, 0, 0, 0, mask.data()));
-    if (R == 0) for (auto &v : mask) v = 0;
-    for (int32_t v : mask) h->nmask += v;
-    XH_CHECK(h->nmask > 0, XH_ERR_ARG, "xh_ca2_create: the mask of radius %g is empty", R);
-    XH_TRY(xh_buf_upload(ctx, h->d_mask, mask.data(), sizeof(int32_t) * mask.size()));
+    XH_TRY(xh_circular_mask2d(ctx, "xh_ca2_create", D, R, h->d_mask, &h->nmask));
     const size_t DD = (size_t)D * D;
-    XH_TRY(xh_buf_alloc(ctx, h->d_ev, sizeof(double) * kEv * capacity));
+    XH_TRY(h->ev.create(ctx, capacity, kEv, 1));
     XH_TRY(xh_buf_alloc(ctx, h->d_P, sizeof(double) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_Ifp, sizeof(double) * DD * capacity));
     XH_TRY(xh_buf_alloc(ctx, h->d_E, sizeof(double) * DD * capacity));
-    XH_TRY(xh_buf_alloc(ctx, h->d_cost, sizeof(double) * capacity));
-    XH_HIP(hipHostMalloc((void **)&h->h_ev, sizeof(double) * kEv * capacity, hipHostMallocDefault));
-    XH_HIP(hipHostMalloc((void **)&h->h_cost, sizeof(double) * capacity, hipHostMallocDefault));
     // size the projector's scratch now, so that no evaluation allocates
-    XH_HIP(hipMemsetAsync(h->d_ev.p, 0, h->d_ev.bytes, ctx->stream));
-    XH_TRY(xh_fp_project_f64(h->fp, (const double *)h->d_ev.p, kEv, capacity, nullptr, 0, (double *)h->d_P.p));
+    XH_HIP(hipMemsetAsync(h->ev.d_rows.p, 0, h->ev.d_rows.bytes, ctx->stream));
+    XH_TRY(xh_fp_project_f64(h->fp, h->ev.dev_rows(), kEv, capacity, nullptr, 0, (double *)h->d_P.p));
     XH_HIP(hipStreamSynchronize(ctx->stream));
     // the searched variables (L498-521): only those whose step is non-zero
     if (prm->optimize_gray) { h->active.push_back(0); h->active.push_back(1); }
@@ -412,17 +352,6 @@ int xh_ca2_destroy(xh_ca2 *h)
 {
     delete h;
     return XH_OK;
-}
-
-static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_ca2_row *rows);
-
-int xh_ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_ca2_row *rows)
-{
-    XH_CHECK(h && h_images && rows && n >= 1, XH_ERR_ARG, "xh_ca2_load: bad argument");
-    h->last_rows = 0;       // the images of the last evaluation belong to the particles that are being replaced
-    const int rc = ca2_load(h, h_images, n, ydim, xdim, rows);
-    if (rc != XH_OK) h->parts.clear();      // a load that fails leaves no particles, not half-filled ones
-    return rc;
 }
 
 static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_ca2_row *rows)
@@ -453,7 +382,7 @@ static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, i
     const double iTs = 1.0 / h->prm.sampling;
     XH_TRY(xh_buf_alloc(ctx, h->d_If, sizeof(double) * DD * n));
     XH_TRY(xh_buf_alloc(ctx, h->d_ctfPart, h->anyCTF ? sizeof(double) * per * n : 0));
-    XH_TRY(xh_buf_alloc(ctx, h->d_ctfRow, h->anyCTF ? sizeof(double) * per * h->capacity : 0));
+    XH_TRY(xh_buf_alloc(ctx, h->d_ctfRow, h->anyCTF ? sizeof(double) * per * h->ev.capacity : 0));
     XhBuf d_rows;
     if (h->anyCTF) {
         // per particle an evaluation-style row holding its CtfSide: first the CTF image at the input defocus (what an evaluation that
@@ -478,24 +407,8 @@ static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, i
             }
         }
     }
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)256 << 20) / (DD * sizeof(xh_cd))));
-    XhBuf d_img, d_F;
-    XH_TRY(xh_buf_alloc(ctx, d_img, sizeof(float) * DD * chunk));
-    XH_TRY(xh_buf_alloc(ctx, d_F, sizeof(xh_cd) * DD * chunk));
-    xh_cd *F = (xh_cd *)d_F.p;
-    const double w1 = h->prm.sampling / h->prm.max_resolution;
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = std::min(chunk, n - i0);
-        const size_t total = DD * m;
-        const unsigned g = (unsigned)((total + 255) / 256);
-        XH_HIP(hipMemcpyAsync(d_img.p, h_images + DD * i0, sizeof(float) * total, hipMemcpyHostToDevice, ctx->stream));
-        XH_LAUNCH256(ctx, xh_k_to_complex64<float>, g, (const float *)d_img.p, F, total);
-        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, false));
-        XH_LAUNCH256(ctx, k_ca2_lowpass, g, F, total, D, w1, 0.02, h->anyCTF ? (const double *)d_rows.p + (size_t)kEv * i0 : (const double *)nullptr, iTs);
-        XH_TRY(xh_fft2d64(ctx, h->fft, F, m, true));
-        XH_LAUNCH256(ctx, xh_k_real64<double>, g, (const xh_cd *)F, (double *)h->d_If.p + DD * i0, total);
-        XH_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    XH_TRY(xh_lowpass_images(ctx, h->fft, h_images, n, D, h->prm.sampling / h->prm.max_resolution, iTs, (const double *)d_rows.p, kEv, kEvCtf,
+                             (double *)h->d_If.p));
     for (int i = 0; i < n; ++i) {
         Particle &pt = h->parts[i];
         const xh_ca2_row &r = rows[i];
@@ -516,33 +429,32 @@ static int ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, i
     return XH_OK;
 }
 
+int xh_ca2_load(xh_ca2 *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_ca2_row *rows)
+{
+    XH_CHECK(h && h_images && rows && n >= 1, XH_ERR_ARG, "xh_ca2_load: bad argument");
+    h->ev.last_rows = 0;    // the images of the last evaluation belong to the particles that are being replaced
+    const int rc = ca2_load(h, h_images, n, ydim, xdim, rows);
+    if (rc != XH_OK) h->parts.clear();      // a load that fails leaves no particles, not half-filled ones
+    return rc;
+}
+
 int xh_ca2_cost(xh_ca2 *h, int32_t m, const int32_t *h_particle, const double *h_vars, double *h_cost)
 {
     XH_CHECK(h && h_particle && h_vars && h_cost && m >= 0, XH_ERR_ARG, "xh_ca2_cost: bad argument");
     XH_HIP(hipSetDevice(h->ctx->device));
     const int np = (int)h->parts.size();
     for (int r = 0; r < m; ++r) XH_CHECK(h_particle[r] >= 0 && h_particle[r] < np, XH_ERR_ARG, "xh_ca2_cost: row %d names particle %d of %d", r, h_particle[r], np);
-    std::vector<int> dest((size_t)h->capacity);
-    int r = 0;
-    while (r < m) {
-        int k = 0;
-        for (; r < m && k < h->capacity; ++r) {
-            const double *x = h_vars + 13 * (size_t)r;
-            if (ca2_out_of_bounds(h, h->parts[h_particle[r]], x)) { h_cost[r] = kBarrier; continue; }    // no device work (L364-375)
-            XH_TRY(ca2_fill_row(h, h_particle[r], x, h->h_ev + (size_t)kEv * k));
-            dest[k++] = r;
-        }
-        if (k == 0) continue;
-        XH_TRY(ca2_eval(h, k));
-        for (int j = 0; j < k; ++j) h_cost[dest[j]] = h->h_cost[j];
-    }
-    return XH_OK;
+    // a row out of bounds costs the barrier and takes no device work (L364-375); xh_ca2_stats goes on reporting the last refine
+    return h->ev.cost_rows(
+        m, [&](int r) { return ca2_out_of_bounds(h, h->parts[h_particle[r]], h_vars + 13 * (size_t)r); },
+        [&](int r, double *row) { return ca2_fill_row(h, h_particle[r], h_vars + 13 * (size_t)r, row); }, [&](int k) { return ca2_eval(h, k); },
+        [&](int r, const double *res) { h_cost[r] = res ? *res : kBarrier; });
 }
 
 int xh_ca2_last_images(xh_ca2 *h, int32_t row, double *d_P, double *d_E, double *d_Ifilteredp)
 {
     XH_CHECK(h, XH_ERR_ARG, "xh_ca2_last_images: null handle");
-    XH_CHECK(row >= 0 && row < h->last_rows, XH_ERR_STATE, "xh_ca2_last_images: row %d of the %d the last evaluation held", row, h->last_rows);
+    XH_CHECK(row >= 0 && row < h->ev.last_rows, XH_ERR_STATE, "xh_ca2_last_images: row %d of the %d the last evaluation held", row, h->ev.last_rows);
     XH_HIP(hipSetDevice(h->ctx->device));
     const size_t bytes = sizeof(double) * h->D * h->D;
     hipStream_t st = h->ctx->stream;
@@ -556,7 +468,7 @@ int xh_ca2_last_images(xh_ca2 *h, int32_t row, double *d_P, double *d_E, double 
 int xh_ca2_measures(xh_ca2 *h, int32_t row, double *h_out)
 {
     XH_CHECK(h && h_out, XH_ERR_ARG, "xh_ca2_measures: null argument");
-    XH_CHECK(row >= 0 && row < h->last_rows, XH_ERR_STATE, "xh_ca2_measures: row %d of the %d the last evaluation held", row, h->last_rows);
+    XH_CHECK(row >= 0 && row < h->ev.last_rows, XH_ERR_STATE, "xh_ca2_measures: row %d of the %d the last evaluation held", row, h->ev.last_rows);
     XH_HIP(hipSetDevice(h->ctx->device));
     const int D = h->D;
     const size_t N = (size_t)D * D;
@@ -689,7 +601,7 @@ int xh_ca2_refine(xh_ca2 *h, double *h_vars, double *h_cost, int32_t *h_iter, in
     XH_CHECK(!h->parts.empty(), XH_ERR_STATE, "xh_ca2_refine: no particles loaded");
     XH_CHECK(!h->active.empty(), XH_ERR_ARG, "xh_ca2_refine: no --optimize* flag is set, there is nothing to search");
     XH_HIP(hipSetDevice(h->ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = XhRowEval::now();
     const int np = (int)h->parts.size(), nact = (int)h->active.size();
     h->prob2part.clear();
     for (int i = 0; i < np; ++i) {
@@ -705,8 +617,8 @@ int xh_ca2_refine(xh_ca2 *h, double *h_vars, double *h_cost, int32_t *h_iter, in
     std::vector<int64_t> ev((size_t)nprob, 0);
     for (int q = 0; q < nprob; ++q)
         for (int k = 0; k < nact; ++k) p[(size_t)q * nact + k] = h->parts[h->prob2part[q]].p0[h->active[k]];
-    h->t_device = 0; h->steps = 0; h->rows = 0;
-    XH_TRY(xh_powell_lockstep(nprob, nv.data(), nact, p.data(), steps.data(), 0.01, h->capacity, ca2_batch, ca2_pre, h, fret.data(), it.data(),
+    h->ev.reset();
+    XH_TRY(xh_powell_lockstep(nprob, nv.data(), nact, p.data(), steps.data(), 0.01, h->ev.capacity, ca2_batch, ca2_pre, h, fret.data(), it.data(),
                               ev.data()));
     for (int q = 0; q < nprob; ++q) {
         const int i = h->prob2part[q];
@@ -719,14 +631,14 @@ int xh_ca2_refine(xh_ca2 *h, double *h_vars, double *h_cost, int32_t *h_iter, in
         const Particle &pt = h->parts[i];
         if (pt.hasCTF && (pt.ctf.DeltafU + h_vars[13 * (size_t)i + 10] < 0 || pt.ctf.DeltafU + h_vars[13 * (size_t)i + 11] < 0)) h_enabled[i] = -1;
     }
-    h->t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    h->ev.t_total = XhRowEval::since(t0);
     return XH_OK;
 }
 
 int xh_ca2_stats(const xh_ca2 *h, double *h_stats)
 {
     XH_CHECK(h && h_stats, XH_ERR_ARG, "xh_ca2_stats: null argument");
-    h_stats[0] = (double)h->steps; h_stats[1] = (double)h->rows; h_stats[2] = h->t_device; h_stats[3] = h->t_total;
+    h->ev.stats(h_stats);
     return XH_OK;
 }
 

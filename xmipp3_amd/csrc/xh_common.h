@@ -85,6 +85,25 @@ int xh_buf_upload(xh_ctx *ctx, XhBuf &b, const void *src, size_t bytes);
 // *grown tells whether it did
 int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes, bool *grown = nullptr);
 
+// Page-locked host memory with one owner, XhBuf's twin: move-only, allocated through the context, freed by its destructor. A handle's
+// destructor body synchronises the stream; its members, this one among them, go after the body, so no copy is still using the memory.
+struct XhPinned {
+    void *p = nullptr;
+    XhPinned() = default;
+    XhPinned(const XhPinned &) = delete;
+    XhPinned &operator=(const XhPinned &) = delete;
+    XhPinned(XhPinned &&o) noexcept : p(o.p) { o.p = nullptr; }
+    XhPinned &operator=(XhPinned &&o) noexcept
+    {
+        std::swap(p, o.p);      // o's destructor frees what this held
+        return *this;
+    }
+    ~XhPinned() { if (p) (void)hipHostFree(p); }
+    double *f64() const { return (double *)p; }
+};
+// frees b, then allocates `bytes` of page-locked memory
+int xh_pinned_alloc(xh_ctx *ctx, XhPinned &b, size_t bytes);
+
 // a grow-only device buffer that lives with a 2-D transform plan (frame-after-frame callers: dose filter, binning)
 int xh_fft2d_user_scratch(xh_fft2d *f, size_t bytes, void **p);
 int xh_fft2d_rows_of_real_pairs(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int Y, float *d_work, int *n1, int *n2);

@@ -1,6 +1,7 @@
-// xh_ctf.h -- the CTF value on the device, shared by the CTF pre-steps (xh_ctfops.hip) and the continuous assignment (xh_ca2.hip):
-// produceSideInfo on the host, then getValuePureAt / getValuePureWithoutDampingAt / the damping envelope at a continuous frequency,
-// in double precision with the reference's formulas (data/ctf.h:424-500, 1002-1029; data/ctf.cpp:645-679, 1392-1402).
+// xh_ctf.h -- the CTF value on the device, shared by the CTF pre-steps (xh_ctfops.hip), the continuous assignment (xh_ca2.hip) and the
+// Zernike3D alignment (xh_asa.hip): produceSideInfo on the host, its 18 doubles read back out of an evaluation row on the device, then
+// getValuePureAt / getValuePureWithoutDampingAt / the damping envelope at a continuous frequency, in double precision with the
+// reference's formulas (data/ctf.h:424-500, 1002-1029; data/ctf.cpp:645-679, 1392-1402).
 #ifndef XH_CTF_H
 #define XH_CTF_H
 #include <cmath>
@@ -36,6 +37,17 @@ static inline CtfSide side_info(const xh_ctf_params &c)
     d.VPP_radius = c.VPP_radius;
     return d;
 }
+
+// A CtfSide rides in an evaluation row as 18 doubles (the host memcpy's it there); q points at the first. A macro, not a function: the
+// copy loop has to stay in the kernel's own body. In a callee it is unrolled before it is inlined, d_ctf_at then sees the fields as
+// values from the first pass on, and the compiler contracts its sums of two products the other way round (last-bit changes of the CTF).
+static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evaluation row as 18 doubles");
+#define D_CTF_SIDE_FROM_ROW(s, q)                              \
+    CtfSide s;                                                 \
+    {                                                          \
+        double *sp_ = reinterpret_cast<double *>(&s);          \
+        for (int k_ = 0; k_ < 18; ++k_) sp_[k_] = (q)[k_];     \
+    }
 
 __device__ __forceinline__ double d_bessj0(double x)
 {

@@ -58,6 +58,11 @@ int xh_buf_reserve(xh_ctx *ctx, XhBuf &b, size_t bytes, bool *grown)
     if (grown) *grown = true;
     return XH_OK;
 }
+int xh_pinned_alloc(xh_ctx *ctx, XhPinned &b, size_t bytes)
+{
+    b = XhPinned();
+    return xh_host_alloc(ctx, bytes, &b.p);
+}
 
 extern "C" {
 

@@ -245,7 +245,7 @@ struct xh_rf {
     // copy).  Entering a half waits for ITS event -- recorded a whole half ago -- so the host never waits for the copy it has just
     // queued.  (One area with one event made the host wait, at every wrap, until the stream had reached the previous call's copies:
     // with 200-byte CTF records a 4096-projection call wraps every second step, 9 ms of idle device per step in `--mode grid`.)
-    unsigned char *h_stage = nullptr;
+    XhPinned h_stage;
     size_t stageCap = 0, stageUsed = 0;          // capacity of ONE half, bytes used in the current half
     int stageHalf = 0;
     hipEvent_t stageEv[2] = {nullptr, nullptr};
@@ -270,7 +270,6 @@ struct xh_rf {
     {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
-        if (h_stage) (void)hipHostFree(h_stage);
         for (hipEvent_t e : stageEv)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : evPool) (void)hipEventDestroy(e);
@@ -291,10 +290,8 @@ static int stage_upload(xh_rf *rf, void *d_dst, const void *h_src, size_t bytes)
             // a larger area: every copy out of the old one must have left it
             for (int h = 0; h < 2; ++h)
                 if (rf->stagePending[h]) { XH_HIP(hipEventSynchronize(rf->stageEv[h])); rf->stagePending[h] = false; }
-            if (rf->h_stage) XH_HIP(hipHostFree(rf->h_stage));
-            rf->h_stage = nullptr;
             rf->stageCap = std::max(need, std::max<size_t>(2 * rf->stageCap, (size_t)8 << 20));
-            XH_HIP(hipHostMalloc((void **)&rf->h_stage, 2 * rf->stageCap, hipHostMallocDefault));
+            XH_TRY(xh_pinned_alloc(ctx, rf->h_stage, 2 * rf->stageCap));
             rf->stageHalf = 0;
         } else {
             rf->stageHalf ^= 1;
@@ -302,7 +299,7 @@ static int stage_upload(xh_rf *rf, void *d_dst, const void *h_src, size_t bytes)
         }
         rf->stageUsed = 0;
     }
-    unsigned char *slot = rf->h_stage + (size_t)rf->stageHalf * rf->stageCap + rf->stageUsed;
+    unsigned char *slot = (unsigned char *)rf->h_stage.p + (size_t)rf->stageHalf * rf->stageCap + rf->stageUsed;
     memcpy(slot, h_src, bytes);
     XH_HIP(hipMemcpyAsync(d_dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
     rf->stageUsed += need;

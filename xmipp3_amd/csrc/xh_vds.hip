@@ -164,60 +164,26 @@ struct xh_vds {
     XhBuf B[2];                    // scratch volumes: raw and VO, LS and LR
     XhBuf C, partials, result;
     XhBuf G;                       // the field [3][N] of apply and strain, allocated at the first use
-    double *pinned = nullptr;      // 3 doubles, page-locked
+    XhPinned pinned;               // 3 doubles
     double sumVI = 0, outDiff2 = 0, outSumVD = 0;
     int64_t evals = 0;
     int costRc = XH_OK;
     ~xh_vds()
     {
         if (ctx) (void)hipSetDevice(ctx->device);
-        if (pinned) (void)hipHostFree(pinned);
     }
 };
 
 namespace {
-
-int vds_check_degrees(const char *who, int L1, int L2)
-{
-    XH_CHECK(L1 >= 0 && L2 >= 0, XH_ERR_ARG, "%s: negative degree (l1 %d, l2 %d)", who, L1, L2);
-    XH_CHECK(L1 <= VDS_MAX_L1 && L2 <= VDS_MAX_L2, XH_ERR_UNSUPPORTED, "%s: degrees l1 = %d, l2 = %d are not supported (l1 <= %d, l2 <= %d)", who, L1, L2,
-             VDS_MAX_L1, VDS_MAX_L2);
-    return XH_OK;
-}
-
-// x [3 vecSize] (cx, then cy, then cz) -> the kernel's layout; *l2eff = the smallest h whose terms hold every non-zero coefficient
-void vds_pack(const xh_vds *h, const double *x, VdsCoef &C, int *l2eff)
-{
-    int last = -1;
-    for (int i = 0; i < 3 * VDS_MAXT; ++i) C.c[i] = 0.0;
-    for (int idx = 0; idx < h->vecSize; ++idx)
-        for (int d = 0; d < 3; ++d) {
-            const double v = x[(size_t)d * h->vecSize + idx];
-            C.c[3 * idx + d] = v;
-            if (v != 0.0) last = idx;      // a NaN counts as non-zero
-        }
-    int e = 0;
-    while (e < h->L2 && vds_num_terms(h->L1, e) <= last) ++e;
-    *l2eff = e;
-}
 
 int vds_launch_cost(xh_vds *h, const VdsCoef &C, int l2)
 {
     const double *I = (const double *)h->I.p, *R = (const double *)h->R.p;
     double *part = (double *)h->partials.p;
     const int l1 = h->L1;
-#define VDS_CASE(A, B)                                                                  \
-    if (l1 == A && l2 == B) {                                                           \
-        XH_LAUNCH256(h->ctx, (k_vds_cost<A, B>), h->grid, I, R, h->g, C, l1, l2, part); \
-        return XH_OK;                                                                   \
-    }
-    VDS_CASE(1, 0) VDS_CASE(1, 1)
-    VDS_CASE(2, 0) VDS_CASE(2, 1) VDS_CASE(2, 2)
-    VDS_CASE(3, 0) VDS_CASE(3, 1) VDS_CASE(3, 2) VDS_CASE(3, 3)
-    VDS_CASE(4, 0) VDS_CASE(4, 1) VDS_CASE(4, 2) VDS_CASE(4, 3) VDS_CASE(4, 4)
-    VDS_CASE(5, 0) VDS_CASE(5, 1) VDS_CASE(5, 2) VDS_CASE(5, 3) VDS_CASE(5, 4)
-#undef VDS_CASE
-    XH_LAUNCH256(h->ctx, (k_vds_cost<-1, -1>), h->grid, I, R, h->g, C, l1, l2, part);
+#define VDS_LAUNCH(A, B) XH_LAUNCH256(h->ctx, (k_vds_cost<A, B>), h->grid, I, R, h->g, C, l1, l2, part)
+    ZK_DISPATCH(l1, l2, VDS_LAUNCH);
+#undef VDS_LAUNCH
     return XH_OK;
 }
 
@@ -289,7 +255,7 @@ extern "C" {
 int xh_vds_num_terms(int32_t L1, int32_t L2, int32_t *n)
 {
     XH_CHECK(n, XH_ERR_ARG, "xh_vds_num_terms: null argument");
-    XH_TRY(vds_check_degrees("xh_vds_num_terms", L1, L2));
+    XH_TRY(zk_check_degrees("xh_vds_num_terms", L1, L2));
     *n = vds_num_terms(L1, L2);
     return XH_OK;
 }
@@ -297,7 +263,7 @@ int xh_vds_num_terms(int32_t L1, int32_t L2, int32_t *n)
 int xh_vds_terms(int32_t L1, int32_t L2, int32_t *out)
 {
     XH_CHECK(out, XH_ERR_ARG, "xh_vds_terms: null argument");
-    XH_TRY(vds_check_degrees("xh_vds_terms", L1, L2));
+    XH_TRY(zk_check_degrees("xh_vds_terms", L1, L2));
     int idx = 0;
     for (int h = 0; h <= L2; ++h)
         for (int l = h; l <= L1; l += 2)
@@ -308,7 +274,7 @@ int xh_vds_terms(int32_t L1, int32_t L2, int32_t *out)
 int xh_vds_zsh(int32_t l1, int32_t n, int32_t l2, int32_t m, double xr, double yr, double zr, double r, double *out)
 {
     XH_CHECK(out, XH_ERR_ARG, "xh_vds_zsh: null argument");
-    XH_TRY(vds_check_degrees("xh_vds_zsh", l1, l2));
+    XH_TRY(zk_check_degrees("xh_vds_zsh", l1, l2));
     XH_CHECK(n >= 0 && n <= l1 && (l1 - n) % 2 == 0 && m >= -l2 && m <= l2, XH_ERR_ARG, "xh_vds_zsh: (l1 %d, n %d, l2 %d, m %d) is no basis term", l1, n, l2, m);
     *out = vds_radial(l1, n, r, r * r) * vds_harmonic(l2, m, xr, yr, zr, xr * xr, yr * yr, zr * zr);
     return XH_OK;
@@ -347,7 +313,7 @@ int xh_vds_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t L1, int3
     XH_CHECK(ctx && out, XH_ERR_ARG, "xh_vds_create: null argument");
     XH_CHECK(Z >= 1 && Y >= 1 && X >= 2, XH_ERR_ARG, "xh_vds_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_vds_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
-    XH_TRY(vds_check_degrees("xh_vds_create", L1, L2));
+    XH_TRY(zk_check_degrees("xh_vds_create", L1, L2));
     if (Rmax < 0) Rmax = (double)(X / 2);
     XH_CHECK(std::isfinite(Rmax) && Rmax > 0 && std::isfinite(lambda), XH_ERR_ARG, "xh_vds_create: Rmax %g, lambda %g", Rmax, lambda);
     XH_HIP(hipSetDevice(ctx->device));
@@ -374,7 +340,7 @@ int xh_vds_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t L1, int3
     XH_TRY(xh_buf_alloc(ctx, h->C, sizeof(xh_cd) * NF));
     XH_TRY(xh_buf_alloc(ctx, h->partials, sizeof(double) * 3 * h->grid));
     XH_TRY(xh_buf_alloc(ctx, h->result, sizeof(double) * 3));
-    XH_HIP(hipHostMalloc((void **)&h->pinned, sizeof(double) * 3, hipHostMallocDefault));
+    XH_TRY(xh_pinned_alloc(ctx, h->pinned, sizeof(double) * 3));
     *out = h.release();
     return XH_OK;
 }
@@ -446,12 +412,12 @@ int xh_vds_cost(xh_vds *h, const double *h_x, double *h_out)
     XH_CHECK(h->g.npairs > 0, XH_ERR_STATE, "xh_vds_cost: no pairs loaded");
     XH_HIP(hipSetDevice(h->ctx->device));
     VdsCoef C;
-    int l2;
-    vds_pack(h, h_x, C, &l2);
+    const int l2 = zk_pack(h->L1, h->L2, h->vecSize, h_x, C.c);
     XH_TRY(vds_launch_cost(h, C, l2));
-    XH_TRY(xh_reduce_finish(h->ctx, (const double *)h->partials.p, (int)h->grid, 3, (double *)h->result.p, h->pinned));
+    XH_TRY(xh_reduce_finish(h->ctx, (const double *)h->partials.p, (int)h->grid, 3, (double *)h->result.p, h->pinned.f64()));
     const double count = (double)h->g.npairs * (double)h->g.N;
-    const double diff2 = h->pinned[0] + h->outDiff2, sumVD = h->pinned[1] + h->outSumVD, modg = h->pinned[2];
+    const double *sums = h->pinned.f64();
+    const double diff2 = sums[0] + h->outDiff2, sumVD = sums[1] + h->outSumVD, modg = sums[2];
     const double deformation = std::sqrt(modg / count);
     h_out[0] = std::sqrt(diff2 / count) + h->lambda * (deformation + std::fabs(h->sumVI - sumVD) / h->sumVI);
     h_out[1] = diff2;
@@ -489,8 +455,7 @@ int xh_vds_apply(xh_vds *h, const double *h_raw, const double *h_x, double *h_VO
     hipStream_t st = h->ctx->stream;
     const size_t vb = h->B[0].bytes;
     VdsCoef C;
-    int l2;
-    vds_pack(h, h_x, C, &l2);
+    zk_pack(h->L1, h->L2, h->vecSize, h_x, C.c);
     XH_HIP(hipMemcpyAsync(h->B[0].p, h_raw, vb, hipMemcpyHostToDevice, st));
     double *G = nullptr;
     if (h_G) {

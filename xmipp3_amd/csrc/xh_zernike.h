@@ -1,6 +1,8 @@
 // xh_zernike.h -- the Zernike3D basis and the trilinear sampler shared by xmipp_volume_deform_sph (xh_vds.hip) and
 // xmipp_angular_sph_alignment (xh_asa.hip): the radial polynomials, the solid harmonics, the term count, the displacement of one voxel
-// and interpolatedElement3D. The mathematics and the reference's S_4^0 exception are described at the head of xh_vds.hip.
+// and interpolatedElement3D; and the host side both programs need before a launch: the degree check, the packing of a coefficient vector
+// with its effective l2, and the table of compiled (L1, L2) pairs. The mathematics and the reference's S_4^0 exception are described at
+// the head of xh_vds.hip.
 #ifndef XH_ZERNIKE_H
 #define XH_ZERNIKE_H
 #include "xh_common.h"
@@ -83,6 +85,47 @@ struct ZkDims { int Z, Y, X; };
 // term idx at c[3 idx + (0, 1, 2)] = (cx, cy, cz)
 struct VdsCoef { double c[3 * VDS_MAXT]; };
 
+// ---------------------------------------------------------------- the host side
+inline int zk_check_degrees(const char *who, int L1, int L2)
+{
+    XH_CHECK(L1 >= 0 && L2 >= 0, XH_ERR_ARG, "%s: negative degree (l1 %d, l2 %d)", who, L1, L2);
+    XH_CHECK(L1 <= VDS_MAX_L1 && L2 <= VDS_MAX_L2, XH_ERR_UNSUPPORTED, "%s: degrees l1 = %d, l2 = %d are not supported (l1 <= %d, l2 <= %d)", who, L1, L2,
+             VDS_MAX_L1, VDS_MAX_L2);
+    return XH_OK;
+}
+
+// x [3 vecSize] (cx, then cy, then cz) -> VdsCoef's layout at c [3 VDS_MAXT]. Returns the effective l2: the smallest h whose terms hold
+// every non-zero coefficient, which names the instantiation that evaluates these coefficients.
+inline int zk_pack(int L1, int L2, int vecSize, const double *x, double *c)
+{
+    int last = -1;
+    for (int i = 0; i < 3 * VDS_MAXT; ++i) c[i] = 0.0;
+    for (int idx = 0; idx < vecSize; ++idx)
+        for (int d = 0; d < 3; ++d) {
+            const double v = x[(size_t)d * vecSize + idx];
+            c[3 * idx + d] = v;
+            if (v != 0.0) last = idx;      // a NaN counts as non-zero
+        }
+    int e = 0;
+    while (e < L2 && vds_num_terms(L1, e) <= last) ++e;
+    return e;
+}
+
+// The compiled (L1, L2) pairs, written once: runs STMT(A, B) with the constants A == l1 and B == l2, STMT(-1, -1) (the run-time degrees)
+// for any other pair.
+#define ZK_CASE_(A, B, STMT) if (zk_l1_ == A && zk_l2_ == B) { STMT(A, B); } else
+#define ZK_DISPATCH(l1, l2, STMT)                                                                       \
+    do {                                                                                                \
+        const int zk_l1_ = (l1), zk_l2_ = (l2);                                                         \
+        ZK_CASE_(1, 0, STMT) ZK_CASE_(1, 1, STMT)                                                       \
+        ZK_CASE_(2, 0, STMT) ZK_CASE_(2, 1, STMT) ZK_CASE_(2, 2, STMT)                                  \
+        ZK_CASE_(3, 0, STMT) ZK_CASE_(3, 1, STMT) ZK_CASE_(3, 2, STMT) ZK_CASE_(3, 3, STMT)             \
+        ZK_CASE_(4, 0, STMT) ZK_CASE_(4, 1, STMT) ZK_CASE_(4, 2, STMT) ZK_CASE_(4, 3, STMT) ZK_CASE_(4, 4, STMT) \
+        ZK_CASE_(5, 0, STMT) ZK_CASE_(5, 1, STMT) ZK_CASE_(5, 2, STMT) ZK_CASE_(5, 3, STMT) ZK_CASE_(5, 4, STMT) \
+        { STMT(-1, -1); }                                                                               \
+    } while (0)
+
+// ---------------------------------------------------------------- the device side
 // The displacement of one voxel. L1 >= 0: compile-time degrees, everything unrolls; L1 < 0: the run-time degrees (l1, l2).
 // At r = 0 only the l2 = 0 terms count.
 template <int L1, int L2>

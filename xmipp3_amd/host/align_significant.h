@@ -101,14 +101,7 @@ public:
     // load (:94-190) and validate (:192-204): disabled rows dropped, odd sizes cropped to even ones
     void load(Data &h, bool isRef)
     {
-        MetaDataVec all;
-        all.read(h.fn);
-        const size_t origN = all.size();
-        h.md.labels = all.labels;
-        h.md.rows.clear();
-        const int en = all.col("enabled");
-        for (auto &r : all.rows)
-            if (en < 0 || atol(r[en].c_str()) > 0) h.md.rows.push_back(r);
+        const size_t origN = readEnabledRows(h.fn, h.md);
         h.n = h.md.size();
         if (isRef && origN != h.n) std::cerr << h.fn << " contains disabled images. This is not expected and might lead to wrong result\n";
         if (!h.md.containsLabel("image")) REPORT_ERROR(ERR_MD_BADLABEL, h.fn + ": does not have MDL_IMAGE label");

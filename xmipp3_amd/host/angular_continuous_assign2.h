@@ -101,12 +101,8 @@ public:
 
     void run() override
     {
-        MetaDataVec all, md;
-        all.read(fn_in);
-        md.labels = all.labels;
-        const int en = all.col("enabled");
-        for (auto &r : all.rows)
-            if (en < 0 || atol(r[en].c_str()) > 0) md.rows.push_back(r);
+        MetaDataVec md;
+        readEnabledRows(fn_in, md);
         const size_t n = md.size();
         if (n == 0) REPORT_ERROR(ERR_MD_NOOBJ, "no enabled images in " + fn_in);
         if (!md.containsLabel("image")) REPORT_ERROR(ERR_MD_BADLABEL, fn_in + ": does not have the image label");
@@ -161,10 +157,7 @@ public:
                 std::copy(one.begin(), one.end(), imgs.begin() + k * per);
                 // processImage :421-445
                 xh_ca2_row &r = rows[k];
-                std::memset(&r, 0, sizeof(r));
-                r.rot = md.getDouble("angleRot", id, 0); r.tilt = md.getDouble("angleTilt", id, 0); r.psi = md.getDouble("anglePsi", id, 0);
-                r.shift_x = md.getDouble("shiftX", id, 0); r.shift_y = md.getDouble("shiftY", id, 0);
-                r.flip = md.getDouble("flip", id, 0) != 0;
+                readPoseRow(md, id, hasCTF, r);
                 r.gray_a = 1; r.gray_b = 0;
                 if (md.containsLabel("continuousScaleX")) {
                     r.scale_x = md.getDouble("continuousScaleX", id, 0); r.scale_y = md.getDouble("continuousScaleY", id, 0);
@@ -173,8 +166,6 @@ public:
                     r.flip = md.getDouble("continuousFlip", id, 0) != 0;
                 }
                 if (l1 && md.containsLabel("continuousA")) { r.gray_a = md.getDouble("continuousA", id, 1); r.gray_b = md.getDouble("continuousB", id, 0); }
-                r.has_ctf = hasCTF;
-                if (hasCTF) readCtfRow(md, id, r.ctf);
             }
             xhCheck(xh_ca2_load(h, imgs.data(), (int)m, (int)D, (int)D, rows.data()));
             std::vector<double> X(13 * m), cost(m);

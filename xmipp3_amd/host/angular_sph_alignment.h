@@ -104,12 +104,8 @@ public:
 
     void run() override
     {
-        MetaDataVec all, md;
-        all.read(fn_in);
-        md.labels = all.labels;
-        const int en = all.col("enabled");
-        for (auto &r : all.rows)
-            if (en < 0 || atol(r[en].c_str()) > 0) md.rows.push_back(r);
+        MetaDataVec md;
+        readEnabledRows(fn_in, md);
         if (md.size() == 0) REPORT_ERROR(ERR_MD_NOOBJ, "no enabled images in " + fn_in);
         if (!md.containsLabel("image")) REPORT_ERROR(ERR_MD_BADLABEL, fn_in + ": does not have the image label");
         if (md.containsLabel("ctfModel") && !md.containsLabel("ctfDefocusU"))
@@ -176,14 +172,7 @@ public:
                 readImage(names[k], one, I);
                 if (I.x != D || I.y != D || I.z != 1) REPORT_ERROR(ERR_MULTIDIM_SIZE, names[k] + ": the images must have the size of the reference volume");
                 std::copy(one.begin(), one.end(), imgs.begin() + k * per);
-                // processImage :304-325
-                xh_asa_row &r = rows[k];
-                std::memset(&r, 0, sizeof(r));
-                r.rot = md.getDouble("angleRot", id, 0); r.tilt = md.getDouble("angleTilt", id, 0); r.psi = md.getDouble("anglePsi", id, 0);
-                r.shift_x = md.getDouble("shiftX", id, 0); r.shift_y = md.getDouble("shiftY", id, 0);
-                r.flip = md.getDouble("flip", id, 0) != 0;
-                r.has_ctf = hasCTF;
-                if (hasCTF) readCtfRow(md, id, r.ctf);
+                readPoseRow(md, id, hasCTF, rows[k]);      // processImage :304-325
             }
             xhCheck(xh_asa_load(h, imgs.data(), (int)m, (int)D, (int)D, rows.data()));
             std::vector<double> X((size_t)nvars * m), cost(m), deformation(m);

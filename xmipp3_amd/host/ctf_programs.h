@@ -22,6 +22,18 @@ inline void readCtfRow(const MetaDataVec &md, size_t id, xh_ctf_params &c)
     c.phase_shift = md.getDouble("ctfPhaseShift", id, 0); c.VPP_radius = md.getDouble("ctfVPPRadius", id, 0);
 }
 
+// processImage's reading of a particle's pose and CTF (angular_continuous_assign2.cpp:421-445, angular_sph_alignment.cpp:304-325) into
+// a zeroed row of a per-particle program (xh_ca2_row, xh_asa_row)
+template <class Row> inline void readPoseRow(const MetaDataVec &md, size_t id, bool hasCTF, Row &r)
+{
+    std::memset(&r, 0, sizeof(r));
+    r.rot = md.getDouble("angleRot", id, 0); r.tilt = md.getDouble("angleTilt", id, 0); r.psi = md.getDouble("anglePsi", id, 0);
+    r.shift_x = md.getDouble("shiftX", id, 0); r.shift_y = md.getDouble("shiftY", id, 0);
+    r.flip = md.getDouble("flip", id, 0) != 0;
+    r.has_ctf = hasCTF;
+    if (hasCTF) readCtfRow(md, id, r.ctf);
+}
+
 class ProgCTFPhaseFlipping : public XmippProgram {
 public:
     std::string fn_in, fn_out, fnt_ctf;

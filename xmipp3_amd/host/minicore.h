@@ -206,6 +206,19 @@ public:
     }
 };
 
+// md = the rows of fn whose `enabled` is positive (every row of a file without that column); returns the number of rows the file holds
+inline size_t readEnabledRows(const std::string &fn, MetaDataVec &md)
+{
+    MetaDataVec all;
+    all.read(fn);
+    md.labels = all.labels;
+    md.rows.clear();
+    const int en = all.col("enabled");
+    for (auto &r : all.rows)
+        if (en < 0 || atol(r[en].c_str()) > 0) md.rows.push_back(r);
+    return all.size();
+}
+
 // getBlocksInMetaDataFile (xmippCore metadata_extension): the names of the data_ blocks of a metadata file, in file order
 inline std::vector<std::string> getBlocksInMetaDataFile(const std::string &path)
 {

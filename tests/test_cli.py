@@ -93,6 +93,30 @@ def test_no_gpu_means_xmipp_error_not_fallback(bins, tmp_path):
     assert not (tmp_path / "out.xmd").exists()
 
 
+def _check_matching(out_xmd, pm, parts, dirs, ids, nbrs, thr=1):
+    """the rows the matcher wrote against oracle.PM pm on the same neighbour lists (stack positions), same visiting-order parity"""
+    n, nrefs = len(parts), len(ids)
+    labels, rows = xmipp_io.read_xmd(str(out_xmd))
+    assert labels == ["itemId", "image", "angleRot", "angleTilt", "anglePsi", "shiftX", "shiftY", "ref", "flip", "scale", "maxCC"]
+    assert len(rows) == n
+    pos = {ids[i]: i for i in range(nrefs)}
+    lists = [[pos[int(v)] for v in s.split()] for s in nbrs]
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    er, ep, ef, _ = pm.match(parts, off, np.concatenate(lists).astype(np.int32), ref_threads=thr)
+    ex, ey, ec = pm.translate(parts, er[:, 0], ep[:, 0], ef[:, 0], 6.0)
+    c = {l: i for i, l in enumerate(labels)}
+    for i, row in enumerate(rows):
+        assert int(row[c["itemId"]]) == 100 + i
+        assert int(row[c["ref"]]) == ids[er[i, 0]]
+        assert int(row[c["flip"]]) == ef[i, 0]
+        assert abs(float(row[c["anglePsi"]]) - ep[i, 0] * 360.0 / pm.N) < 1e-5
+        assert abs(float(row[c["angleRot"]]) - dirs[er[i, 0]][0]) < 1e-5 and abs(float(row[c["angleTilt"]]) - dirs[er[i, 0]][1]) < 1e-5
+        assert abs(float(row[c["shiftX"]]) - ex[i]) < 1e-3 and abs(float(row[c["shiftY"]]) - ey[i]) < 1e-3
+        assert abs(float(row[c["maxCC"]]) - ec[i]) < 1e-5
+    return labels, rows, c
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("box", [32, 40])
 def test_cli_pipeline_matches_oracle(bins, tmp_path, oracle, box):
@@ -105,26 +129,7 @@ def test_cli_pipeline_matches_oracle(bins, tmp_path, oracle, box):
     r = _run([os.path.join(bins, "xmipp_angular_projection_matching"), "-i", str(tmp_path / "exp.xmd"), "-o", str(tmp_path / "out.xmd"),
               "--ref", str(tmp_path / "ref.stk"), "--max_shift", "6", "--batch", "4", "--thr", str(thr)])
     assert r.returncode == 0, r.stderr
-    labels, rows = xmipp_io.read_xmd(str(tmp_path / "out.xmd"))
-    assert labels == ["itemId", "image", "angleRot", "angleTilt", "anglePsi", "shiftX", "shiftY", "ref", "flip", "scale", "maxCC"]
-    assert len(rows) == n
-    # oracle on the same neighbour lists (stack positions), same visiting-order parity
-    pos = {ids[i]: i for i in range(nrefs)}
-    lists = [[pos[int(v)] for v in s.split()] for s in nbrs]
-    off = np.zeros(n + 1, np.int32)
-    off[1:] = np.cumsum([len(l) for l in lists])
-    pm = oracle.PM(refs)
-    er, ep, ef, _ = pm.match(parts, off, np.concatenate(lists).astype(np.int32), ref_threads=thr)
-    ex, ey, ec = pm.translate(parts, er[:, 0], ep[:, 0], ef[:, 0], 6.0)
-    c = {l: i for i, l in enumerate(labels)}
-    for i, row in enumerate(rows):
-        assert int(row[c["itemId"]]) == 100 + i
-        assert int(row[c["ref"]]) == ids[er[i, 0]]
-        assert int(row[c["flip"]]) == ef[i, 0]
-        assert abs(float(row[c["anglePsi"]]) - ep[i, 0] * 360.0 / pm.N) < 1e-5
-        assert abs(float(row[c["angleRot"]]) - dirs[er[i, 0]][0]) < 1e-5 and abs(float(row[c["angleTilt"]]) - dirs[er[i, 0]][1]) < 1e-5
-        assert abs(float(row[c["shiftX"]]) - ex[i]) < 1e-3 and abs(float(row[c["shiftY"]]) - ey[i]) < 1e-3
-        assert abs(float(row[c["maxCC"]]) - ec[i]) < 1e-5
+    labels, rows, c = _check_matching(tmp_path / "out.xmd", oracle.PM(refs), parts, dirs, ids, nbrs, thr)
     # reconstruction from the assigned angles (shifts and flips applied by the program)
     r = _run([os.path.join(bins, "xmipp_reconstruct_fourier_accel"), "-i", str(tmp_path / "out.xmd"), "-o", str(tmp_path / "rec.vol"),
               "--batch", "5", "--sym", "c2"])
@@ -144,6 +149,31 @@ def test_cli_pipeline_matches_oracle(bins, tmp_path, oracle, box):
     rf.mirror_and_crop()
     exp = rf.finish()
     assert np.abs(got - exp).max() <= 1e-4 * np.abs(exp).max()
+
+
+@pytest.mark.gpu
+def test_cli_matcher_with_a_ctfparam_file(bins, tmp_path, oracle):
+    """--ctf <ctfparam metadata>: the gallery is filtered with the table the program builds from the file (generateCTF, APM:366-402;
+    host/ctf_model.h). The rows must be those of oracle.PM fed the table built from the oracle's own CTF value, for plain and for
+    phase-flipped data (the table's absolute value)."""
+    refs, dirs, parts, ids, nbrs = _write_dataset(tmp_path, D=32)
+    D = refs.shape[1]
+    # a round CTF (the program refuses astigmatism) with every factor of the envelope between 0.2 and 0.95 over the band
+    kw = dict(Tm=1.4, kV=300.0, DeltafU=6000.0, DeltafV=6000.0, Cs=2.7, Ca=2.0, espr=0.003, ispr=2e-12, alpha=3e-5, DeltaF=80.0, DeltaR=1.5, Q0=0.07, K=1.0)
+    names = dict(Tm="ctfSamplingRate", kV="ctfVoltage", DeltafU="ctfDefocusU", DeltafV="ctfDefocusV", Cs="ctfSphericalAberration",
+                 Ca="ctfChromaticAberration", espr="ctfEnergyLoss", ispr="ctfLensStability", alpha="ctfConvergenceCone",
+                 DeltaF="ctfLongitudinalDisplacement", DeltaR="ctfTransversalDisplacement", Q0="ctfQ0", K="ctfK")
+    xmipp_io.write_xmd(str(tmp_path / "gallery.ctfparam"), [("noname", [names[k] for k in kw], [[repr(v) for v in kw.values()]])])
+    p = oracle.ctf_params(**kw)
+    f = [(i if i <= D // 2 else i - D) / D * (1.0 / kw["Tm"]) for i in range(D)]
+    table = np.array([[oracle.lib().xo_ctf_value_pure_nok(p, fx, fy) / kw["K"] for fx in f] for fy in f])
+    assert np.isfinite(table).all() and np.abs(table).max() > 0.5 and (table < -0.1).any()
+    for flipped in (False, True):
+        out = tmp_path / f"out_{int(flipped)}.xmd"
+        r = _run([os.path.join(bins, "xmipp_angular_projection_matching"), "-i", str(tmp_path / "exp.xmd"), "-o", str(out), "--ref", str(tmp_path / "ref.stk"),
+                  "--max_shift", "6", "--batch", "4", "--ctf", str(tmp_path / "gallery.ctfparam")] + (["--phase_flipped"] if flipped else []), timeout=120)
+        assert r.returncode == 0, r.stderr
+        _check_matching(out, oracle.PM(refs, Mctf=np.abs(table) if flipped else table, paddim=D), parts, dirs, ids, nbrs)
 
 
 @pytest.mark.gpu

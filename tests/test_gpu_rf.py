@@ -104,10 +104,11 @@ def test_shift_reuses_the_matchers_coefficients(gpu):
     assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("kind", ["astigmatic", "round", "round_envelope", "astigmatic_envelope"])
+@pytest.mark.parametrize("kind", ["astigmatic", "round", "round_envelope", "astigmatic_envelope", "phase_plate", "large_focal_spread"])
 def test_ctf_arrays(gpu, oracle, kind):
     """k_rf_ctf has per-image shortcuts (no atan2 for a round CTF, no exp without envelope terms); every
-    combination must equal the general double-precision formula (ctf.h:376-501)."""
+    combination must equal the general double-precision formula (ctf.h:376-501). phase_plate: the VPP term (phase_shift as the row
+    holds it); large_focal_spread: K5 u^2 passes 8 at a quarter of the band, both branches of J0."""
     xa, ctx, torch = gpu
     D = 64
     rf = xa.RecFourier(ctx, D, min_ctf=0.01, sampling=1.5)
@@ -118,6 +119,10 @@ def test_ctf_arrays(gpu, oracle, kind):
         kw["DeltafV"] = kw["DeltafU"]
     if kind.endswith("envelope"):
         kw.update(Ca=2.0, espr=0.6, ispr=0.3, alpha=0.1, DeltaF=3.0, DeltaR=0.5)
+    if kind == "phase_plate":
+        kw.update(phase_shift=1.3, VPP_radius=0.02)
+    if kind == "large_focal_spread":
+        kw.update(DeltaF=3000.0)
     c, m = rf.ctf_arrays([ctf_params(**kw)])
     ce, me = o.ctf_arrays(oracle.ctf_params(**kw))
     c, m = c.cpu().numpy()[0], m.cpu().numpy()[0]
@@ -705,15 +710,16 @@ def test_device_volume_against_the_double_precision_program(gpu, oracle):
     assert np.corrcoef(got.ravel(), exp.ravel())[0, 1] > 0.99999
 
 
-@pytest.mark.parametrize("niter,kind", [(1, "plain"), (0, "plain"), (3, "plain"), (1, "sym_weights_ctf"), (1, "odd_box")])
+@pytest.mark.parametrize("niter,kind", [(1, "plain"), (0, "plain"), (3, "plain"), (1, "sym_weights_ctf"), (1, "odd_box"), (1, "all_terms_ctf")])
 def test_double_precision_program_on_the_device(gpu, oracle, niter, kind):
     """ProgRecFourier's own arithmetic (xh_rf2_*, the program behind xmipp_reconstruct_fourier) against its restatement
     oracle.RF2: double accumulators, image-driven scatter, wrap + conjugate, correctWeight (--iter 0, 1 and 3 with the
-    re-processing passes), symmetry, weights, CTF, a box that is not a power of two. Sums differ by their order only:
+    re-processing passes), symmetry, weights, CTF, a box that is not a power of two, a CTF with every term of the model on
+    (astigmatism, each factor of the envelope between 0.2 and 0.95 over the band, envR0/1/2, a phase plate). Sums differ by their order only:
     1e-9 of the peak (the judged bar is 1e-6)."""
     xa, ctx, torch = gpu
     from xmipp3_amd.api import ctf_params
-    D, n = (45, 24) if kind == "odd_box" else (32, 60)
+    D, n = {"odd_box": (45, 24), "all_terms_ctf": (32, 6)}.get(kind, (32, 60))
     vol = synth.phantom(D, seed=5, nblobs=12)
     rng = np.random.default_rng(6)
     ang = synth.random_angles(n, rng)
@@ -726,6 +732,12 @@ def test_double_precision_program_on_the_device(gpu, oracle, niter, kind):
         sym = np.stack([np.eye(3), np.diag([-1.0, -1.0, 1.0])])
         defoci = rng.uniform(10000.0, 30000.0, n)
         kw = dict(kV=300.0, Cs=2.7, Q0=0.07, K=1.0, azimuthal_angle=20.0)
+        dctf = [ctf_params(DeltafU=float(d), DeltafV=float(d) + 800.0, **kw) for d in defoci]
+        octf = [oracle.ctf_params(DeltafU=float(d), DeltafV=float(d) + 800.0, **kw) for d in defoci]
+    if kind == "all_terms_ctf":
+        kw = dict(kV=300.0, Cs=2.7, Q0=0.07, K=1.0, azimuthal_angle=20.0, Ca=2.0, espr=0.003, ispr=2e-12, alpha=3e-5, DeltaF=80.0, DeltaR=1.5,
+                  envR0=0.02, envR1=-0.05, envR2=0.1, phase_shift=1.3, VPP_radius=0.02)
+        defoci = rng.uniform(10000.0, 30000.0, n)
         dctf = [ctf_params(DeltafU=float(d), DeltafV=float(d) + 800.0, **kw) for d in defoci]
         octf = [oracle.ctf_params(DeltafU=float(d), DeltafV=float(d) + 800.0, **kw) for d in defoci]
     ref = oracle.RF2(D, niter_weight=niter)

@@ -222,7 +222,7 @@ void asa_fill_row(const xh_asa *h, int part, const double *x, double *row)
         c.DeltafU = pt.ctf.DeltafU + t[5];
         c.DeltafV = pt.ctf.DeltafV + t[6];
         c.azimuthal_angle = pt.ctf.azimuthal_angle + t[7];
-        const CtfSide s = side_info(c);
+        const CtfSide s = side_info(c, true);
         row[kRowCtf] = 1;
         std::memcpy(row + kRowSide, &s, sizeof(s));
     } else

@@ -193,7 +193,7 @@ CtfSide ca2_side(const xh_ca2 *h, const Particle &pt, double dU, double dV, doub
     c.DeltafU = pt.ctf.DeltafU + dU;
     c.DeltafV = (same_rule && h->prm.same_defocus) ? c.DeltafU : pt.ctf.DeltafV + dV;
     c.azimuthal_angle = pt.ctf.azimuthal_angle + dAngle;
-    return side_info(c);
+    return side_info(c, true);
 }
 
 // A of L579-598 / L385-392 with the flip, inverted; *ident when it is the identity within XMIPP_EQUAL_ACCURACY

@@ -1,39 +1,51 @@
-// xh_ctf.h -- the CTF value on the device, shared by the CTF pre-steps (xh_ctfops.hip), the continuous assignment (xh_ca2.hip) and the
-// Zernike3D alignment (xh_asa.hip): produceSideInfo on the host, its 18 doubles read back out of an evaluation row on the device, then
-// getValuePureAt / getValuePureWithoutDampingAt / the damping envelope at a continuous frequency, in double precision with the
-// reference's formulas (data/ctf.h:424-500, 1002-1029; data/ctf.cpp:645-679, 1392-1402).
+// xh_ctf.h -- the CTF model, written once for the device and the host: produceSideInfo, then getValuePureAt /
+// getValuePureWithoutDampingAt / the damping envelope at a continuous frequency, in double precision with the reference's formulas
+// (data/ctf.h:424-502, 1002-1029; data/ctf.cpp:645-679, 1392-1402). Plain C++ apart from the qualifier macro: the host programs
+// compile it with g++.
+//
+// Callers and the unit of phase_shift that each hands to side_info:
+//   xh_ctfops.hip, xh_ca2.hip, xh_asa.hip (through xh_image2d.h)   degrees, as the metadata holds it: side_info converts, like
+//                                                                  ctf_phase_flip.cpp:99 and wiener2d.cpp:149 before produceSideInfo
+//   xh_rf.hip (the gridder's CTF planes, xh_rf2's scatter),        as it is: readFromMdRow passes the column on and so do these
+//   host/ctf_model.h (the matcher's --ctf gallery filter)
 #ifndef XH_CTF_H
 #define XH_CTF_H
 #include <cmath>
-#include "xh_common.h"
+#include "../../include/xmipp_hip.h"
+
+#ifdef __HIPCC__
+#define XH_CTF_FN __host__ __device__ __forceinline__
+#else
+#define XH_CTF_FN inline
+#endif
 
 namespace {
-constexpr double kPI = 3.14159265358979323846;
+constexpr double kCtfPI = 3.14159265358979323846;
 
 struct CtfSide {
     double K1, K2, K3, K5, K6, K7, Ksin, Kcos, rad_azimuth, defocus_average, defocus_deviation;
     double DeltaR, K, envR0, envR1, envR2, phase_shift, VPP_radius;
 };
 
-// produceSideInfo, data/ctf.cpp:645-679,1392-1402; phase_shift arrives in degrees (ctf_phase_flip.cpp:99, wiener2d.cpp:149)
-static inline CtfSide side_info(const xh_ctf_params &c)
+// produceSideInfo, data/ctf.cpp:645-679,1392-1402
+static inline CtfSide side_info(const xh_ctf_params &c, bool phaseShiftInDegrees)
 {
     CtfSide d;
     const double local_Cs = c.Cs * 1e7, local_Ca = c.Ca * 1e7, local_kV = c.kV * 1e3, local_ispr = c.ispr * 1e6;
     const double lambda = 12.2643247 / std::sqrt(local_kV * (1. + 0.978466e-6 * local_kV));
-    d.K1 = kPI * lambda;
-    d.K2 = kPI / 2 * local_Cs * lambda * lambda * lambda;
-    d.K3 = std::pow(0.25 * kPI * local_Ca * lambda * (c.espr / c.kV + 2 * local_ispr), 2) / std::log(2.0);
-    d.K5 = kPI * c.DeltaF * lambda;
-    d.K6 = kPI * kPI * c.alpha * c.alpha;
+    d.K1 = kCtfPI * lambda;
+    d.K2 = kCtfPI / 2 * local_Cs * lambda * lambda * lambda;
+    d.K3 = std::pow(0.25 * kCtfPI * local_Ca * lambda * (c.espr / c.kV + 2 * local_ispr), 2) / std::log(2.0);
+    d.K5 = kCtfPI * c.DeltaF * lambda;
+    d.K6 = kCtfPI * kCtfPI * c.alpha * c.alpha;
     d.K7 = local_Cs * lambda * lambda;
     d.Ksin = std::sqrt(1 - c.Q0 * c.Q0);
     d.Kcos = c.Q0;
-    d.rad_azimuth = c.azimuthal_angle * kPI / 180.;
+    d.rad_azimuth = c.azimuthal_angle * kCtfPI / 180.;
     d.defocus_average = -(c.DeltafU + c.DeltafV) * 0.5;
     d.defocus_deviation = -(c.DeltafU - c.DeltafV) * 0.5;
     d.DeltaR = c.DeltaR; d.K = c.K; d.envR0 = c.envR0; d.envR1 = c.envR1; d.envR2 = c.envR2;
-    d.phase_shift = (c.phase_shift * kPI) / 180;
+    d.phase_shift = phaseShiftInDegrees ? (c.phase_shift * kCtfPI) / 180 : c.phase_shift;
     d.VPP_radius = c.VPP_radius;
     return d;
 }
@@ -49,7 +61,10 @@ static_assert(sizeof(CtfSide) == 18 * sizeof(double), "CtfSide rides in an evalu
         for (int k_ = 0; k_ < 18; ++k_) sp_[k_] = (q)[k_];     \
     }
 
-__device__ __forceinline__ double d_bessj0(double x)
+// J0(0) as d_bessj0 gives it: the quotient of the two leading coefficients, not 1
+constexpr double kCtfJ0At0 = 57568490574.0 / 57568490411.0;
+
+XH_CTF_FN double d_bessj0(double x)
 {
     const double ax = fabs(x);
     if (ax < 8.0) {
@@ -64,12 +79,17 @@ __device__ __forceinline__ double d_bessj0(double x)
     return sqrt(0.636619772 / ax) * (cos(xx) * a1 - z * sin(xx) * a2);
 }
 
-// getValuePureAt (damping) / getValuePureWithoutDampingAt after precomputeValues(X, Y)
-__device__ __forceinline__ double d_ctf_at(const CtfSide &s, double X, double Y, bool damping)
+// getValuePureAt (damping) / getValuePureWithoutDampingAt after precomputeValues(X, Y).
+// SHORTCUTS (the gridder's, whose CTF is uniform over a block) skips terms that a zero coefficient leaves without effect, each bit for
+// bit the general formula: x + 0 * cos(.) == x, so defocus_deviation == 0 needs no atan2 / cos; exp(-0 * finite) == 1, so K3 == 0 and
+// K6 == 0 need no exp; K5 == 0 gives J0(0).
+template <bool SHORTCUTS = false>
+XH_CTF_FN double d_ctf_at(const CtfSide &s, double X, double Y, bool damping)
 {
     const double u2 = X * X + Y * Y, u = sqrt(u2), u4 = u2 * u2;
     double deltaf;
     if (fabs(X) < 1e-6 && fabs(Y) < 1e-6) deltaf = 0;
+    else if (SHORTCUTS && s.defocus_deviation == 0) deltaf = s.defocus_average;
     else deltaf = s.defocus_average + s.defocus_deviation * cos(2 * (atan2(Y, X) - s.rad_azimuth));
     double VPP = 0;
     if (round(s.VPP_radius * 1000) != 0) VPP = -s.phase_shift * (1 - exp(-u2 / (2 * s.VPP_radius * s.VPP_radius)));
@@ -77,19 +97,19 @@ __device__ __forceinline__ double d_ctf_at(const CtfSide &s, double X, double Y,
     double sine_part, cosine_part;
     sincos(argument, &sine_part, &cosine_part);
     if (!damping) return -(s.Ksin * sine_part - s.Kcos * cosine_part);
-    const double Eespr = exp(-s.K3 * u4);
-    const double EdeltaF = d_bessj0(s.K5 * u2);
+    const double Eespr = (SHORTCUTS && s.K3 == 0) ? 1.0 : exp(-s.K3 * u4);
+    const double EdeltaF = (SHORTCUTS && s.K5 == 0) ? kCtfJ0At0 : d_bessj0(s.K5 * u2);
     const double xs = u * s.DeltaR;
-    const double EdeltaR = (xs == 0) ? 1.0 : sin(kPI * xs) / (kPI * xs);
+    const double EdeltaR = (xs == 0) ? 1.0 : sin(kCtfPI * xs) / (kCtfPI * xs);
     const double aux = s.K7 * u2 * u + deltaf * u;
-    const double Ealpha = exp(-s.K6 * aux * aux);
+    const double Ealpha = (SHORTCUTS && s.K6 == 0) ? 1.0 : exp(-s.K6 * aux * aux);
     double E = Eespr * EdeltaF * EdeltaR * Ealpha + s.envR0 + s.envR1 * u + s.envR2 * u2;
     if (E < 0) E = 0;
     return -s.K * (s.Ksin * sine_part - s.Kcos * cosine_part) * E;
 }
 
 // the damping envelope alone, E of getValueDampingAt (ctf.h:424-449) clamped at 0: generateEnvelope's -getValueDampingAt() for K = 1
-__device__ __forceinline__ double d_ctf_envelope(const CtfSide &s, double X, double Y)
+XH_CTF_FN double d_ctf_envelope(const CtfSide &s, double X, double Y)
 {
     const double u2 = X * X + Y * Y, u = sqrt(u2), u4 = u2 * u2;
     double deltaf;
@@ -98,7 +118,7 @@ __device__ __forceinline__ double d_ctf_envelope(const CtfSide &s, double X, dou
     const double Eespr = exp(-s.K3 * u4);
     const double EdeltaF = d_bessj0(s.K5 * u2);
     const double xs = u * s.DeltaR;
-    const double EdeltaR = (xs == 0) ? 1.0 : sin(kPI * xs) / (kPI * xs);
+    const double EdeltaR = (xs == 0) ? 1.0 : sin(kCtfPI * xs) / (kCtfPI * xs);
     const double aux = s.K7 * u2 * u + deltaf * u;
     const double Ealpha = exp(-s.K6 * aux * aux);
     const double E = Eespr * EdeltaF * EdeltaR * Ealpha + s.envR0 + s.envR1 * u + s.envR2 * u2;

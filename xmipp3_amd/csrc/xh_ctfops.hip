@@ -138,7 +138,7 @@ int xh_ctfop_phase_flip(xh_ctfop *h, float *d_img, const xh_ctf_params *ctf, dou
     hipLaunchKernelGGL(k_ctf_embed, dim3(nb), dim3(256), 0, ctx->stream, (const float *)d_img, h->ydim, h->xdim, w, h->ydim, h->xdim, 0, 0);
     XH_LAUNCH_CHECK();
     XH_TRY(xh_fft2d_exec(h->fft, (float *)w, 0));
-    hipLaunchKernelGGL(k_ctf_flip, dim3(nb), dim3(256), 0, ctx->stream, w, h->ydim, h->xdim, side_info(*ctf), 1.0 / sampling_rate);
+    hipLaunchKernelGGL(k_ctf_flip, dim3(nb), dim3(256), 0, ctx->stream, w, h->ydim, h->xdim, side_info(*ctf, true), 1.0 / sampling_rate);
     XH_LAUNCH_CHECK();
     XH_TRY(xh_fft2d_exec(h->fft, (float *)w, 1));
     hipLaunchKernelGGL(k_ctf_extract, dim3(nb), dim3(256), 0, ctx->stream, (const xc_cf *)w, h->ydim, h->xdim, 0, 0, d_img, h->ydim, h->xdim);
@@ -161,7 +161,7 @@ int xh_ctfop_wiener2d(xh_ctfop *h, float *d_imgs, int32_t n, const xh_ctf_params
     xc_cf *w = (xc_cf *)h->work.p;
     for (int k = 0; k < n; ++k) {
         float *img = d_imgs + (size_t)k * itot;
-        const CtfSide s = side_info(ctfs[k]);
+        const CtfSide s = side_info(ctfs[k], true);
         XH_HIP(hipMemsetAsync(h->sum.p, 0, sizeof(double), ctx->stream));
         hipLaunchKernelGGL(k_ctf_wiener_ctf, dim3(nbp), dim3(256), 0, ctx->stream, (double *)h->ctfIm.p, h->pY, h->pX, s, 1.0 / sampling_rate,
                            correct_envelope, phase_flipped, (double *)h->sum.p);

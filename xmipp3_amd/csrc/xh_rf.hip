@@ -22,6 +22,7 @@
 #include "xh_fftreg.h"
 #include "xh_plan.h"
 #include "xh_bspline.h"
+#include "xh_ctf.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -543,9 +544,7 @@ k_rf_shift_band(const float *__restrict__ coefs, const float *__restrict__ imgs,
 }
 
 // ---- CTF planes (RFA:548-592; data/ctf.h:452-502,1002-1029; data/ctf.cpp:645-679,1392-1402)
-struct XhCtfDev {
-    double K1, K2, K3, K5, K6, K7, Ksin, Kcos, rad_azimuth, defocus_average, defocus_deviation;
-    double DeltaR, K, envR0, envR1, envR2, phase_shift, VPP_radius;
+struct XhCtfDev : CtfSide {                                  // side_info(c, false): phase_shift as the metadata row holds it
     // d_ctf_pixel_fast (filled by ctf_params_upload; fast == 0: the general formula only):
     //   Ksin sin(a) - Kcos cos(a) = amp sin(a - phi);  E = E0 + envR2 u^2;  cos / sin of twice the azimuth
     double amp = 0, phi = 0, E0 = 0, c2az = 0, s2az = 0;
@@ -631,20 +630,6 @@ k_rf_colsA(const float *__restrict__ imgs, xh_cf *__restrict__ T, const xh_cf *_
     }
 }
 
-__device__ double d_bessj0(double x)
-{
-    double ax = fabs(x);
-    if (ax < 8.0) {
-        double y = x * x;
-        double a1 = 57568490574.0 + y * (-13362590354.0 + y * (651619640.7 + y * (-11214424.18 + y * (77392.33017 + y * (-184.9052456)))));
-        double a2 = 57568490411.0 + y * (1029532985.0 + y * (9494680.718 + y * (59272.64853 + y * (267.8532712 + y * 1.0))));
-        return a1 / a2;
-    }
-    double z = 8.0 / ax, y = z * z, xx = ax - 0.785398164;
-    double a1 = 1.0 + y * (-0.1098628627e-2 + y * (0.2734510407e-4 + y * (-0.2073370639e-5 + y * 0.2093887211e-6)));
-    double a2 = -0.1562499995e-1 + y * (0.1430488765e-3 + y * (-0.6911147651e-5 + y * (0.7621095161e-6 - y * 0.934935152e-7)));
-    return sqrt(0.636619772 / ax) * (cos(xx) * a1 - z * sin(xx) * a2);
-}
 // one pixel of preloadCTF (RFA:548-592 / RFG:552-593): CTF factor and modulator
 __device__ __forceinline__ void d_ctf_pixel(const XhCtfDev &c, int x, int y, int P, double iTs, double minCTF, int phaseFlipped,
                                             float &ctfOut, float &modOut)
@@ -655,31 +640,9 @@ __device__ __forceinline__ void d_ctf_pixel(const XhCtfDev &c, int x, int y, int
     const double xr = (double)(x <= P / 2 ? x : x - P);
     float freqX = (float)(pow2 ? xr * (1.0 / (double)P) : xr / (double)P);
     const double X = freqX * iTs, Y = freqY * iTs;
-    const double u2 = X * X + Y * Y;
-    const double u = sqrt(u2);
-    const double u4 = u2 * u2;
-    // Per-image (block-uniform) shortcuts, each bit-identical to the general formula (ctf.h:376-501):
-    // x + 0*cos(.) == x and exp(-0*finite) == 1 exactly, so a non-astigmatic CTF needs no atan2/cos and a
-    // CTF without energy-spread / convergence-cone terms no exp.
-    double deltaf;
-    if (fabs(X) < 1e-6 && fabs(Y) < 1e-6) deltaf = 0;
-    else if (c.defocus_deviation == 0) deltaf = c.defocus_average;
-    else deltaf = c.defocus_average + c.defocus_deviation * cos(2 * (atan2(Y, X) - c.rad_azimuth));
-    double VPP = 0.0;
-    if (round(c.VPP_radius * 1000) != 0) VPP = -c.phase_shift * (1 - exp(-u2 / (2 * c.VPP_radius * c.VPP_radius)));
-    const double argument = VPP + c.K1 * deltaf * u2 + c.K2 * u4;
-    double sine_part, cosine_part;
-    sincos(argument, &sine_part, &cosine_part);
-    const double Eespr = c.K3 == 0 ? 1.0 : exp(-c.K3 * u4);
-    // d_bessj0(0) is the quotient of the two leading coefficients (not 1): the compiler folds the same IEEE division
-    const double EdeltaF = c.K5 == 0 ? 57568490574.0 / 57568490411.0 : d_bessj0(c.K5 * u2);
-    const double xs = u * c.DeltaR;
-    const double EdeltaR = (xs == 0) ? 1.0 : sin(3.14159265358979323846 * xs) / (3.14159265358979323846 * xs);
-    const double aux = (c.K7 * u2 * u + deltaf * u);
-    const double Ealpha = c.K6 == 0 ? 1.0 : exp(-c.K6 * aux * aux);
-    double E = Eespr * EdeltaF * EdeltaR * Ealpha + c.envR0 + c.envR1 * u + c.envR2 * u2;
-    if (E < 0) E = 0;
-    const double pure = -c.K * (c.Ksin * sine_part - c.Kcos * cosine_part) * E;
+    // from (X, Y) to the pure value: the shared evaluator, with its shortcuts for the terms that a zero coefficient switches off (the
+    // CTF is uniform over a block): most particles' CTFs need no atan2 / cos, no exp and no Bessel function
+    const double pure = d_ctf_at<true>(c, X, Y, true);
     float CTFVal = (float)(c.K * pure);   // getValuePureNoKAt multiplies by K (ctf.h:499-502)
     float modulatorVal = 1.f;
     if (isnan(CTFVal)) {
@@ -1593,27 +1556,12 @@ static int ctf_params_upload(xh_rf *rf, const xh_ctf_params *h_ctf, int n)
     std::vector<XhCtfDev> hc(n);
     for (int i = 0; i < n; ++i) {
         const xh_ctf_params &c = h_ctf[i];
-        // produceSideInfo, data/ctf.cpp:645-679,1392-1402
-        const double local_Cs = c.Cs * 1e7, local_Ca = c.Ca * 1e7, local_kV = c.kV * 1e3, local_ispr = c.ispr * 1e6;
-        const double lambda = 12.2643247 / std::sqrt(local_kV * (1. + 0.978466e-6 * local_kV));
         XhCtfDev &d = hc[i];
-        d.K1 = kPI * lambda;
-        d.K2 = kPI / 2 * local_Cs * lambda * lambda * lambda;
-        d.K3 = std::pow(0.25 * kPI * local_Ca * lambda * (c.espr / c.kV + 2 * local_ispr), 2) / std::log(2.0);
-        d.K5 = kPI * c.DeltaF * lambda;
-        d.K6 = kPI * kPI * c.alpha * c.alpha;
-        d.K7 = local_Cs * lambda * lambda;
-        d.Ksin = std::sqrt(1 - c.Q0 * c.Q0);
-        d.Kcos = c.Q0;
-        d.rad_azimuth = c.azimuthal_angle * kPI / 180.;
-        d.defocus_average = -(c.DeltafU + c.DeltafV) * 0.5;
-        d.defocus_deviation = -(c.DeltafU - c.DeltafV) * 0.5;
-        d.DeltaR = c.DeltaR; d.K = c.K; d.envR0 = c.envR0; d.envR1 = c.envR1; d.envR2 = c.envR2;
-        d.phase_shift = c.phase_shift; d.VPP_radius = c.VPP_radius;
+        static_cast<CtfSide &>(d) = side_info(c, false);
         // d_ctf_pixel_fast: no phase plate, no energy spread / focal spread / convergence cone / DeltaR term, no envR1 (which needs u)
         d.amp = std::hypot(d.Ksin, d.Kcos);
         d.phi = std::atan2(d.Kcos, d.Ksin);
-        d.E0 = 57568490574.0 / 57568490411.0 + c.envR0;      // the J0(0) quotient of d_ctf_pixel
+        d.E0 = kCtfJ0At0 + c.envR0;
         d.c2az = std::cos(2 * d.rad_azimuth); d.s2az = std::sin(2 * d.rad_azimuth);
         d.fast = rf->ctf_fast && std::round(c.VPP_radius * 1000) == 0 && d.K3 == 0 && d.K5 == 0 && d.K6 == 0 && c.DeltaR == 0 && c.envR1 == 0
                  && std::isfinite(d.amp) && std::isfinite(d.E0) && rf->p.min_ctf > 0;
@@ -2155,29 +2103,6 @@ __global__ void __launch_bounds__(256) k_rf2_pad(const float *__restrict__ imgs,
     out[((size_t)img * P + (i + off + sh) % P) * P + (j + off + sh) % P] = xh_cd{(double)imgs[t], 0.0};
 }
 
-// CTF value of RF:600-625 (getValuePureNoKAt at the double digital frequency / Ts)
-__device__ __forceinline__ double d_rf2_ctf(const XhCtfDev &c, double X, double Y)
-{
-    const double u2 = X * X + Y * Y, u = sqrt(u2), u4 = u2 * u2;
-    double deltaf;
-    if (fabs(X) < 1e-6 && fabs(Y) < 1e-6) deltaf = 0;
-    else deltaf = c.defocus_average + c.defocus_deviation * cos(2 * (atan2(Y, X) - c.rad_azimuth));
-    double VPP = 0.0;
-    if (round(c.VPP_radius * 1000) != 0) VPP = -c.phase_shift * (1 - exp(-u2 / (2 * c.VPP_radius * c.VPP_radius)));
-    const double argument = VPP + c.K1 * deltaf * u2 + c.K2 * u4;
-    double sine_part, cosine_part;
-    sincos(argument, &sine_part, &cosine_part);
-    const double Eespr = exp(-c.K3 * u4);
-    const double EdeltaF = d_bessj0(c.K5 * u2);
-    const double xs = u * c.DeltaR;
-    const double EdeltaR = (xs == 0) ? 1.0 : sin(3.14159265358979323846 * xs) / (3.14159265358979323846 * xs);
-    const double aux = (c.K7 * u2 * u + deltaf * u);
-    const double Ealpha = exp(-c.K6 * aux * aux);
-    double E = Eespr * EdeltaF * EdeltaR * Ealpha + c.envR0 + c.envR1 * u + c.envR2 * u2;
-    if (E < 0) E = 0;
-    return c.K * (-c.K * (c.Ksin * sine_part - c.Kcos * cosine_part) * E);
-}
-
 // one thread per (projection x symmetry matrix, Fourier pixel of the half spectrum)
 __global__ void __launch_bounds__(256)
 k_rf2_scatter(const xh_cd *__restrict__ spectra, const double *__restrict__ A_SL, const float *__restrict__ weights, const int *__restrict__ imgOf,
@@ -2196,7 +2121,8 @@ k_rf2_scatter(const xh_cd *__restrict__ spectra, const double *__restrict__ A_SL
     if (fx * fx + fy * fy > maxRes2) return;
     double wCTF = 1, wMod = 1;
     if (ctf && !reprocess) {
-        wCTF = d_rf2_ctf(ctf[img], fx * iTs, fy * iTs);
+        // RF:600-625: getValuePureNoKAt at the double digital frequency / Ts
+        wCTF = d_ctf_at(ctf[img], fx * iTs, fy * iTs, true) * ctf[img].K;
         if (isnan(wCTF)) { if (i == 0 && j == 0) wMod = wCTF = 1.0; else wMod = wCTF = 0.0; }
         if (fabs(wCTF) < minCTF) { wMod = fabs(wCTF); wCTF = (wCTF >= 0) ? 1.0 : -1.0; }
         else wCTF = 1.0 / wCTF;
@@ -2403,19 +2329,7 @@ int xh_rf2_insert(xh_rf2 *h, const float *d_imgs, const xh_ctf_params *h_ctf, co
     std::vector<XhCtfDev> hc;
     if (h_ctf && !reprocess) {
         hc.resize(n);
-        for (int i = 0; i < n; ++i) {
-            const xh_ctf_params &c = h_ctf[i];
-            const double local_Cs = c.Cs * 1e7, local_Ca = c.Ca * 1e7, local_kV = c.kV * 1e3, local_ispr = c.ispr * 1e6;
-            const double lambda = 12.2643247 / std::sqrt(local_kV * (1. + 0.978466e-6 * local_kV));
-            XhCtfDev &d = hc[i];
-            d.K1 = kPI * lambda; d.K2 = kPI / 2 * local_Cs * lambda * lambda * lambda;
-            d.K3 = std::pow(0.25 * kPI * local_Ca * lambda * (c.espr / c.kV + 2 * local_ispr), 2) / std::log(2.0);
-            d.K5 = kPI * c.DeltaF * lambda; d.K6 = kPI * kPI * c.alpha * c.alpha; d.K7 = local_Cs * lambda * lambda;
-            d.Ksin = std::sqrt(1 - c.Q0 * c.Q0); d.Kcos = c.Q0; d.rad_azimuth = c.azimuthal_angle * kPI / 180.;
-            d.defocus_average = -(c.DeltafU + c.DeltafV) * 0.5; d.defocus_deviation = -(c.DeltafU - c.DeltafV) * 0.5;
-            d.DeltaR = c.DeltaR; d.K = c.K; d.envR0 = c.envR0; d.envR1 = c.envR1; d.envR2 = c.envR2;
-            d.phase_shift = c.phase_shift; d.VPP_radius = c.VPP_radius;
-        }
+        for (int i = 0; i < n; ++i) static_cast<CtfSide &>(hc[i]) = side_info(h_ctf[i], false);
         XH_TRY(xh_buf_reserve(ctx, h->d_ctf, sizeof(XhCtfDev) * (size_t)n));
         XH_HIP(hipMemcpyAsync(h->d_ctf.p, hc.data(), sizeof(XhCtfDev) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
         d_c = (const XhCtfDev *)h->d_ctf.p;

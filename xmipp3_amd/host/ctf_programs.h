@@ -7,21 +7,6 @@
 
 namespace mc {
 
-// CTFDescription::readFromMdRow (data/ctf.cpp:389-470): the columns a ctfparam file / a particle row carries
-inline void readCtfRow(const MetaDataVec &md, size_t id, xh_ctf_params &c)
-{
-    xh_ctf_defaults(&c);     // data/ctf.cpp:365-388
-    c.Tm = md.getDouble("ctfSamplingRate", id, 1); c.kV = md.getDouble("ctfVoltage", id, 100);
-    c.DeltafU = md.getDouble("ctfDefocusU", id, 0); c.DeltafV = md.getDouble("ctfDefocusV", id, c.DeltafU);
-    c.azimuthal_angle = md.getDouble("ctfDefocusAngle", id, 0); c.Cs = md.getDouble("ctfSphericalAberration", id, 0);
-    c.Ca = md.getDouble("ctfChromaticAberration", id, 0); c.espr = md.getDouble("ctfEnergyLoss", id, 0);
-    c.ispr = md.getDouble("ctfLensStability", id, 0); c.alpha = md.getDouble("ctfConvergenceCone", id, 0);
-    c.DeltaF = md.getDouble("ctfLongitudinalDisplacement", id, 0); c.DeltaR = md.getDouble("ctfTransversalDisplacement", id, 0);
-    c.Q0 = md.getDouble("ctfQ0", id, 0); c.K = md.getDouble("ctfK", id, 1);
-    c.envR0 = md.getDouble("ctfEnvR0", id, 0); c.envR1 = md.getDouble("ctfEnvR1", id, 0); c.envR2 = md.getDouble("ctfEnvR2", id, 0);
-    c.phase_shift = md.getDouble("ctfPhaseShift", id, 0); c.VPP_radius = md.getDouble("ctfVPPRadius", id, 0);
-}
-
 // processImage's reading of a particle's pose and CTF (angular_continuous_assign2.cpp:421-445, angular_sph_alignment.cpp:304-325) into
 // a zeroed row of a per-particle program (xh_ca2_row, xh_asa_row)
 template <class Row> inline void readPoseRow(const MetaDataVec &md, size_t id, bool hasCTF, Row &r)

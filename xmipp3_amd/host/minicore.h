@@ -86,6 +86,7 @@ public:
     bool getValue(const std::string &l, double &v, size_t id) const { std::string s; if (!getValue(l, s, id)) return false; v = atof(s.c_str()); return true; }
     bool getValue(const std::string &l, long &v, size_t id) const { std::string s; if (!getValue(l, s, id)) return false; v = atol(s.c_str()); return true; }
     double getDouble(const std::string &l, size_t id, double def) const { double v = def; getValue(l, v, id); return v; }
+    double getDouble(int c, size_t id, double def) const { return c < 0 || rows[id][c].empty() ? def : atof(rows[id][c].c_str()); }   // c = col(label)
 
     static std::vector<std::string> tokenize(const std::string &line)
     {

@@ -11,6 +11,7 @@
 #define XMIPP3_AMD_PROGRAMS_H
 #include "minicore.h"
 #include "fastio.h"
+#include "ctf_model.h"
 #include "sampling_gen.h"
 #include <chrono>
 #include <exception>
@@ -53,46 +54,6 @@ struct DeviceBuffer {
     void reserve(xh_ctx *c, size_t b) { if (b <= bytes) return; release(); ctx = c; xhCheck(xh_malloc(c, b, &p)); bytes = b; }
     template <typename T> T *as() { return (T *)p; }
 };
-
-// CTFDescription::getValueAt for the pure CTF (data/ctf.h:452-496,1002-1029; data/ctf.cpp:645-679,1392-1402);
-// host copy used only to build the gallery filter of --ctf (generateCTF, data/ctf.h:1219-1240)
-inline double bessj0_host(double x)
-{
-    double ax = std::fabs(x);
-    if (ax < 8.0) {
-        double y = x * x;
-        double a1 = 57568490574.0 + y * (-13362590354.0 + y * (651619640.7 + y * (-11214424.18 + y * (77392.33017 + y * (-184.9052456)))));
-        double a2 = 57568490411.0 + y * (1029532985.0 + y * (9494680.718 + y * (59272.64853 + y * (267.8532712 + y * 1.0))));
-        return a1 / a2;
-    }
-    double z = 8.0 / ax, y = z * z, xx = ax - 0.785398164;
-    double a1 = 1.0 + y * (-0.1098628627e-2 + y * (0.2734510407e-4 + y * (-0.2073370639e-5 + y * 0.2093887211e-6)));
-    double a2 = -0.1562499995e-1 + y * (0.1430488765e-3 + y * (-0.6911147651e-5 + y * (0.7621095161e-6 - y * 0.934935152e-7)));
-    return std::sqrt(0.636619772 / ax) * (std::cos(xx) * a1 - z * std::sin(xx) * a2);
-}
-inline double ctfValueAt(const xh_ctf_params &c, double X, double Y)
-{
-    const double PI = 3.14159265358979323846;
-    const double local_Cs = c.Cs * 1e7, local_Ca = c.Ca * 1e7, local_kV = c.kV * 1e3, local_ispr = c.ispr * 1e6;
-    const double lambda = 12.2643247 / std::sqrt(local_kV * (1. + 0.978466e-6 * local_kV));
-    const double K1 = PI * lambda, K2 = PI / 2 * local_Cs * lambda * lambda * lambda;
-    const double K3 = std::pow(0.25 * PI * local_Ca * lambda * (c.espr / c.kV + 2 * local_ispr), 2) / std::log(2.0);
-    const double K5 = PI * c.DeltaF * lambda, K6 = PI * PI * c.alpha * c.alpha, K7 = local_Cs * lambda * lambda;
-    const double Ksin = std::sqrt(1 - c.Q0 * c.Q0), Kcos = c.Q0;
-    const double ang = std::atan2(Y, X), u2 = X * X + Y * Y, u = std::sqrt(u2), u4 = u2 * u2;
-    double deltaf = 0;
-    if (!(std::fabs(X) < 1e-6 && std::fabs(Y) < 1e-6))
-        deltaf = -(c.DeltafU + c.DeltafV) * 0.5 - (c.DeltafU - c.DeltafV) * 0.5 * std::cos(2 * (ang - c.azimuthal_angle * PI / 180.));
-    double VPP = 0;
-    if (std::round(c.VPP_radius * 1000) != 0) VPP = -c.phase_shift * (1 - std::exp(-u2 / (2 * c.VPP_radius * c.VPP_radius)));
-    const double arg = VPP + K1 * deltaf * u2 + K2 * u4;
-    const double xs = u * c.DeltaR;
-    const double aux = K7 * u2 * u + deltaf * u;
-    double E = std::exp(-K3 * u4) * bessj0_host(K5 * u2) * (xs == 0 ? 1.0 : std::sin(PI * xs) / (PI * xs)) * std::exp(-K6 * aux * aux) + c.envR0 +
-               c.envR1 * u + c.envR2 * u2;
-    if (E < 0) E = 0;
-    return -c.K * (Ksin * std::sin(arg) - Kcos * std::cos(arg)) * E;
-}
 
 // Sampling::readSamplingFile (data/sampling.cpp:1592-1659): blocks extra / neighbors / projectionDirections.
 // my_neighbors[image] is kept as shared lists (fastio.h: NeighbourLists): with every image searching the whole gallery
@@ -325,24 +286,11 @@ public:
                 MetaDataVec md;
                 md.read(fn_ctf);
                 xh_ctf_params c;
-                xh_ctf_defaults(&c);
-                c.Tm = md.getDouble("ctfSamplingRate", 0, 1); c.kV = md.getDouble("ctfVoltage", 0, 100);
-                c.DeltafU = md.getDouble("ctfDefocusU", 0, 0); c.DeltafV = md.getDouble("ctfDefocusV", 0, c.DeltafU);
-                c.azimuthal_angle = md.getDouble("ctfDefocusAngle", 0, 0); c.Cs = md.getDouble("ctfSphericalAberration", 0, 0);
-                c.Ca = md.getDouble("ctfChromaticAberration", 0, 0); c.espr = md.getDouble("ctfEnergyLoss", 0, 0);
-                c.ispr = md.getDouble("ctfLensStability", 0, 0); c.alpha = md.getDouble("ctfConvergenceCone", 0, 0);
-                c.DeltaF = md.getDouble("ctfLongitudinalDisplacement", 0, 0); c.DeltaR = md.getDouble("ctfTransversalDisplacement", 0, 0);
-                c.Q0 = md.getDouble("ctfQ0", 0, 0); c.K = md.getDouble("ctfK", 0, 1);
+                readCtfRow(md, 0, c);
+                // the reference reads these too (data/ctf.cpp:384, 1182); this program never has: kept out until that is decided on its own
+                c.envR0 = c.envR1 = c.envR2 = c.phase_shift = c.VPP_radius = 0;
                 if (std::fabs(c.DeltafV - c.DeltafU) > 1.) REPORT_ERROR(ERR_VALUE_INCORRECT, "ERROR!! Only non-astigmatic CTFs are allowed!");
-                const double iTs = 1.0 / c.Tm;
-                for (int i = 0; i < paddim; ++i) {
-                    const double fy = (double)(i <= paddim / 2 ? i : i - paddim) / paddim * iTs;
-                    for (int j = 0; j < paddim; ++j) {
-                        const double fx = (double)(j <= paddim / 2 ? j : j - paddim) / paddim * iTs;
-                        const double v = ctfValueAt(c, fx, fy);
-                        Mctf[(size_t)i * paddim + j] = phase_flipped ? std::fabs(v) : v;
-                    }
-                }
+                Mctf = ctfFilterTable(c, paddim, phase_flipped);
             }
         }
         for (int d : parseDevices(device, gpus, deviceList)) {
@@ -826,11 +774,7 @@ public:
         DeviceBuffer d_shift;
         const int cImage = SF.col("image"), cRot = SF.col("angleRot"), cTilt = SF.col("angleTilt"), cPsi = SF.col("anglePsi"), cSx = SF.col("shiftX"),
                   cSy = SF.col("shiftY"), cFlip = SF.col("flip"), cWeight = SF.col("weight");
-        const char *ctfLabels[16] = {"ctfSamplingRate", "ctfVoltage", "ctfDefocusU", "ctfDefocusV", "ctfDefocusAngle", "ctfSphericalAberration", "ctfChromaticAberration",
-                                     "ctfEnergyLoss", "ctfLensStability", "ctfConvergenceCone", "ctfLongitudinalDisplacement", "ctfTransversalDisplacement", "ctfQ0",
-                                     "ctfK", "ctfPhaseShift", "ctfVPPRadius"};
-        int cCtf[16];
-        for (int i = 0; i < 16; ++i) cCtf[i] = SF.col(ctfLabels[i]);
+        const CtfColumns ctfCols(SF);
 
         auto prepare = [&](size_t k) {
             BatchInput in;
@@ -852,15 +796,9 @@ public:
                 if (do_weights) in.w[i] = (float)SF.getDouble(cWeight, id, 1.0);
                 if (hasCTF) {
                     xh_ctf_params &c = in.ctfs[i];
-                    xh_ctf_defaults(&c);     // data/ctf.cpp:365-388
-                    c.Tm = SF.getDouble(cCtf[0], id, 1); c.kV = SF.getDouble(cCtf[1], id, 100);
-                    c.DeltafU = SF.getDouble(cCtf[2], id, 0); c.DeltafV = SF.getDouble(cCtf[3], id, c.DeltafU);
-                    c.azimuthal_angle = SF.getDouble(cCtf[4], id, 0); c.Cs = SF.getDouble(cCtf[5], id, 0);
-                    c.Ca = SF.getDouble(cCtf[6], id, 0); c.espr = SF.getDouble(cCtf[7], id, 0);
-                    c.ispr = SF.getDouble(cCtf[8], id, 0); c.alpha = SF.getDouble(cCtf[9], id, 0);
-                    c.DeltaF = SF.getDouble(cCtf[10], id, 0); c.DeltaR = SF.getDouble(cCtf[11], id, 0);
-                    c.Q0 = SF.getDouble(cCtf[12], id, 0); c.K = SF.getDouble(cCtf[13], id, 1);
-                    c.phase_shift = SF.getDouble(cCtf[14], id, 0); c.VPP_radius = SF.getDouble(cCtf[15], id, 0);
+                    ctfCols.read(SF, id, c);
+                    // the reference reads these too (data/ctf.cpp:384); this program never has: kept out until that is decided on its own
+                    c.envR0 = c.envR1 = c.envR2 = 0;
                 }
             }
             return in;

@@ -22,7 +22,8 @@ passes=(
 )
 i=0
 for p in "${passes[@]}"; do
-  timeout 600 rocprofv3 --pmc $p --output-format csv -d $out/p$i -- python3 tools/bench_grid.py --reps 1 "$@" > $out/p$i.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $p --output-format csv -d $out/p$i -- python3 tools/bench_grid.py --reps 1 "$@" > $out/p$i.log 2>&1 \
+    || { echo "pmc_grid.sh: pass $i ($p) failed, see $out/p$i.log" >&2; exit 1; }      # nothing more runs on a device a pass may have left in trouble
   i=$((i+1))
 done
 python3 - "$out" "$kern" "$tag" <<'PY'

@@ -911,6 +911,7 @@ __device__ __forceinline__ bool d_hit(float y, float z, float a1, float a2, floa
 }
 
 #include "xh_rf_grid.h"
+#include "xh_rf_tiles.h"
 
 // ---- finaliser ---------------------------------------------------------------------------
 // mirrorAndCrop RFA:861-887 in gather form. in: (mv+1)^3, out: (mv+1)^2 (half+1)
@@ -1258,42 +1259,13 @@ int xh_rf_create(xh_ctx *ctx, const xh_rf_params *p, xh_rf **out)
     XH_TRY(xh_plan_create<float>(ctx, rf->P, rf->planP32));
     XH_TRY(xh_plan_create<double>(ctx, rf->P, rf->planP64));
     XH_TRY(xh_buf_alloc(ctx, rf->d_tileCounter, sizeof(int) * 512));
-    // k_rf_grid: tiles of 2 x 2 x 2 units (16 x 16 x 8 voxels) that a projection can reach (sphere of radius sizeX + blob), in raster
-    // order (z, y, x) cut into 8 contiguous z-slabs of equal estimated work, one per XCD (block b runs on XCD b % 8: a projection's
-    // patch is pulled into one or two L2s instead of all eight). A tile at distance rho from the centre is crossed by a fraction ~1/rho
-    // of all central planes: that is its weight. Inside a class Morton order (the waves of the chip work on a narrow band of
-    // consecutive tiles, and a compact band shares more of the projections' patches in the L2 than a row of the raster). Class
-    // offsets at d_tileCounter + 32.
+    // k_rf_grid's tile list (xh_rf_tiles.h: eight XCD classes, in each the heavy tiles around the origin first, then Morton order).
+    // Class offsets at d_tileCounter + 32.
     {
-        const int tzs = 8;                                     // voxels per tile in z
-        const int tpx = (rf->mv + 1 + 15) / 16, tpz = (rf->mv + 1 + tzs - 1) / tzs;
-        const double hz = 0.5 * tzs - 0.5;
-        const double R = rf->sizeX + p->blob_radius + std::sqrt(2 * 7.5 * 7.5 + hz * hz) + 1.0;
-        std::vector<unsigned> packed;
-        std::vector<double> wsum;
-        double acc = 0;
-        for (int tz = 0; tz < tpz; ++tz)
-            for (int ty = 0; ty < tpx; ++ty)
-                for (int tx = 0; tx < tpx; ++tx) {
-                    const double cx = tx * 16 + 7.5 - rf->mv / 2, cy = ty * 16 + 7.5 - rf->mv / 2, cz = tz * tzs + hz - rf->mv / 2;
-                    const double d = std::sqrt(cx * cx + cy * cy + cz * cz);
-                    if (d <= R) { packed.push_back((unsigned)(tx | (ty << 10) | (tz << 20))); acc += 1.0 / std::max(d, 8.0); wsum.push_back(acc); }
-                }
-        int classOff[9];
-        classOff[0] = 0;
-        for (int c = 1; c < 8; ++c)
-            classOff[c] = (int)(std::lower_bound(wsum.begin(), wsum.end(), acc * c / 8.0) - wsum.begin());
-        classOff[8] = (int)packed.size();
-        auto spread = [](unsigned v) { unsigned long long x = v & 0x3ff; x = (x | x << 16) & 0x30000ffULL; x = (x | x << 8) & 0x300f00fULL; x = (x | x << 4) & 0x30c30c3ULL; x = (x | x << 2) & 0x9249249ULL; return x; };
-        // Morton order; tiles are half as tall as wide: on (x, y, z / 2) with the low bit of z last
-        auto key = [&](unsigned t) {
-            return (spread(t & 0x3ff) | spread((t >> 10) & 0x3ff) << 1 | spread((t >> 21) & 0x1ff) << 2) << 1 | ((t >> 20) & 1);
-        };
-        for (int c = 0; c < 8; ++c)
-            std::sort(packed.begin() + classOff[c], packed.begin() + classOff[c + 1], [&](unsigned u, unsigned w) { return key(u) < key(w); });
-        XH_TRY(xh_buf_alloc(ctx, rf->d_gtiles, sizeof(unsigned) * std::max<size_t>(1, packed.size())));
-        if (hipMemcpy(rf->d_gtiles.p, packed.data(), sizeof(unsigned) * packed.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
-        if (hipMemcpy((int *)rf->d_tileCounter.p + 32, classOff, sizeof(classOff), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+        const XgTileList tl = xg_tile_list(rf->mv, p->blob_radius, std::max(1, ctx->num_cus) * XgCfg<4>::NW);
+        XH_TRY(xh_buf_alloc(ctx, rf->d_gtiles, sizeof(unsigned) * std::max<size_t>(1, tl.tiles.size())));
+        if (hipMemcpy(rf->d_gtiles.p, tl.tiles.data(), sizeof(unsigned) * tl.tiles.size(), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
+        if (hipMemcpy((int *)rf->d_tileCounter.p + 32, tl.classOff, sizeof(tl.classOff), hipMemcpyHostToDevice) != hipSuccess) return XH_ERR_HIP;
     }
     *out = rf.release();
     return XH_OK;

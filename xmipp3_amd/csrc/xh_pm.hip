@@ -410,43 +410,51 @@ k_pm_ringdft(const T *__restrict__ polar, const double *__restrict__ stat, xh_c2
 // ---- per-ring DFT as a matrix product on the matrix cores (fp32 coarse pass only) ---------------
 // out[slot][k] = (1/n) sum_s (x[slot][s] - mean[slot]) * tw[(s*k) mod n] is, per ring, the product of
 // a [slots x n] matrix with the [n x nk] DFT matrix: 54 MFLOP per 256-px particle, which the direct
-// kernel above does at VALU rate. Here a wave owns 32 slots x 32 frequencies per accumulator pair
-// (re, im) on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation). The DFT matrix is never
+// kernel above does at VALU rate. Here a wave owns 32 slots x 32 frequencies per accumulator
+// on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation). The DFT matrix is never
 // stored: every lane walks its own (s*k) mod n through the ring's n-entry twiddle table in LDS.
 // Block = (ring, 32 slots); the samples are staged through LDS in chunks (coalesced reads, mean
-// subtracted on the way in); wave w takes frequency tiles w, w+4, w+8, w+12 of each round of 16.
+// subtracted on the way in); wave w takes frequency tiles w, w+4 of each round of 8.
+//
+// Two folds quarter the plain sum. The samples are real: with E[s] = x[s] + x[n-s], O[s] = x[s] - x[n-s]
+// (E[0] = x[0], E[h] = x[h], O = 0 there; h = n/2, n is even for every ring)
+//   Re X[k] = sum_{s=0}^{h} E[s] tw[sk].x,   Im X[k] = sum_{s=0}^{h} O[s] tw[sk].y
+// and tw[s(h-k)] = ((-1)^s tw[sk].x, -(-1)^s tw[sk].y), so with the sums split by the parity of s
+//   Ce = sum_{s even} E[s] tw[sk].x   Co = sum_{s odd} E[s] tw[sk].x   Se, So the same of O[s] tw[sk].y
+//   X[k] = (Ce + Co, Se + So)         X[h-k] = (Ce - Co, So - Se)
+// only k = 0..h/2 is multiplied out; the other half of the spectrum is two additions in the epilogue.
 typedef float xh_f32x16_rd __attribute__((ext_vector_type(16)));
-#define XH_RD_CH 256
-#define XH_RD_LD (XH_RD_CH + 3)      // row stride of the staged samples: odd multiple of banks apart, three zero columns behind a chunk
-#define XH_RD_KT 3
+#define XH_RD_CH 256                 // folded samples per staged chunk: XH_RD_CH / 2 of either parity
+#define XH_RD_LD (XH_RD_CH / 2 + 3)  // row stride of the staged samples: odd, three zero columns behind a chunk
+#ifndef XH_RD_KT
+#define XH_RD_KT 2                   // frequency tiles per wave: four accumulators each
+#endif
 // one round of a block: NA live frequency tiles for this wave (kt0 + wv + 4*i, i < NA). Every wave of
 // the block runs the same number of barriers whatever its NA.
+// sP: rows 0-31 E at even s, 32-63 E at odd s, 64-95 O at even s, 96-127 O at odd s; column = (s - chunk start) / 2
 template <int NA>
-__device__ __forceinline__ void rd_round(float (*sX)[XH_RD_LD], float (*sO)[XH_RD_LD], const xh_cf *sT, const float *__restrict__ polar,
+__device__ __forceinline__ void rd_round(float (*sP)[XH_RD_LD], const xh_cf *sT, const float *__restrict__ polar,
                                          const float *sMean, xh_cf *__restrict__ out, int n, int nk, int kt0,
                                          int slot0, int nslots, int nsamples, int soffr, int coffr, int ncoef, int conjugate)
 {
     constexpr int NR = NA > 0 ? NA : 1;
+    constexpr int PB = 32 * XH_RD_LD;          // one block of 32 rows
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int sl = lane >> 5, kl = lane & 31;
-    xh_f32x16_rd accR[NR], accI[NR];
-    int j[NR], dj[NR], kq[NR];
+    xh_f32x16_rd aCe[NR], aCo[NR], aSe[NR], aSo[NR];
+    int je[NR], jo[NR], dj[NR], kq[NR];
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) { accR[i][e] = 0.f; accI[i][e] = 0.f; }
+        for (int e = 0; e < 16; ++e) { aCe[i][e] = 0.f; aCo[i][e] = 0.f; aSe[i][e] = 0.f; aSo[i][e] = 0.f; }
         kq[i] = ((kt0 + wv + 4 * i) * 32 + kl) % n;
-        j[i] = 0;
-        dj[i] = (2 * kq[i]) % n;
+        je[i] = jo[i] = 0;
+        dj[i] = (4 * kq[i]) % n;
     }
-    // The samples are real: with E[s] = x[s] + x[n-s], O[s] = x[s] - x[n-s] (E[0] = x[0], E[n/2] = x[n/2], O = 0 there)
-    //   Re X[k] = sum_{s=0}^{n/2} E[s] tw[sk].x,   Im X[k] = sum_{s=0}^{n/2} O[s] tw[sk].y
-    // -- half the matrix-core work of the plain sum over n samples. The fold happens on the way into LDS.
     const int nh = n >> 1, nf = nh + 1;
     // The samples of a chunk pass through registers on their way to LDS. (Fetching chunk c+1 while the matrix cores work on
-    // chunk c needs those 64 registers for the whole chunk and, with four frequency tiles per wave, 454 registers: one wave per
-    // SIMD, matrix cores 32 % busy. Three tiles per wave and no prefetch fit two waves per SIMD -- the other workgroup's matrix
-    // work covers this one's staging: 2.41 -> 1.69 ms per 4096 particles.)
+    // chunk c needs those 64 registers for the whole chunk: one wave per SIMD. Without the prefetch two waves per SIMD fit --
+    // the other workgroup's matrix work covers this one's staging.)
     float preA[32], preB[32];
     auto fetch = [&](int sc) {
         const int ss = min(sc + tid, nh);
@@ -461,66 +469,89 @@ __device__ __forceinline__ void rd_round(float (*sX)[XH_RD_LD], float (*sO)[XH_R
     for (int sc = 0; sc < nf; sc += XH_RD_CH) {
         fetch(sc);
         __syncthreads();            // previous chunk consumed (and sT / sMean visible on the first pass)
-        const int ss = sc + tid;
+        const int ss = sc + tid;    // sc is even: the parity of the sample is the parity of tid
         const bool inRing = ss < nf, edge = ss == 0 || ss == nh;
+        float *dE = &sP[(tid & 1) * 32][tid >> 1];
 #pragma unroll
         for (int q = 0; q < 32; ++q) {
             const float xa = preA[q] - sMean[q], xb = preB[q] - sMean[q];
-            sX[q][tid] = inRing ? (edge ? xa : xa + xb) : 0.f;
-            sO[q][tid] = inRing && !edge ? xa - xb : 0.f;
+            dE[q * XH_RD_LD] = inRing ? (edge ? xa : xa + xb) : 0.f;
+            dE[2 * PB + q * XH_RD_LD] = inRing && !edge ? xa - xb : 0.f;
         }
         __syncthreads();
         if (NA > 0) {
-            // A step takes two samples (lanes 0-31 the first, 32-63 the second) through 2 NA matrix instructions. Its
-            // operands -- the sample pair and NA twiddles -- are read from LDS one whole step ahead, into the other of two
-            // register sets (the loop body is two steps), at the top of the step before: the wave never waits for LDS
-            // while the matrix core has work. Steps beyond the chunk's samples meet the zero columns behind them.
-            const int steps = (min(XH_RD_CH, nf - sc) + 1) >> 1;
-            const float *pe = &sX[kl][sl], *po = &sO[kl][sl];
-            xh_cf w0[NR], w1[NR];
-            float e0, o0, e1 = 0.f, o1 = 0.f;
+            // A step takes two samples of either parity (lanes 0-31 the first, lanes 32-63 the next of that parity) through
+            // 4 NA matrix instructions. Its operands -- the four samples and 2 NA twiddles -- are read from LDS one whole step
+            // ahead, into the other of two register sets (the loop body is two steps), at the top of the step before: the
+            // wave never waits for LDS while the matrix core has work. Steps beyond the chunk's samples meet the zero
+            // columns behind them.
+            const int steps = (((min(XH_RD_CH, nf - sc) + 1) >> 1) + 1) >> 1;
+            const float *ps = &sP[kl][sl];
+            xh_cf we0[NR], wo0[NR], we1[NR], wo1[NR];
+            float ee0, eo0, oe0, oo0, ee1 = 0.f, eo1 = 0.f, oe1 = 0.f, oo1 = 0.f;
 #pragma unroll
-            for (int i = 0; i < NA; ++i) w1[i] = xh_cf{0.f, 0.f};
+            for (int i = 0; i < NA; ++i) { we1[i] = xh_cf{0.f, 0.f}; wo1[i] = we1[i]; }
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                j[i] = ((sc + sl) * kq[i]) % n;                 // sample sc + sl opens the chunk
-                w0[i] = sT[j[i] + (j[i] >> 4)];                 // one pad entry per 16: strides s*k stop piling onto one bank
-                j[i] += dj[i];
-                if (j[i] >= n) j[i] -= n;
+                je[i] = ((sc + 2 * sl) * kq[i]) % n;             // samples sc + 2 sl and sc + 2 sl + 1 open the chunk
+                jo[i] = je[i] + kq[i];
+                if (jo[i] >= n) jo[i] -= n;
+                we0[i] = sT[je[i] + (je[i] >> 4)];               // one pad entry per 16: strides s*k stop piling onto one bank
+                wo0[i] = sT[jo[i] + (jo[i] >> 4)];
+                je[i] += dj[i];
+                if (je[i] >= n) je[i] -= n;
+                jo[i] += dj[i];
+                if (jo[i] >= n) jo[i] -= n;
             }
-            e0 = pe[0]; o0 = po[0];
-            pe += 2; po += 2;
+            ee0 = ps[0]; eo0 = ps[PB]; oe0 = ps[2 * PB]; oo0 = ps[3 * PB];
+            ps += 2;
             for (int t = 0; t < steps; t += 2) {
-#define XH_RD_STEP(WC, WN, EC, OC, EN, ON)                                                              \
-                EN = pe[0]; ON = po[0];                                                                 \
-                _Pragma("unroll") for (int i = 0; i < NA; ++i) WN[i] = sT[j[i] + (j[i] >> 4)];          \
-                __builtin_amdgcn_sched_barrier(0);                                                      \
-                _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                        \
-                    accR[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(EC, WC[i].x, accR[i], 0, 0, 0);      \
-                    accI[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(OC, WC[i].y, accI[i], 0, 0, 0);      \
-                    j[i] += dj[i];                                                                      \
-                    if (j[i] >= n) j[i] -= n;                                                           \
-                }                                                                                       \
-                pe += 2; po += 2;                                                                       \
+#define XH_RD_STEP(C, N)                                                                                    \
+                ee##N = ps[0]; eo##N = ps[PB]; oe##N = ps[2 * PB]; oo##N = ps[3 * PB];                      \
+                _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                            \
+                    we##N[i] = sT[je[i] + (je[i] >> 4)];                                                    \
+                    wo##N[i] = sT[jo[i] + (jo[i] >> 4)];                                                    \
+                }                                                                                           \
+                __builtin_amdgcn_sched_barrier(0);                                                          \
+                _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                            \
+                    aCe[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ee##C, we##C[i].x, aCe[i], 0, 0, 0);      \
+                    aSe[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(oe##C, we##C[i].y, aSe[i], 0, 0, 0);      \
+                    aCo[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(eo##C, wo##C[i].x, aCo[i], 0, 0, 0);      \
+                    aSo[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(oo##C, wo##C[i].y, aSo[i], 0, 0, 0);      \
+                    je[i] += dj[i];                                                                         \
+                    if (je[i] >= n) je[i] -= n;                                                             \
+                    jo[i] += dj[i];                                                                         \
+                    if (jo[i] >= n) jo[i] -= n;                                                             \
+                }                                                                                           \
+                ps += 2;                                                                                    \
                 __builtin_amdgcn_sched_barrier(0);
-                XH_RD_STEP(w0, w1, e0, o0, e1, o1)
-                XH_RD_STEP(w1, w0, e1, o1, e0, o0)
+                XH_RD_STEP(0, 1)
+                XH_RD_STEP(1, 0)
 #undef XH_RD_STEP
             }
         }
     }
+    // all four sums of a (slot, k) sit in this lane: X[k] and X[h-k] leave from here. The frequency that is its own partner
+    // (h even, k = h/2) is written once, by the first formula.
     const float inv = 1.f / (float)n;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
         const int k = (kt0 + wv + 4 * i) * 32 + kl;
         if (k >= nk) continue;
+        const int k2 = nh - k;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int row = (e & 3) + 8 * (e >> 2) + 4 * sl;
             if (slot0 + row >= nslots) continue;
-            float re = accR[i][e] * inv, im = accI[i][e] * inv;
+            xh_cf *o = out + (size_t)(slot0 + row) * ncoef + coffr;
+            float re = (aCe[i][e] + aCo[i][e]) * inv, im = (aSe[i][e] + aSo[i][e]) * inv;
             if (conjugate) im = im * (-1.f);
-            out[(size_t)(slot0 + row) * ncoef + coffr + k] = xh_cf{re, im};
+            o[k] = xh_cf{re, im};
+            if (k2 != k) {
+                re = (aCe[i][e] - aCo[i][e]) * inv; im = (aSo[i][e] - aSe[i][e]) * inv;
+                if (conjugate) im = im * (-1.f);
+                o[k2] = xh_cf{re, im};
+            }
         }
     }
 }
@@ -530,32 +561,30 @@ k_pm_ringdft_mfma(const float *__restrict__ polar, const double *__restrict__ st
                   const int *__restrict__ coff, int nsamples, int ncoef, int conjugate, int nslots, int nrings)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    float (*sX)[XH_RD_LD] = reinterpret_cast<float (*)[XH_RD_LD]>(smem);
-    float (*sO)[XH_RD_LD] = sX + 32;
-    xh_cf *sT = reinterpret_cast<xh_cf *>(smem + sizeof(float) * 64 * XH_RD_LD);
+    float (*sP)[XH_RD_LD] = reinterpret_cast<float (*)[XH_RD_LD]>(smem);
+    xh_cf *sT = reinterpret_cast<xh_cf *>(smem + sizeof(float) * 128 * XH_RD_LD);
     const int r = nrings - 1 - blockIdx.x;        // long rings first
     const int slot0 = blockIdx.y * 32;
-    const int n = nsam[r], nk = n / 2 + 1, nkt = (nk + 31) / 32;
+    const int n = nsam[r], nk = n / 4 + 1, nkt = (nk + 31) / 32;      // the frequencies 0..h/2 that are multiplied out
     const int tid = threadIdx.x, wv = tid >> 6;
     __shared__ float sMean[32];
     for (int i = tid; i < n; i += 256) sT[i + (i >> 4)] = tw[soff[r] + i];
     // slots past the end contribute nothing: their samples are read from the last valid slot and never stored
     if (tid < 32) sMean[tid] = (float)stat[2 * min(slot0 + tid, nslots - 1)];
-    if (tid < 64 * 3) sX[tid / 3][XH_RD_CH + tid % 3] = 0.f;     // the zero columns behind a chunk (sX and sO are contiguous)
+    for (int i = tid; i < 128 * 3; i += 256) sP[i / 3][XH_RD_CH / 2 + i % 3] = 0.f;     // the zero columns behind a chunk
     for (int kt0 = 0; kt0 < nkt; kt0 += 4 * XH_RD_KT) {
-        const int left = nkt - kt0 - wv;          // tiles kt0+wv, +4, +8, +12 that exist
+        const int left = nkt - kt0 - wv;          // tiles kt0+wv, +4, ... that exist
         const int nact = __builtin_amdgcn_readfirstlane(left <= 0 ? 0 : min(XH_RD_KT, (left + 3) / 4));
-#define XH_RD_GO(NA_) rd_round<NA_>(sX, sO, sT, polar, sMean, out, n, nk, kt0, slot0, nslots, nsamples, soff[r], coff[r], ncoef, conjugate)
-#if XH_RD_KT >= 4
-        if (nact == 4) XH_RD_GO(4);
-        else
-#endif
+#define XH_RD_GO(NA_) rd_round<NA_>(sP, sT, polar, sMean, out, n, nk, kt0, slot0, nslots, nsamples, soff[r], coff[r], ncoef, conjugate)
 #if XH_RD_KT >= 3
         if (nact == 3) XH_RD_GO(3);
         else
 #endif
+#if XH_RD_KT >= 2
         if (nact == 2) XH_RD_GO(2);
-        else if (nact == 1) XH_RD_GO(1);
+        else
+#endif
+        if (nact == 1) XH_RD_GO(1);
         else XH_RD_GO(0);
 #undef XH_RD_GO
     }
@@ -564,26 +593,28 @@ k_pm_ringdft_mfma(const float *__restrict__ polar, const double *__restrict__ st
 // ---- the same product in fp64 for the re-scored particles: v_mfma_f64_16x16x4_f64 --------------------------------------
 // The direct kernel (k_pm_ringdft<double>) is bound by its LDS gathers: every lane reads a 16-byte twiddle per 2 FMAs
 // (4 TFLOP/s of the 78 the vector units have). On the matrix cores a wave's 16 slots x 16 frequencies share their
-// operands: per instruction (16 x 16 x 4: 2048 flops) the lanes read one sample and one twiddle each. Same fold of the
-// real samples as above; block = (ring, 16 slots), wave w owns the frequency tiles w, w + 4, ... (up to XH_RD64_NT).
+// operands: per instruction (16 x 16 x 4: 2048 flops) the lanes read one sample and one twiddle each. Same two folds as
+// above (samples and frequencies: four partial sums per frequency, k = 0..h/2 multiplied out); block = (ring, 16 slots), wave w
+// owns the frequency tiles w, w + 4, ... (up to XH_RD64_NT).
 // Layout of the instruction: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15], D[row = (lane >> 4) + 4 e][col = lane & 15].
 typedef double xh_f64x4_rd __attribute__((ext_vector_type(4)));
-#define XH_RD64_CH 128
-#define XH_RD64_LD (XH_RD64_CH + 1)
-#define XH_RD64_NT 8
+#define XH_RD64_CH 128                   // folded samples per staged chunk: XH_RD64_CH / 2 of either parity
+#define XH_RD64_LD (XH_RD64_CH / 2 + 1)
+#define XH_RD64_NT 4                     // frequency tiles per wave: four accumulators each
 __global__ void __launch_bounds__(256)
 k_pm_ringdft_mfma64(const double *__restrict__ polar, const double *__restrict__ stat, xh_cd *__restrict__ out,
                     const xh_cd *__restrict__ tw, const int *__restrict__ nsam, const int *__restrict__ soff,
                     const int *__restrict__ coff, int nsamples, int ncoef, int conjugate, int nslots, int nrings)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    double (*sE)[XH_RD64_LD] = reinterpret_cast<double (*)[XH_RD64_LD]>(smem);
-    double (*sO)[XH_RD64_LD] = sE + 16;
-    xh_cd *sT = reinterpret_cast<xh_cd *>(smem + sizeof(double) * 32 * XH_RD64_LD);        // 32 * 129 * 8 bytes: 16-byte aligned
+    // rows 0-15 E at even s, 16-31 E at odd s, 32-47 O at even s, 48-63 O at odd s; column = (s - chunk start) / 2
+    double (*sP)[XH_RD64_LD] = reinterpret_cast<double (*)[XH_RD64_LD]>(smem);
+    constexpr int PB = 16 * XH_RD64_LD;
+    xh_cd *sT = reinterpret_cast<xh_cd *>(smem + sizeof(double) * 64 * XH_RD64_LD);        // 64 * 65 * 8 bytes: 16-byte aligned
     __shared__ double sMean[16];
     const int r = nrings - 1 - blockIdx.x;        // long rings first
     const int slot0 = blockIdx.y * 16;
-    const int n = nsam[r], nh = n >> 1, nf = nh + 1, nk = nf, nkt = (nk + 15) >> 4;
+    const int n = nsam[r], nh = n >> 1, nf = nh + 1, nk = n / 4 + 1, nkt = (nk + 15) >> 4;     // frequencies 0..h/2 are multiplied out
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int soffr = soff[r];
@@ -592,65 +623,83 @@ k_pm_ringdft_mfma64(const double *__restrict__ polar, const double *__restrict__
     for (int kt0 = 0; kt0 < nkt; kt0 += 4 * XH_RD64_NT) {
         const int left = nkt - kt0 - wv;
         const int nact = left <= 0 ? 0 : min(XH_RD64_NT, (left + 3) / 4);
-        xh_f64x4_rd accR[XH_RD64_NT], accI[XH_RD64_NT];
-        int j[XH_RD64_NT], dj[XH_RD64_NT], kq[XH_RD64_NT];
+        xh_f64x4_rd aCe[XH_RD64_NT], aCo[XH_RD64_NT], aSe[XH_RD64_NT], aSo[XH_RD64_NT];
+        int je[XH_RD64_NT], jo[XH_RD64_NT], dj[XH_RD64_NT], kq[XH_RD64_NT];
 #pragma unroll
         for (int i = 0; i < XH_RD64_NT; ++i) {
-            accR[i] = (xh_f64x4_rd){0., 0., 0., 0.}; accI[i] = accR[i];
+            aCe[i] = (xh_f64x4_rd){0., 0., 0., 0.}; aCo[i] = aCe[i]; aSe[i] = aCe[i]; aSo[i] = aCe[i];
             kq[i] = ((kt0 + wv + 4 * i) * 16 + li) % n;
-            dj[i] = (4 * kq[i]) % n;
-            j[i] = 0;
+            dj[i] = (8 * kq[i]) % n;
+            je[i] = jo[i] = 0;
         }
         for (int sc = 0; sc < nf; sc += XH_RD64_CH) {
             __syncthreads();                      // previous chunk consumed (sT, sMean visible on the first pass)
-            // fold on the way in: thread <-> (column tid & 127, slots (tid >> 7) + 2 q)
+            // fold on the way in: thread <-> (sample sc + (tid & 127), slots (tid >> 7) + 2 q); sc is even
             {
                 const int col = tid & (XH_RD64_CH - 1), ss = sc + col;
                 const bool inRing = ss < nf, edge = ss == 0 || ss == nh;
                 const int sa = min(ss, nh), sb = sa == 0 ? 0 : n - sa;
+                double *dE = &sP[(col & 1) * 16][col >> 1];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int sl = (tid >> 7) + 2 * q;
                     const double *row = polar + (size_t)min(slot0 + sl, nslots - 1) * nsamples + soffr;
                     const double xa = row[sa] - sMean[sl], xb = row[sb] - sMean[sl];
-                    sE[sl][col] = inRing ? (edge ? xa : xa + xb) : 0.;
-                    sO[sl][col] = inRing && !edge ? xa - xb : 0.;
+                    dE[sl * XH_RD64_LD] = inRing ? (edge ? xa : xa + xb) : 0.;
+                    dE[2 * PB + sl * XH_RD64_LD] = inRing && !edge ? xa - xb : 0.;
                 }
             }
             __syncthreads();
             if (nact > 0) {
-                const int steps = (min(XH_RD64_CH, nf - sc) + 3) >> 2;
+                // a step takes four samples of either parity: lane group lk the samples sc + 2 (4 t + lk) and the one after it
+                const int steps = (((min(XH_RD64_CH, nf - sc) + 1) >> 1) + 3) >> 2;
 #pragma unroll
-                for (int i = 0; i < XH_RD64_NT; ++i) j[i] = (int)(((long long)(sc + lk) * kq[i]) % n);
-                const double *pe = &sE[li][lk], *po = &sO[li][lk];
+                for (int i = 0; i < XH_RD64_NT; ++i) {
+                    je[i] = (int)(((long long)(sc + 2 * lk) * kq[i]) % n);
+                    jo[i] = je[i] + kq[i];
+                    if (jo[i] >= n) jo[i] -= n;
+                }
+                const double *ps = &sP[li][lk];
                 for (int t = 0; t < steps; ++t) {
-                    const double e = pe[4 * t], o = po[4 * t];
+                    const double ee = ps[4 * t], eo = ps[PB + 4 * t], oe = ps[2 * PB + 4 * t], oo = ps[3 * PB + 4 * t];
 #pragma unroll
                     for (int i = 0; i < XH_RD64_NT; ++i) {
                         if (i < nact) {
-                            const xh_cd w = sT[j[i] + (j[i] >> 3)];
-                            accR[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(e, w.x, accR[i], 0, 0, 0);
-                            accI[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(o, w.y, accI[i], 0, 0, 0);
-                            j[i] += dj[i];
-                            if (j[i] >= n) j[i] -= n;
+                            const xh_cd we = sT[je[i] + (je[i] >> 3)], wo = sT[jo[i] + (jo[i] >> 3)];
+                            aCe[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(ee, we.x, aCe[i], 0, 0, 0);
+                            aSe[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(oe, we.y, aSe[i], 0, 0, 0);
+                            aCo[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(eo, wo.x, aCo[i], 0, 0, 0);
+                            aSo[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(oo, wo.y, aSo[i], 0, 0, 0);
+                            je[i] += dj[i];
+                            if (je[i] >= n) je[i] -= n;
+                            jo[i] += dj[i];
+                            if (jo[i] >= n) jo[i] -= n;
                         }
                     }
                 }
             }
         }
+        // X[k] and X[h-k] from the four sums of this lane; the frequency that is its own partner is written once, by the first formula
         const double inv = 1.0 / (double)n;
 #pragma unroll
         for (int i = 0; i < XH_RD64_NT; ++i) {
             if (i >= nact) continue;
             const int k = (kt0 + wv + 4 * i) * 16 + li;
             if (k >= nk) continue;
+            const int k2 = nh - k;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int slot = slot0 + lk + 4 * e;
                 if (slot >= nslots) continue;
-                double re = accR[i][e] * inv, im = accI[i][e] * inv;
+                xh_cd *o = out + (size_t)slot * ncoef + coff[r];
+                double re = (aCe[i][e] + aCo[i][e]) * inv, im = (aSe[i][e] + aSo[i][e]) * inv;
                 if (conjugate) im = im * (-1.0);
-                out[(size_t)slot * ncoef + coff[r] + k] = xh_cd{re, im};
+                o[k] = xh_cd{re, im};
+                if (k2 != k) {
+                    re = (aCe[i][e] - aCo[i][e]) * inv; im = (aSo[i][e] - aSe[i][e]) * inv;
+                    if (conjugate) im = im * (-1.0);
+                    o[k2] = xh_cd{re, im};
+                }
             }
         }
     }
@@ -3482,7 +3531,7 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
     }
     }
     if (std::is_same<T, float>::value && !d_count) {
-        const size_t smemM = sizeof(float) * 64 * XH_RD_LD + sizeof(xh_cf) * (L.N + L.N / 16 + 1);
+        const size_t smemM = sizeof(float) * 128 * XH_RD_LD + sizeof(xh_cf) * (L.N + L.N / 16 + 1);
         XH_HIP(hipFuncSetAttribute((const void *)k_pm_ringdft_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smemM));
         hipLaunchKernelGGL(k_pm_ringdft_mfma, dim3(L.nrings, (unsigned)((nps + 31) / 32)), dim3(256), smemM, ctx->stream,
                            (const float *)polarBuf.p, (const double *)statBuf.p, (xh_cf *)outBuf.p, (const xh_cf *)twBuf.p,
@@ -3493,7 +3542,7 @@ static int run_prep(xh_pm *pm, const void *imgs, bool imgsAreFloat, const int *d
     }
     if (std::is_same<T, double>::value && !d_count) {
         // fp64 on the matrix cores (the re-scored particles, the reference bank)
-        const size_t smemD = sizeof(double) * 32 * XH_RD64_LD + sizeof(xh_cd) * (L.N + L.N / 8 + 1);
+        const size_t smemD = sizeof(double) * 64 * XH_RD64_LD + sizeof(xh_cd) * (L.N + L.N / 8 + 1);
         hipLaunchKernelGGL(k_pm_ringdft_mfma64, dim3(L.nrings, (unsigned)((nps + 15) / 16)), dim3(256), smemD, ctx->stream,
                            (const double *)polarBuf.p, (const double *)statBuf.p, (xh_cd *)outBuf.p, (const xh_cd *)twBuf.p,
                            (const int *)pm->d_nsam.p, (const int *)pm->d_soff.p, (const int *)pm->d_coff.p, L.nsamples, L.ncoef,

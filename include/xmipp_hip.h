@@ -332,7 +332,8 @@ int xh_pm_get_option(const xh_pm *pm, const char *name, double *value);
  *              (fourier_projection.cpp:72-89,247-330); d_vol: D^3 floats, [z][y][x], Xmipp origin.
  *   project == project(rot, tilt, psi, ctf) + projection() for n orientations at once
  *              (fourier_projection.cpp:91-245); h_angles: n x (rot, tilt, psi) degrees; d_ctf: optional
- *              [D][D/2+1] doubles multiplied onto the slice; d_out: n x D x D floats.
+ *              [D][D/2+1] doubles multiplied onto the slice; d_out: n x D x D floats. n = 0 does nothing
+ *              and reads neither pointer.
  * Only cubic B-spline interpolation (the program's default) is implemented; degree 0/1 fail loudly. */
 typedef struct xh_fp xh_fp;
 int xh_fp_create(xh_ctx *ctx, const float *d_vol, int32_t D, double padding, double max_freq,

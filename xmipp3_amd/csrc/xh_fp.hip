@@ -314,7 +314,8 @@ int xh_fp_coefs(const xh_fp *fp, double *h_re, double *h_im)
 
 int xh_fp_project(xh_fp *fp, const double *h_angles, int32_t n, const double *d_ctf, float *d_out)
 {
-    XH_CHECK(fp && h_angles && d_out && n >= 0, XH_ERR_ARG, "xh_fp_project: bad argument");
+    // no projections: nothing to read or write, and an empty stack has no address
+    XH_CHECK(fp && n >= 0 && (n == 0 || (h_angles && d_out)), XH_ERR_ARG, "xh_fp_project: bad argument");
     XH_HIP(hipSetDevice(fp->ctx->device));
     if (n == 0) return XH_OK;
     xh_ctx *ctx = fp->ctx;

@@ -833,6 +833,63 @@ int xh_asa_refine(xh_asa *h, double *h_vars, double *h_cost, int32_t *h_enabled,
 /* of the last xh_asa_cost or xh_asa_refine: device steps, rows evaluated on the device, seconds inside device steps, seconds in all */
 int xh_asa_stats(const xh_asa *h, double *h_stats);
 
+/* ---- xmipp_forward_art_zernike3d (reconstruction_adapt_cuda11/forward_art_zernike3d_gpu.cpp, reconstruction_cuda11/
+ * cuda_forward_art_zernike3d.{cpp,cu}) ----
+ * ART reconstruction of the undeformed volume from particles that each carry a pose and a Zernike3D deformation: per image the volume
+ * is splatted through the image's field onto P and W planes (one pair per sigma), the planes are Gaussian-filtered, the residual against
+ * the shifted (and CTF-inverted) particle is formed, and the residual is spread back along the same field, plus a regulariser. The
+ * volume and the regulariser's four fields stay on the device over the whole run; a sweep over many images is one stream of kernels.
+ * Everything is fp64. The contract and the deviations from the reference are at the head of xmipp3_amd/csrc/xh_faz.hip. */
+typedef struct xh_faz xh_faz;
+typedef struct {
+    double RDef, sampling, lambda, ltv, ltk, ll1, lst;      /* --RDef, --sampling, --regularization, --ltv, --ltk, --ll1, --lst */
+    int32_t l1, l2, step, use_zernike, use_ctf, phase_flipped;
+} xh_faz_params;
+/* one particle's input row (processImage :401-431) */
+typedef struct {
+    double rot, tilt, psi, shift_x, shift_y;
+    int32_t flip, has_ctf;
+    xh_ctf_params ctf;      /* read when has_ctf and use_ctf (readFromMdRow); Tm is replaced by --sampling */
+} xh_faz_row;
+/* the program's defaults (defineParams :132-168) */
+void xh_faz_defaults(xh_faz_params *p);
+/* host only: sortOrthogonal (:628-690) over n projection directions (rot, tilt in degrees); sort_last = --sort_last (-1: all). order [n] */
+int xh_faz_sort_orthogonal(int32_t n, const double *h_rot, const double *h_tilt, int32_t sort_last, int32_t *h_order);
+/* host only: the schedule of --save_iter over one iteration of n images (:587-592): h_flags[k] = 1 when the partial volume is written
+ * after the k-th image */
+int xh_faz_save_schedule(int32_t n, int32_t save_iter, int32_t *h_flags);
+/* host only: the checks a program makes before it touches a device: the degrees, and the length of a coefficient vector against
+ * 3 vecSize (ncoef < 0: not checked) */
+int xh_faz_check(int32_t l1, int32_t l2, int32_t ncoef);
+/* preProcess (:175-380). D: the side of the volume and of the images (<= 1024). h_V0 [D][D][D] doubles (host; null: zeros). h_maskF /
+ * h_maskB [D][D][D] int32 (host): a mask read from a file, set to 0 here where k^2 + i^2 + j^2 >= RDef^2; null: the sphere
+ * k^2 + i^2 + j^2 <= RDef^2. h_sigma [nsigma] (1 .. 8). h_sym [nsym][9] (nullable, nsym 0): the right matrices of the symmetry group
+ * without the identity; every image is then presented once per matrix, the identity first, with the rotation E R_sym. */
+int xh_faz_create(xh_ctx *ctx, int32_t D, const double *h_V0, const int32_t *h_maskF, const int32_t *h_maskB, const double *h_sigma,
+                  int32_t nsigma, const double *h_sym, int32_t nsym, const xh_faz_params *prm, xh_faz **out);
+int xh_faz_destroy(xh_faz *h);
+/* RDef as resolved, vecSize, the bricks of the forward list, the presentations per image (1 + nsym); null pointers are skipped */
+int xh_faz_info(const xh_faz *h, double *RDef, int32_t *vecSize, int32_t *nbricks, int32_t *per_image);
+/* n particles h_images [n][ydim][xdim] (host) with their rows and, with use_zernike, their coefficients h_coef [n][3 vecSize] (cx of every
+ * term, then cy, then cz: the sphCoefficients vector); replaces what was loaded. Step 4 of the contract (CTF inversion, shift and flip)
+ * runs here for all of them. */
+int xh_faz_load(xh_faz *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_faz_row *rows, const double *h_coef);
+/* steps 2-7 for the loaded images first .. first + count - 1 in order, every presentation of an image in turn, without a host
+ * synchronisation in between; h_errors [count][per_image]: sqrt(sum diff^2 / N) of every presentation (NaN when no pixel has weight) */
+int xh_faz_sweep(xh_faz *h, int32_t first, int32_t count, double *h_errors);
+/* steps 2-5 for presentation `sym` (0: the identity) of loaded image `index` against the current volume, which is not updated. Device
+ * outputs, doubles, null pointers skipped: raw and filtered P and W [nsigma][D][D], Idiff, Iws and the prepared particle [D][D]. */
+int xh_faz_forward(xh_faz *h, int32_t index, int32_t sym, double *d_P_raw, double *d_W_raw, double *d_P, double *d_W, double *d_Idiff,
+                   double *d_Iws, double *d_particle, double *h_error);
+/* the refined volume [D][D][D] doubles (host) */
+int xh_faz_get_volume(xh_faz *h, double *h_V);
+int xh_faz_set_volume(xh_faz *h, const double *h_V);
+/* for the benchmark: with timing on, a sweep records events around its stages (they do not synchronise; the sweep still waits once, at
+ * its end) and xh_faz_stage_ms returns the milliseconds of the last sweep, summed over its presentations: h_ms[5] = the splat (with the
+ * clearing of the planes), the filter (conversion, two transforms, the multiply), the residual, the regulariser, the backward kernel */
+int xh_faz_set_timing(xh_faz *h, int32_t on);
+int xh_faz_stage_ms(const xh_faz *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,15 @@ class AsaRow(C.Structure):
                                                                                           ("ctf", CtfParams)]
 
 
+class FazParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("RDef", "sampling", "lambda_", "ltv", "ltk", "ll1", "lst")] + [
+        (n, C.c_int32) for n in ("l1", "l2", "step", "use_zernike", "use_ctf", "phase_flipped")]
+
+
+class FazRow(C.Structure):
+    _fields_ = AsaRow._fields_
+
+
 # every symbol include/xmipp_hip.h declares: name -> (restype, argtypes)
 vp, i32, i64, d, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 pvp = C.POINTER(C.c_void_p)
@@ -192,6 +201,20 @@ SIGNATURES = {
     "xh_asa_last": (C.c_int, [vp, i32, vp, vp, vp, vp]),
     "xh_asa_refine": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "xh_asa_stats": (C.c_int, [vp, vp]),
+    "xh_faz_defaults": (None, [C.POINTER(FazParams)]),
+    "xh_faz_sort_orthogonal": (C.c_int, [i32, vp, vp, i32, vp]),
+    "xh_faz_save_schedule": (C.c_int, [i32, i32, vp]),
+    "xh_faz_check": (C.c_int, [i32, i32, i32]),
+    "xh_faz_create": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(FazParams), pvp]),
+    "xh_faz_destroy": (C.c_int, [vp]),
+    "xh_faz_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "xh_faz_load": (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
+    "xh_faz_sweep": (C.c_int, [vp, i32, i32, vp]),
+    "xh_faz_forward": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
+    "xh_faz_get_volume": (C.c_int, [vp, vp]),
+    "xh_faz_set_volume": (C.c_int, [vp, vp]),
+    "xh_faz_set_timing": (C.c_int, [vp, i32]),
+    "xh_faz_stage_ms": (C.c_int, [vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

@@ -9,7 +9,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import AsaParams, AsaRow, Ca2Params, Ca2Row, CtfParams, RfParams, XhError, check, lib
+from ._lib import AsaParams, AsaRow, FazParams, FazRow, Ca2Params, Ca2Row, CtfParams, RfParams, XhError, check, lib
 
 
 def _torch():
@@ -1280,6 +1280,130 @@ class AngularSphAlignment(_LockstepRows):
         en, it, ev = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
         check(lib().xh_asa_refine(self.h, _np_ptr(x), _np_ptr(cost), _np_ptr(en), _np_ptr(de), _np_ptr(it), _np_ptr(ev)))
         return x, cost, en, de, it, ev
+
+
+def faz_sort_orthogonal(rot, tilt, sort_last=2):
+    """the order in which xmipp_forward_art_zernike3d presents its images: every next direction has the smallest sum of |dot products| with
+    the last `sort_last` ones presented (-1: with all of them); rot, tilt in degrees (host only)"""
+    rot = np.ascontiguousarray(rot, np.float64).reshape(-1)
+    tilt = np.ascontiguousarray(tilt, np.float64).reshape(-1)
+    assert rot.shape == tilt.shape
+    out = np.zeros(rot.shape[0], np.int32)
+    check(lib().xh_faz_sort_orthogonal(rot.shape[0], _np_ptr(rot), _np_ptr(tilt), int(sort_last), _np_ptr(out)))
+    return out
+
+
+def faz_save_schedule(n, save_iter):
+    """--save_iter over one iteration of n images: [n] flags, 1 where the partial volume is written after that image (host only)"""
+    out = np.zeros(int(n), np.int32)
+    check(lib().xh_faz_save_schedule(int(n), int(save_iter), _np_ptr(out)))
+    return out
+
+
+class ForwardArtZernike3D(_Handle):
+    """Device side of xmipp_forward_art_zernike3d: ART reconstruction of the undeformed volume of side D from particles with a pose and
+    Zernike3D coefficients. volume: float64 [D, D, D] (numpy; None: zeros); maskf / maskb: int32 [D, D, D] (numpy; None: the sphere of
+    radius RDef); sigma: the Gaussian sigmas; sym: [nsym, 3, 3] right matrices of the symmetry group without the identity. Keyword
+    arguments are the fields of xh_faz_params (lam is --regularization). The volume stays on the device between calls."""
+
+    _destroy = "xh_faz_destroy"
+
+    def __init__(self, ctx, D, volume=None, maskf=None, maskb=None, sigma=(2.0,), sym=None, **params):
+        self.D = int(D)
+        self.params = FazParams()
+        lib().xh_faz_defaults(C.byref(self.params))
+        for k, v in params.items():
+            k = "lambda_" if k in ("lam", "lambda_") else k
+            if not hasattr(self.params, k):
+                raise XhError(f"ForwardArtZernike3D: unknown parameter {k}")
+            setattr(self.params, k, v)
+
+        def vol(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape != (self.D,) * 3:
+                raise XhError(f"ForwardArtZernike3D: {what} of shape {a.shape} against a volume of size {self.D} (not supported)")
+            return a
+        volume, maskf, maskb = vol(volume, np.float64, "a volume"), vol(maskf, np.int32, "a mask"), vol(maskb, np.int32, "a mask")
+        sg = np.ascontiguousarray(sigma, np.float64).reshape(-1)
+        s = None if sym is None else np.ascontiguousarray(sym, np.float64).reshape(-1, 9)
+        self.nsigma = sg.shape[0]
+        self.n = 0
+        h = C.c_void_p()
+        check(lib().xh_faz_create(ctx.h, self.D, _np_ptr(volume), _np_ptr(maskf), _np_ptr(maskb), _np_ptr(sg), self.nsigma, _np_ptr(s),
+                                  0 if s is None else s.shape[0], C.byref(self.params), C.byref(h)))
+        super().__init__(ctx, h)
+        rd, vs, nb, per = C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().xh_faz_info(self.h, C.byref(rd), C.byref(vs), C.byref(nb), C.byref(per)))
+        self.RDef, self.vecSize, self.nbricks, self.per_image = rd.value, vs.value, nb.value, per.value
+
+    def load(self, images, rows=None, coefficients=None):
+        """images: [n, D, D] float32 (host); rows: per particle a dict with any of rot, tilt, psi, shift_x, shift_y, flip, ctf (a
+        CtfParams); coefficients: [n, 3 vecSize] (cx of every term, then cy, then cz), needed with use_zernike"""
+        img = np.ascontiguousarray(images, np.float32)
+        assert img.ndim == 3
+        n = img.shape[0]
+        co = None
+        if coefficients is not None:
+            co = np.ascontiguousarray(coefficients, np.float64)
+            if co.shape != (n, 3 * self.vecSize):
+                raise XhError(f"ForwardArtZernike3D.load: coefficients of shape {co.shape}, the degrees need ({n}, {3 * self.vecSize})")
+        arr = (FazRow * n)()
+        for i in range(n):
+            for k, v in (rows[i] if rows is not None else {}).items():
+                if not hasattr(arr[i], k) or k == "has_ctf":
+                    raise XhError(f"ForwardArtZernike3D.load: unknown column {k}")
+                if k == "ctf":
+                    if v is not None:
+                        arr[i].ctf, arr[i].has_ctf = v, 1
+                else:
+                    setattr(arr[i], k, int(v) if k == "flip" else float(v))
+        check(lib().xh_faz_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr, _np_ptr(co)))
+        self.n = n
+
+    def sweep(self, first=0, count=None):
+        """forward, residual, regulariser and update for the loaded images first .. first + count - 1 in order -> errors [count, per_image]"""
+        count = self.n - first if count is None else int(count)
+        err = np.zeros((count, self.per_image))
+        check(lib().xh_faz_sweep(self.h, int(first), count, _np_ptr(err)))
+        return err
+
+    def forward(self, index, sym=0):
+        """the forward model of one presentation against the current volume, which is not updated -> dict of float64 cuda tensors P_raw,
+        W_raw, P, W [nsigma, D, D], Idiff, Iws, particle [D, D], and error"""
+        torch = _torch()
+        D, S = self.D, self.nsigma
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.ctx.torch_device)  # noqa: E731
+        out = {"P_raw": mk(S, D, D), "W_raw": mk(S, D, D), "P": mk(S, D, D), "W": mk(S, D, D), "Idiff": mk(D, D), "Iws": mk(D, D),
+               "particle": mk(D, D)}
+        err = C.c_double()
+        check(lib().xh_faz_forward(self.h, int(index), int(sym), *[_ptr(out[k]) for k in ("P_raw", "W_raw", "P", "W", "Idiff", "Iws", "particle")],
+                                   C.byref(err)))
+        out["error"] = err.value
+        return out
+
+    def get_volume(self):
+        out = np.empty((self.D,) * 3)
+        check(lib().xh_faz_get_volume(self.h, _np_ptr(out)))
+        return out
+
+    def set_volume(self, volume):
+        v = np.ascontiguousarray(volume, np.float64)
+        assert v.shape == (self.D,) * 3
+        check(lib().xh_faz_set_volume(self.h, _np_ptr(v)))
+
+    STAGES = ("splat", "filter", "residual", "regulariser", "backward")
+
+    def set_timing(self, on=True):
+        """sweeps record events around their stages (the benchmark's switch)"""
+        check(lib().xh_faz_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        """milliseconds per stage of the last timed sweep, summed over its presentations"""
+        ms = np.zeros(len(self.STAGES))
+        check(lib().xh_faz_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
 
 
 class ProjectionMatcher(_Handle):

@@ -7,7 +7,8 @@
 //   xh_ctfops.hip, xh_ca2.hip, xh_asa.hip (through xh_image2d.h)   degrees, as the metadata holds it: side_info converts, like
 //                                                                  ctf_phase_flip.cpp:99 and wiener2d.cpp:149 before produceSideInfo
 //   xh_rf.hip (the gridder's CTF planes, xh_rf2's scatter),        as it is: readFromMdRow passes the column on and so do these
-//   host/ctf_model.h (the matcher's --ctf gallery filter)
+//   host/ctf_model.h (the matcher's --ctf gallery filter),
+//   xh_faz.hip (the ART's CTFINV filter)
 #ifndef XH_CTF_H
 #define XH_CTF_H
 #include <cmath>

@@ -1,6 +1,7 @@
-// xh_image2d.h -- the particle-image pieces shared by the continuous assignment (xh_ca2.hip) and the Zernike3D alignment (xh_asa.hip), in
-// doubles: FourierFilter's raised-cosine low pass with a row's CTF factor (xh_k_lowpass_ctf), the particle load through it
-// (xh_lowpass_images), the 2-D circular mask, applyGeometry's LINEAR branch and the masked correlation index of a cost kernel.
+// xh_image2d.h -- the particle-image pieces shared by the continuous assignment (xh_ca2.hip), the Zernike3D alignment (xh_asa.hip) and
+// the Zernike3D ART reconstruction (xh_faz.hip), in doubles: FourierFilter's raised-cosine low pass with a row's CTF factor
+// (xh_k_lowpass_ctf), its CTFINV mask (xh_k_ctfinv), the particle load through the low pass (xh_lowpass_images), the 2-D circular mask,
+// applyGeometry's LINEAR branch and the masked correlation index of a cost kernel.
 #ifndef XH_IMAGE2D_H
 #define XH_IMAGE2D_H
 #include "xh_common.h"
@@ -59,6 +60,31 @@ xh_k_lowpass_ctf(xh_cd *__restrict__ F, size_t total, int D, double w1, double r
                 m *= v;
             }
         }
+    }
+    const xh_cd v = F[idx];
+    F[idx] = xh_cd{v.x * m, v.y * m};
+}
+
+// FourierFilter CTFINV (fourier_filter.cpp:533-541) on the full spectra F [images][D][D], the 1 / D^2 of the inverse folded in: 0 where
+// |ctf| <= minCTF, else 1 / ctf, with ctf = getValueAt with its damping (its absolute value when phaseFlipped); an image whose row says it
+// has no CTF is only normalised. Rows and the half-spectrum index are those of xh_k_lowpass_ctf. A template, so that only the files that
+// launch it hold it.
+template <bool PHASE_FLIPPED>
+__global__ void __launch_bounds__(256)
+xh_k_ctfinv(xh_cd *__restrict__ F, size_t total, int D, const double *__restrict__ rows, int stride, int ctf, double iTs, double minCTF)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int j = idx % D, i = (idx / D) % D;
+    double m = 1.0 / ((double)D * (double)D);
+    const double *q = rows + (size_t)stride * (idx / ((size_t)D * D)) + ctf;
+    if (q[0] != 0.0) {
+        D_CTF_SIDE_FROM_ROW(s, q + 1)
+        int ih = i, jh = j;
+        if (jh > D / 2) { jh = D - jh; ih = (D - ih) % D; }
+        double v = d_ctf_at(s, d_digfreq(jh, D) * iTs, d_digfreq(ih, D) * iTs, true);
+        if (PHASE_FLIPPED) v = fabs(v);
+        m = fabs(v) <= minCTF ? 0.0 : m / v;
     }
     const xh_cd v = F[idx];
     F[idx] = xh_cd{v.x * m, v.y * m};

@@ -1,6 +1,7 @@
-// xh_zernike.h -- the Zernike3D basis and the trilinear sampler shared by xmipp_volume_deform_sph (xh_vds.hip) and
-// xmipp_angular_sph_alignment (xh_asa.hip): the radial polynomials, the solid harmonics, the term count, the displacement of one voxel
-// and interpolatedElement3D; and the host side both programs need before a launch: the degree check, the packing of a coefficient vector
+// xh_zernike.h -- the Zernike3D basis and the trilinear sampler shared by xmipp_volume_deform_sph (xh_vds.hip),
+// xmipp_angular_sph_alignment (xh_asa.hip) and xmipp_forward_art_zernike3d (xh_faz.hip, the basis alone): the radial polynomials, the
+// solid harmonics, the term count, the displacement of one voxel and interpolatedElement3D; and the host side the programs need before a
+// launch: the degree check, the packing of a coefficient vector
 // with its effective l2, and the table of compiled (L1, L2) pairs. The mathematics and the reference's S_4^0 exception are described at
 // the head of xh_vds.hip.
 #ifndef XH_ZERNIKE_H

@@ -54,6 +54,7 @@ struct XhDestroy {
     void operator()(xh_ca2 *h) const { xh_ca2_destroy(h); }
     void operator()(xh_vds *h) const { xh_vds_destroy(h); }
     void operator()(xh_asa *h) const { xh_asa_destroy(h); }
+    void operator()(xh_faz *h) const { xh_faz_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 

@@ -30,7 +30,7 @@ namespace mc {
 
 // ------------------------------------------------------------------ errors
 enum ErrorType { ERR_ARG_BADCMDLINE = 1, ERR_ARG_INCORRECT = 2, ERR_ARG_MISSING = 3, ERR_IO_NOTEXIST = 20, ERR_IO_NOREAD = 21,
-                 ERR_MD_NOOBJ = 30, ERR_MD_BADLABEL = 31, ERR_MULTIDIM_SIZE = 40, ERR_MATRIX_DIM = 41, ERR_VALUE_INCORRECT = 50,
+                 ERR_MD_NOOBJ = 30, ERR_MD_BADLABEL = 31, ERR_MD_MISSINGLABEL = 32, ERR_MULTIDIM_SIZE = 40, ERR_MATRIX_DIM = 41, ERR_VALUE_INCORRECT = 50,
                  ERR_GPU = 60, ERR_NOT_IMPLEMENTED = 61, ERR_LOGIC_ERROR = 62 };
 struct XmippError : public std::runtime_error {
     int code;
@@ -100,6 +100,11 @@ public:
                 size_t j = line.find(q, i + 1);
                 if (j == std::string::npos) j = line.size();
                 t.push_back(line.substr(i + 1, j - i - 1));
+                i = j + 1;
+            } else if (line[i] == '[') {      // a vector written unquoted, "[ v0 v1 ... ]" (sphCoefficients): one value, brackets kept
+                size_t j = line.find(']', i + 1);
+                if (j == std::string::npos) j = line.size() - 1;
+                t.push_back(line.substr(i, j - i + 1));
                 i = j + 1;
             } else {
                 size_t j = i;

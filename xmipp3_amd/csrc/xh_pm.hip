@@ -2182,7 +2182,9 @@ k_pm_idft_dump(const float4 *__restrict__ raw, float *__restrict__ out, const xh
 // of 1e3 the fp32 map is off by ~6e-5 of its peak, ten times s6_eps. Every image therefore enters a transform multiplied by
 // the power of two 2^e that brings its RMS into [0.5, 1), and its map leaves multiplied by 2^-(e_ref + e_img): both steps
 // are exact, so a map is computed as that of unit-scale inputs (both halves of every packing of one size) whatever the
-// scales, and is returned at the scale of the input. z itself (statisticsAdjust, correlationIndex) stays unscaled.
+// scales, and is returned at the scale of the input. z itself (statisticsAdjust, correlationIndex) stays unscaled. The coarse
+// pass never stores that z: its row kernel packs the rotated reference (a real plane) with the particle's own row on the way
+// into LDS, and its bestShift takes the particle's bands from the particle (d_s6_mimg): 256 KB less written and read per particle.
 // Blank: the reference's correlation map of an image whose pixels are all equal, or of an all-zero reference, is constant;
 // statisticsAdjust makes it zero (sd == 0) and bestShift returns (0, 0) -- or, where the rounding of the reference's own sums
 // leaves sd != 0, a one-element window in the map's corner that max_shift (at most D / 2 by default) rejects. On the device
@@ -2270,6 +2272,15 @@ k_pm_s6_scale(const float *__restrict__ parts, const int *__restrict__ refno, co
         const bool blank = r.y || (mn == mx && (!flip[p] || mx == 0));
         out[p] = make_int4(r.x, e, blank ? 1 : 0, 0);
     }
+}
+// Mimg (APM:820-828) read from the particle itself, pixel (row offset ro = i * D, column j): the coarse pass keeps no copy of it.
+// flip: applyGeometry(LINEAR, A = diag(-1,1,1), IS_INV, DONT_WRAP) is an exact copy of source column 2 cen - j; the mirrored
+// coordinate cen - j leaves [minp - 1e-6, maxp + 1e-6] exactly where that column is D (column 0 of an even box): 0 there.
+__device__ __forceinline__ float d_s6_mimg(const float *__restrict__ img, int ro, int j, int D, bool fl)
+{
+    if (!fl) return img[ro + j];
+    const int js = 2 * (D / 2) - j;
+    return js < D ? img[ro + js] : 0.f;
 }
 
 // =========================================================================== S6 (fp64)
@@ -2585,8 +2596,8 @@ k_pm_bestshift(const T *__restrict__ Rraw, int rstride, const xh_c2<T> *__restri
 #define XH_BS_BAND 16
 #endif
 __global__ void __launch_bounds__(256)
-k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ zimg, const int *__restrict__ refno,
-                      const unsigned char *__restrict__ flip, int D, double maxShift, double *__restrict__ shiftX,
+k_pm_bestshift_coarse(const float *__restrict__ Rraw, const float *__restrict__ zref, const float *__restrict__ particles,
+                      const int *__restrict__ refno, const unsigned char *__restrict__ flip, int D, double maxShift, double *__restrict__ shiftX,
                       double *__restrict__ shiftY, double *__restrict__ maxCC, const XhTrPart *__restrict__ part, int nparts,
                       unsigned char *__restrict__ flag, double eps, const int4 *__restrict__ sc)
 {
@@ -2689,7 +2700,9 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
     __syncthreads();
     const double ox = sh[0], oy = sh[1];
     // ---- translate(LINEAR, Mimg, (ox, oy), WRAP) + correlationIndex(Mref, Mtrans) (APM:850-851)
-    const xh_cf *Z = zimg + (size_t)p * n;    // .x = Mref, .y = Mimg
+    const float *Mr = zref + (size_t)p * n;   // Mref (k_pm_tr_build); Mimg is the particle itself, mirrored by the read (d_s6_mimg)
+    const float *img = particles + (size_t)p * n;
+    const bool fl = flip[p] != 0;
     // out(x, y) samples Mimg at (x - ox, y - oy).  The taps of a column (row) depend on the column (row) only: every thread keeps
     // its column's (256 is a multiple of D, so a thread stays in one column), the rows' go through LDS -- found with the reference's
     // own expressions (translate -> applyGeometry LINEAR, WRAP: a coordinate up to half a pixel before the first sample is NOT
@@ -2736,7 +2749,7 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
         if (contig) {
             float st[XH_BS_BAND + 1];
 #pragma unroll
-            for (int r = 0; r < XH_BS_BAND + 1; ++r) st[r] = Z[(((rb + r) & msk) << lgD) + threadIdx.x].y;
+            for (int r = 0; r < XH_BS_BAND + 1; ++r) st[r] = d_s6_mimg(img, ((rb + r) & msk) << lgD, threadIdx.x, D, fl);
 #pragma unroll
             for (int r = 0; r < XH_BS_BAND + 1; ++r) sImg[r][threadIdx.x] = st[r];
         }
@@ -2744,17 +2757,22 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
 #pragma unroll 4
         for (int rr = 0; rr < XH_BS_BAND; ++rr) {
             const int i = i0 + rr, t = (i << lgD) + threadIdx.x;
-            const xh_cf zc = Z[t];
+            const float mref = Mr[t];
             const float wyv = sWy[i];
             float q00, q01, q10, q11;
             if (contig) { q00 = sImg[rr][m1]; q01 = sImg[rr][m2]; q10 = sImg[rr + 1][m1]; q11 = sImg[rr + 1][m2]; }
             else {
                 const int r1 = sN1[i], r2 = sN2[i];
-                q00 = Z[r1 + m1].y; q01 = Z[r1 + m2].y; q10 = Z[r2 + m1].y; q11 = Z[r2 + m2].y;
+                q00 = d_s6_mimg(img, r1, m1, D, fl); q01 = d_s6_mimg(img, r1, m2, D, fl);
+                q10 = d_s6_mimg(img, r2, m1, D, fl); q11 = d_s6_mimg(img, r2, m2, D, fl);
             }
             const float wy_1 = 1.f - wyv, wx_1 = 1.f - wx;
-            const float vf = wy_1 * (wx_1 * q00 + wx * q01) + wyv * (wx_1 * q10 + wx * q11);
-            const double val = (double)vf, rr_ = (double)zc.x;
+            // Every rounding written out. Left to the compiler, which product of a sum it fuses into the add depends on the code
+            // around the expression (this loop and the one below came out differently, and a change to the loads turned this
+            // one round): one fp32 rounding per pixel, 1e-9 of cc. This form is the one the results have had since round 5.
+            const float top = __fmaf_rn(wx, q01, __fmul_rn(wx_1, q00)), bot = __fmaf_rn(wx, q11, __fmul_rn(wx_1, q10));
+            const float vf = __fadd_rn(__fmul_rn(wy_1, top), __fmul_rn(wyv, bot));
+            const double val = (double)vf, rr_ = (double)mref;
             sx += rr_; sxx += rr_ * rr_; sy += val; syy += val * val; sxy += rr_ * val;
         }
         __syncthreads();
@@ -2765,20 +2783,22 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int t = t0 + u * 256;
-            const xh_cf zc = Z[t];
-            r[u] = zc.x; q00[u] = zc.y; q01[u] = q10[u] = q11[u] = 0.f; wy[u] = 0.f;
-            if (!ident) {
+            r[u] = Mr[t]; q01[u] = q10[u] = q11[u] = 0.f; wy[u] = 0.f;
+            if (ident) q00[u] = d_s6_mimg(img, t & ~msk, t & msk, D, fl);
+            else {
                 const int i = t >> lgD;
                 const int r1 = sN1[i], r2 = sN2[i];
                 wy[u] = sWy[i];
-                q00[u] = Z[r1 + m1].y; q01[u] = Z[r1 + m2].y;
-                q10[u] = Z[r2 + m1].y; q11[u] = Z[r2 + m2].y;
+                q00[u] = d_s6_mimg(img, r1, m1, D, fl); q01[u] = d_s6_mimg(img, r1, m2, D, fl);
+                q10[u] = d_s6_mimg(img, r2, m1, D, fl); q11[u] = d_s6_mimg(img, r2, m2, D, fl);
             }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float wy_1 = 1.f - wy[u], wx_1 = 1.f - wx;
-            const float vf = ident ? q00[u] : (wy_1 * (wx_1 * q00[u] + wx * q01[u]) + wy[u] * (wx_1 * q10[u] + wx * q11[u]));
+            // (the same here; this loop's form: the other product of either sum is the fused one, and the rows' sum is fused too)
+            const float top = __fmaf_rn(wx_1, q00[u], __fmul_rn(wx, q01[u])), bot = __fmaf_rn(wx_1, q10[u], __fmul_rn(wx, q11[u]));
+            const float vf = ident ? q00[u] : __fmaf_rn(wy_1, top, __fmul_rn(wy[u], bot));
             const double val = (double)vf, rr = (double)r[u];
             sx += rr; sxx += rr * rr; sy += val; syy += val * val; sxy += rr * val;
         }
@@ -2800,7 +2820,8 @@ k_pm_bestshift_coarse(const float *__restrict__ Rraw, const xh_cf *__restrict__ 
 // The radix-2 kernels below spend log2(D) LDS round trips per line and the step took seven kernels
 // and ~15 MB of HBM traffic per 256-px particle. Here a thread keeps a whole radix-R butterfly in
 // registers (fp64), LDS is touched once per transform, and the step is three kernels:
-//   k_pm_tr_rows : build z = Mref + i*Mimg (APM:812-828), keep it for correlationIndex, forward row FFTs
+//   k_pm_tr_rows : build z = Mref + i*Mimg (APM:812-828), keep it for correlationIndex, forward row FFTs (the double-precision
+//                  chain; the coarse pass keeps Mref alone and reads Mimg from the particle, see k_pm_tr_build and d_s6_mimg)
 //   k_pm_tr_cols_pair: forward column FFTs, cross-power spectrum of the two packed images, inverse column
 //                  FFTs -- a block owns column pairs (kx, -kx) so the Hermitian partner is in LDS; two particles
 //                  share one inverse transform
@@ -2822,11 +2843,14 @@ __global__ void k_pm_tr_angles(const int *__restrict__ psi, double2 *__restrict_
     const double ang = (double)psi[p] * (360. / (double)N) * 3.14159265358979323846 / 180.0;
     cs[p] = make_double2(cos(ang), sin(ang));
 }
-template <typename T, typename TC>
+// ZT = xh_c2<T>: z = Mref + i Mimg (the double-precision chain). ZT = T: the rotated reference alone, a real plane (the coarse
+// pass: its consumers take the particle from where it already lies, see d_s6_mimg); particles and flip are not touched.
+template <typename T, typename TC, typename ZT>
 __global__ void __launch_bounds__(256)
 k_pm_tr_build(const float *__restrict__ particles, const TC *__restrict__ refCoef, const int *__restrict__ refno,
-              const double2 *__restrict__ cs, const unsigned char *__restrict__ flip, xh_c2<T> *__restrict__ z, int D)
+              const double2 *__restrict__ cs, const unsigned char *__restrict__ flip, ZT *__restrict__ z, int D)
 {
+    constexpr bool PLANE = sizeof(ZT) == sizeof(T);
     __shared__ T sC[XH_TRBW * XH_TRBW];       // T = double: the reference's arithmetic; float: the coarse pass of xh_pm_translate
     const int tid = threadIdx.x, p = blockIdx.y;
     const int tpr = D / XH_TRB;
@@ -2873,28 +2897,30 @@ k_pm_tr_build(const float *__restrict__ particles, const TC *__restrict__ refCoe
         }
     }
     __syncthreads();
-    const float *img = particles + (size_t)p * D * D;
-    xh_c2<T> *zp = z + (size_t)p * D * D;
-    const bool fl = flip[p] != 0;
+    ZT *zp = z + (size_t)p * D * D;
     const int j = tj0 + (tid & (XH_TRB - 1));
     // the particle's pixels first: four independent loads in flight under the interpolation
-    float pix[XH_TRB * XH_TRB / 256];
-    bool pixOk = ref >= 0;
-    int jsrc = j;
-    if (fl) {
-        const T mx = -(T)(j - cen);
-        pixOk = pixOk && !(mx < minp - (T)1e-6 || mx > maxp + (T)1e-6);
-        jsrc = 2 * cen - j;
+    float pix[XH_TRB * XH_TRB / 256];         // (unused, like particles and flip, where z is the reference plane alone)
+    if constexpr (!PLANE) {
+        const float *img = particles + (size_t)p * D * D;
+        const bool fl = flip[p] != 0;
+        bool pixOk = ref >= 0;
+        int jsrc = j;
+        if (fl) {
+            const T mx = -(T)(j - cen);
+            pixOk = pixOk && !(mx < minp - (T)1e-6 || mx > maxp + (T)1e-6);
+            jsrc = 2 * cen - j;
+        }
+#pragma unroll
+        for (int k = 0; k < XH_TRB * XH_TRB / 256; ++k) {
+            const int i = ti0 + (tid / XH_TRB) + (256 / XH_TRB) * k;
+            pix[k] = pixOk ? img[(unsigned)(i * D + jsrc)] : 0.f;
+        }
     }
 #pragma unroll
     for (int k = 0; k < XH_TRB * XH_TRB / 256; ++k) {
         const int i = ti0 + (tid / XH_TRB) + (256 / XH_TRB) * k;
-        pix[k] = pixOk ? img[(unsigned)(i * D + jsrc)] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < XH_TRB * XH_TRB / 256; ++k) {
-        const int i = ti0 + (tid / XH_TRB) + (256 / XH_TRB) * k;
-        xh_c2<T> out = xh_c2<T>{(T)0, (T)pix[k]};
+        xh_c2<T> out = xh_c2<T>{(T)0, PLANE ? (T)0 : (T)pix[k]};
         if (ref >= 0) {
             const T x = j - cen, y = i - cen;
             T xp = c * x - sn * y, yp = sn * x + c * y;
@@ -2929,7 +2955,8 @@ k_pm_tr_build(const float *__restrict__ particles, const TC *__restrict__ refCoe
                 out.x = columns;
             }
         }
-        zp[(unsigned)(i * D + j)] = out;
+        if constexpr (PLANE) zp[(unsigned)(i * D + j)] = out.x;
+        else zp[(unsigned)(i * D + j)] = out;
     }
 }
 
@@ -3177,10 +3204,12 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
     }
 }
 
-// fp32 pass of S6 (see xh_pm_translate): forward rows of the prebuilt z
+// fp32 pass of S6 (see xh_pm_translate): forward rows of z = Mref + i Mimg, formed here from the prebuilt reference plane and the
+// particle's own row (mirrored where flip says so; 0 for refno < 0, as the plane is)
 template <int R1, int R2>
 __global__ void __launch_bounds__(256)
-k_pm_s6f_rows(const xh_cf *__restrict__ z, xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, const int4 *__restrict__ sc)
+k_pm_s6f_rows(const float *__restrict__ zr, const float *__restrict__ particles, const int *__restrict__ refno,
+              const unsigned char *__restrict__ flip, xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, const int4 *__restrict__ sc)
 {
     typedef TrGeom<R1, R2, float> G;
     constexpr int D = G::D;
@@ -3192,15 +3221,38 @@ k_pm_s6f_rows(const xh_cf *__restrict__ z, xh_cf *__restrict__ w, const xh_cd *_
     for (int i = tid; i < D; i += 256) sW[i] = xh_cf{(float)WD[i].x, (float)WD[i].y};
     {
         // all of the thread's elements in flight before the first is stored (the plain loop compiles to load - wait - store)
-        constexpr int NE = G::LN * D / 256;
-        xh_cf in[NE];
+        // a thread takes two neighbouring pixels of either image per step: 8-byte loads, LN consecutive rows are one run. A
+        // mirrored row is the same run backwards; its pairs start at odd columns, so they come as two 4-byte loads.
+        constexpr int NE = G::LN * D / 512;
+        float2 re[NE], im[NE];
+        const float2 *zr2 = reinterpret_cast<const float2 *>(zr + ((size_t)p * D + row0) * D);
+        const float *img = particles + ((size_t)p * D + row0) * D;
+        const bool have = refno[p] >= 0, fl = flip[p] != 0;
 #pragma unroll
-        for (int u = 0; u < NE; ++u) in[u] = z[((size_t)p * D + row0) * D + tid + 256 * u];      // LN consecutive rows: one run
+        for (int u = 0; u < NE; ++u) re[u] = zr2[tid + 256 * u];
+        if (!have) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) im[u] = make_float2(0.f, 0.f);
+        } else if (!fl && ((uintptr_t)img & 7) == 0) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) im[u] = reinterpret_cast<const float2 *>(img)[tid + 256 * u];
+        } else if (!fl) {                              // a caller's pointer need not be aligned to more than its floats
+#pragma unroll
+            for (int u = 0; u < NE; ++u) im[u] = make_float2(img[2 * (tid + 256 * u)], img[2 * (tid + 256 * u) + 1]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = 2 * (tid + 256 * u), l = e / D, j = e - l * D;
+                im[u] = make_float2(d_s6_mimg(img, l * D, j, D, true), d_s6_mimg(img, l * D, j + 1, D, true));
+            }
+        }
         const int eR = sc[p].x, eI = sc[p].y;          // the balance (k_pm_s6_scale)
 #pragma unroll
         for (int u = 0; u < NE; ++u) {
-            const int e = tid + 256 * u, l = e / D, j = e - l * D;
-            s[l * G::LS + (j / R2) * G::S1 + (j % R2)] = xh_cf{ldexpf(in[u].x, eR), ldexpf(in[u].y, eI)};
+            const int e = 2 * (tid + 256 * u), l = e / D, j = e - l * D;
+            xh_cf *d = s + l * G::LS + (j / R2) * G::S1 + (j % R2);      // R2 is even: j + 1 is the next element of the same group
+            d[0] = xh_cf{ldexpf(re[u].x, eR), ldexpf(im[u].x, eI)};
+            d[1] = xh_cf{ldexpf(re[u].y, eR), ldexpf(im[u].y, eI)};
         }
     }
     __syncthreads();
@@ -4513,10 +4565,11 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
     const size_t trBytes = pm->tr_chunk_mb > 0 ? (size_t)pm->tr_chunk_mb << 20 : (size_t)4096u << 20;
     // grid.y carries the particle index: at most 65535 per launch
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n, 65535), trBytes / (per * sizeof(xh_cd))));
-    XH_TRY(xh_buf_reserve(ctx, pm->d_t1, sizeof(xh_cd) * per * chunk));
     XH_TRY(xh_buf_reserve(ctx, pm->d_t2, sizeof(xh_cd) * per * chunk));
     if (D == 64 || D == 128 || D == 256) {
-        // register-blocked three-kernel path
+        // register-blocked three-kernel path. z: the coarse pass keeps the rotated references alone, a real fp32 plane per particle;
+        // the double-precision chain keeps z = Mref + i Mimg of the particles it is given (all of them, or the flagged few)
+        XH_TRY(xh_buf_reserve(ctx, pm->d_t1, (pm->s6_fp32 && pm->s6_capture != 64 ? sizeof(float) : sizeof(xh_cd)) * per * chunk));
         XH_TRY(xh_buf_reserve(ctx, pm->d_t3, sizeof(double) * per * chunk));
         XH_TRY(xh_buf_reserve(ctx, pm->d_trAngles, sizeof(double2) * (size_t)chunk));
         XH_TRY(xh_buf_reserve(ctx, pm->d_trPart, sizeof(XhTrPart) * (size_t)chunk * 64));
@@ -4525,6 +4578,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         // the chain in double precision over m particles (the reference's arithmetic)
         auto chain64 = [&](const float *parts, const int *refno, const int *psi, const unsigned char *flip, int m, double *sx, double *sy,
                            double *cc) -> int {
+            XH_TRY(xh_buf_reserve(ctx, pm->d_t1, sizeof(xh_cd) * per * (size_t)m));     // after a coarse pass: that pass is done with its z
             xh_cd *z = (xh_cd *)pm->d_t1.p, *w = (xh_cd *)pm->d_t2.p;
             double *R = (double *)pm->d_t3.p;
             int nparts = 0;
@@ -4539,7 +4593,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         }                                                                                                                   \
         hipLaunchKernelGGL(k_pm_tr_angles, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, psi,                            \
                            (double2 *)pm->d_trAngles.p, m, L.N);                                                            \
-        hipLaunchKernelGGL((k_pm_tr_build<double, double>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream, \
+        hipLaunchKernelGGL((k_pm_tr_build<double, double, xh_cd>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream, \
                            parts, (const double *)pm->d_refCoef.p, refno,                                                   \
                            (const double2 *)pm->d_trAngles.p, flip, z, D);                                                  \
         hipLaunchKernelGGL((k_pm_tr_rows<A_, B_, true>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream,                \
@@ -4561,10 +4615,12 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
             XH_LAUNCH_CHECK();
             return XH_OK;
         };
-        // the same chain in fp32 with the ambiguity flags (see above); buffers are the first halves of the double-precision ones
+        // the same chain in fp32 with the ambiguity flags (see above); w and R are the first halves of the double-precision ones, z a real
+        // fp32 plane (a quarter of the double-precision z, which chain64 sizes for the particles it is given)
         auto chain32 = [&](const float *parts, const int *refno, const int *psi, const unsigned char *flip, int m, double *sx, double *sy,
                            double *cc, unsigned char *flag) -> int {
-            xh_cf *z = (xh_cf *)pm->d_t1.p, *w = (xh_cf *)pm->d_t2.p;
+            float *z = (float *)pm->d_t1.p;            // the rotated references, a real plane per particle
+            xh_cf *w = (xh_cf *)pm->d_t2.p;
             float *R = (float *)pm->d_t3.p;
             int nparts = 0;
             hipLaunchKernelGGL(k_pm_s6_scale, dim3(m), dim3(256), 0, ctx->stream, parts, refno, flip, (const int2 *)pm->d_refScale.p, (int)per, sc);
@@ -4573,10 +4629,10 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
         typedef TrGeom<A_, B_, float> G;                                                                                    \
         hipLaunchKernelGGL(k_pm_tr_angles, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, psi,                            \
                            (double2 *)pm->d_trAngles.p, m, L.N);                                                            \
-        hipLaunchKernelGGL((k_pm_tr_build<float, float>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream,   \
+        hipLaunchKernelGGL((k_pm_tr_build<float, float, float>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream, \
                            parts, (const float *)pm->d_refCoef32.p, refno, (const double2 *)pm->d_trAngles.p, flip, z, D);  \
-        hipLaunchKernelGGL((k_pm_s6f_rows<A_, B_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const xh_cf *)z, w, \
-                           (const xh_cd *)pm->d_WD64.p, (const int4 *)sc);                                                  \
+        hipLaunchKernelGGL((k_pm_s6f_rows<A_, B_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const float *)z, parts, \
+                           refno, flip, w, (const xh_cd *)pm->d_WD64.p, (const int4 *)sc);                                  \
         hipLaunchKernelGGL((k_pm_s6f_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
                            (const xh_cd *)pm->d_WD64.p, m);                                                                 \
         hipLaunchKernelGGL((k_pm_s6f_irows<A_, B_, true>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream,    \
@@ -4588,7 +4644,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
             else XH_TRF(16, 16)
 #undef XH_TRF
             XH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const xh_cf *)z, refno, flip, D, max_shift, sx, sy, cc,
+            hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const float *)z, parts, refno, flip, D, max_shift, sx, sy, cc,
                                (const XhTrPart *)pm->d_trPart.p, nparts, flag, pm->s6_eps, (const int4 *)sc);
             XH_LAUNCH_CHECK();
             return XH_OK;
@@ -4642,6 +4698,7 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
     }
     const XhPlan<double> &planD = pm->planD.plan;
     const int lpb = xh_plan_lpb(planD, 64 * 1024, 16);
+    XH_TRY(xh_buf_reserve(ctx, pm->d_t1, sizeof(xh_cd) * per * chunk));
     XH_TRY(xh_buf_reserve(ctx, pm->d_trScale, sizeof(int4) * (size_t)chunk));
     const int4 *sc = (const int4 *)pm->d_trScale.p;
     const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << planD.logM;

@@ -308,10 +308,16 @@ int xh_pm_rows_pruned(const xh_pm *pm, int64_t *rows_pruned);
  * A gallery with flat correlation peaks leaves a large part of the rows standing: when more than 10 % of a chunk's rows
  * survive, the next chunk (of this or of the next call) is contracted at every frequency with its coefficients kept, which
  * is cheaper from 9 % on; below 6 % it goes back (set_option "adaptive_finish" 0: never; get_option "dense_chunks": how
- * many chunks of the last call took that form). Identical results either way. */
+ * many chunks of the last call took that form). Identical results either way.
+ * Before the survivors' frequencies K0..nk-1 are contracted they are transformed from their frequencies below K0 alone: a row whose
+ * low-only maximum plus its Cauchy-Schwarz term lies more than 2 tau below the best (low-only maximum - term) of the particle cannot
+ * be the winner or a candidate of the re-score and is left out (set_option "low_pass" 0: every survivor is finished; identical
+ * results either way). get_option "low_pass_rows_in" / "low_pass_rows_out": the survivors of the last call that this test looked at
+ * and those it left to finish; "low_pass_rows_transformed": the low-only transforms it took (a particle's four planned rows had
+ * theirs already). xh_pm_rows_pruned keeps counting the rows the sums of moduli skipped. */
 int xh_pm_two_level_cut(const xh_pm *pm, int32_t *K0, int32_t *nk);
 /* tuning knobs: "tau_rel" (fp32 ambiguity margin relative to sum_r 2*pi*r), "chunk_rows" (rows per launch chunk), "prune", "k0",
- * "mask_lists", "group_high", "high_cap", "adaptive_finish", "tr_chunk_mb", "s6_fp32", "s6_eps", "s6_capture" (see above and below).
+ * "mask_lists", "group_high", "low_pass", "high_cap", "adaptive_finish", "tr_chunk_mb", "s6_fp32", "s6_eps", "s6_capture" (see above and below).
  * "threads" n (1..16): the reference program's --thr (angular_projection_matching.cpp:64,631,1018-1108).  Its n worker threads take
  * the positions i % n of a particle's neighbour list and their results are merged, worker 0 first, strictly greater wins -- which
  * only shows where two correlation values are EXACTLY equal (duplicated references): the winner is then the one with the smallest
@@ -320,7 +326,8 @@ int xh_pm_two_level_cut(const xh_pm *pm, int32_t *K0, int32_t *nk);
 int xh_pm_set_option(xh_pm *pm, const char *name, double value);
 /* current value of "tau_rel" (ambiguity margin of the fp32 coarse search, relative to sum_r 2 pi r) or "s6_eps" (margin of the
  * fp32 pass of xh_pm_translate, relative to the maximum of the correlation map): the tests hold the measured fp32 errors against them;
- * "adaptive_finish", "dense_chunks": see xh_pm_two_level_cut */
+ * "adaptive_finish", "dense_chunks", "low_pass", "low_pass_rows_in", "low_pass_rows_out", "low_pass_rows_transformed": see
+ * xh_pm_two_level_cut */
 int xh_pm_get_option(const xh_pm *pm, const char *name, double *value);
 
 /* ---- FourierProjector: central-slice projections of a volume ------------------

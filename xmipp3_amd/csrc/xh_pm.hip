@@ -138,8 +138,11 @@ struct xh_pm {
     XhBuf d_bpart, d_rowBound, d_rowTail, d_topRows, d_thr, d_survList, d_survSpan, d_highStore;
     int group_high;              // the surviving rows' frequencies >= K0 particle by particle (k_pm_rows_high; 0: each transforming wave its own, for A/B)
     int high_cap;                // rows of the store behind k_pm_rows_high (0: max(65536, rows / 16); the tests set a few to reach the rows beyond it)
+    int low_pass;                // the survivors' low frequencies first, a second threshold from them (k_pm_low_keep; 0: every survivor is finished, for A/B)
     int64_t stat_pruned;
+    int64_t stat_low_in, stat_low_out, stat_low_rows;      // last call: survivors the low pass looked at, those it kept, rows it transformed for that
     int lastPruneRows;           // rows of the last chunk that went through k_pm_survivors (0: none)
+    int lastLowPass;             // ... and whether its survivors went through k_pm_low_keep
     // A map with flat correlation peaks lets a third of the rows through the bounds, and a surviving row that contracts its own
     // frequencies (d_row_high, 410 KB of operands out of the L2s) costs 60 ns where the matrix cores contract a row for 4.3 ns and the
     // transform of a stored row takes 13.5: above ~9 % survivors the whole chunk is cheaper contracted at every frequency with its
@@ -1297,7 +1300,7 @@ __device__ __forceinline__ float4 d_row_high(const XhHigh &H, int slot, int ref,
 #endif
 // one ring's worth of a batch: x = the particle's coefficient, y[u] = the rows' references'
 #define XH_HIGH_STEP(x_, y_)                                    \
-    _Pragma("unroll") for (int u = 0; u < XH_HIGH_ROWS; ++u) {  \
+    _Pragma("unroll") for (int u = 0; u < NR; ++u) {            \
         acc[u].x = fmaf((x_).x, (y_)[u].x, acc[u].x);           \
         acc[u].y = fmaf((x_).x, (y_)[u].y, acc[u].y);           \
         acc[u].z = fmaf((x_).y, (y_)[u].x, acc[u].z);           \
@@ -1306,8 +1309,101 @@ __device__ __forceinline__ float4 d_row_high(const XhHigh &H, int slot, int ref,
 #ifndef XH_HIGH_UNROLL
 #define XH_HIGH_UNROLL 2            // rings in flight per lane (1 / 2 / 4: S3 1.90 / 1.91 / 1.95 ms per 4096 x 1000 rows)
 #endif
-// items[i] = (first list position, rows <= XH_HIGH_ROWS) of one particle (k_pm_survivors), *nitems of them: a workgroup takes one at a
-// time, so that a particle with a hundred surviving rows is spread over thirteen workgroups
+// One item: ns <= NR rows of one particle from list position pos0 on.  NR is the width of the batch the code is written for: after the
+// low pass (k_pm_low_keep) most particles have one row left, and a batch of XH_HIGH_ROWS would issue that row's loads and multiply-adds
+// eight times over; per row and frequency the multiply-adds and their order are the same at every width, so the same bits.
+template <int NR>
+__device__ __forceinline__ void d_rows_high_item(const XhHigh &H, const int *__restrict__ rowList, int pos0, int ns, const int *scoff,
+                                                 float4 *__restrict__ out)
+{
+    // (a narrow batch has few loads per ring: more rings in flight instead)
+    constexpr int UNR = NR <= 2 ? 8 / NR : XH_HIGH_UNROLL;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nkHigh = H.nk - H.K0, nchunks = (nkHigh + 63) / 64;
+    // the rows of the batch: wave-uniform (scalar registers), the lane's frequency comes in through the index alone
+    const xh_cf *a[NR], *b[NR];
+    bool same = true;
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        const int row = __builtin_amdgcn_readfirstlane(rowList[pos0 + (u < ns ? u : 0)]);
+        const int slot = row / H.nq, ref = row - slot * H.nq;
+        a[u] = H.A + (size_t)slot * H.ncoef;
+        b[u] = H.B + (size_t)ref * H.ncoef;
+        same = same && slot == __builtin_amdgcn_readfirstlane(rowList[pos0]) / H.nq;
+    }
+    // 64 frequencies at a time; a wave takes a long chunk (low frequencies: every ring) and then a short one
+    for (int j = 0;; ++j) {
+        const int c = (j & 1) ? (j + 1) * XH_HIGH_WAVES - 1 - wv : j * XH_HIGH_WAVES + wv;
+        if (c >= nchunks) break;
+        const int k = H.K0 + 64 * c + lane;
+        const bool live = k < H.nk;
+        const int rs = live ? H.rstart[k] : H.nrings;
+        // the rings every live frequency of the chunk reaches (r >= rhi), and the few before them that only the lower ones do
+        int rlo = rs, rhi = live ? rs : 0;
+        for (int o = 32; o > 0; o >>= 1) { rlo = min(rlo, __shfl_xor(rlo, o, 64)); rhi = max(rhi, __shfl_xor(rhi, o, 64)); }
+        rlo = __builtin_amdgcn_readfirstlane(rlo); rhi = __builtin_amdgcn_readfirstlane(rhi);
+        float4 acc[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (same && H.nrings <= 1024) {              // (the rows of a particle share its slot unless the search has 5-D translations)
+            for (int r = rlo; r < rhi; ++r) {
+                const int o = scoff[r] + k;
+                if (r >= rs) {
+                    const xh_cf x = a[0][o];
+                    xh_cf y[NR];
+#pragma unroll
+                    for (int u = 0; u < NR; ++u) y[u] = b[u][o];
+                    XH_HIGH_STEP(x, y)
+                }
+            }
+            if (live) {
+                int r = rhi;
+                for (; r + UNR <= H.nrings; r += UNR) {
+                    xh_cf x[UNR], y[UNR][NR];
+#pragma unroll
+                    for (int q = 0; q < UNR; ++q) {
+                        const int o = scoff[r + q] + k;
+                        x[q] = a[0][o];
+#pragma unroll
+                        for (int u = 0; u < NR; ++u) y[q][u] = b[u][o];
+                    }
+#pragma unroll
+                    for (int q = 0; q < UNR; ++q) XH_HIGH_STEP(x[q], y[q])
+                }
+                for (; r < H.nrings; ++r) {
+                    const int o = scoff[r] + k;
+                    const xh_cf x = a[0][o];
+                    xh_cf y[NR];
+#pragma unroll
+                    for (int u = 0; u < NR; ++u) y[u] = b[u][o];
+                    XH_HIGH_STEP(x, y)
+                }
+            }
+        } else {
+            for (int r = rlo; r < H.nrings; ++r) {
+                const int o = H.coff[r] + k;
+                if (r >= rs) {
+#pragma unroll
+                    for (int u = 0; u < NR; ++u) {
+                        const xh_cf x = a[u][o], y = b[u][o];
+                        acc[u].x = fmaf(x.x, y.x, acc[u].x);
+                        acc[u].y = fmaf(x.x, y.y, acc[u].y);
+                        acc[u].z = fmaf(x.y, y.x, acc[u].z);
+                        acc[u].w = fmaf(x.y, y.y, acc[u].w);
+                    }
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int u = 0; u < NR; ++u)
+                if (u < ns) out[(size_t)(pos0 + u) * nkHigh + (k - H.K0)] = acc[u];
+        }
+    }
+}
+#undef XH_HIGH_STEP
+// items[i] = (first list position, rows <= XH_HIGH_ROWS) of one particle (k_pm_survivors, k_pm_low_keep), *nitems of them: a workgroup
+// takes one at a time, so that a particle with a hundred surviving rows is spread over thirteen workgroups
 __global__ void __launch_bounds__(64 * XH_HIGH_WAVES)
 k_pm_rows_high(XhHigh H, const int *__restrict__ rowList, const int2 *__restrict__ items, const int *__restrict__ nitems,
                float4 *__restrict__ out)
@@ -1315,97 +1411,17 @@ k_pm_rows_high(XhHigh H, const int *__restrict__ rowList, const int2 *__restrict
     __shared__ int scoff[1024];
     for (int i = threadIdx.x; i < H.nrings && i < 1024; i += blockDim.x) scoff[i] = H.coff[i];
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nkHigh = H.nk - H.K0, nchunks = (nkHigh + 63) / 64;
     const int ni = *nitems;
     for (int item = blockIdx.x; item < ni; item += gridDim.x) {
         const int2 it = items[item];
         const int pos0 = it.x;
         if (pos0 >= H.highCap) continue;
         const int ns = min(it.y, H.highCap - pos0);
-        // the rows of the batch: wave-uniform (scalar registers), the lane's frequency comes in through the index alone
-        const xh_cf *a[XH_HIGH_ROWS], *b[XH_HIGH_ROWS];
-        bool same = true;
-#pragma unroll
-        for (int u = 0; u < XH_HIGH_ROWS; ++u) {
-            const int row = __builtin_amdgcn_readfirstlane(rowList[pos0 + (u < ns ? u : 0)]);
-            const int slot = row / H.nq, ref = row - slot * H.nq;
-            a[u] = H.A + (size_t)slot * H.ncoef;
-            b[u] = H.B + (size_t)ref * H.ncoef;
-            same = same && slot == __builtin_amdgcn_readfirstlane(rowList[pos0]) / H.nq;
-        }
-        // 64 frequencies at a time; a wave takes a long chunk (low frequencies: every ring) and then a short one
-        for (int j = 0;; ++j) {
-            const int c = (j & 1) ? (j + 1) * XH_HIGH_WAVES - 1 - wv : j * XH_HIGH_WAVES + wv;
-            if (c >= nchunks) break;
-            const int k = H.K0 + 64 * c + lane;
-            const bool live = k < H.nk;
-            const int rs = live ? H.rstart[k] : H.nrings;
-            // the rings every live frequency of the chunk reaches (r >= rhi), and the few before them that only the lower ones do
-            int rlo = rs, rhi = live ? rs : 0;
-            for (int o = 32; o > 0; o >>= 1) { rlo = min(rlo, __shfl_xor(rlo, o, 64)); rhi = max(rhi, __shfl_xor(rhi, o, 64)); }
-            rlo = __builtin_amdgcn_readfirstlane(rlo); rhi = __builtin_amdgcn_readfirstlane(rhi);
-            float4 acc[XH_HIGH_ROWS];
-#pragma unroll
-            for (int u = 0; u < XH_HIGH_ROWS; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (same && H.nrings <= 1024) {              // (the rows of a particle share its slot unless the search has 5-D translations)
-                for (int r = rlo; r < rhi; ++r) {
-                    const int o = scoff[r] + k;
-                    if (r >= rs) {
-                        const xh_cf x = a[0][o];
-                        xh_cf y[XH_HIGH_ROWS];
-#pragma unroll
-                        for (int u = 0; u < XH_HIGH_ROWS; ++u) y[u] = b[u][o];
-                        XH_HIGH_STEP(x, y)
-                    }
-                }
-                if (live) {
-                    int r = rhi;
-                    for (; r + XH_HIGH_UNROLL <= H.nrings; r += XH_HIGH_UNROLL) {
-                        xh_cf x[XH_HIGH_UNROLL], y[XH_HIGH_UNROLL][XH_HIGH_ROWS];
-#pragma unroll
-                        for (int q = 0; q < XH_HIGH_UNROLL; ++q) {
-                            const int o = scoff[r + q] + k;
-                            x[q] = a[0][o];
-#pragma unroll
-                            for (int u = 0; u < XH_HIGH_ROWS; ++u) y[q][u] = b[u][o];
-                        }
-#pragma unroll
-                        for (int q = 0; q < XH_HIGH_UNROLL; ++q) XH_HIGH_STEP(x[q], y[q])
-                    }
-                    for (; r < H.nrings; ++r) {
-                        const int o = scoff[r] + k;
-                        const xh_cf x = a[0][o];
-                        xh_cf y[XH_HIGH_ROWS];
-#pragma unroll
-                        for (int u = 0; u < XH_HIGH_ROWS; ++u) y[u] = b[u][o];
-                        XH_HIGH_STEP(x, y)
-                    }
-                }
-            } else {
-                for (int r = rlo; r < H.nrings; ++r) {
-                    const int o = H.coff[r] + k;
-                    if (r >= rs) {
-#pragma unroll
-                        for (int u = 0; u < XH_HIGH_ROWS; ++u) {
-                            const xh_cf x = a[u][o], y = b[u][o];
-                            acc[u].x = fmaf(x.x, y.x, acc[u].x);
-                            acc[u].y = fmaf(x.x, y.y, acc[u].y);
-                            acc[u].z = fmaf(x.y, y.x, acc[u].z);
-                            acc[u].w = fmaf(x.y, y.y, acc[u].w);
-                        }
-                    }
-                }
-            }
-            if (live) {
-#pragma unroll
-                for (int u = 0; u < XH_HIGH_ROWS; ++u)
-                    if (u < ns) out[(size_t)(pos0 + u) * nkHigh + (k - H.K0)] = acc[u];
-            }
-        }
+        if (ns == 1) d_rows_high_item<1>(H, rowList, pos0, ns, scoff, out);
+        else if (ns == 2) d_rows_high_item<2>(H, rowList, pos0, ns, scoff, out);
+        else d_rows_high_item<XH_HIGH_ROWS>(H, rowList, pos0, ns, scoff, out);
     }
 }
-#undef XH_HIGH_STEP
 
 template <int R1, int R2, int R3>
 __global__ void __launch_bounds__(256, 2)
@@ -1615,6 +1631,18 @@ __device__ __forceinline__ int d_row_ref(const RowMap &M, int row, int slot) { r
 // every row whose bound lies more than 2 tau below it (tau: the ambiguity margin of S4, so a skipped row can
 // be neither the winner nor a candidate for the fp64 re-score). The result is identical with or without
 // pruning; what is saved depends on the data (rows whose bound stays above the best are still transformed).
+//
+// The second stage (two-level contraction only; option "low_pass", k_pm_low_keep) applies the same argument once more before the
+// survivors' frequencies >= K0 are contracted, which is the expensive part of finishing a row (205 KB of a reference's coefficients
+// per row).  The sum of moduli is the loose part of the bound; the transform of a row's low frequencies alone costs a fraction of
+// finishing it, and every sample of the full row lies within rowTail of it (Cauchy-Schwarz over the frequencies >= K0, see
+// k_pm_prune_thr).  So with lb2 = max over the survivors of (low-only maximum - rowTail) <= G, the particle's maximum:
+//   - a dropped row has  full maximum <= low-only maximum + rowTail < lb2 - 2 tau <= G - 2 tau;
+//   - k_pm_select makes a row the winner or a candidate of the fp64 re-score only at or above G - tau;
+//   - the spare tau covers the fp32 difference between a low-only and a full transform of the same row (measured: at most
+//     4.1e-7 S against tau = 2e-6 S).
+// refno, psi, flip, the ambiguous particles and the candidate rows are therefore the same sets in the same order with the stage
+// on or off, and everything downstream of them bit for bit the same.
 #ifndef XH_PRUNE_T
 #define XH_PRUNE_T 4
 #endif
@@ -1761,24 +1789,118 @@ k_pm_prune_plan(const float2 *__restrict__ bpart, int nslices, size_t nrowsTotal
 __global__ void __launch_bounds__(256)
 k_pm_survivors(const float *__restrict__ rowBound, const float *__restrict__ thr, int rowsPerParticle, int nrows,
                RowRes *__restrict__ res, int *__restrict__ list, int *__restrict__ count, int2 *__restrict__ items, int *__restrict__ nitems,
-               int perItem)
+               int perItem, const int *__restrict__ topRows, int *__restrict__ lowCount)
 {
     // block per particle: its survivors are listed next to each other, so the four waves of a transforming workgroup
     // (which take four consecutive list entries) mostly work on one particle and share its coefficient rows in the caches
     // (the frequencies >= K0 of a surviving row are contracted by the wave that transforms it: 205 KB of the particle's and
     // 205 KB of the reference's coefficients per row)
+    // topRows given (the low pass follows, k_pm_low_keep): the list is what that pass has to transform, the survivors that are not
+    // among the particle's planned rows -- those were transformed from their low frequencies already -- and lowCount its length;
+    // count still receives every survivor
     __shared__ int sc[256];
-    __shared__ int sBase;
+    __shared__ int sBase, sAll;
     const int p = blockIdx.x, r0 = p * rowsPerParticle;
     const float t = thr[p];
-    int c = 0;
+    int planned[XH_PRUNE_T];
+#pragma unroll
+    for (int u = 0; u < XH_PRUNE_T; ++u) planned[u] = topRows ? topRows[p * XH_PRUNE_T + u] : -1;
+    if (threadIdx.x == 0) sAll = 0;
+    __syncthreads();
+    int c = 0, call = 0;
     for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256) {
         // (an off-list reference of a masked search carries -inf and is dropped whatever the threshold is: a NaN threshold --
         // a particle without variance -- prunes nothing else)
         const bool keep = rowBound[r] != -INFINITY && !(rowBound[r] < t);
         if (!keep) { RowRes q; q.best = -3.0e38f; q.idx = 0; q.second = -3.0e38f; q.pad = 0; res[r] = q; }
-        c += keep ? 1 : 0;
+        bool listed = keep;
+#pragma unroll
+        for (int u = 0; u < XH_PRUNE_T; ++u) listed = listed && r != planned[u];
+        c += listed ? 1 : 0;
+        call += keep ? 1 : 0;
     }
+    if (topRows && call) atomicAdd(&sAll, call);
+    sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                    // inclusive scan
+        const int v = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
+        __syncthreads();
+        sc[threadIdx.x] += v;
+        __syncthreads();
+    }
+    if (threadIdx.x == 255) {
+        const int cnt = sc[255];
+        if (topRows) {
+            sBase = cnt ? atomicAdd(lowCount, cnt) : 0;
+            if (sAll) atomicAdd(count, sAll);
+        } else
+            sBase = cnt ? atomicAdd(count, cnt) : 0;
+        if (items && cnt) {                                // the particle's stretch of the list in pieces of perItem rows (k_pm_rows_high)
+            const int nb = (cnt + perItem - 1) / perItem, ib = atomicAdd(nitems, nb);
+            for (int i = 0; i < nb; ++i) items[ib + i] = make_int2(sBase + i * perItem, min(perItem, cnt - i * perItem));
+        }
+    }
+    __syncthreads();
+    int o = sBase + sc[threadIdx.x] - c;
+    for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256) {
+        bool listed = rowBound[r] != -INFINITY && !(rowBound[r] < t);
+#pragma unroll
+        for (int u = 0; u < XH_PRUNE_T; ++u) listed = listed && r != planned[u];
+        if (listed) list[o++] = r;
+    }
+}
+
+// The second stage of the branch and bound (see the argument above k_pm_prune_plan).  Every survivor of the first stage now carries
+// the result of its low frequencies alone in res: the planned rows from the first transforming launch, the others from the low pass.
+// Every sample of the full row lies within rowTail of the low-only row, so
+//   lb2 = max over the survivors of (low-only best - rowTail)   is a lower bound of the particle's maximum (never below the first
+//         stage's, which took the same expression over the planned rows only), and
+//   low-only best + rowTail                                      is an upper bound of the row's maximum,
+// where the first stage had the sum of the low moduli.  A row stays iff its upper bound reaches lb2 - 2 tau (NaN-safe like the first
+// stage; a value that is not finite anywhere among the survivors keeps them all); the others get the "no value" result, planned rows
+// included -- a low-only result must not reach k_pm_select.  Block per particle; list, count, items and nitems as k_pm_survivors
+// writes them, for k_pm_rows_high and the transforming launch.
+__global__ void __launch_bounds__(256)
+k_pm_low_keep(const float *__restrict__ rowBound, const float *__restrict__ thr, const float *__restrict__ rowTail, RowMap M,
+              const double *__restrict__ refSigma, const double *__restrict__ stat32, int rowsPerParticle, float tau2,
+              RowRes *__restrict__ res, int *__restrict__ list, int *__restrict__ count, int2 *__restrict__ items,
+              int *__restrict__ nitems, int perItem)
+{
+    __shared__ int sc[256];
+    __shared__ float sv[256];
+    __shared__ int sBase, sBad;
+    const int p = blockIdx.x, r0 = p * rowsPerParticle;
+    const float t = thr[p];
+    if (threadIdx.x == 0) sBad = 0;
+    __syncthreads();
+    float lb = -3.0e38f;
+    bool bad = false;
+    for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256) {
+        if (!(rowBound[r] != -INFINITY && !(rowBound[r] < t))) continue;          // not a survivor of the first stage
+        const int slot = d_row_slot(M, r);
+        const float den = (float)refSigma[d_row_ref(M, r, slot)] * (float)stat32[2 * slot + 1];
+        const float v = res[r].best / den - rowTail[r];
+        bad = bad || !(fabsf(v) <= 3.0e38f);
+        lb = fmaxf(lb, v);
+    }
+    if (bad) sBad = 1;
+    sv[threadIdx.x] = lb;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sv[threadIdx.x] = fmaxf(sv[threadIdx.x], sv[threadIdx.x + o]);
+        __syncthreads();
+    }
+    const float t2 = sBad ? -3.0e38f : sv[0] - tau2;
+    // 0: not a survivor of the first stage, 1: dropped here, 2: stays
+    auto fate = [&](int r) {
+        if (!(rowBound[r] != -INFINITY && !(rowBound[r] < t))) return 0;
+        const int slot = d_row_slot(M, r);
+        const float den = (float)refSigma[d_row_ref(M, r, slot)] * (float)stat32[2 * slot + 1];
+        // 1.0001: the factor k_pm_prune_plan gives its bound, for the rounding of the fp32 sums and of the transform
+        return res[r].best / den + 1.0001f * rowTail[r] < t2 ? 1 : 2;
+    };
+    int c = 0;
+    for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256) c += fate(r) == 2 ? 1 : 0;
     sc[threadIdx.x] = c;
     __syncthreads();
     for (int o = 1; o < 256; o <<= 1) {                    // inclusive scan
@@ -1790,15 +1912,19 @@ k_pm_survivors(const float *__restrict__ rowBound, const float *__restrict__ thr
     if (threadIdx.x == 255) {
         const int cnt = sc[255];
         sBase = cnt ? atomicAdd(count, cnt) : 0;
-        if (items && cnt) {                                   // the particle's stretch of the list in pieces of perItem rows (k_pm_rows_high)
+        if (items && cnt) {
             const int nb = (cnt + perItem - 1) / perItem, ib = atomicAdd(nitems, nb);
             for (int i = 0; i < nb; ++i) items[ib + i] = make_int2(sBase + i * perItem, min(perItem, cnt - i * perItem));
         }
     }
     __syncthreads();
     int o = sBase + sc[threadIdx.x] - c;
-    for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256)
-        if (rowBound[r] != -INFINITY && !(rowBound[r] < t)) list[o++] = r;
+    // (the rows of the count above, visited by the same thread: res[r] is as it was then)
+    for (int r = r0 + threadIdx.x; r < r0 + rowsPerParticle; r += 256) {
+        const int f = fate(r);
+        if (f == 2) list[o++] = r;
+        else if (f == 1) { RowRes q; q.best = -3.0e38f; q.idx = 0; q.second = -3.0e38f; q.pad = 0; res[r] = q; }
+    }
 }
 
 // thr[p] = (best normalised value among the particle's listed rows) - 2 tau; NaN => nothing is pruned.
@@ -3701,6 +3827,9 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     pm->lastPruneRows = 0;
     pm->adaptive_finish = 1;
     pm->group_high = 1;
+    pm->low_pass = 1;
+    pm->stat_low_in = pm->stat_low_out = pm->stat_low_rows = 0;
+    pm->lastLowPass = 0;
     pm->high_cap = 0;
     pm->finish_dense = 0;
     pm->stat_dense_chunks = 0;
@@ -4025,6 +4154,7 @@ int xh_pm_set_option(xh_pm *pm, const char *name, double value)
     else if (!strcmp(name, "prune")) pm->use_prune = (int)value;
     else if (!strcmp(name, "mask_lists")) pm->use_mask_lists = (int)value;
     else if (!strcmp(name, "group_high")) pm->group_high = (int)value;
+    else if (!strcmp(name, "low_pass")) pm->low_pass = (int)value;
     else if (!strcmp(name, "high_cap")) pm->high_cap = (int)value;
     else if (!strcmp(name, "adaptive_finish")) { pm->adaptive_finish = (int)value; pm->finish_dense = value >= 2; }      // (2: start in the dense form)
     else if (!strcmp(name, "threads")) {
@@ -4085,7 +4215,7 @@ int xh_pm_last_stats(const xh_pm *pm, int64_t *rows, int64_t *rp, int64_t *rr)
 
 // S2+S3 for a prepared chunk. h_poff: chunk-local row offsets [m+1]; d_ids device ref ids per row or null (dense)
 // prune: row map of the chunk for the S3 branch and bound (null: every row is transformed); nparticles and tau2
-// (= 2 tau, normalised units) go with it; d_pruned counts the skipped rows
+// (= 2 tau, normalised units) go with it; d_pruned: four counters, [1] the rows that survive the bounds, [2] and [3] the low pass's
 static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d_ids, bool dense, int nq, hipEvent_t evMid = nullptr,
                     const RowMap *prune = nullptr, int nparticles = 0, float tau2 = 0.f, int *d_pruned = nullptr,
                     const unsigned *d_mask = nullptr, int maskW = 0, int listedRows = 0)
@@ -4200,7 +4330,8 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
                                nparticles, tau2, (float *)pm->d_thr.p, (const float *)pm->d_rowTail.p);
             XH_LAUNCH_CHECK();
             // survivors, compacted on the device; d_pruned[1] counts them (the host derives the pruned rows)
-            XH_TRY(xh_buf_reserve(ctx, pm->d_survList, sizeof(int) * (size_t)nrows));
+            // (twice: with the low pass the first half lists what that pass transforms, the second half what is finished)
+            XH_TRY(xh_buf_reserve(ctx, pm->d_survList, sizeof(int) * 2 * (size_t)nrows));
             // the survivors' frequencies >= K0 particle by particle (k_pm_rows_high); the store holds what an ordinary gallery leaves (rows beyond it are finished by the transforming wave, and a gallery that
             // leaves that many switches its next chunk to the full contraction anyway)
             const int nkHigh = L.nk - H.K0;
@@ -4218,12 +4349,33 @@ static int run_rows(xh_pm *pm, int m, const std::vector<int> &poff, const int *d
                 d_nitems = (int *)(d_items + maxItems);
                 XH_HIP(hipMemsetAsync(d_nitems, 0, sizeof(int), ctx->stream));
             }
+            // the low pass (two-level form, survivors finished particle by particle): the survivors that are not planned rows are
+            // transformed from their low frequencies too, and k_pm_low_keep lists those that are still in reach; d_pruned[2] counts the
+            // rows of that pass, d_pruned[3] what it leaves to finish
+            const bool lowPass = pm->low_pass && grouped && !boundsOnly && K0 < L.nk;
+            int *survList = (int *)pm->d_survList.p;
             hipLaunchKernelGGL(k_pm_survivors, dim3(nparticles), dim3(256), 0, ctx->stream, (const float *)pm->d_rowBound.p,
-                               (const float *)pm->d_thr.p, nrows / nparticles, nrows, (RowRes *)pm->d_rowres.p, (int *)pm->d_survList.p,
-                               d_pruned + 1, d_items, d_nitems, XH_HIGH_ROWS);
+                               (const float *)pm->d_thr.p, nrows / nparticles, nrows, (RowRes *)pm->d_rowres.p, survList,
+                               d_pruned + 1, lowPass ? (int2 *)nullptr : d_items, lowPass ? (int *)nullptr : d_nitems, XH_HIGH_ROWS,
+                               lowPass ? (const int *)pm->d_topRows.p : (const int *)nullptr, d_pruned + 2);
             XH_LAUNCH_CHECK();
             pm->lastPruneRows = d_mask ? listedRows : nrows;
-            nr = nrows; rowList = (const int *)pm->d_survList.p; nrDev = d_pruned + 1;
+            pm->lastLowPass = lowPass ? 1 : 0;
+            nr = nrows; rowList = survList; nrDev = d_pruned + 1;
+            if (lowPass) {
+                nrDev = d_pruned + 2;
+                grid = std::max(8, std::min((nr + 3) / 4, ctx->num_cus * 8) / 8 * 8);
+                H.zeroHigh = 1;
+                XH_IDFT3_ANY();
+                H.zeroHigh = 0;
+                XH_LAUNCH_CHECK();
+                hipLaunchKernelGGL(k_pm_low_keep, dim3(nparticles), dim3(256), 0, ctx->stream, (const float *)pm->d_rowBound.p,
+                                   (const float *)pm->d_thr.p, (const float *)pm->d_rowTail.p, *prune, (const double *)pm->d_refSigma.p,
+                                   (const double *)pm->d_stat32.p, nrows / nparticles, tau2, (RowRes *)pm->d_rowres.p, survList + nrows,
+                                   d_pruned + 3, d_items, d_nitems, XH_HIGH_ROWS);
+                XH_LAUNCH_CHECK();
+                rowList = survList + nrows; nrDev = d_pruned + 3;
+            }
             if (grouped) {
                 H.highStore = (const float4 *)pm->d_highStore.p; H.highCap = highCap;
                 hipLaunchKernelGGL(k_pm_rows_high, dim3(std::min(nparticles, ctx->num_cus * 8)), dim3(64 * XH_HIGH_WAVES), 0, ctx->stream, H, rowList,
@@ -4305,6 +4457,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
     pm->stat_rows = pm->stat_resc_p = pm->stat_resc_r = 0;
     pm->coefFirst = pm->coefCount = 0;
     pm->stat_pruned = 0;
+    pm->stat_low_in = pm->stat_low_out = pm->stat_low_rows = 0;
     // chunking: bound the S2->S3 intermediate (rows * nk * 16 B)
     // the S2->S3 intermediate is sized for parallelism (thousands of tiles in flight), not thrift: 4 GiB of 288
     // (with the two-level contraction a row only holds the frequencies below K0: far more rows per chunk)
@@ -4425,9 +4578,11 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
         pm->coefFirst = p0; pm->coefCount = D >= 2 * XH_FIR_K ? m : 0;   // the recursive form rounds differently
         XH_HIP(hipEventRecord(pm->ev[1], ctx->stream));
         // S2 + S3
-        XH_TRY(xh_buf_reserve(ctx, pm->d_counters, sizeof(int) * 4));
-        XH_HIP(hipMemsetAsync(pm->d_counters.p, 0, sizeof(int) * 4, ctx->stream));
+        // (counters: ambiguous particles, candidate rows, then run_rows' four: [3] the survivors of the bounds, [4] and [5] the low pass)
+        XH_TRY(xh_buf_reserve(ctx, pm->d_counters, sizeof(int) * 6));
+        XH_HIP(hipMemsetAsync(pm->d_counters.p, 0, sizeof(int) * 6, ctx->stream));
         pm->lastPruneRows = 0;
+        pm->lastLowPass = 0;
         XH_TRY(run_rows(pm, ms, poff, d_ids, !lists, pm->nrefs, pm->ev[2], &M, m, 2.f * tauAbs, (int *)pm->d_counters.p + 2, d_mask, maskW,
                         listedRows));
         XH_HIP(hipEventRecord(pm->ev[3], ctx->stream));
@@ -4443,7 +4598,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
         XH_LAUNCH_CHECK();
         XH_HIP(hipEventRecord(pm->ev[4], ctx->stream));
         // S5: read the counters (tiny D2H) to size the fp64 work
-        int counters[4];
+        int counters[6];
         XH_HIP(hipMemcpyAsync(counters, pm->d_counters.p, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
         XH_HIP(hipStreamSynchronize(ctx->stream));
         {
@@ -4454,6 +4609,7 @@ int xh_pm_match_ex(xh_pm *pm, const float *d_particles, int32_t n, const int32_t
         pm->stat_resc_p += counters[0];
         pm->stat_resc_r += counters[1];
         if (pm->lastPruneRows > 0) pm->stat_pruned += pm->lastPruneRows - counters[3];
+        if (pm->lastLowPass) { pm->stat_low_in += counters[3]; pm->stat_low_rows += counters[4]; pm->stat_low_out += counters[5]; }
         if (pm->lastPruneRows > 0 && nrows > 0) {
             // the next chunk's form (see adaptive_finish): break-even at 0.09 of the chunk's rows surviving; the full contraction's own
             // bounds are tighter than the two-level ones, hence two thresholds
@@ -4762,6 +4918,12 @@ int xh_pm_get_option(const xh_pm *pm, const char *name, double *value)
     else if (!strcmp(name, "s6_eps")) *value = pm->s6_eps;
     else if (!strcmp(name, "adaptive_finish")) *value = pm->adaptive_finish;
     else if (!strcmp(name, "dense_chunks")) *value = pm->stat_dense_chunks;      // chunks of the last match call contracted at every frequency
+    else if (!strcmp(name, "low_pass")) *value = pm->low_pass;
+    // the low pass of the last match call (k_pm_low_keep): survivors of the bounds it looked at, those it left to finish, and the rows it
+    // transformed from their low frequencies to decide (the planned rows had been)
+    else if (!strcmp(name, "low_pass_rows_in")) *value = (double)pm->stat_low_in;
+    else if (!strcmp(name, "low_pass_rows_out")) *value = (double)pm->stat_low_out;
+    else if (!strcmp(name, "low_pass_rows_transformed")) *value = (double)pm->stat_low_rows;
     else { xh_set_error("xh_pm_get_option: unknown option %s", name); return XH_ERR_ARG; }
     return XH_OK;
 }

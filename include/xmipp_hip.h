@@ -897,6 +897,84 @@ int xh_faz_set_volume(xh_faz *h, const double *h_V);
 int xh_faz_set_timing(xh_faz *h, int32_t on);
 int xh_faz_stage_ms(const xh_faz *h, double *h_ms);
 
+/* ---- projectVolume in real space: four rays per pixel through the voxel grid ------------------------
+ * Replaces projectVolume(V, P, Ydim, Xdim, rot, tilt, psi, roffset) (libraries/data/projection.cpp:337-589), the projector that
+ * xmipp_subtract_projection (reconstruction/subtract_projection.cpp:258,280,653) uses for its mask projections of every particle and,
+ * with --realSpaceProjection, for the volume itself. fp64; the contract and the deviations are at the head of xmipp3_amd/csrc/xh_rsp.hip.
+ *   create  : d_vol [D][D][D] doubles on the device, [z][y][x], Xmipp origin; it is read here and not kept. XH_RSP_VALUE: project()
+ *             writes the line integrals (ray_sum * 0.25, L582). XH_RSP_SUPPORT: project() writes 1.0 where the line integral of a
+ *             non-negative volume is positive and 0.0 elsewhere, from v > 0 packed into bits; a volume with a negative voxel takes the
+ *             value walk followed by > 0 instead (xh_rsp_info's packed = 0).
+ *   project : h_angles n x (rot, tilt, psi) degrees (Projection::setAngles, L345); h_offsets n x (x, y), the roffset subtracted from
+ *             every ray's pixel coordinates (L412-413), or null (roffset == nullptr); d_out n x D x D doubles. Asynchronous on the
+ *             context's stream. n = 0 does nothing.
+ *   steps   : for the benchmark: the voxel steps the four rays of every pixel walk in the handle's mode (the bits end a ray at its
+ *             first hit), d_steps n x D x D int32. */
+typedef struct xh_rsp xh_rsp;
+enum { XH_RSP_VALUE = 0, XH_RSP_SUPPORT = 1 };
+int xh_rsp_create(xh_ctx *ctx, const double *d_vol, int32_t D, int32_t mode, xh_rsp **out);
+int xh_rsp_destroy(xh_rsp *h);
+int xh_rsp_info(const xh_rsp *h, int32_t *D, int32_t *mode, int32_t *packed);
+int xh_rsp_project(xh_rsp *h, const double *h_angles, const double *h_offsets, int32_t n, double *d_out);
+int xh_rsp_steps(xh_rsp *h, const double *h_angles, const double *h_offsets, int32_t n, int32_t *d_steps);
+
+/* ---- xmipp_subtract_projection (libraries/reconstruction/subtract_projection.{h,cpp}) ----
+ * Projects the refined volume at each particle's pose, fits the projection to the particle in Fourier space (order 0: T(w) = beta00,
+ * order 1: T(w) = beta01 + beta1 w, the better adjusted R2 wins) and removes it, keeping or removing the region of a 3-D mask. The
+ * reference runs one particle at a time on CPU threads; here `capacity` particles go through one stream of kernels per device step.
+ * Everything is fp64. The contract and the deviations from the reference are at the head of xmipp3_amd/csrc/xh_sub.hip. */
+typedef struct xh_sub xh_sub;
+typedef struct {
+    double sampling, max_resolution, padding, cirmaskrad;      /* --sampling, --max_resolution (-1: sampling), --padding, --cirmaskrad (-1: D / 2) */
+    int32_t subtract, real_space, ignore_ctf, boost, non_negative, pad_;   /* --subtract, --realSpaceProjection, --ignoreCTF, --boost, --nonNegative */
+} xh_sub_params;
+/* one particle's input row (processParticle L246-252, applyCTF L219-225) */
+typedef struct {
+    double rot, tilt, psi, shift_x, shift_y;
+    int32_t has_ctf, pad_;      /* has_ctf: the row holds ctfDefocusU */
+    xh_ctf_params ctf;          /* read when has_ctf and not --ignoreCTF (readFromMdRow); Tm is replaced by --sampling, K comes from the row */
+} xh_sub_row;
+/* one particle's results (writeParticle L161-174): subtractionR2, subtractionBeta0, subtractionBeta1, subtractionB; model 0 or 1;
+ * disable: --nonNegative and beta00 < 0; enabled: -1 when --nonNegative and (disable or R2adj < 0), else 1. beta00 and R20adj are the
+ * order-0 figures whatever model won (for the tests). */
+typedef struct {
+    double R2adj, beta0, beta1, b, beta00, R20adj;
+    int32_t model, disable, enabled, pad_;
+} xh_sub_result;
+/* the program's defaults (defineParams L116-151) */
+void xh_sub_defaults(xh_sub_params *p);
+/* host only: the integer frequency map wi [D][D/2+1] (L554-563; null: skipped) and maxwiIdx (L572-580) */
+int xh_sub_freq_map(int32_t D, double sampling, double max_resolution, int32_t *h_wi, int32_t *maxwiIdx);
+/* host only: the fit of L732-759 from the per-wi sums h_sums [maxwiIdx + 1][4] = num0, den0, sum (re + im) of PiMFourier, sum (re + im) of
+ * IiMFourier, and a11 = sum 2 wi over the cells with 0 < wi < maxwiIdx: h_betas = beta00, beta01, beta1. solveLinearSystem is least squares
+ * through the normal equations (parity with xmippCore unpinned: SURVEY.md Appendix B). The device runs this same code. */
+int xh_sub_fit(const double *h_sums, int32_t maxwiIdx, double a11, double *h_betas);
+/* host only: evaluateFitting for both models and checkBestModel (L323-364) from sum (re + im), sum (re^2 + im^2) of IFourier and the two
+ * sums of squared errors over `cells` half-spectrum cells: h_out = R2adj of the chosen model, the model (0 when R21adj == R20adj), R20adj */
+int xh_sub_choose(double sumY, double sumY2, double sumE0, double sumE1, double cells, double *h_out);
+/* preProcess (L514-632). h_vol [D][D][D] doubles (host, Xmipp origin). h_roi: the --mask_roi volume or null (no ROI mask). h_maskvol: the
+ * --mask volume or null (the 2-D disc of --cirmaskrad). capacity: particles per device step. */
+int xh_sub_create(xh_ctx *ctx, const double *h_vol, int32_t D, const double *h_roi, const double *h_maskvol, const xh_sub_params *prm,
+                  int32_t capacity, xh_sub **out);
+int xh_sub_destroy(xh_sub *h);
+/* maxwiIdx, the side of applyCTF's padded window, a11; null pointers are skipped */
+int xh_sub_info(const xh_sub *h, int32_t *maxwiIdx, int32_t *padded, double *a11);
+/* n particles h_images [n][ydim][xdim] (host) with their rows; replaces what was loaded. Non-square particles and particles of another size
+ * than the volume: XH_ERR_UNSUPPORTED. */
+int xh_sub_load(xh_sub *h, const float *h_images, int32_t n, int32_t ydim, int32_t xdim, const xh_sub_row *rows);
+/* processImage (L634-826) for every loaded particle, in chunks of `capacity`: h_out [n][D][D] doubles (Idiff), h_res [n] */
+int xh_sub_run(xh_sub *h, double *h_out, xh_sub_result *h_res);
+/* test hook: the planes of particle `index` of the last chunk, device doubles [D][D], null pointers skipped: P (the projection before the
+ * CTF), Pctf (after it, before the mask), PmaskImg, M, iM, Idiff; on the host the sums [maxwiIdx + 1][4] of xh_sub_fit and its betas [3] */
+int xh_sub_last(xh_sub *h, int32_t index, double *d_P, double *d_Pctf, double *d_PmaskImg, double *d_M, double *d_iM, double *d_Idiff,
+                double *h_sums, double *h_betas);
+/* for the benchmark: with timing on, a run records events around its stages (they do not synchronise; a chunk still waits once, at its
+ * end) and xh_sub_stage_ms returns the milliseconds of the last run, summed over its chunks: h_ms[7] = the projection (with the
+ * translation), the CTF (pad, two transforms, the multiply, the crop), the mask projections, b with the four spectra, the sums per wi with
+ * the fit, the two models with the choice, the output (spectrum, inverse transform, difference) */
+int xh_sub_set_timing(xh_sub *h, int32_t on);
+int xh_sub_stage_ms(const xh_sub *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

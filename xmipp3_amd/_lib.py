@@ -59,6 +59,21 @@ class FazRow(C.Structure):
     _fields_ = AsaRow._fields_
 
 
+class SubParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("sampling", "max_resolution", "padding", "cirmaskrad")] + [
+        (n, C.c_int32) for n in ("subtract", "real_space", "ignore_ctf", "boost", "non_negative", "pad_")]
+
+
+class SubRow(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("rot", "tilt", "psi", "shift_x", "shift_y")] + [("has_ctf", C.c_int32), ("pad_", C.c_int32),
+                                                                                          ("ctf", CtfParams)]
+
+
+class SubResult(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("R2adj", "beta0", "beta1", "b", "beta00", "R20adj")] + [
+        (n, C.c_int32) for n in ("model", "disable", "enabled", "pad_")]
+
+
 # every symbol include/xmipp_hip.h declares: name -> (restype, argtypes)
 vp, i32, i64, d, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 pvp = C.POINTER(C.c_void_p)
@@ -215,6 +230,23 @@ SIGNATURES = {
     "xh_faz_set_volume": (C.c_int, [vp, vp]),
     "xh_faz_set_timing": (C.c_int, [vp, i32]),
     "xh_faz_stage_ms": (C.c_int, [vp, vp]),
+    "xh_rsp_create": (C.c_int, [vp, vp, i32, i32, pvp]),
+    "xh_rsp_destroy": (C.c_int, [vp]),
+    "xh_rsp_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "xh_rsp_project": (C.c_int, [vp, vp, vp, i32, vp]),
+    "xh_rsp_steps": (C.c_int, [vp, vp, vp, i32, vp]),
+    "xh_sub_defaults": (None, [C.POINTER(SubParams)]),
+    "xh_sub_freq_map": (C.c_int, [i32, d, d, vp, C.POINTER(i32)]),
+    "xh_sub_fit": (C.c_int, [vp, i32, d, vp]),
+    "xh_sub_choose": (C.c_int, [d, d, d, d, d, vp]),
+    "xh_sub_create": (C.c_int, [vp, vp, i32, vp, vp, C.POINTER(SubParams), i32, pvp]),
+    "xh_sub_destroy": (C.c_int, [vp]),
+    "xh_sub_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]),
+    "xh_sub_load": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "xh_sub_run": (C.c_int, [vp, vp, vp]),
+    "xh_sub_last": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "xh_sub_set_timing": (C.c_int, [vp, i32]),
+    "xh_sub_stage_ms": (C.c_int, [vp, vp]),
     "xh_rotation_estimate": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "xh_movie_dose_filter": (C.c_int, [vp, vp, vp, i32, i32, d, d, d, d]),
     "xh_movie_bin_frame": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, i32]),

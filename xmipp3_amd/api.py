@@ -1093,6 +1093,160 @@ class FourierProjector(_Handle):
         return out
 
 
+class RealSpaceProjector(_Handle):
+    """Device side of projectVolume in real space (data/projection.cpp:337-589): four rays per pixel through the voxel grid of a
+    volume `[z][y][x]` (float64, cuda, Xmipp origin). mode "value": the line integrals; mode "support": 1.0 where the line integral
+    of a non-negative volume is positive, from the volume's v > 0 packed into bits (`packed`; a volume with a negative voxel takes the
+    value walk followed by > 0)."""
+
+    _destroy = "xh_rsp_destroy"
+    MODES = {"value": 0, "support": 1}
+
+    def __init__(self, ctx, vol, mode="value"):
+        torch = _torch()
+        if mode not in self.MODES:
+            raise XhError(f"RealSpaceProjector: mode {mode!r} is neither 'value' nor 'support'")
+        if not (vol.is_cuda and vol.dtype == torch.float64 and vol.is_contiguous() and vol.dim() == 3
+                and vol.shape[0] == vol.shape[1] == vol.shape[2]):
+            raise XhError("RealSpaceProjector: the volume must be a contiguous cubic float64 cuda tensor")
+        self.D, self.mode = vol.shape[0], mode
+        h = C.c_void_p()
+        check(lib().xh_rsp_create(ctx.h, _ptr(vol), self.D, self.MODES[mode], C.byref(h)))
+        super().__init__(ctx, h)
+        packed = C.c_int32()
+        check(lib().xh_rsp_info(h, None, None, C.byref(packed)))
+        self.packed = bool(packed.value)
+
+    def _args(self, angles, offsets):
+        ang = np.ascontiguousarray(angles, np.float64).reshape(-1, 3)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.float64).reshape(-1, 2)
+        if off is not None and off.shape[0] != ang.shape[0]:
+            raise XhError(f"RealSpaceProjector: {ang.shape[0]} orientations but {off.shape[0]} offsets")
+        return ang, off
+
+    def project(self, angles, offsets=None):
+        """angles: [n, 3] (rot, tilt, psi) in degrees; offsets: optional [n, 2], the roffset (x, y). Returns [n, D, D] float64."""
+        torch = _torch()
+        ang, off = self._args(angles, offsets)
+        out = torch.empty((ang.shape[0], self.D, self.D), dtype=torch.float64, device=self.ctx.torch_device)
+        check(lib().xh_rsp_project(self.h, _np_ptr(ang), _np_ptr(off), ang.shape[0], _ptr(out)))
+        return out
+
+    def steps(self, angles, offsets=None):
+        """The voxel steps the four rays of every pixel walk in this handle's mode: [n, D, D] int32."""
+        torch = _torch()
+        ang, off = self._args(angles, offsets)
+        out = torch.empty((ang.shape[0], self.D, self.D), dtype=torch.int32, device=self.ctx.torch_device)
+        check(lib().xh_rsp_steps(self.h, _np_ptr(ang), _np_ptr(off), ang.shape[0], _ptr(out)))
+        return out
+
+
+def sub_freq_map(D, sampling=1.0, max_resolution=-1.0):
+    """Host only: xmipp_subtract_projection's integer frequency map wi [D, D//2+1] and maxwiIdx."""
+    wi = np.empty((D, D // 2 + 1), np.int32)
+    mx = C.c_int32()
+    check(lib().xh_sub_freq_map(int(D), float(sampling), float(max_resolution), _np_ptr(wi), C.byref(mx)))
+    return wi, mx.value
+
+
+def sub_fit(sums, maxwi, a11):
+    """Host only: beta00, beta01, beta1 from the per-wi sums [maxwi + 1, 4] (xh_sub_fit)."""
+    s = np.ascontiguousarray(sums, np.float64)
+    if s.shape != (maxwi + 1, 4):
+        raise XhError(f"sub_fit: sums of shape {s.shape}, expected {(maxwi + 1, 4)}")
+    out = np.empty(3)
+    check(lib().xh_sub_fit(_np_ptr(s), int(maxwi), float(a11), _np_ptr(out)))
+    return tuple(out)
+
+
+def sub_choose(sumY, sumY2, sumE0, sumE1, cells):
+    """Host only: checkBestModel on the sums of evaluateFitting: (R2adj, model, R20adj)."""
+    out = np.empty(3)
+    check(lib().xh_sub_choose(float(sumY), float(sumY2), float(sumE0), float(sumE1), float(cells), _np_ptr(out)))
+    return out[0], int(out[1]), out[2]
+
+
+class SubtractProjection(_Handle):
+    """Device side of xmipp_subtract_projection (reconstruction/subtract_projection.cpp). vol, roi (--mask_roi) and mask (--mask): host
+    arrays [D, D, D]; params: sampling, max_resolution, padding, cirmaskrad, subtract, real_space, ignore_ctf, boost, non_negative."""
+
+    _destroy = "xh_sub_destroy"
+
+    def __init__(self, ctx, vol, roi=None, mask=None, capacity=64, **params):
+        from ._lib import SubParams
+        prm = SubParams()
+        lib().xh_sub_defaults(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(SubParams._fields_) or k == "pad_":
+                raise XhError(f"SubtractProjection: unknown parameter {k!r}")
+            setattr(prm, k, type(getattr(prm, k))(v))
+        vol = np.ascontiguousarray(vol, np.float64)
+        if vol.ndim != 3 or not (vol.shape[0] == vol.shape[1] == vol.shape[2]):
+            raise XhError(f"SubtractProjection: the volume must be cubic, got {vol.shape}")
+        self.D = vol.shape[0]
+        aux = []
+        for name, a in (("roi", roi), ("mask", mask)):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64)
+                if a.shape != vol.shape:
+                    raise XhError(f"SubtractProjection: the {name} volume has shape {a.shape}, the volume {vol.shape}")
+            aux.append(a)
+        h = C.c_void_p()
+        check(lib().xh_sub_create(ctx.h, _np_ptr(vol), self.D, _np_ptr(aux[0]), _np_ptr(aux[1]), C.byref(prm), int(capacity), C.byref(h)))
+        super().__init__(ctx, h)
+        a, b, c = C.c_int32(), C.c_int32(), C.c_double()
+        check(lib().xh_sub_info(h, C.byref(a), C.byref(b), C.byref(c)))
+        self.maxwi, self.padded, self.a11 = a.value, b.value, c.value
+        self.n = 0
+
+    def load(self, images, rows):
+        """images [n, D, D] float32 (host); rows: dicts with rot, tilt, psi, shift_x, shift_y and optionally ctf (a CtfParams)."""
+        from ._lib import SubRow
+        img = np.ascontiguousarray(images, np.float32)
+        n = img.shape[0]
+        if len(rows) != n:
+            raise XhError(f"SubtractProjection.load: {n} images but {len(rows)} rows")
+        arr = (SubRow * n)()
+        for r, q in zip(arr, rows):
+            for k in ("rot", "tilt", "psi", "shift_x", "shift_y"):
+                setattr(r, k, float(q.get(k, 0.0)))
+            if q.get("ctf") is not None:
+                r.has_ctf = 1
+                r.ctf = q["ctf"]
+        check(lib().xh_sub_load(self.h, _np_ptr(img), n, img.shape[1], img.shape[2], arr))
+        self.n = n
+
+    def run(self):
+        """Returns Idiff [n, D, D] float64 and a list of dicts (R2adj, beta0, beta1, b, beta00, R20adj, model, disable, enabled)."""
+        from ._lib import SubResult
+        out = np.empty((self.n, self.D, self.D), np.float64)
+        res = (SubResult * max(self.n, 1))()
+        check(lib().xh_sub_run(self.h, _np_ptr(out), res))
+        names = [f[0] for f in SubResult._fields_ if f[0] != "pad_"]
+        return out, [{k: getattr(r, k) for k in names} for r in res[:self.n]]
+
+    STAGES = ("projection", "ctf", "masks", "prepare_spectra", "sums_fit", "models", "output")
+
+    def set_timing(self, on=True):
+        check(lib().xh_sub_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        ms = np.empty(len(self.STAGES))
+        check(lib().xh_sub_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms.tolist()))
+
+    def last(self, index):
+        """The planes of particle `index` of the last chunk (host arrays), its sums [maxwi + 1, 4] and its betas."""
+        torch = _torch()
+        planes = {k: torch.empty((self.D, self.D), dtype=torch.float64, device=self.ctx.torch_device) for k in ("P", "Pctf", "PmaskImg", "M", "iM", "Idiff")}
+        sums = np.empty((self.maxwi + 1, 4))
+        betas = np.empty(3)
+        check(lib().xh_sub_last(self.h, int(index), *[_ptr(planes[k]) for k in ("P", "Pctf", "PmaskImg", "M", "iM", "Idiff")], _np_ptr(sums), _np_ptr(betas)))
+        out = {k: v.cpu().numpy() for k, v in planes.items()}
+        out["sums"], out["betas"] = sums, betas
+        return out
+
+
 class _LockstepRows(_Handle):
     """What the per-particle Powell programs share: load's rows, cost and stats. A subclass names its ABI prefix (_abi) and its row
     struct (_Row, with _row_defaults), and sets nvars before the first cost."""

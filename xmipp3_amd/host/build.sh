@@ -21,5 +21,6 @@ $CXX $FLAGS angular_continuous_assign2_main.cpp -o ../bin/xmipp_angular_continuo
 $CXX $FLAGS volume_deform_sph_main.cpp -o ../bin/xmipp_volume_deform_sph $LINK &
 $CXX $FLAGS angular_sph_alignment_main.cpp -o ../bin/xmipp_angular_sph_alignment $LINK &
 $CXX $FLAGS forward_art_zernike3d_main.cpp -o ../bin/xmipp_forward_art_zernike3d $LINK &
+$CXX $FLAGS subtract_projection_main.cpp -o ../bin/xmipp_subtract_projection $LINK &
 wait
-echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph,angular_sph_alignment,forward_art_zernike3d}"
+echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph,angular_sph_alignment,forward_art_zernike3d,subtract_projection}"

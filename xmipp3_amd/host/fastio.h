@@ -55,6 +55,8 @@ struct XhDestroy {
     void operator()(xh_vds *h) const { xh_vds_destroy(h); }
     void operator()(xh_asa *h) const { xh_asa_destroy(h); }
     void operator()(xh_faz *h) const { xh_faz_destroy(h); }
+    void operator()(xh_rsp *h) const { xh_rsp_destroy(h); }
+    void operator()(xh_sub *h) const { xh_sub_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 

@@ -975,6 +975,77 @@ int xh_sub_last(xh_sub *h, int32_t index, double *d_P, double *d_Pctf, double *d
 int xh_sub_set_timing(xh_sub *h, int32_t on);
 int xh_sub_stage_ms(const xh_sub *h, double *h_ms);
 
+/* ---- xmipp_resolution_monogenic_signal, MonoRes (libraries/reconstruction/resolution_monogenic_signal.{h,cpp}, the Monogenic class of
+ * libraries/data/monogenic_signal.{h,cpp}) ----
+ * The local resolution map of a volume (or of two half maps) by a sweep over frequencies: at each one the monogenic (Riesz) amplitude of
+ * the high-passed map is compared, voxel by voxel, with a threshold taken from the noise. The reference runs on CPU threads; here the
+ * whole sweep stays on the device and the host reads one small record per frequency. Everything is fp64. The kernels, the reference
+ * behaviours kept as written and the deviations are listed at the head of xmipp3_amd/csrc/xh_mono.hip. Volumes are [Z][Y][X]. */
+typedef struct xh_mono xh_mono;
+typedef struct {
+    double sampling, minRes, maxRes, freq_step, significance;   /* --sampling_rate, --minRes (overwritten by 2 sampling, run :362), --maxRes, --step, --significance */
+    int32_t gaussian, noise_only_in_halves;                     /* --gaussian, --noiseonlyinhalves */
+} xh_mono_params;
+/* statisticsInBinaryMask2 / statisticsInOutBinaryMask2 (monogenic_signal.cpp :424-508) */
+typedef struct {
+    double NS, NN, sumS, sumS2, sumN, sumN2, meanS, sdS2, meanN, sdN2, thr95;
+} xh_mono_stats;
+/* one evaluated frequency of run (:392-536): threshold and z are 0 where the sweep left before computing them; assigned: the assign
+ * kernel ran */
+typedef struct {
+    xh_mono_stats stats;
+    double resolution, freq, freqH, freqL, threshold, z, max_meanS;
+    int32_t assigned, pad_;
+} xh_mono_step;
+/* why the sweep ended: resolution2eval's break (:407), NS / NVoxelsOriginalMask < 0.025 (:460), NS == 0 (:481), meanS < 0.001 max_meanS
+ * (:499), z < criticalZ (:525), resolution < minRes (:531) */
+enum { XH_MONO_STOP_RANGE = 1, XH_MONO_STOP_MASK_DONE = 2, XH_MONO_STOP_NO_POINTS = 3, XH_MONO_STOP_LOW_SIGNAL = 4, XH_MONO_STOP_ZTEST = 5,
+       XH_MONO_STOP_MIN_RES = 6 };
+/* the program's defaults (defineParams :51-87) */
+void xh_mono_defaults(xh_mono_params *p);
+/* host only: icdf_gauss (xmippCore) restated as Abramowitz-Stegun 26.2.23 (parity unpinned) */
+int xh_mono_icdf_gauss(double p, double *out);
+/* host only: Monogenic::resolution2eval (monogenic_signal.cpp :212-272), state in and out as in the reference; a resolution <= 0 breaks */
+int xh_mono_resolution2eval(int32_t *count_res, double step, double *resolution, double *last_resolution, double *freq, double *freqL,
+                            int32_t *last_fourier_idx, int32_t volsize, int32_t *continueIter, int32_t *breakIter, double sampling, double maxRes);
+/* host only: the shell walk of findCliffValue (:70-105) over per-shell sums (shell r: r^2 <= k^2 + i^2 + j^2 < (r + 1)^2) */
+int xh_mono_cliff_radius(const double *h_sum, const double *h_sum2, const double *h_N, int32_t nshell, int32_t radius, int32_t X, int32_t *radiuslimit);
+/* host only: the number of shells the per-shell sums of a Z x Y x X volume have */
+int xh_mono_num_shells(int32_t Z, int32_t Y, int32_t X, int32_t *nshell);
+/* every buffer of a Z x Y x X volume (each side 2 .. 1024) */
+int xh_mono_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_mono **out);
+int xh_mono_destroy(xh_mono *h);
+/* ProgMonogenicSignalRes::run (:338-557) with produceSideInfo (:90-166), refiningMask (:203-256) and postProcessingLocalResolutions
+ * (:259-335). d_vol: the map, or the first half map with d_vol2 the second (null: single map). d_mask: the --mask volume as int32;
+ * d_mask_excl: --maskExcl or null. h_steps (nullable) receives the first max_steps records, *n_steps the number of evaluated
+ * frequencies, *stop the reason above. Outputs on the device: d_mean (nullable, written with half maps: meanMap), d_refined int32
+ * (refinedMask), d_chimera (monoresResolutionChimera), d_resmap (monoresResolutionMap). Synchronous. */
+int xh_mono_run(xh_mono *h, const double *d_vol, const double *d_vol2, const int32_t *d_mask, const int32_t *d_mask_excl, const xh_mono_params *prm,
+                xh_mono_step *h_steps, int32_t max_steps, int32_t *n_steps, int32_t *stop, double *d_mean, int32_t *d_refined, double *d_chimera,
+                double *d_resmap);
+/* after a run: proteinRadiusVolumeAndShellStatistics' radius, findCliffValue's radiuslimit, NVoxelsOriginalMask as the sweep used it;
+ * always: the number of shells. Null pointers are skipped */
+int xh_mono_info(const xh_mono *h, int32_t *radius, int32_t *radiuslimit, int64_t *nvoxels, int32_t *nshell);
+/* test hook: amplitudeMonoSig3D_LPF (:283-415; banded != 0) or monogenicAmplitude_3D_Fourier (:575-661) of the map d_vol, to d_out */
+int xh_mono_amplitude(xh_mono *h, const double *d_vol, double freq, double freqH, double freqL, int32_t banded, double *d_out);
+/* test hook: realGaussianFilter (data/fourier_filter.cpp :849) of d_vol in place */
+int xh_mono_gaussian(xh_mono *h, double *d_vol, double sigma);
+/* test hook: the statistics of one (amplitude, mask): d_ampN null is statisticsInOutBinaryMask2 on d_ampS, else statisticsInBinaryMask2;
+ * thr95 = sorted noise values [size_t(NN significance)]. An empty noise set is refused */
+int xh_mono_statistics(xh_mono *h, const double *d_ampS, const double *d_ampN, const int32_t *d_mask, double significance, xh_mono_stats *out);
+/* test hook: element `rank` (from 0) of the sorted values of d_vals [n] whose d_mask is not 0 (null: all), n at most Z Y X */
+int xh_mono_select(xh_mono *h, const double *d_vals, const int32_t *d_mask, size_t n, size_t rank, double *out);
+/* test hook: setLocalResolutionHalfMaps (halves != 0, :518-539) / setLocalResolutionMap (:548-569) on caller arrays [n], in place */
+int xh_mono_assign(xh_mono *h, const double *d_amp, int32_t *d_mask, double *d_res, size_t n, double threshold, double resolution, double resolution_2,
+                   int32_t halves);
+/* test hook: findCliffValue's per-shell sum, sum2 and N of d_vol about the Xmipp origin, each [xh_mono_num_shells] on the host */
+int xh_mono_shell_sums(xh_mono *h, const double *d_vol, double *h_sum, double *h_sum2, double *h_N);
+/* for the benchmark: with timing on a run records events around the stages of every frequency (and waits once more per frequency to read
+ * them); h_ms[7] = split / filter, the batched inverse line passes, the amplitude row pass, smoothing, statistics, select, assign, summed
+ * over the last run's frequencies (both maps with half maps) */
+int xh_mono_set_timing(xh_mono *h, int32_t on);
+int xh_mono_stage_ms(const xh_mono *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,20 @@ class CtfParams(C.Structure):
         "DeltaF", "DeltaR", "Q0", "K", "envR0", "envR1", "envR2", "phase_shift", "VPP_radius")]
 
 
+class MonoParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("sampling", "minRes", "maxRes", "freq_step", "significance")] + [("gaussian", C.c_int32),
+                                                                                                           ("noise_only_in_halves", C.c_int32)]
+
+
+class MonoStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("NS", "NN", "sumS", "sumS2", "sumN", "sumN2", "meanS", "sdS2", "meanN", "sdN2", "thr95")]
+
+
+class MonoStep(C.Structure):
+    _fields_ = [("stats", MonoStats)] + [(n, C.c_double) for n in ("resolution", "freq", "freqH", "freqL", "threshold", "z", "max_meanS")] + [
+        ("assigned", C.c_int32), ("pad_", C.c_int32)]
+
+
 class Ca2Params(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "max_shift", "max_scale", "max_angular_change", "max_defocus_change", "max_resolution", "max_gray_scale", "max_gray_shift",
@@ -180,6 +194,24 @@ SIGNATURES = {
     "xh_halves_band_timing": (C.c_int, [vp, C.POINTER(C.c_int32), vp]),
     "xh_halves_circular_mask": (C.c_int, [i32, i32, i32, d, d, d, d, vp]),
     "xh_halves_binary_mask": (C.c_int, [vp, sz, vp]),
+    "xh_mono_defaults": (None, [vp]),
+    "xh_mono_icdf_gauss": (C.c_int, [d, C.POINTER(C.c_double)]),
+    "xh_mono_resolution2eval": (C.c_int, [C.POINTER(i32), d, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(i32), d, d]),
+    "xh_mono_cliff_radius": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(i32)]),
+    "xh_mono_num_shells": (C.c_int, [i32, i32, i32, C.POINTER(i32)]),
+    "xh_mono_create": (C.c_int, [vp, i32, i32, i32, pvp]),
+    "xh_mono_destroy": (C.c_int, [vp]),
+    "xh_mono_run": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, vp, vp]),
+    "xh_mono_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)]),
+    "xh_mono_amplitude": (C.c_int, [vp, vp, d, d, d, i32, vp]),
+    "xh_mono_gaussian": (C.c_int, [vp, vp, d]),
+    "xh_mono_statistics": (C.c_int, [vp, vp, vp, vp, d, vp]),
+    "xh_mono_select": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_double)]),
+    "xh_mono_assign": (C.c_int, [vp, vp, vp, vp, sz, d, d, d, i32]),
+    "xh_mono_shell_sums": (C.c_int, [vp, vp, vp, vp, vp]),
+    "xh_mono_set_timing": (C.c_int, [vp, i32]),
+    "xh_mono_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

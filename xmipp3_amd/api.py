@@ -814,6 +814,156 @@ def halves_binary_mask(values):
     check(lib().xh_halves_binary_mask(_np_ptr(v), v.size, _np_ptr(m)))
     return m
 
+class MonoRes(_Handle):
+    """The device side of xmipp_resolution_monogenic_signal (MonoRes): the local resolution map of a volume, or of two half maps,
+    [Z, Y, X] float64 tensors on the device; masks are int32 tensors."""
+
+    _destroy = "xh_mono_destroy"
+
+    STOP = {1: "range", 2: "mask_done", 3: "no_points", 4: "low_signal", 5: "ztest", 6: "min_res"}
+    STAGES = ("split", "inverse", "rows", "smooth", "stats", "select", "assign")
+
+    def __init__(self, ctx, shape):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        h = C.c_void_p()
+        check(lib().xh_mono_create(ctx.h, *self.shape, C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _vol(self, t, dtype=None):
+        torch = _torch()
+        dtype = dtype or torch.float64
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == self.shape, (t.shape, t.dtype)
+        return t
+
+    def run(self, vol, mask, vol2=None, mask_excl=None, sampling=1.0, min_res=30.0, max_res=1.0, step=0.25, significance=0.95, gaussian=False,
+            noise_only_in_halves=False, max_steps=4096):
+        """ProgMonogenicSignalRes::run. Returns a dict: mean (half maps only), refined_mask (int32), chimera, resolution_map (device
+        tensors), steps (one dict per evaluated frequency), stop (why the sweep ended), radius, radiuslimit, nvoxels."""
+        torch = _torch()
+        from ._lib import MonoParams, MonoStep
+        prm = MonoParams()
+        lib().xh_mono_defaults(C.byref(prm))
+        prm.sampling, prm.minRes, prm.maxRes, prm.freq_step, prm.significance = float(sampling), float(min_res), float(max_res), float(step), float(significance)
+        prm.gaussian, prm.noise_only_in_halves = int(bool(gaussian)), int(bool(noise_only_in_halves))
+        steps = (MonoStep * int(max_steps))()
+        n, stop = C.c_int32(), C.c_int32()
+        mean = torch.empty(self.shape, dtype=torch.float64, device="cuda") if vol2 is not None else None
+        refined = torch.empty(self.shape, dtype=torch.int32, device="cuda")
+        chimera = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        resmap = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        check(lib().xh_mono_run(self.h, _ptr(self._vol(vol)), None if vol2 is None else _ptr(self._vol(vol2)), _ptr(self._vol(mask, torch.int32)),
+                                None if mask_excl is None else _ptr(self._vol(mask_excl, torch.int32)), C.byref(prm), C.cast(steps, C.c_void_p), int(max_steps),
+                                C.byref(n), C.byref(stop), _ptr(mean), _ptr(refined), _ptr(chimera), _ptr(resmap)))
+        recs = []
+        for k in range(min(n.value, int(max_steps))):
+            r = steps[k]
+            rec = {f: getattr(r.stats, f) for f, _ in r.stats._fields_}
+            rec.update({f: getattr(r, f) for f in ("resolution", "freq", "freqH", "freqL", "threshold", "z", "max_meanS", "assigned")})
+            recs.append(rec)
+        out = {"mean": mean, "refined_mask": refined, "chimera": chimera, "resolution_map": resmap, "steps": recs, "stop": self.STOP.get(stop.value, stop.value)}
+        out.update(self.info())
+        return out
+
+    def info(self):
+        r, rl, ns = C.c_int32(), C.c_int32(), C.c_int32()
+        nv = C.c_int64()
+        check(lib().xh_mono_info(self.h, C.byref(r), C.byref(rl), C.byref(nv), C.byref(ns)))
+        return {"radius": r.value, "radiuslimit": rl.value, "nvoxels": nv.value, "nshell": ns.value}
+
+    def amplitude(self, vol, freq, freqH, freqL, banded=True):
+        """amplitudeMonoSig3D_LPF (banded) or monogenicAmplitude_3D_Fourier of a map, as a new device tensor"""
+        torch = _torch()
+        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        check(lib().xh_mono_amplitude(self.h, _ptr(self._vol(vol)), float(freq), float(freqH), float(freqL), int(bool(banded)), _ptr(out)))
+        return out
+
+    def gaussian(self, vol, sigma):
+        """realGaussianFilter of a copy of vol"""
+        out = self._vol(vol).clone()
+        check(lib().xh_mono_gaussian(self.h, _ptr(out), float(sigma)))
+        return out
+
+    def statistics(self, ampS, mask, ampN=None, significance=0.95):
+        from ._lib import MonoStats
+        st = MonoStats()
+        check(lib().xh_mono_statistics(self.h, _ptr(self._vol(ampS)), None if ampN is None else _ptr(self._vol(ampN)), _ptr(self._vol(mask, _torch().int32)),
+                                       float(significance), C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def select(self, vals, rank, mask=None):
+        """element `rank` of the sorted values (of those whose mask is not 0); vals a 1-D float64 device tensor"""
+        torch = _torch()
+        assert vals.is_cuda and vals.dtype == torch.float64 and vals.is_contiguous() and vals.dim() == 1
+        assert mask is None or (mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous() and mask.shape == vals.shape)
+        v = C.c_double()
+        check(lib().xh_mono_select(self.h, _ptr(vals), _ptr(mask), vals.numel(), int(rank), C.byref(v)))
+        return v.value
+
+    def assign(self, amp, mask, res, threshold, resolution, resolution_2, halves):
+        """the assign step on 1-D caller tensors, in place"""
+        torch = _torch()
+        assert amp.dtype == torch.float64 and res.dtype == torch.float64 and mask.dtype == torch.int32 and amp.numel() == mask.numel() == res.numel()
+        check(lib().xh_mono_assign(self.h, _ptr(amp), _ptr(mask), _ptr(res), amp.numel(), float(threshold), float(resolution), float(resolution_2), int(bool(halves))))
+
+    def shell_sums(self, vol):
+        """findCliffValue's per-shell (sum, sum2, N) of a map about the Xmipp origin"""
+        ns = self.info()["nshell"]
+        s, s2, n = np.zeros(ns), np.zeros(ns), np.zeros(ns)
+        check(lib().xh_mono_shell_sums(self.h, _ptr(self._vol(vol)), _np_ptr(s), _np_ptr(s2), _np_ptr(n)))
+        return s, s2, n
+
+    def set_timing(self, on):
+        check(lib().xh_mono_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        ms = np.zeros(len(self.STAGES))
+        check(lib().xh_mono_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
+
+
+def mono_icdf_gauss(p):
+    """icdf_gauss as MonoRes uses it (host only)"""
+    v = C.c_double()
+    check(lib().xh_mono_icdf_gauss(float(p), C.byref(v)))
+    return v.value
+
+
+def mono_resolution_sweep(volsize, sampling, max_res, step, limit=100000):
+    """resolution2eval called as run does until it breaks: the list of (decision, resolution, freq) with decision 'eval', 'continue' or
+    'break' (host only; the sweep's other stop rules are not applied)"""
+    count, last_idx, cont, brk = C.c_int32(0), C.c_int32(-1), C.c_int32(), C.c_int32()
+    res, last, freq, freqL = C.c_double(), C.c_double(max_res), C.c_double(), C.c_double()
+    out = []
+    for _ in range(limit):
+        check(lib().xh_mono_resolution2eval(C.byref(count), float(step), C.byref(res), C.byref(last), C.byref(freq), C.byref(freqL), C.byref(last_idx),
+                                            int(volsize), C.byref(cont), C.byref(brk), float(sampling), float(max_res)))
+        if cont.value:
+            out.append(("continue", res.value, freq.value))
+            continue
+        if brk.value:
+            out.append(("break", res.value, freq.value))
+            break
+        out.append(("eval", res.value, freq.value))
+        last.value = res.value
+    return out
+
+
+def mono_cliff_radius(s, s2, n, radius, X):
+    """the shell walk of findCliffValue over per-shell sums (host only)"""
+    s, s2, n = (np.ascontiguousarray(a, np.float64) for a in (s, s2, n))
+    out = C.c_int32()
+    check(lib().xh_mono_cliff_radius(_np_ptr(s), _np_ptr(s2), _np_ptr(n), s.size, int(radius), int(X), C.byref(out)))
+    return out.value
+
+
+def mono_num_shells(shape):
+    out = C.c_int32()
+    check(lib().xh_mono_num_shells(*(int(v) for v in shape), C.byref(out)))
+    return out.value
+
+
 def vds_num_terms(L1, L2):
     """terms of the Zernike3D basis of degrees (L1, L2) (host only)"""
     n = C.c_int32()

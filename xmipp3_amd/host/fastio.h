@@ -57,6 +57,7 @@ struct XhDestroy {
     void operator()(xh_faz *h) const { xh_faz_destroy(h); }
     void operator()(xh_rsp *h) const { xh_rsp_destroy(h); }
     void operator()(xh_sub *h) const { xh_sub_destroy(h); }
+    void operator()(xh_mono *h) const { xh_mono_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 

@@ -287,7 +287,10 @@ int xh_pm_last_coefficients(const xh_pm *pm, const float **d_coefs, int32_t *fir
  * the supported range is an RMS within 2^-64 .. 2^64 of 1 for every particle and reference, in any ratio to each other
  * (tests/test_gpu_pm_scale.py holds 1e-3 .. 1e3 either way). A particle whose pixels are all equal (unmirrored, or zero)
  * or an all-zero reference gets the reference's shift for a constant map, (0, 0). Repeats are ordered: the same input gives
- * the same bits from run to run. */
+ * the same bits from run to run.
+ * "s6_layout" 1 | 0: between its row and column transforms the fp32 pass keeps the spectra column-major (a column is one run in
+ * memory, which the column pass reads and writes whole) or row-major (the earlier kernels, kept for comparison). Same arithmetic
+ * in the same order: identical results either way. */
 int xh_pm_translate_stats(const xh_pm *pm, int64_t *repeated);
 /* statistics of the last xh_pm_match call: rows evaluated, particles re-scored in fp64 */
 int xh_pm_last_stats(const xh_pm *pm, int64_t *rows, int64_t *rescored_particles,
@@ -317,7 +320,7 @@ int xh_pm_rows_pruned(const xh_pm *pm, int64_t *rows_pruned);
  * theirs already). xh_pm_rows_pruned keeps counting the rows the sums of moduli skipped. */
 int xh_pm_two_level_cut(const xh_pm *pm, int32_t *K0, int32_t *nk);
 /* tuning knobs: "tau_rel" (fp32 ambiguity margin relative to sum_r 2*pi*r), "chunk_rows" (rows per launch chunk), "prune", "k0",
- * "mask_lists", "group_high", "low_pass", "high_cap", "adaptive_finish", "tr_chunk_mb", "s6_fp32", "s6_eps", "s6_capture" (see above and below).
+ * "mask_lists", "group_high", "low_pass", "high_cap", "adaptive_finish", "tr_chunk_mb", "s6_fp32", "s6_eps", "s6_layout", "s6_capture" (see above and below).
  * "threads" n (1..16): the reference program's --thr (angular_projection_matching.cpp:64,631,1018-1108).  Its n worker threads take
  * the positions i % n of a particle's neighbour list and their results are merged, worker 0 first, strictly greater wins -- which
  * only shows where two correlation values are EXACTLY equal (duplicated references): the winner is then the one with the smallest
@@ -327,7 +330,7 @@ int xh_pm_set_option(xh_pm *pm, const char *name, double value);
 /* current value of "tau_rel" (ambiguity margin of the fp32 coarse search, relative to sum_r 2 pi r) or "s6_eps" (margin of the
  * fp32 pass of xh_pm_translate, relative to the maximum of the correlation map): the tests hold the measured fp32 errors against them;
  * "adaptive_finish", "dense_chunks", "low_pass", "low_pass_rows_in", "low_pass_rows_out", "low_pass_rows_transformed": see
- * xh_pm_two_level_cut */
+ * xh_pm_two_level_cut; "s6_layout": see xh_pm_translate_stats */
 int xh_pm_get_option(const xh_pm *pm, const char *name, double *value);
 
 /* ---- FourierProjector: central-slice projections of a volume ------------------

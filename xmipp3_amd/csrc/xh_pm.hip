@@ -138,6 +138,7 @@ struct xh_pm {
     XhBuf d_bpart, d_rowBound, d_rowTail, d_topRows, d_thr, d_survList, d_survSpan, d_highStore;
     int group_high;              // the surviving rows' frequencies >= K0 particle by particle (k_pm_rows_high; 0: each transforming wave its own, for A/B)
     int high_cap;                // rows of the store behind k_pm_rows_high (0: max(65536, rows / 16); the tests set a few to reach the rows beyond it)
+    int s6_layout;               // fp32 S6 chain: w column-major between the line passes (S6Cm; 0: row-major, the earlier kernels, for A/B)
     int low_pass;                // the survivors' low frequencies first, a second threshold from them (k_pm_low_keep; 0: every survivor is finished, for A/B)
     int64_t stat_pruned;
     int64_t stat_low_in, stat_low_out, stat_low_rows;      // last call: survivors the low pass looked at, those it kept, rows it transformed for that
@@ -3330,9 +3331,24 @@ k_pm_tr_irows(const xh_cd *__restrict__ w, double *__restrict__ Rout, const xh_c
     }
 }
 
+// Between the line passes of the fp32 chain w is column-major, w[p][kx][y] (option "s6_layout" 1; CM below): a column of a particle
+// is one run of D elements, which k_pm_s6f_cols_pair reads and writes whole, where the row-major layout gave it a 32-byte piece of
+// every 128-byte line it touched.  The row kernels pay for it with one more trip through LDS: their LN rows go to / come from memory
+// as LN consecutive y of one kx (128 bytes at LN = 16), thread = (l = tid % LN, g = tid / LN).  Element u of thread g is the
+// frequency kx = k1 + R1 k2 with k2 = (g + NG u) % R2, k1 = (g + NG u) / R2: it lies at k1 S1 + k2 of line l, where tr_fwd2 / tr_inv2
+// have it, and neighbouring lanes are neighbouring lines (the map TrGeom::LS is padded for).  Only addresses and lane maps differ
+// from the row-major kernels (CM = false: option "s6_layout" 0); every operation keeps its operands and its order.
+template <int R1, int R2> struct S6Cm {
+    typedef TrGeom<R1, R2, float> G;
+    static constexpr int NG = 256 / G::LN;      // frequencies kx per step of the workgroup
+    static constexpr int NU = G::D / NG;        // steps
+    static __device__ __forceinline__ int k1(int g, int u) { return (g + NG * u) / R2; }
+    static __device__ __forceinline__ int k2(int g, int u) { return (g + NG * u) % R2; }
+};
+
 // fp32 pass of S6 (see xh_pm_translate): forward rows of z = Mref + i Mimg, formed here from the prebuilt reference plane and the
 // particle's own row (mirrored where flip says so; 0 for refno < 0, as the plane is)
-template <int R1, int R2>
+template <int R1, int R2, bool CM>
 __global__ void __launch_bounds__(256)
 k_pm_s6f_rows(const float *__restrict__ zr, const float *__restrict__ particles, const int *__restrict__ refno,
               const unsigned char *__restrict__ flip, xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, const int4 *__restrict__ sc)
@@ -3394,13 +3410,30 @@ k_pm_s6f_rows(const float *__restrict__ zr, const float *__restrict__ particles,
     if (tid < G::LN * R1) {
         const int l = tid / R1, k1 = tid - l * R1;
         tr_fwd2<R1, R2>(v, s + l * G::LS, k1);
-        xh_cf *dst = w + ((size_t)p * D + row0 + l) * D;
+        if constexpr (!CM) {
+            xh_cf *dst = w + ((size_t)p * D + row0 + l) * D;
 #pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) dst[k1 + R1 * k2] = v[k2];
+            for (int k2 = 0; k2 < R2; ++k2) dst[k1 + R1 * k2] = v[k2];
+        } else {
+            xh_cf *sl = s + l * G::LS + k1 * G::S1;     // where this thread's own inputs lay: no other thread reads or writes them
+#pragma unroll
+            for (int k2 = 0; k2 < R2; ++k2) sl[k2] = v[k2];
+        }
+    }
+    if constexpr (CM) {
+        typedef S6Cm<R1, R2> C;
+        __syncthreads();
+        const int l = tid % G::LN, g = tid / G::LN;
+        xh_cf *dst = w + (size_t)p * D * D + row0 + l;
+#pragma unroll
+        for (int u = 0; u < C::NU; ++u) {
+            const int k1 = C::k1(g, u), k2 = C::k2(g, u);
+            dst[(size_t)(k1 + R1 * k2) * D] = s[l * G::LS + k1 * G::S1 + k2];
+        }
     }
 }
 
-template <int R1, int R2>
+template <int R1, int R2, bool CM>
 __global__ void __launch_bounds__(256)
 k_pm_s6f_cols_pair(xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, int m)
 {
@@ -3414,9 +3447,9 @@ k_pm_s6f_cols_pair(xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, int m)
     const int tid = threadIdx.x;
     const int pa = 2 * blockIdx.y, pb = min(pa + 1, m - 1);
     // The blocks of one particle pair that share 128-byte lines of its rows (neighbouring column groups) get block indices
-    // 8 apart: consecutive indices go to consecutive XCDs, so those blocks meet in one L2.
+    // 8 apart: consecutive indices go to consecutive XCDs, so those blocks meet in one L2.  (Column-major, no two blocks share a line.)
     const int ngrp = gridDim.x >> 3;
-    const int bx = (gridDim.x & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * ngrp + (int)(blockIdx.x >> 3);
+    const int bx = (CM || (gridDim.x & 7)) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * ngrp + (int)(blockIdx.x >> 3);
     for (int i = tid; i < D; i += 256) sW[i] = xh_cf{(float)WD[i].x, (float)WD[i].y};
     // line l: particle l / HL; within a particle, c = l % HL < HP: column P = blockIdx.x*HP + c, c >= HP: its partner D - P
     auto column = [&](int c) {
@@ -3427,12 +3460,19 @@ k_pm_s6f_cols_pair(xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, int m)
     };
     xh_cf v[G::RM];
     __syncthreads();
+    // the first and the last pass, thread = (line, n2): column-major a line is a run in memory and neighbouring lanes take
+    // neighbouring elements of it; row-major neighbouring lanes take the same element of neighbouring columns
+    const int cl = CM ? tid / R2 : tid % G::LN, n2 = CM ? tid % R2 : tid / G::LN;
     if (tid < G::LN * R2) {
-        const int cl = tid % G::LN, n2 = tid / G::LN;
         const xh_cf *img = w + (size_t)(cl < HL ? pa : pb) * D * D;
         const int col = column(cl % HL);
+        if constexpr (CM) {
 #pragma unroll
-        for (int n1 = 0; n1 < R1; ++n1) v[n1] = img[(size_t)(n1 * R2 + n2) * D + col];
+            for (int n1 = 0; n1 < R1; ++n1) v[n1] = img[(size_t)col * D + n1 * R2 + n2];
+        } else {
+#pragma unroll
+            for (int n1 = 0; n1 < R1; ++n1) v[n1] = img[(size_t)(n1 * R2 + n2) * D + col];
+        }
         tr_fwd1<R1, R2>(v, s + cl * G::LS, sW, n2);
     }
     __syncthreads();
@@ -3482,18 +3522,22 @@ k_pm_s6f_cols_pair(xh_cf *__restrict__ w, const xh_cd *__restrict__ WD, int m)
     if (act2 && cl2 < HL) tr_inv2<R1, R2>(v, s + cl2 * G::LS, sW, k1);
     __syncthreads();
     if (tid < G::LN * R2) {
-        const int cl = tid % G::LN, n2 = tid / G::LN;
         if (cl < HL) {
             tr_inv1<R1, R2>(v, s + cl * G::LS, n2);
             xh_cf *img = w + (size_t)pa * D * D;
             const int col = column(cl);
+            if constexpr (CM) {
 #pragma unroll
-            for (int n1 = 0; n1 < R1; ++n1) img[(size_t)(n1 * R2 + n2) * D + col] = v[n1];
+                for (int n1 = 0; n1 < R1; ++n1) img[(size_t)col * D + n1 * R2 + n2] = v[n1];
+            } else {
+#pragma unroll
+                for (int n1 = 0; n1 < R1; ++n1) img[(size_t)(n1 * R2 + n2) * D + col] = v[n1];
+            }
         }
     }
 }
 
-template <int R1, int R2, bool PAIR = false>
+template <int R1, int R2, bool PAIR, bool CM>
 __global__ void __launch_bounds__(256)
 k_pm_s6f_irows(const xh_cf *__restrict__ w, float *__restrict__ Rout, const xh_cd *__restrict__ WD, XhTrPart *__restrict__ part, int m,
                const int4 *__restrict__ sc)
@@ -3507,13 +3551,30 @@ k_pm_s6f_irows(const xh_cf *__restrict__ w, float *__restrict__ Rout, const xh_c
     // PAIR: the buffer of particle 2 blockIdx.y holds the combined columns of two particles (k_pm_tr_cols_pair)
     const int p = PAIR ? 2 * blockIdx.y : blockIdx.y, p2 = PAIR ? min(p + 1, m - 1) : p, row0 = blockIdx.x * G::LN;
     for (int i = tid; i < D; i += 256) sW[i] = xh_cf{(float)WD[i].x, (float)WD[i].y};
+    if constexpr (CM) {
+        // the LN rows come as LN consecutive y of every kx, all loads in flight before the first goes to LDS
+        typedef S6Cm<R1, R2> C;
+        const int l = tid % G::LN, g = tid / G::LN;
+        const xh_cf *src = w + (size_t)p * D * D + row0 + l;
+        xh_cf t[C::NU];
+#pragma unroll
+        for (int u = 0; u < C::NU; ++u) t[u] = src[(size_t)(C::k1(g, u) + R1 * C::k2(g, u)) * D];
+#pragma unroll
+        for (int u = 0; u < C::NU; ++u) s[l * G::LS + C::k1(g, u) * G::S1 + C::k2(g, u)] = t[u];
+    }
     __syncthreads();
     xh_cf v[G::RM];
     if (tid < G::LN * R1) {
         const int l = tid / R1, k1 = tid - l * R1;
-        const xh_cf *src = w + ((size_t)p * D + row0 + l) * D;
+        if constexpr (CM) {
+            const xh_cf *sl = s + l * G::LS + k1 * G::S1;       // tr_inv2 writes where this thread reads: no barrier between
 #pragma unroll
-        for (int k2 = 0; k2 < R2; ++k2) v[k2] = src[k1 + R1 * k2];
+            for (int k2 = 0; k2 < R2; ++k2) v[k2] = sl[k2];
+        } else {
+            const xh_cf *src = w + ((size_t)p * D + row0 + l) * D;
+#pragma unroll
+            for (int k2 = 0; k2 < R2; ++k2) v[k2] = src[k1 + R1 * k2];
+        }
         tr_inv2<R1, R2>(v, s + l * G::LS, sW, k1);
     }
     __syncthreads();
@@ -3828,6 +3889,7 @@ int xh_pm_create(xh_ctx *ctx, int32_t D, int32_t Ri, int32_t Ro, int32_t nrefs, 
     pm->adaptive_finish = 1;
     pm->group_high = 1;
     pm->low_pass = 1;
+    pm->s6_layout = 1;
     pm->stat_low_in = pm->stat_low_out = pm->stat_low_rows = 0;
     pm->lastLowPass = 0;
     pm->high_cap = 0;
@@ -4155,6 +4217,7 @@ int xh_pm_set_option(xh_pm *pm, const char *name, double value)
     else if (!strcmp(name, "mask_lists")) pm->use_mask_lists = (int)value;
     else if (!strcmp(name, "group_high")) pm->group_high = (int)value;
     else if (!strcmp(name, "low_pass")) pm->low_pass = (int)value;
+    else if (!strcmp(name, "s6_layout")) pm->s6_layout = (int)value != 0;
     else if (!strcmp(name, "high_cap")) pm->high_cap = (int)value;
     else if (!strcmp(name, "adaptive_finish")) { pm->adaptive_finish = (int)value; pm->finish_dense = value >= 2; }      // (2: start in the dense form)
     else if (!strcmp(name, "threads")) {
@@ -4787,17 +4850,22 @@ int xh_pm_translate(xh_pm *pm, const float *d_particles, int32_t n, const int32_
                            (double2 *)pm->d_trAngles.p, m, L.N);                                                            \
         hipLaunchKernelGGL((k_pm_tr_build<float, float, float>), dim3((D / XH_TRB) * (D / XH_TRB), m), dim3(256), 0, ctx->stream, \
                            parts, (const float *)pm->d_refCoef32.p, refno, (const double2 *)pm->d_trAngles.p, flip, z, D);  \
-        hipLaunchKernelGGL((k_pm_s6f_rows<A_, B_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const float *)z, parts, \
-                           refno, flip, w, (const xh_cd *)pm->d_WD64.p, (const int4 *)sc);                                  \
-        hipLaunchKernelGGL((k_pm_s6f_cols_pair<A_, B_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
-                           (const xh_cd *)pm->d_WD64.p, m);                                                                 \
-        hipLaunchKernelGGL((k_pm_s6f_irows<A_, B_, true>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream,    \
-                           (const xh_cf *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m, (const int4 *)sc); \
+        XH_S6F(A_, B_, true) else XH_S6F(A_, B_, false)                                                                     \
         nparts = D / G::LN;                                                                                                 \
+    }
+#define XH_S6F(A_, B_, CM_)                                                                                                 \
+    if (CM_ == (pm->s6_layout != 0)) {                                                                                      \
+        hipLaunchKernelGGL((k_pm_s6f_rows<A_, B_, CM_>), dim3(D / G::LN, m), dim3(256), G::smem, ctx->stream, (const float *)z, parts, \
+                           refno, flip, w, (const xh_cd *)pm->d_WD64.p, (const int4 *)sc);                                  \
+        hipLaunchKernelGGL((k_pm_s6f_cols_pair<A_, B_, CM_>), dim3(2 * D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, w, \
+                           (const xh_cd *)pm->d_WD64.p, m);                                                                 \
+        hipLaunchKernelGGL((k_pm_s6f_irows<A_, B_, true, CM_>), dim3(D / G::LN, (m + 1) / 2), dim3(256), G::smem, ctx->stream, \
+                           (const xh_cf *)w, R, (const xh_cd *)pm->d_WD64.p, (XhTrPart *)pm->d_trPart.p, m, (const int4 *)sc); \
     }
             if (D == 64) XH_TRF(8, 8)
             else if (D == 128) XH_TRF(16, 8)
             else XH_TRF(16, 16)
+#undef XH_S6F
 #undef XH_TRF
             XH_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_pm_bestshift_coarse, dim3(m), dim3(256), 0, ctx->stream, (const float *)R, (const float *)z, parts, refno, flip, D, max_shift, sx, sy, cc,
@@ -4919,6 +4987,7 @@ int xh_pm_get_option(const xh_pm *pm, const char *name, double *value)
     else if (!strcmp(name, "adaptive_finish")) *value = pm->adaptive_finish;
     else if (!strcmp(name, "dense_chunks")) *value = pm->stat_dense_chunks;      // chunks of the last match call contracted at every frequency
     else if (!strcmp(name, "low_pass")) *value = pm->low_pass;
+    else if (!strcmp(name, "s6_layout")) *value = pm->s6_layout;
     // the low pass of the last match call (k_pm_low_keep): survivors of the bounds it looked at, those it left to finish, and the rows it
     // transformed from their low frequencies to decide (the planned rows had been)
     else if (!strcmp(name, "low_pass_rows_in")) *value = (double)pm->stat_low_in;

@@ -490,21 +490,29 @@ k_rf_shift_band(const float *__restrict__ coefs, const float *__restrict__ imgs,
     const float minp = -cen, maxp = D - cen - 1;
     float xp = flip ? sh.x - (float)(j - cen) : (float)(j - cen) - sh.x;
     if (xp < minp - 1e-6f || xp > maxp + 1e-6f) xp = d_realwrap<float>(xp, minp - 0.5f, maxp + 0.5f);
-    float yp[XH_SHB], ys[XH_SHB];
+    // What a row of the band needs -- its source ordinate, the first row of its footprint and its four weights -- depends on the row
+    // and on sh.y only: lane k of every wave works it out for row k (the lanes past XH_SHB repeat rows 0 .. XH_SHB - 1), with the
+    // expressions every thread used to evaluate for all sixteen rows (no contraction in this file: the same bits), and the wave
+    // reads the values back as scalars.
+    const int kl = j & (XH_SHB - 1);
+    float ypl = (float)(i0 + kl - cen) - sh.y;
+    if (ypl < minp - 1e-6f || ypl > maxp + 1e-6f) ypl = d_realwrap<float>(ypl, minp - 0.5f, maxp + 0.5f);
+    const float ysl = ypl - (float)(-cen);
+    const int m1l = (int)ceilf(ysl - 2.f);
+    float wyl[4];
+    d_bspline03_w4<float>(ysl, m1l, wyl);
     int m1[XH_SHB];
     bool chain = true;
 #pragma unroll
     for (int k = 0; k < XH_SHB; ++k) {
-        yp[k] = (float)(i0 + k - cen) - sh.y;
-        if (yp[k] < minp - 1e-6f || yp[k] > maxp + 1e-6f) yp[k] = d_realwrap<float>(yp[k], minp - 0.5f, maxp + 0.5f);
-        ys[k] = yp[k] - (float)(-cen);
-        m1[k] = (int)ceilf(ys[k] - 2.f);
+        m1[k] = __builtin_amdgcn_readlane(m1l, k);
         chain = chain && m1[k] == m1[0] + k;
     }
     const float *cf = coefs + base;
     if (!chain) {                                       // (the same for every thread of the band: the rows depend on the row index only)
 #pragma unroll
-        for (int k = 0; k < XH_SHB; ++k) out[base + (size_t)(i0 + k) * D + j] = d_interp<float>(cf, D, xp, yp[k]);
+        for (int k = 0; k < XH_SHB; ++k)
+            out[base + (size_t)(i0 + k) * D + j] = d_interp<float>(cf, D, xp, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ypl), k)));
         return;
     }
     float st[XH_SHB + 3];
@@ -535,7 +543,8 @@ k_rf_shift_band(const float *__restrict__ coefs, const float *__restrict__ imgs,
 #pragma unroll
     for (int k = 0; k < XH_SHB; ++k) {
         float wy[4];
-        d_bspline03_w4<float>(ys[k], m1[k], wy);
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) wy[tt] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wyl[tt]), k));
         float columns = 0;
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt) columns += rows[k + tt] * wy[tt];

@@ -1049,6 +1049,50 @@ int xh_mono_shell_sums(xh_mono *h, const double *d_vol, double *h_sum, double *h
 int xh_mono_set_timing(xh_mono *h, int32_t on);
 int xh_mono_stage_ms(const xh_mono *h, double *h_ms);
 
+/* ---- xmipp_volume_local_sharpening, LocalDeblur (libraries/reconstruction/volume_local_sharpening.{h,cpp}, ProgLocSharpening) ----
+ * Sharpens a map with the local resolution map MonoRes gives: an iteration applies twice the operator L, a bank of narrow band-pass
+ * filters (one per resolution, 0.2 A apart) whose outputs are weighted voxel by voxel with exp(-K (res - resVol)^2) and summed. The
+ * reference runs fp64 FFTW transforms on CPU threads; here the band filter, the weights and the sum over bands stay on the device and the
+ * host reads one small record per iteration. Everything is fp64. The kernels, the reference behaviours kept as written and the refusals
+ * are listed at the head of xmipp3_amd/csrc/xh_ldb.hip. Volumes are [Z][Y][X]. */
+typedef struct xh_ldb xh_ldb;
+/* one iteration of run (:311-398): norm = |op|, porc = lastnorm 100 / norm, subst = porc - lastporc (:345-348), lambda as used by this
+ * iteration's update (:360-364, :378), stop: the rule subst < 1 && i > 2 has fired (:350-355) */
+typedef struct {
+    double norm, porc, subst, lambda;
+    int32_t stop, pad_;
+} xh_ldb_iter;
+/* host only: the bands of localfiltering (:231-244) for a spectrum of zsize planes: res from 2 sampling below max_res in repeated
+ * additions of 0.2, a band whose DIGFREQ2FFT_IDX(sampling / res, zsize) equals the last processed one skipped. max_res is the loop's
+ * bound, which run sets to the map's maximum + 2 (:298). h_bands [cap][4] receives res, w = sampling / res, wL = sampling / (res - 0.2)
+ * and the index of the first cap bands, *n their number. 2 sampling - 0.2 <= 0 is refused */
+int xh_ldb_bands(int32_t zsize, double sampling, double max_res, double *h_bands, int32_t cap, int32_t *n);
+/* every buffer of a Z x Y x X volume (each side 2 .. 1024), the plans and the spectra of `batch` bands (1 .. 64, rounded up to an even
+ * number: two bands share a complex line in the row kernel) */
+int xh_ldb_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t batch, xh_ldb **out);
+int xh_ldb_destroy(xh_ldb *h);
+/* produceSideInfo (:58-130): copies the volume and the resolution map, takes maxRes before the clamp (:132-149), raises resolutions in
+ * (0, 2 sampling) to 2 sampling (:115-123), computes desvOutside (:151-179), the band list for maxRes + 2 and lastweight (:263). A map
+ * without a voxel at or above 2 sampling is refused. Synchronous */
+int xh_ldb_load(xh_ldb *h, const double *d_vol, const double *d_res, double sampling, double K);
+/* after a load: maxRes (before the + 2 of run), desvOutside, the number of voxels with resVol < 2 sampling, the number of bands;
+ * h_bands [cap][6]: res, w, wL, index, and the band's table of kept lines: kcount (z planes whose y lines are transformed) and jcount
+ * (columns kept in every pass). Null pointers are skipped */
+int xh_ldb_info(const xh_ldb *h, double *maxRes, double *desvOutside, int64_t *noutside, int32_t *nbands, double *h_bands, int32_t cap);
+/* test hook: the clamped resolution map, to d_out */
+int xh_ldb_resmap(xh_ldb *h, double *d_out);
+/* test hook: localfiltering (:219-283) of the volume d_in, to d_out */
+int xh_ldb_localfilter(xh_ldb *h, const double *d_in, double *d_out);
+/* run (:285-407) on the loaded volume: at most niter iterations (>= 1), lambda == 1 estimated at the first one (:360-364). h_iters
+ * (nullable) receives the first max_iters records, *n_iters the last i, *stopped whether the stop rule ended the loop, *lambda_out the
+ * lambda in use at the end (MDL_COST, :400), d_out the sharpened map. Synchronous */
+int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, int32_t max_iters, int32_t *n_iters, int32_t *stopped, double *lambda_out,
+               double *d_out);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[5] = forward transforms, split, the y and z line passes, the
+ * row pass, finishing, summed since set_timing or the start of the last run */
+int xh_ldb_set_timing(xh_ldb *h, int32_t on);
+int xh_ldb_stage_ms(const xh_ldb *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,10 @@ class MonoStep(C.Structure):
         ("assigned", C.c_int32), ("pad_", C.c_int32)]
 
 
+class LdbIter(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("norm", "porc", "subst", "lambda_")] + [("stop", C.c_int32), ("pad_", C.c_int32)]
+
+
 class Ca2Params(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "max_shift", "max_scale", "max_angular_change", "max_defocus_change", "max_resolution", "max_gray_scale", "max_gray_shift",
@@ -212,6 +216,16 @@ SIGNATURES = {
     "xh_mono_shell_sums": (C.c_int, [vp, vp, vp, vp, vp]),
     "xh_mono_set_timing": (C.c_int, [vp, i32]),
     "xh_mono_stage_ms": (C.c_int, [vp, vp]),
+    "xh_ldb_bands": (C.c_int, [i32, d, d, vp, i32, C.POINTER(i32)]),
+    "xh_ldb_create": (C.c_int, [vp, i32, i32, i32, i32, pvp]),
+    "xh_ldb_destroy": (C.c_int, [vp]),
+    "xh_ldb_load": (C.c_int, [vp, vp, vp, d, d]),
+    "xh_ldb_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i32), vp, i32]),
+    "xh_ldb_resmap": (C.c_int, [vp, vp]),
+    "xh_ldb_localfilter": (C.c_int, [vp, vp, vp]),
+    "xh_ldb_run": (C.c_int, [vp, d, i32, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), vp]),
+    "xh_ldb_set_timing": (C.c_int, [vp, i32]),
+    "xh_ldb_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

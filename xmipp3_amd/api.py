@@ -964,6 +964,86 @@ def mono_num_shells(shape):
     return out.value
 
 
+class LocalDeblur(_Handle):
+    """The device side of xmipp_volume_local_sharpening (LocalDeblur): sharpens a volume with its local resolution map, [Z, Y, X] float64
+    tensors on the device. batch: the band spectra held at once (rounded up to an even number; any value gives the same bytes)."""
+
+    _destroy = "xh_ldb_destroy"
+
+    STAGES = ("forward", "split", "yz", "rows", "finish")
+
+    def __init__(self, ctx, shape, batch=8):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        h = C.c_void_p()
+        check(lib().xh_ldb_create(ctx.h, *self.shape, int(batch), C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _vol(self, t, what="volume"):
+        torch = _torch()
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise XhError(f"LocalDeblur: the {what} must be a contiguous float64 cuda tensor")
+        if tuple(t.shape) != self.shape:
+            raise XhError(f"LocalDeblur: the {what} has shape {tuple(t.shape)}, the handle {self.shape}")
+        return t
+
+    def load(self, vol, resmap, sampling=1.0, K=0.025):
+        """produceSideInfo: the volume and its resolution map (both are copied)"""
+        check(lib().xh_ldb_load(self.h, _ptr(self._vol(vol)), _ptr(self._vol(resmap, "resolution map")), float(sampling), float(K)))
+
+    def info(self):
+        """maxRes (before run's + 2), desvOutside, the number of voxels below 2 sampling and the band list: one dict per band with res, w,
+        wL, idx and the kept lines of the y and z passes (kcount planes, jcount columns)"""
+        mr, dv, no, nb = C.c_double(), C.c_double(), C.c_int64(), C.c_int32()
+        check(lib().xh_ldb_info(self.h, C.byref(mr), C.byref(dv), C.byref(no), C.byref(nb), None, 0))
+        b = np.zeros((nb.value, 6))
+        check(lib().xh_ldb_info(self.h, None, None, None, None, _np_ptr(b), nb.value))
+        bands = [{"res": r[0], "w": r[1], "wL": r[2], "idx": int(r[3]), "kcount": int(r[4]), "jcount": int(r[5])} for r in b]
+        return {"maxRes": mr.value, "desvOutside": dv.value, "noutside": no.value, "bands": bands}
+
+    def resmap(self):
+        """the resolution map as load left it (clamped)"""
+        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        check(lib().xh_ldb_resmap(self.h, _ptr(out)))
+        return out
+
+    def localfilter(self, v):
+        """localfiltering of a volume, as a new device tensor"""
+        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        check(lib().xh_ldb_localfilter(self.h, _ptr(self._vol(v)), _ptr(out)))
+        return out
+
+    def run(self, lam=1.0, niter=50):
+        """ProgLocSharpening::run on the loaded volume: (sharpened map, lambda, one dict per iteration: norm, porc, subst, lambda, stop)"""
+        from ._lib import LdbIter
+        cap = max(int(niter), 1)
+        recs = (LdbIter * cap)()
+        n, stopped, lout = C.c_int32(), C.c_int32(), C.c_double()
+        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        check(lib().xh_ldb_run(self.h, float(lam), int(niter), C.cast(recs, C.c_void_p), cap, C.byref(n), C.byref(stopped), C.byref(lout), _ptr(out)))
+        its = [{"norm": r.norm, "porc": r.porc, "subst": r.subst, "lambda": r.lambda_, "stop": bool(r.stop)} for r in recs[:n.value]]
+        return out, lout.value, its
+
+    def set_timing(self, on):
+        check(lib().xh_ldb_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        ms = np.zeros(len(self.STAGES))
+        check(lib().xh_ldb_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
+
+
+def ldb_bands(zsize, sampling, max_res):
+    """the bands of LocalDeblur's localfiltering for a spectrum of zsize planes, max_res being the loop's bound (the map's maximum + 2):
+    a list of (res, w, wL, idx) (host only)"""
+    n = C.c_int32()
+    check(lib().xh_ldb_bands(int(zsize), float(sampling), float(max_res), None, 0, C.byref(n)))
+    b = np.zeros((n.value, 4))
+    check(lib().xh_ldb_bands(int(zsize), float(sampling), float(max_res), _np_ptr(b), n.value, C.byref(n)))
+    return [(r[0], r[1], r[2], int(r[3])) for r in b]
+
+
 def vds_num_terms(L1, L2):
     """terms of the Zernike3D basis of degrees (L1, L2) (host only)"""
     n = C.c_int32()

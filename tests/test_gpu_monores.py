@@ -1,7 +1,10 @@
 """GPU parity of xmipp_resolution_monogenic_signal (xh_mono_*, MonoRes in api.py) against the numpy fp64 restatement of the reference
 (tests/monores_ref.py): the monogenic amplitude of one frequency, the per-shell sums, the one-rank select, the statistics, the assign
 step, and the program end to end. Volumes are seeded synthetic ones: blobs with a texture low-passed to two local resolutions, zero
-beyond a sphere, plus Gaussian noise inside a larger sphere; half maps are the same signal with independent noise."""
+beyond a sphere, plus Gaussian noise inside a larger sphere; half maps are the same signal with independent noise.
+
+The stages whose kernels choose a tile from the size (amplitude, Gaussian filter, shell sums, statistics, select) also run at the shapes of
+tests/volume_tiles.py, where they leave the tile of the small shapes; the end-to-end sweep stays at 32^3."""
 import os
 import subprocess
 
@@ -9,12 +12,19 @@ import numpy as np
 import pytest
 
 from tests import monores_ref as R
+from tests import volume_tiles as T
 from tests import xmipp_io
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROG = os.path.join(ROOT, "xmipp3_amd", "bin", "xmipp_resolution_monogenic_signal")
+SMALL = [(24, 20, 18), (21, 21, 21)]
+# where the stages that depend on the size leave the tile of SMALL (tests/volume_tiles.py, asserted by tests/test_volume_tiles.py):
+# POW2_X the bit-reversed placement of k_mn_rows_amp; X160 and X300 its rpb = 2 (with a tail workgroup) and 1; Z130 the z line pass at
+# 64 KiB of LDS. BIG takes every grid-stride loop into another lap; it has tests of its own, one frequency and one sigma
+STAGE_SHAPES = SMALL + [T.POW2_X, T.X160, T.X300, T.Z130]
+BIG = T.BIG
 
 
 @pytest.fixture(scope="module")
@@ -45,9 +55,13 @@ def _plane_error(got, exp):
     return max(float(np.abs(got[k] - exp[k]).max() / np.abs(exp[k]).max()) for k in range(exp.shape[0]))
 
 
-@pytest.mark.parametrize("shape", [(24, 20, 18), (21, 21, 21)])
+@pytest.mark.parametrize("shape", STAGE_SHAPES)
 @pytest.mark.parametrize("freq", [0.015, 0.25, 0.49])      # freqH clips to 0, the middle, freqL clips to 0.5
 def test_amplitude_of_one_frequency(gpu, shape, freq):
+    _check_amplitude(gpu, shape, freq)
+
+
+def _check_amplitude(gpu, shape, freq):
     xa, ctx, torch = gpu
     v, F = _amp_input(shape)
     freqL, freqH = min(freq + 0.02, 0.5), max(freq - 0.02, 0.0)
@@ -60,8 +74,12 @@ def test_amplitude_of_one_frequency(gpu, shape, freq):
     assert err <= 1e-10
 
 
-@pytest.mark.parametrize("shape", [(24, 20, 18), (21, 21, 21)])
+@pytest.mark.parametrize("shape", STAGE_SHAPES)
 def test_amplitude_unbanded(gpu, shape):
+    _check_amplitude_unbanded(gpu, shape)
+
+
+def _check_amplitude_unbanded(gpu, shape):
     xa, ctx, torch = gpu
     v, F = _amp_input(shape)
     exp = R.monogenic_amplitude_3d_fourier(F, shape)
@@ -71,27 +89,66 @@ def test_amplitude_unbanded(gpu, shape):
     assert err <= 1e-10
 
 
-@pytest.mark.parametrize("shape", [(24, 20, 18), (21, 21, 21)])
+@pytest.mark.parametrize("shape", STAGE_SHAPES)
 @pytest.mark.parametrize("sigma", [3.0, 4.0])
 def test_gaussian_filter(gpu, shape, sigma):
+    _check_gaussian_filter(gpu, shape, sigma)
+
+
+def _check_gaussian_filter(gpu, shape, sigma):
     xa, ctx, torch = gpu
     v, _ = _amp_input(shape)
     exp = R.real_gaussian_filter(v, sigma)
     got = xa.MonoRes(ctx, shape).gaussian(torch.from_numpy(v).cuda(), sigma).cpu().numpy()
+    print(f"gaussian {shape} sigma {sigma}: error {np.abs(got - exp).max() / np.abs(exp).max():.3e} of the maximum")
     assert np.abs(got - exp).max() <= 1e-10 * np.abs(exp).max()
 
 
+@pytest.fixture(scope="module")
+def big(gpu):
+    """BIG has more half-spectrum elements than the grid cap has threads: k_mn_split, k_mn_lowpass and k_mn_gauss take a second lap over
+    NF; the loops over the N voxels (k_mn_stats, k_mn_sel_pass with its run-length carried from lap to lap) a third"""
+    xa, ctx, torch = gpu
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    t = T.tiling(BIG)
+    print(f"{BIG}: {t.NF} half-spectrum elements, {t.N} voxels on {cus} CUs, grid cap {256 * 4 * cus} threads")
+    assert t.NF > 256 * 4 * cus, f"{t.NF} half-spectrum elements do not exceed the grid cap of {256 * 4 * cus} threads on {cus} CUs"
+    return BIG
+
+
+def test_amplitude_past_the_grid_cap(gpu, big):
+    _check_amplitude(gpu, big, 0.25)
+
+
+def test_amplitude_unbanded_past_the_grid_cap(gpu, big):
+    _check_amplitude_unbanded(gpu, big)
+
+
+def test_gaussian_filter_past_the_grid_cap(gpu, big):
+    _check_gaussian_filter(gpu, big, 3.0)
+
+
 # ---------------------------------------------------------------- per-shell sums
-@pytest.mark.parametrize("shape,Rzero", [((21, 21, 21), 8), ((24, 24, 24), 10), ((24, 20, 18), 7)])
+# T.SHELLS has 262 shells: a thread of k_mn_shell_planes takes two (r += 256) and k_mn_shell_final runs in several workgroups. With Rzero
+# below X / 2 the cliff assertion applies, but the shells beyond Rzero sum zeros: T.SHELLS also runs with no voxel cut (Rzero beyond the
+# box), so that the shells of a thread's second lap (r >= 256) carry sums that are compared
+@pytest.mark.parametrize("shape,Rzero", [((21, 21, 21), 8), ((24, 24, 24), 10), ((24, 20, 18), 7), (T.BIG, 30), (T.SHELLS, 4), (T.SHELLS, 300)])
 def test_shell_sums_and_cliff_radius(gpu, shape, Rzero):
     xa, ctx, torch = gpu
     v = noisy_map(shape, 9)
     v[R.r2_map(shape) >= Rzero * Rzero] = 0.0
     es, es2, en = R.shell_sums(v)
     ea, ea2, _ = R.shell_sums(np.abs(v))
-    s, s2, n = xa.MonoRes(ctx, shape).shell_sums(torch.from_numpy(v).cuda())
+    m = xa.MonoRes(ctx, shape)
+    assert m.info()["nshell"] == T.tiling(shape).nshell
+    s, s2, n = m.shell_sums(torch.from_numpy(v).cuda())
     k = es.size
     assert np.array_equal(n[:k], en) and not n[k:].any() and not s[k:].any()         # counts exact
+    live = ea > 0
+    if Rzero * Rzero > R.r2_map(shape).max():
+        assert live.all() and k > 256 and en[256:].sum() > 50          # nothing was cut: every shell has terms, the second lap's included
+    print(f"shell sums {shape} Rzero {Rzero}: {n.size} shells, {int(live.sum())} with terms, largest error of a shell's terms: sum "
+          f"{np.max(np.abs(s[:k] - es)[live] / ea[live]):.3e}, sum of squares {np.max(np.abs(s2[:k] - es2)[live] / ea2[live]):.3e}")
     assert np.all(np.abs(s[:k] - es) <= 1e-10 * ea) and np.all(np.abs(s2[:k] - es2) <= 1e-10 * ea2)
     assert int(n.sum()) == v.size
     lim = xa.mono_cliff_radius(s, s2, n, 3, shape[2])
@@ -146,8 +203,35 @@ def test_select_counts_only_the_set(gpu):
         m.select(d, 0, torch.from_numpy(np.zeros(a.size, np.int32)).cuda())
 
 
+@pytest.mark.parametrize("masked", [False, True])
+def test_select_past_the_grid_cap(gpu, big, masked):
+    """531 360 values drawn as "wide" is: a thread of k_mn_sel_pass takes a third lap over them and carries its run of equal digits
+    (last, cnt) from one lap into the next. The mask drops about half. One rank lies inside a planted run of 4096 equal values"""
+    xa, ctx, torch = gpu
+    rng = np.random.default_rng(13)
+    n = T.tiling(big).N
+    a = rng.standard_normal(n) * np.exp(rng.uniform(-30, 30, n))
+    planted = 0.37
+    a[100000:104096] = planted
+    mask = (rng.uniform(size=n) < 0.5).astype(np.int32) if masked else None
+    srt = np.sort(a if mask is None else a[mask != 0])
+    first, run = int(np.searchsorted(srt, planted, "left")), int((srt == planted).sum())
+    assert run == 4096 if mask is None else 1500 < run < 2600
+    assert 0.4 * n < srt.size < 0.6 * n if masked else srt.size == n
+    inside = first + run // 2
+    assert 0 < first and inside + 1 < srt.size and srt[inside] == planted
+    m = xa.MonoRes(ctx, big)
+    d = torch.from_numpy(a).cuda()
+    dm = None if mask is None else torch.from_numpy(mask).cuda()
+    for rank in (0, srt.size // 2, srt.size - 1, inside):
+        got = m.select(d, rank, dm)
+        assert np.float64(got).tobytes() == srt[rank].tobytes(), (rank, got, srt[rank])
+    with pytest.raises(xa.XhError):
+        m.select(d, srt.size, dm)
+
+
 # ---------------------------------------------------------------- statistics
-@pytest.mark.parametrize("shape", [(21, 21, 21), (24, 20, 18)])
+@pytest.mark.parametrize("shape", [(21, 21, 21), (24, 20, 18), T.BIG])
 @pytest.mark.parametrize("halves", [False, True])
 def test_statistics(gpu, shape, halves):
     xa, ctx, torch = gpu
@@ -162,6 +246,7 @@ def test_statistics(gpu, shape, halves):
     sig, noi = mask >= 1, (mask >= 0) if halves else (mask == 0)
     vN = ampN if halves else ampS
     for key, terms in (("sumS", ampS[sig]), ("sumS2", ampS[sig] ** 2), ("sumN", vN[noi]), ("sumN2", vN[noi] ** 2)):
+        print(f"statistics {shape} halves {halves} {key}: error {abs(got[key] - exp[key]) / np.abs(terms).sum():.3e} of the terms")
         assert abs(got[key] - exp[key]) <= 1e-10 * np.abs(terms).sum(), key
     assert got["thr95"] == exp["thr95"]
     for key in ("meanS", "meanN", "sdS2", "sdN2"):

@@ -1093,6 +1093,60 @@ int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, in
 int xh_ldb_set_timing(xh_ldb *h, int32_t on);
 int xh_ldb_stage_ms(const xh_ldb *h, double *h_ms);
 
+/* ---- xmipp_resolution_fso, the Fourier Shell Occupancy (libraries/reconstruction/resolution_fso.{h,cpp}, ProgFSO) ----
+ * Two half maps give the global FSC, one directional FSC per direction of a half sphere (each through a Gaussian-weighted cone), the FSO
+ * curve with the Bingham isotropy test, the resolution distribution on the projection sphere and, optionally, the 3DFSC. The reference
+ * sweeps every Fourier coefficient below Nyquist once per direction on CPU threads; here one pass over the coefficients serves every
+ * direction, and the host keeps what is O(directions x shells). The kernels, what is left out and why, and the refusals are listed at the
+ * head of xmipp3_amd/csrc/xh_fso.hip. Volumes are [Z][Y][X] doubles; L = X / 2 + 1 shells. */
+typedef struct xh_fso xh_fso;
+/* host only, replaces the table of generateDirections (:572-898): an icosahedron with one vertex on +z and its upper ring at tilt atan 2,
+ * rot 36 + 72 k, `level` (0 .. 5) rounds of edge-midpoint subdivision projected to the sphere, one direction of every antipodal pair,
+ * vertices first and then each round's new points, the angles rounded to 4 decimals of a degree. Level 3: 321 directions, level 2: 81.
+ * h_rot_tilt_deg [cap][2] receives the first cap, *n their number */
+int xh_fso_directions(int32_t level, float *h_rot_tilt_deg, int32_t cap, int32_t *n);
+/* host only: degrees to the float radians of :985, then the unit vectors of fscDir_fast :408-410 by sinf / cosf: h_dirs [n][3] */
+int xh_fso_unit_vectors(const float *h_rot_tilt_deg, int32_t n, float *h_dirs);
+/* host only: incompleteGammaFunction (:510-569). The 41 entries are P(5, i / 2) to 5 significant digits, then to float; the index is
+ * round(2 x) clamped to 0 .. 40 */
+double xh_fso_incomplete_gamma(double x);
+/* host only: the cone's constants as fscDir_fast computes them from --anglecone (run :1344, :419, :425). An angle outside (0, 90) is
+ * refused */
+int xh_fso_cone(double ang_con_deg, float *cosAngle, float *aux);
+/* host only: what run and fscDir_fast do with the sums of every direction, with one thread, the directions in ascending order: the float
+ * FSC max(0, num / (sqrt(den1 den2) + 1e-38)) (:468-469) to h_fsc [ndir][L]; the directional resolution, xdim sampling / i at the first
+ * i > 2 with FSC <= thrs or -1 (:480-485), to h_resol [ndir]; the FSO curve, shells 0 .. 4 set to 1 (:989-999, :1468-1470), to
+ * h_fso [L]; the Bingham statistic of :1426-1464 (the argument of xh_fso_incomplete_gamma) to h_bingham [L]. h_sums [ndir][L][3] */
+int xh_fso_decide(const double *h_sums, const float *h_dirs, int32_t ndir, int32_t L, int32_t xdim, double sampling, double thrs, float *h_fsc, double *h_resol,
+                  float *h_fso, double *h_bingham);
+/* host only: resolutionDistribution (:1194-1261): h_out [360][91], the weighted directional resolution at (rot, tilt) in degrees */
+int xh_fso_resolution_distribution(const float *h_dirs, int32_t ndir, const double *h_resol, double ang_con_deg, double *h_out);
+/* every buffer of a Z x Y x X box (sides 8 .. 1024; an odd X beside an even Y or Z is refused). seg: the coefficients a workgroup of the
+ * cone stage takes, at most 2048; 0 is the default (512) */
+int xh_fso_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t seg, xh_fso **out);
+int xh_fso_destroy(xh_fso *h);
+/* prepareData (:1002-1032) without CenterFFT, the two transforms of run (:1324-1325), defineFrequencies (:111-205) and
+ * arrangeFSC_and_fscGlobal (:209-321). d_mask may be null. h_sums [L][3] receives num, den1, den2 of every shell in fp64 (:314-316; the
+ * host forms the FSC of :331), h_shell_count [L] (nullable) freqElems, *ncomps (nullable) the number of kept coefficients. Synchronous */
+int xh_fso_load(xh_fso *h, const double *d_half1, const double *d_half2, const double *d_mask, double *h_sums, int64_t *h_shell_count, int64_t *ncomps);
+/* the shells; after a load: the kept coefficients and the segments of the cone stage; always: seg. Null pointers are skipped */
+int xh_fso_info(const xh_fso *h, int64_t *ncomps, int32_t *nshell, int32_t *nseg, int32_t *seg);
+/* test hook: the layout of :290-312 on the host, each array [ncomps]: fx, fy, fz, freqidx, arr2indx, real_z1z2, absz1_vec, absz2_vec */
+int xh_fso_layout(xh_fso *h, float *h_fx, float *h_fy, float *h_fz, int32_t *h_freqidx, int32_t *h_arr2indx, float *h_real_z1z2, float *h_absz1, float *h_absz2);
+/* the sums of fscDir_fast (:428-457) for ndir (1 .. 1024) directions at once. h_dirs [ndir][3]: x_dir, y_dir, z_dir; cosAngle and aux as
+ * :419-425 compute them. h_sums [ndir][L][3] receives num, den1, den2 in fp64 (the host forms :468-469), h_count [ndir] the coefficients
+ * inside each cone. Two calls give the same bytes. Synchronous */
+int xh_fso_directional(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngle, float aux, double *h_sums, int64_t *h_count);
+/* the 3DFSC (:492-507 of every direction in ascending order, :1501-1508, the line fixes :1521-1539) from the directional FSCs
+ * h_fsc [ndir][L] (float, as :469 stores them) to d_half [Z][Y][X/2+1] (threeD_FSC.mrc); d_full [Z][Y][X] (nullable) receives
+ * createFullFourier (:1297-1306) of it (3dFSC.mrc). Cubic boxes only. The threshold of run enters aniFilter only, which is left out.
+ * Synchronous */
+int xh_fso_threedfsc(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngle, float aux, const float *h_fsc, double *d_half, double *d_full);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[5] = the transforms (with the mask), the layout (with the
+ * global sums), the cones, the segment reduction, the 3DFSC, summed since set_timing */
+int xh_fso_set_timing(xh_fso *h, int32_t on);
+int xh_fso_stage_ms(const xh_fso *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

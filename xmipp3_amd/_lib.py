@@ -226,6 +226,21 @@ SIGNATURES = {
     "xh_ldb_run": (C.c_int, [vp, d, i32, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), vp]),
     "xh_ldb_set_timing": (C.c_int, [vp, i32]),
     "xh_ldb_stage_ms": (C.c_int, [vp, vp]),
+    "xh_fso_directions": (C.c_int, [i32, vp, i32, C.POINTER(i32)]),
+    "xh_fso_unit_vectors": (C.c_int, [vp, i32, vp]),
+    "xh_fso_incomplete_gamma": (C.c_double, [d]),
+    "xh_fso_cone": (C.c_int, [d, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "xh_fso_decide": (C.c_int, [vp, vp, i32, i32, i32, d, d, vp, vp, vp, vp]),
+    "xh_fso_resolution_distribution": (C.c_int, [vp, i32, vp, d, vp]),
+    "xh_fso_create": (C.c_int, [vp, i32, i32, i32, i32, pvp]),
+    "xh_fso_destroy": (C.c_int, [vp]),
+    "xh_fso_load": (C.c_int, [vp, vp, vp, vp, vp, vp, C.POINTER(i64)]),
+    "xh_fso_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "xh_fso_layout": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "xh_fso_directional": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, vp, vp]),
+    "xh_fso_threedfsc": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]),
+    "xh_fso_set_timing": (C.c_int, [vp, i32]),
+    "xh_fso_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

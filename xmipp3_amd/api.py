@@ -1044,6 +1044,152 @@ def ldb_bands(zsize, sampling, max_res):
     return [(r[0], r[1], r[2], int(r[3])) for r in b]
 
 
+class FSO(_Handle):
+    """The device side of xmipp_resolution_fso: global FSC, directional FSCs through Gaussian-weighted cones, FSO curve, 3DFSC of two
+    half maps, [Z, Y, X] float64 tensors on the device. seg: the sorted coefficients a workgroup of the cone stage takes (0: the
+    default); any value gives sums that differ in the last bits only, and the same bytes on every run."""
+
+    _destroy = "xh_fso_destroy"
+
+    STAGES = ("transforms", "layout", "cones", "segment_reduce", "threedfsc")
+
+    def __init__(self, ctx, shape, seg=0):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        self.L = self.shape[2] // 2 + 1
+        h = C.c_void_p()
+        check(lib().xh_fso_create(ctx.h, *self.shape, int(seg), C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _vol(self, t, what="half map"):
+        torch = _torch()
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise XhError(f"FSO: the {what} must be a contiguous float64 cuda tensor")
+        if tuple(t.shape) != self.shape:
+            raise XhError(f"FSO: the {what} has shape {tuple(t.shape)}, the handle {self.shape}")
+        return t
+
+    def load(self, half1, half2, mask=None):
+        """the transforms and the shell-sorted layout. Returns (sums [L, 3]: num, den1, den2 of the global FSC in fp64, the shells'
+        sizes [L])"""
+        sums, cnt, n = np.zeros((self.L, 3)), np.zeros(self.L, np.int64), C.c_int64()
+        check(lib().xh_fso_load(self.h, _ptr(self._vol(half1)), _ptr(self._vol(half2)), None if mask is None else _ptr(self._vol(mask, "mask")), _np_ptr(sums),
+                                _np_ptr(cnt), C.byref(n)))
+        return sums, cnt
+
+    def info(self):
+        n, L, ns, seg = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().xh_fso_info(self.h, C.byref(n), C.byref(L), C.byref(ns), C.byref(seg)))
+        return {"ncomps": n.value, "nshell": L.value, "nseg": ns.value, "seg": seg.value}
+
+    def layout(self):
+        """test hook: the sorted arrays as a dict of numpy arrays: fx, fy, fz, freqidx, arr2indx, real_z1z2, absz1, absz2"""
+        n = self.info()["ncomps"]
+        names = ("fx", "fy", "fz", "freqidx", "arr2indx", "real_z1z2", "absz1", "absz2")
+        out = {k: np.zeros(n, np.int32 if k in ("freqidx", "arr2indx") else np.float32) for k in names}
+        check(lib().xh_fso_layout(self.h, *(_np_ptr(out[k]) for k in names)))
+        return out
+
+    def directional(self, dirs, cos_angle, aux):
+        """the cone sums of the unit vectors dirs [ndir, 3] (float32): (sums [ndir, L, 3] fp64, the coefficients inside each cone [ndir])"""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        sums, cnt = np.zeros((len(dirs), self.L, 3)), np.zeros(len(dirs), np.int64)
+        check(lib().xh_fso_directional(self.h, _np_ptr(dirs), len(dirs), float(cos_angle), float(aux), _np_ptr(sums), _np_ptr(cnt)))
+        return sums, cnt
+
+    def threedfsc(self, dirs, cos_angle, aux, fsc, full=True):
+        """the 3DFSC from the directional FSCs fsc [ndir, L] (float32): (half [Z, Y, X/2+1], full [Z, Y, X] or None), device tensors"""
+        torch = _torch()
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        fsc = np.ascontiguousarray(fsc, np.float32)
+        if fsc.shape != (len(dirs), self.L):
+            raise XhError(f"FSO: the directional FSCs have shape {fsc.shape}, expected {(len(dirs), self.L)}")
+        Z, Y, X = self.shape
+        half = torch.empty((Z, Y, X // 2 + 1), dtype=torch.float64, device="cuda")
+        out = torch.empty(self.shape, dtype=torch.float64, device="cuda") if full else None
+        check(lib().xh_fso_threedfsc(self.h, _np_ptr(dirs), len(dirs), float(cos_angle), float(aux), _np_ptr(fsc), _ptr(half), _ptr(out)))
+        return half, out
+
+    def run(self, half1, half2, mask=None, sampling=1.0, anglecone=17.0, threshold=0.143, threedfsc=False, level=3, distribution=True):
+        """ProgFSO::run. Returns a dict: global_sums, global_fsc (num / sqrt(den1 den2)), freq, directions (degrees), dirs, fsc (directional,
+        float32), resolution (per direction), fso, bingham, anisotropy (the table's value), counts, distribution [360, 91] (or None),
+        and with threedfsc the device tensors threedfsc_half and threedfsc_full"""
+        sums, _ = self.load(half1, half2, mask)
+        ang = fso_directions(level)
+        dirs = fso_unit_vectors(ang)
+        cos_angle, aux = fso_cone(anglecone)
+        dsums, counts = self.directional(dirs, cos_angle, aux)
+        fsc, resol, fso, bingham = fso_decide(dsums, dirs, self.shape[2], sampling, threshold)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            gfsc = sums[:, 0] / np.sqrt(sums[:, 1] * sums[:, 2])
+        out = {"global_sums": sums, "global_fsc": gfsc, "freq": np.arange(self.L, dtype=np.float32).astype(np.float64) / (self.shape[2] * float(sampling)),
+               "directions": ang, "dirs": dirs, "fsc": fsc, "resolution": resol, "fso": fso, "bingham": bingham,
+               "anisotropy": np.array([fso_incomplete_gamma(b) for b in bingham]), "counts": counts,
+               "distribution": fso_resolution_distribution(dirs, resol, anglecone) if distribution else None}
+        if threedfsc:
+            out["threedfsc_half"], out["threedfsc_full"] = self.threedfsc(dirs, cos_angle, aux, fsc)
+        return out
+
+    def set_timing(self, on):
+        check(lib().xh_fso_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        ms = np.zeros(len(self.STAGES))
+        check(lib().xh_fso_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
+
+
+def fso_directions(level=3):
+    """the direction set of xmipp_resolution_fso: (rot, tilt) in degrees, float32 [n, 2]; level 3 gives 321, level 2 81 (host only)"""
+    n = C.c_int32()
+    check(lib().xh_fso_directions(int(level), None, 0, C.byref(n)))
+    a = np.zeros((n.value, 2), np.float32)
+    check(lib().xh_fso_directions(int(level), _np_ptr(a), n.value, C.byref(n)))
+    return a
+
+
+def fso_unit_vectors(rot_tilt_deg):
+    """the float unit vectors the cones use, from (rot, tilt) in degrees: float32 [n, 3] (host only)"""
+    a = np.ascontiguousarray(rot_tilt_deg, np.float32).reshape(-1, 2)
+    out = np.zeros((len(a), 3), np.float32)
+    check(lib().xh_fso_unit_vectors(_np_ptr(a), len(a), _np_ptr(out)))
+    return out
+
+
+def fso_incomplete_gamma(x):
+    """the reference's table of the incomplete gamma function P(5, x), indexed by round(2 x) clamped to 0 .. 40 (host only)"""
+    return lib().xh_fso_incomplete_gamma(float(x))
+
+
+def fso_cone(anglecone):
+    """(cosAngle, aux) of a cone of `anglecone` degrees, as floats (host only)"""
+    c, a = C.c_float(), C.c_float()
+    check(lib().xh_fso_cone(float(anglecone), C.byref(c), C.byref(a)))
+    return c.value, a.value
+
+
+def fso_decide(dsums, dirs, xdim, sampling=1.0, threshold=0.143):
+    """the host decisions on the cone sums [ndir, L, 3]: (fsc float32 [ndir, L], resolution [ndir], fso float32 [L], bingham [L]) (host only)"""
+    dsums = np.ascontiguousarray(dsums, np.float64)
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    ndir, L = dsums.shape[:2]
+    assert dsums.shape == (len(dirs), L, 3)
+    fsc, resol, fso, bingham = np.zeros((ndir, L), np.float32), np.zeros(ndir), np.zeros(L, np.float32), np.zeros(L)
+    check(lib().xh_fso_decide(_np_ptr(dsums), _np_ptr(dirs), ndir, L, int(xdim), float(sampling), float(threshold), _np_ptr(fsc), _np_ptr(resol), _np_ptr(fso),
+                              _np_ptr(bingham)))
+    return fsc, resol, fso, bingham
+
+
+def fso_resolution_distribution(dirs, resol, anglecone):
+    """resolutionDistribution: the weighted directional resolution on the grid rot 0 .. 359, tilt 0 .. 90: [360, 91] (host only)"""
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    resol = np.ascontiguousarray(resol, np.float64)
+    out = np.zeros((360, 91))
+    check(lib().xh_fso_resolution_distribution(_np_ptr(dirs), len(dirs), _np_ptr(resol), float(anglecone), _np_ptr(out)))
+    return out
+
+
 def vds_num_terms(L1, L2):
     """terms of the Zernike3D basis of degrees (L1, L2) (host only)"""
     n = C.c_int32()

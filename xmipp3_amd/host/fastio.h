@@ -59,6 +59,7 @@ struct XhDestroy {
     void operator()(xh_sub *h) const { xh_sub_destroy(h); }
     void operator()(xh_mono *h) const { xh_mono_destroy(h); }
     void operator()(xh_ldb *h) const { xh_ldb_destroy(h); }
+    void operator()(xh_fso *h) const { xh_fso_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 

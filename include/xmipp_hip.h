@@ -1147,6 +1147,54 @@ int xh_fso_threedfsc(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngl
 int xh_fso_set_timing(xh_fso *h, int32_t on);
 int xh_fso_stage_ms(const xh_fso *h, double *h_ms);
 
+/* ---- xmipp_volume_subtraction (libraries/reconstruction/volume_subtraction.{h,cpp}, ProgVolumeSubtraction) ----
+ * Adjusts a volume V to a reference V1 by projections onto convex sets (Fourier amplitudes of V1, its value range, the mask, the phases
+ * of V, non-negativity, the standard deviation of V1, optionally a low pass) and forms V1 minus the adjusted V inside a mask. The
+ * reference runs four to six fp64 FFTW transforms and seven passes per iteration on the CPU; here the volume and its spectrum stay on
+ * the device and the host reads two sums per iteration. Everything is fp64. The kernels, the reference behaviours kept as written and
+ * the refusals are listed at the head of xmipp3_amd/csrc/xh_vsub.hip. Volumes are [Z][Y][X], spectra [Z][Y][X/2+1]. */
+typedef struct xh_vsub xh_vsub;
+/* the RMS change of the volume over each step of one runIteration (:376-416), the values computeEnergy (:205-211) forms; filter is 0
+ * without cutFreq */
+typedef struct {
+    double amplitude, minmax, mask, phase, nonneg, scale, filter;
+} xh_vsub_energy;
+/* host only: the bins of radialAverage (:235) for a box and the largest bin round(w X) its octant writes. --radavg is refused where
+ * *maxbin >= *nbins: the reference writes past radial_mean there */
+int xh_vsub_radial_bins(int32_t Z, int32_t Y, int32_t X, int32_t *nbins, int32_t *maxbin);
+/* the plans and every buffer of a Z x Y x X volume (each side 2 .. 1024) */
+int xh_vsub_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_vsub **out);
+int xh_vsub_destroy(xh_vsub *h);
+/* run :424-427, :432, :435: d_mask (null: ones; copied) times d_V1, max(0, .), its minimum, maximum and stddev, V1FourierMag, and with
+ * radavg != 0 V1's radial mean (refused on a box whose bins overflow). Serves any number of adjust calls. Synchronous */
+int xh_vsub_set_reference(xh_vsub *h, const double *d_V1, const double *d_mask, int32_t radavg);
+/* after set_reference: v1min, v1max, std1, the number of radial bins. Null pointers are skipped */
+int xh_vsub_info(const xh_vsub *h, double *v1min, double *v1max, double *std1, int32_t *nbins);
+/* test hook: V1FourierMag [Z][Y][X/2+1] to d_out */
+int xh_vsub_reference_magnitude(xh_vsub *h, double *d_out);
+/* test hook: radialAverage (:223-257) of the magnitude d_mag [Z][Y][X/2+1] to h_mean [nbins]; an empty bin gives NaN as in the reference */
+int xh_vsub_radial_mean(xh_vsub *h, const double *d_mag, double *h_mean);
+/* test hook: computeRadQuotient (:259-275) of the set reference (with its radial mean) against the volume d_V as it is, to h_quotient [nbins] */
+int xh_vsub_quotient(xh_vsub *h, const double *d_V, double *h_quotient);
+/* test hook: one runIteration (:362-418) of the volume d_V to d_out, with the phases (and with radavg the quotient) of the volume d_V0;
+ * neither is masked or clipped first. Synchronous */
+int xh_vsub_iteration(xh_vsub *h, const double *d_V0, const double *d_V, double lambda, int32_t radavg, double cutFreq, double *d_out);
+/* run :428-442: mask and max(0, .) of d_V, its phases, the quotient with radavg != 0 (the reference must have been set with it), `iter`
+ * (>= 0) times runIteration with lambda in [0, 1] and cutFreq in [0, 0.5] (0: no filter). h_energies (nullable) [iter] receives the
+ * energies; d_out has the same bytes with and without them. iter = 0 gives the masked, clipped input. Synchronous */
+int xh_vsub_adjust(xh_vsub *h, const double *d_V, int32_t iter, double lambda, int32_t radavg, double cutFreq, xh_vsub_energy *h_energies, double *d_out);
+/* FourierFilter LOWPASS RAISED_COSINE, w1 = cutFreq in (0, 0.5], raised_w = 0.02 (createFilter :277-282), of d_in to d_out (may be d_in) */
+int xh_vsub_lowpass(xh_vsub *h, const double *d_in, double cutFreq, double *d_out);
+/* filterMask (:332-338): FourierFilter LOWPASS REALGAUSSIAN, w1 = sigma >= 0, of d_mask to d_out (may be d_mask) */
+int xh_vsub_smooth_mask(xh_vsub *h, const double *d_mask, double sigma, double *d_out);
+/* subtraction (:284-306): V1F is d_V1_raw, through xh_vsub_lowpass when cutFreq != 0, and goes to d_V1F (nullable);
+ * d_out = V1 (1 - m) + (V1F - min(Vadj, V1F)) m. d_out may be none of the inputs' memory. Synchronous */
+int xh_vsub_subtract(xh_vsub *h, const double *d_V1_raw, const double *d_Vadj, const double *d_masksub, double cutFreq, double *d_V1F, double *d_out);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[4] = the transforms, the spectrum steps (amplitude, phase),
+ * the real-space steps, the filter (its transforms included), summed over the last adjust */
+int xh_vsub_set_timing(xh_vsub *h, int32_t on);
+int xh_vsub_stage_ms(const xh_vsub *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

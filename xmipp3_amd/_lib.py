@@ -46,6 +46,10 @@ class LdbIter(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("norm", "porc", "subst", "lambda_")] + [("stop", C.c_int32), ("pad_", C.c_int32)]
 
 
+class VsubEnergy(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("amplitude", "minmax", "mask", "phase", "nonneg", "scale", "filter")]
+
+
 class Ca2Params(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "max_shift", "max_scale", "max_angular_change", "max_defocus_change", "max_resolution", "max_gray_scale", "max_gray_shift",
@@ -241,6 +245,21 @@ SIGNATURES = {
     "xh_fso_threedfsc": (C.c_int, [vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]),
     "xh_fso_set_timing": (C.c_int, [vp, i32]),
     "xh_fso_stage_ms": (C.c_int, [vp, vp]),
+    "xh_vsub_radial_bins": (C.c_int, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "xh_vsub_create": (C.c_int, [vp, i32, i32, i32, pvp]),
+    "xh_vsub_destroy": (C.c_int, [vp]),
+    "xh_vsub_set_reference": (C.c_int, [vp, vp, vp, i32]),
+    "xh_vsub_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
+    "xh_vsub_reference_magnitude": (C.c_int, [vp, vp]),
+    "xh_vsub_radial_mean": (C.c_int, [vp, vp, vp]),
+    "xh_vsub_quotient": (C.c_int, [vp, vp, vp]),
+    "xh_vsub_iteration": (C.c_int, [vp, vp, vp, d, i32, d, vp]),
+    "xh_vsub_adjust": (C.c_int, [vp, vp, i32, d, i32, d, vp, vp]),
+    "xh_vsub_lowpass": (C.c_int, [vp, vp, d, vp]),
+    "xh_vsub_smooth_mask": (C.c_int, [vp, vp, d, vp]),
+    "xh_vsub_subtract": (C.c_int, [vp, vp, vp, vp, d, vp, vp]),
+    "xh_vsub_set_timing": (C.c_int, [vp, i32]),
+    "xh_vsub_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

@@ -1140,6 +1140,118 @@ class FSO(_Handle):
         return dict(zip(self.STAGES, ms))
 
 
+class VolumeSubtraction(_Handle):
+    """The device side of xmipp_volume_subtraction: a volume is adjusted to a reference by projections onto convex sets, and the
+    reference minus the adjusted volume is formed inside a mask. [Z, Y, X] float64 tensors on the device; spectra are [Z, Y, X // 2 + 1]."""
+
+    _destroy = "xh_vsub_destroy"
+
+    STAGES = ("transforms", "spectrum", "real", "filter")
+    ENERGIES = ("amplitude", "minmax", "mask", "phase", "nonneg", "scale", "filter")
+
+    def __init__(self, ctx, shape):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        self.half_shape = self.shape[:2] + (self.shape[2] // 2 + 1,)
+        h = C.c_void_p()
+        check(lib().xh_vsub_create(ctx.h, *self.shape, C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _vol(self, t, what="volume", shape=None):
+        torch = _torch()
+        shape = shape or self.shape
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise XhError(f"VolumeSubtraction: the {what} must be a contiguous float64 cuda tensor")
+        if tuple(t.shape) != shape:
+            raise XhError(f"VolumeSubtraction: the {what} has shape {tuple(t.shape)}, the handle {shape}")
+        return t
+
+    def _new(self):
+        return _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+
+    def set_reference(self, v1, mask=None, radavg=False):
+        """the reference volume and the mask (None: ones; the product of both masks, as the reference uses a mask only when it has
+        both). radavg: also V1's radial mean, which adjust(radavg=True) needs"""
+        m = None if mask is None else _ptr(self._vol(mask, "mask"))
+        check(lib().xh_vsub_set_reference(self.h, _ptr(self._vol(v1, "reference")), m, int(bool(radavg))))
+
+    def info(self):
+        """v1min, v1max, std1 of the masked, clipped reference and the number of radial bins"""
+        lo, hi, sd, nb = C.c_double(), C.c_double(), C.c_double(), C.c_int32()
+        check(lib().xh_vsub_info(self.h, C.byref(lo), C.byref(hi), C.byref(sd), C.byref(nb)))
+        return {"v1min": lo.value, "v1max": hi.value, "std1": sd.value, "nbins": nb.value}
+
+    def reference_magnitude(self):
+        """V1FourierMag"""
+        out = _torch().empty(self.half_shape, dtype=_torch().float64, device="cuda")
+        check(lib().xh_vsub_reference_magnitude(self.h, _ptr(out)))
+        return out
+
+    def radial_mean(self, mag):
+        """radialAverage of a magnitude [Z, Y, X // 2 + 1], as a numpy array [nbins]"""
+        out = np.zeros(vsub_radial_bins(self.shape)[0])
+        check(lib().xh_vsub_radial_mean(self.h, _ptr(self._vol(mag, "magnitude", self.half_shape)), _np_ptr(out)))
+        return out
+
+    def quotient(self, v):
+        """computeRadQuotient of the reference against the volume v as it is, as a numpy array [nbins]"""
+        out = np.zeros(vsub_radial_bins(self.shape)[0])
+        check(lib().xh_vsub_quotient(self.h, _ptr(self._vol(v)), _np_ptr(out)))
+        return out
+
+    def iteration(self, v0, v, lam=1.0, radavg=False, cut_freq=0.0):
+        """one runIteration of v with the phases (and the quotient) of v0"""
+        out = self._new()
+        check(lib().xh_vsub_iteration(self.h, _ptr(self._vol(v0)), _ptr(self._vol(v)), float(lam), int(bool(radavg)), float(cut_freq), _ptr(out)))
+        return out
+
+    def adjust(self, v, niter=5, lam=1.0, radavg=False, cut_freq=0.0, energies=False):
+        """the adjusted volume; with energies also one dict per iteration with the RMS change over each step"""
+        from ._lib import VsubEnergy
+        out = self._new()
+        recs = (VsubEnergy * max(int(niter), 1))() if energies else None
+        check(lib().xh_vsub_adjust(self.h, _ptr(self._vol(v)), int(niter), float(lam), int(bool(radavg)), float(cut_freq),
+                                   C.cast(recs, C.c_void_p) if energies else None, _ptr(out)))
+        if not energies:
+            return out
+        return out, [{k: getattr(r, k) for k in self.ENERGIES} for r in recs[:max(int(niter), 0)]]
+
+    def lowpass(self, v, cut_freq):
+        out = self._new()
+        check(lib().xh_vsub_lowpass(self.h, _ptr(self._vol(v)), float(cut_freq), _ptr(out)))
+        return out
+
+    def smooth_mask(self, mask, sigma=3):
+        """the mask through the REALGAUSSIAN low pass with w1 = sigma"""
+        out = self._new()
+        check(lib().xh_vsub_smooth_mask(self.h, _ptr(self._vol(mask, "mask")), float(sigma), _ptr(out)))
+        return out
+
+    def subtract(self, v1_raw, vadj, masksub, cut_freq=0.0):
+        """(V1 (1 - m) + (V1F - min(Vadj, V1F)) m, V1F)"""
+        out, v1f = self._new(), self._new()
+        check(lib().xh_vsub_subtract(self.h, _ptr(self._vol(v1_raw, "reference")), _ptr(self._vol(vadj, "adjusted volume")),
+                                     _ptr(self._vol(masksub, "subtraction mask")), float(cut_freq), _ptr(v1f), _ptr(out)))
+        return out, v1f
+
+    def set_timing(self, on):
+        check(lib().xh_vsub_set_timing(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        ms = np.zeros(len(self.STAGES))
+        check(lib().xh_vsub_stage_ms(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
+
+
+def vsub_radial_bins(shape):
+    """(the bins of the radial average of a [Z, Y, X] box, the largest bin its octant writes); --radavg is refused where the second
+    reaches the first (host only)"""
+    nb, mb = C.c_int32(), C.c_int32()
+    check(lib().xh_vsub_radial_bins(*(int(v) for v in shape), C.byref(nb), C.byref(mb)))
+    return nb.value, mb.value
+
+
 def fso_directions(level=3):
     """the direction set of xmipp_resolution_fso: (rot, tilt) in degrees, float32 [n, 2]; level 3 gives 321, level 2 81 (host only)"""
     n = C.c_int32()

@@ -10,7 +10,23 @@ matrix exempt nothing.
 The pipeline's planes (P, Pctf, Idiff) are held to 1e-10 x the plane's maximum (P on the Fourier path: 1e-9, the bound
 test_gpu_continuous_assign2 holds the projector to), its masks exactly on inputs without a marginal pixel, the sums of the fit to
 1e-10 x the sum of their terms' magnitudes, and b, the betas and R2 to 1e-8 relative after the restatement has asserted
-cond(A1) <= 1e6 and |R21adj - R20adj| >= 1e-6: the restatement feeds its own sums to the same host fit."""
+cond(A1) <= 1e6 and |R21adj - R20adj| >= 1e-6: the restatement feeds its own sums to the same host fit.
+
+At D = 16 and 17 every grid-stride loop of xh_sub.hip runs one lap, k_sub_fit one workgroup and rsp_run one chunk. The shapes that leave
+that case are listed in tests/subtract_shapes.py, which restates the loop lengths and launch sizes and asserts (without a device, in
+tests/test_subtract_shapes.py) that each shape reaches its path; the bounds above hold unchanged at all of them:
+  D = 22, 40        the second lap of k_sub_models (264 half-spectrum cells; 840: three laps and a tail of 72) and up to seven laps of
+                    both loops of k_sub_prepare (D D = 1600), on both projectors, with an ROI mask and a --mask volume
+  D = 41            a padded size of 81 = 3^4 in fftP (the other sizes pad to 31, 43, 79 and 3 x 11)
+  D = 168           a wi bin of 269 cells, the second lap of k_sub_bins; padding 1, so fftP has 168 = 2^3 3 7 points. The sums are the
+                    closest figure of the file, 6.3e-11 of their magnitudes against 1e-10: the last bin (wi = 118, 3 cells) lies seven
+                    orders below the largest cell of the spectrum, and a transform's rounding scales with the whole spectrum. The
+                    restatement's own share, against long double transforms of the same images, is 3.8e-11
+  65 particles      one chunk of 65: two workgroups of k_sub_fit, 17 of k_sub_translate (p = t / D up to 64), blockIdx.y = 64 in
+                    k_sub_bins; against chunks of 64 and 1. 6 of the 65 choose model 1, under an ROI mask (DC cell from F[2 plane])
+  boost, no ROI     particles that choose model 1: the y inv / t1 branch of k_sub_spectrum
+  a timed run       the events of SUB_MARK change no byte
+  4099 projections  the second chunk of rsp_run (d_out + 4096 D D, the re-uploaded parameter block), then a short call on the same handle"""
 import numpy as np
 import pytest
 
@@ -301,6 +317,244 @@ def test_subtract_variants(gpu, oracle, name):
     if name == "ignore_ctf":
         assert np.array_equal(exp[0]["P"], exp[0]["Pctf"])
     h.close()
+
+
+# ------------------------------------------------------------------ past the 16-pixel case: the shapes of tests/subtract_shapes.py
+from tests import subtract_shapes as S  # noqa: E402
+
+MASKVOL = dict(centre=(0.0, 0.0, 0.0), radii=(0.42, 0.4, 0.38))
+_SUB_IN, _SUB_REF = {}, {}
+
+
+def _inputs(oracle, D, n, seed):
+    """_sub_inputs, computed once per (D, n, seed) and left unchanged"""
+    key = (D, n, seed)
+    if key not in _SUB_IN:
+        _SUB_IN[key] = _sub_inputs(oracle, D, n, seed)
+        for a in _SUB_IN[key][:2]:
+            a.setflags(write=False)
+    return _SUB_IN[key]
+
+
+def _expected(key, res, imgs, rows):
+    """the restatement of every particle of a case, computed once per case"""
+    if key not in _SUB_REF:
+        _SUB_REF[key] = [res.process(im, r) for im, r in zip(imgs, rows)]
+    return _SUB_REF[key]
+
+
+def _check_particles(tag, out, results, exp):
+    for i, e in enumerate(exp):
+        err, top = np.abs(out[i] - e["Idiff"]).max(), np.abs(e["Idiff"]).max()
+        print(f"{tag} particle {i}: Idiff max err {err:.3e} of max {top:.3e}")
+        assert err <= 1e-10 * top, (tag, i, err, top)
+        _check_results(f"{tag} particle {i}", results[i], e)
+
+
+@pytest.mark.parametrize("real_space", [0, 1])
+@pytest.mark.parametrize("D", [S.LAP_MODELS, S.LAPS])
+def test_subtract_laps_of_the_model_and_prepare_loops(gpu, oracle, D, real_space):
+    """D = 22: the half spectrum has 264 cells, k_sub_models enters its second lap. D = 40: 840 cells (three laps and a tail of 72) and
+    D D = 1600 in both loops of k_sub_prepare (six laps and a tail of 64). ROI mask and --mask volume, both projectors; 5 particles at
+    capacity 2."""
+    assert S.laps(S.half_cells(D))[0] > 1 and S.laps(S.full_cells(D))[0] > 1
+    vol, imgs, rows = _inputs(oracle, D, 5, 40 + D)
+    prm = dict(ref.PRM, real_space=real_space)
+    res, h = _sub_pair(gpu, oracle, vol, ref.blob_mask(D), ref.blob_mask(D, **MASKVOL), prm, 2)
+    exp = _expected(("laps", D, real_space), res, imgs, rows)
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    tag = f"D {D} real_space {real_space}"
+    _check_planes(f"{tag} particle 4", dict(h.last(0), Idiff=out[4]), exp[4], not real_space)
+    _check_particles(tag, out, results, exp)
+    h.close()
+
+
+def test_subtract_composite_padded_size(gpu, oracle):
+    """D = 41 pads to 81 = 3^4 (the other sizes here pad to primes or to 3 x 11). Fourier path, ROI mask, the disc; 3 particles"""
+    D = S.COMPOSITE
+    vol, imgs, rows = _inputs(oracle, D, 3, 40 + D)
+    res, h = _sub_pair(gpu, oracle, vol, ref.blob_mask(D), None, dict(ref.PRM), 2)
+    assert h.padded == S.padded(D) == 81
+    exp = _expected(("composite", D), res, imgs, rows)
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    _check_planes(f"D {D} particle 2", dict(h.last(0), Idiff=out[2]), exp[2], True)
+    _check_particles(f"D {D}", out, results, exp)
+    h.load(imgs[:2], _dev_rows(rows[:2]))
+    h.run()
+    for i in range(2):
+        _check_planes(f"D {D} particle {i}", h.last(i), exp[i], True)
+    h.close()
+
+
+def test_subtract_a_bin_past_one_lap(gpu, oracle):
+    """D = 168: the largest wi bin has 269 cells, so k_sub_bins enters its second lap (none does below D = 168: 160 stays within 256).
+    Padding 1 (a window of 168 = 2^3 3 7) only to keep the restatement short; no ROI, the disc. Two particles at capacity 1, the first
+    with a CTF: the sums of each are read through last(0), after the two-chunk run and after a run of particle 0 alone."""
+    D = S.BIN
+    cells = S.bin_cells(D)
+    long_bins = np.nonzero(cells > S.THREADS)[0]
+    assert len(long_bins) >= 1 and cells.max() == 269
+    vol, imgs, rows = _inputs(oracle, D, 2, 208)
+    assert rows[0].get("ctf") and not rows[1].get("ctf")
+    res, h = _sub_pair(gpu, oracle, vol, None, None, dict(ref.PRM, padding=1.0), 1)
+    assert h.padded == S.padded(D, 1.0) == D and len(cells) == h.maxwi + 1
+    exp = _expected(("bin", D), res, imgs, rows)
+    for e in exp:
+        assert (e["sum_magnitudes"][long_bins] > 0).all()      # the compared sums include the bins of more than 256 cells
+        assert (e["sum_magnitudes"][cells > 0] > 0).all()
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    _check_planes(f"D {D} particle 1", dict(h.last(0), Idiff=out[1]), exp[1], True)
+    _check_particles(f"D {D}", out, results, exp)
+    h.load(imgs[:1], _dev_rows(rows[:1]))
+    out0, results0 = h.run()
+    assert out0.tobytes() == out[:1].tobytes() and results0 == results[:1]
+    _check_planes(f"D {D} particle 0", dict(h.last(0), Idiff=out0[0]), exp[0], True)
+    h.close()
+
+
+def test_subtract_a_chunk_of_65(gpu, oracle):
+    """65 particles in one chunk: k_sub_fit launches two workgroups, k_sub_translate 17 with p = t / D up to 64, blockIdx.y of k_sub_bins
+    reaches 64. At capacity 64 the same load is a chunk of 64 and one of 1: the same bytes. Both models occur, so model 1 is compared
+    under an ROI mask, where its DC cell (F[2 plane], the spectrum of (I - b) iM) differs from IFourier(0, 0)."""
+    D, n = 16, S.CHUNK_M
+    assert S.fit_blocks(n) == 2 and S.fit_blocks(n - 1) == 1
+    vol, imgs, rows = _inputs(oracle, D, n, 123)
+    roi = ref.blob_mask(D)
+    res, h = _sub_pair(gpu, oracle, vol, roi, None, dict(ref.PRM), n)
+    exp = _expected(("chunk65", D), res, imgs, rows)
+    models = [e["model"] for e in exp]
+    print(f"models: {models.count(0)} x 0, {models.count(1)} x 1")
+    assert 0 in models and 1 in models
+    assert any(e["model"] == 1 and not e["iM"].all() for e in exp)
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    _check_particles("capacity 65", out, results, exp)
+    for i in range(n):
+        _check_planes(f"capacity 65 particle {i}", h.last(i), exp[i], True)
+    h.close()
+    h = gpu[0].SubtractProjection(gpu[1], vol, roi, None, capacity=n - 1, **ref.PRM)
+    h.load(imgs, _dev_rows(rows))
+    out2, results2 = h.run()
+    assert out2.tobytes() == out.tobytes() and results2 == results
+    _check_planes("capacity 64 particle 64", h.last(0), exp[n - 1], True)
+    with pytest.raises(gpu[0].XhError):
+        h.last(1)
+    h.close()
+
+
+def test_subtract_boost_with_model_1(gpu, oracle):
+    """--boost on particles that choose model 1: the branch y inv / t1 of k_sub_spectrum (under an ROI mask the three particles of the
+    boost variant all choose model 0). The step divides by T(w) = beta01 + beta1 wi, so the restatement first shows it away from 0."""
+    D = 16
+    vol, imgs, rows = _inputs(oracle, D, 3, 77)
+    res, h = _sub_pair(gpu, oracle, vol, None, None, dict(ref.PRM, boost=1), 2)
+    exp = _expected(("boost1", D), res, imgs, rows)
+    models = [e["model"] for e in exp]
+    assert any(m == 1 for m in models), models
+    for i, e in enumerate(exp):
+        t1 = np.abs(e["betas"][1] + e["betas"][2] * res.wi).min()
+        print(f"boost particle {i}: model {e['model']} min |T1| {t1:.3f}")
+        assert t1 >= 0.5, (i, t1)
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    assert [r["model"] for r in results] == models
+    _check_planes("boost model 1 particle 2", dict(h.last(0), Idiff=out[2]), exp[2], True)
+    _check_particles("boost model 1", out, results, exp)
+    h.load(imgs[:2], _dev_rows(rows[:2]))
+    h.run()
+    for i in range(2):
+        _check_planes(f"boost model 1 particle {i}", h.last(i), exp[i], True)
+    h.close()
+
+
+def test_subtract_timed_run_changes_no_byte(gpu, oracle):
+    """set_timing(True) puts an event before every stage of every chunk: Idiff and the results keep their bytes, and the seven stages
+    report times. 5 particles at capacity 2: three chunks, summed."""
+    xa = gpu[0]
+    D = S.LAP_MODELS
+    vol, imgs, rows = _inputs(oracle, D, 5, 40 + D)
+    h = xa.SubtractProjection(gpu[1], vol, ref.blob_mask(D), ref.blob_mask(D, **MASKVOL), capacity=2, **ref.PRM)
+    h.load(imgs, _dev_rows(rows))
+    out, results = h.run()
+    assert set(h.stage_ms().values()) == {0.0}                  # an untimed run reports nothing
+    h.set_timing(True)
+    out_t, results_t = h.run()
+    ms = h.stage_ms()
+    print(f"stage ms: {ms}")
+    assert out_t.tobytes() == out.tobytes() and results_t == results
+    assert list(ms) == list(xa.SubtractProjection.STAGES) and len(ms) == 7
+    assert all(v >= 0.0 for v in ms.values()) and sum(ms.values()) > 0.0
+    last_t = h.last(0)
+    h.set_timing(False)
+    out_u, results_u = h.run()
+    assert out_u.tobytes() == out.tobytes() and results_u == results
+    assert set(h.stage_ms().values()) == {0.0}
+    last_u = h.last(0)
+    for k in last_u:
+        assert last_t[k].tobytes() == last_u[k].tobytes(), k
+    h.close()
+
+
+def _rsp_volume():
+    return np.random.default_rng(4099).random((S.RSP_D,) * 3) * ref.blob_mask(S.RSP_D)
+
+
+def _rsp_reference(oracle, with_off):
+    key = ("rsp", with_off)
+    if key not in _REF:
+        _REF[key] = [ref.project_volume(_rsp_volume(), oracle.euler_matrix(*a), ref.OFFSET if with_off else None) for a in S.rsp_angles()]
+        for r in _REF[key]:
+            for x in r:
+                x.setflags(write=False)
+    return _REF[key]
+
+
+@pytest.mark.parametrize("with_off", [False, True])
+def test_ray_projector_two_chunks_of_projections(gpu, oracle, with_off):
+    """4099 projections in one call: rsp_run launches 4096 and then 3, the second launch writes from d_out + 4096 D D on and reads a
+    re-uploaded parameter block. The rows repeat six orientations, and the seam lies between two of them. Every row is held to the
+    restatement of its orientation, in value and in support mode; a call of 3 on the same handle afterwards still answers right."""
+    xa, ctx, torch = gpu
+    D, n = S.RSP_D, S.RSP_N
+    assert S.rsp_chunks(n) == [S.RSP_CHUNK, 3]
+    ang6, which = S.rsp_angles(), S.rsp_rows(n)
+    exact = [a in ref.EXACT_ANGLES for a in ang6]
+    ang = np.array(ang6)[which]
+    off = np.tile(np.array(ref.OFFSET), (n, 1)) if with_off else None
+    exp = _rsp_reference(oracle, with_off)
+    dv = torch.from_numpy(_rsp_volume()).cuda()
+    got = {}
+    for mode in ("value", "support"):
+        rp = xa.RealSpaceProjector(ctx, dv, mode)
+        assert rp.packed == (mode == "support")
+        got[mode] = rp.project(ang, off).cpu().numpy()
+        st = rp.steps(ang, off).cpu().numpy()
+        st6 = rp.steps(ang[:6], None if off is None else off[:6]).cpu().numpy()
+        assert st6.min() >= 0 and st6.max() > 0
+        assert np.array_equal(st, st6[which]), mode
+        # the parameter buffer was reserved for 4096: a short call afterwards
+        few = rp.project(ang[:3], None if off is None else off[:3]).cpu().numpy()
+        assert few.tobytes() == got[mode][:3].tobytes(), mode
+        rp.close()
+    assert got["value"].shape == (n, D, D)
+    for k, (plane, support, marginal) in enumerate(exp):
+        v, s = got["value"][k::6], got["support"][k::6]
+        assert len(v) in (n // 6, n // 6 + 1)
+        top = np.abs(plane).max()
+        assert top > 0
+        err = np.abs(v - plane).max()
+        print(f"offset {with_off} orientation {ang6[k]}: {len(v)} rows, max err {err:.3e} of max {top:.3e}, marginal {marginal.sum()} of {marginal.size}")
+        assert err <= 1e-10 * top, (k, err, top)
+        assert set(np.unique(s)) <= {0.0, 1.0}
+        assert support.any() and not support.all()
+        assert marginal.mean() <= 0.02, (k, marginal.mean())   # a condition on the inputs, met by the restatement alone
+        keep = np.ones_like(marginal) if exact[k] else ~marginal
+        assert np.array_equal(s[:, keep] > 0, np.broadcast_to(support[keep], (len(s), keep.sum()))), k
+        assert np.array_equal(support[keep], plane[keep] > 0), k
+        assert np.array_equal(s[:, keep] > 0, v[:, keep] > 0), k
 
 
 def test_subtract_errors_are_loud(gpu, oracle):

@@ -6,7 +6,10 @@ volume-deformation and continuous-assignment tests; Euler matrices, LINEAR apply
 
 The contract is discontinuous where a component of pos + g crosses an integer (the mask lookup truncates, the sampler takes a floor) and the
 restatement asserts, for every case with a rotation or coefficients, that no voxel is within 1e-9 of such a place: with that, no voxel is
-exempted from any comparison."""
+exempted from any comparison.
+
+The sizes past 17, the RDef values, the degree pairs and the row count of the larger cases are named in tests/zernike_shapes.py, which
+says what each is there for."""
 import functools
 import math
 import os
@@ -16,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import xmipp_io
+from tests import zernike_shapes as shapes
 from tests.test_volume_deform_sph_host import blobs, terms_ref, zsh_ref
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +30,7 @@ from tests.test_gpu_volume_deform_sph import sample  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROG = os.path.join(ROOT, "xmipp3_amd", "bin", "xmipp_angular_sph_alignment")
 SIZES = [16, 17]
+TILED = SIZES + list(shapes.ASA_TILES)      # and the sizes with 7 workgroups per row, the last one partly idle
 MARGIN = 1e-9
 
 
@@ -216,14 +221,14 @@ def test_projection_identity_is_the_in_order_column_sum(gpu, oracle, D):
 
 
 @pytest.mark.parametrize("degrees", [(3, 2), (5, 4)])
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_projection_generic(gpu, oracle, D, degrees):
     vol = volume(D)
     ref = Restated(oracle, vol, *degrees)
     _check_projection(gpu, ref, vol, GENERIC, coefficients(ref, 5 + D, 1.5))
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_projection_user_mask(gpu, oracle, D):
     vol = volume(D)
     k, i, j = np.meshgrid(*(np.arange(D) - D // 2,) * 3, indexing="ij")
@@ -234,7 +239,7 @@ def test_projection_user_mask(gpu, oracle, D):
     assert 0 < count < int((ref.r2 < 25).sum())
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_projection_large_coefficients(gpu, oracle, D):
     vol = volume(D)
     ref = Restated(oracle, vol, 3, 2)
@@ -258,6 +263,94 @@ def test_projection_empty_mask(gpu, oracle, D):
     assert sums[2] == 0 and sums[0] == 0 and not Praw.any()
 
 
+@pytest.mark.parametrize("D,RDef", shapes.ASA_RDEF)
+def test_projection_rdef_off_the_default(gpu, oracle, D, RDef):
+    """a non-integer RDef (|k| <= ceil(RDef) - 1), and two RDef beyond the volume, where the clip of kmin / kmax to the volume binds"""
+    vol = volume(D)
+    ref = Restated(oracle, vol, 3, 2, RDef=RDef)
+    _, count = _check_projection(gpu, ref, vol, GENERIC, coefficients(ref, 9 + D, 1.5), RDef=RDef)
+    ball = ref.r2 < RDef * RDef
+    inside = int(ball.sum())
+    kmin, kmax, B = shapes.k_range(D, RDef)
+    print(f"D {D} RDef {RDef}: count {count} of {inside} voxels in the ball, k {kmin} .. {kmax}, ceil(RDef) - 1 = {B}")
+    assert ball[np.abs(ref.k) == B].any() or kmax < B            # the plane |k| = ceil(RDef) - 1 holds voxels wherever the volume has it
+    if RDef > D // 2:
+        assert kmax < B and count < inside                       # voxels leave the volume
+        assert ball[np.abs(ref.k) == D // 2].any()               # and the ball reaches the volume's first plane, k = -D / 2
+    else:
+        assert (kmin, kmax) == (-B, B) and count == inside
+
+
+@pytest.mark.parametrize("degrees", shapes.PAIRS + [shapes.RUN_TIME])
+def test_projection_every_instantiation(gpu, oracle, degrees):
+    """the 19 compiled (L1, L2) pairs of the dispatch table, each unrolled on its own, and (0, 0), which the run-time form serves"""
+    D = 17
+    vol = volume(D)
+    ref = Restated(oracle, vol, *degrees)
+    _check_projection(gpu, ref, vol, GENERIC, coefficients(ref, 5 + D, 1.5))
+
+
+def _raw(gpu, ref, vol, row, x):
+    """P_raw and the sums of one row on a handle of ref's degrees"""
+    h = handle(gpu, ref, vol)
+    h.load(np.zeros((1, ref.D, ref.D), np.float32), [dict(row)])
+    h.cost([0], x[None])
+    Praw, _, _, sums = h.last(0)
+    return Praw.cpu().numpy(), sums.copy()
+
+
+@pytest.mark.parametrize("h2", range(5))
+def test_projection_effective_l2(gpu, oracle, h2):
+    """a (5, 4) handle whose coefficients stop at the terms of (5, h) runs the (5, h) instantiation: the restatement's values, and the
+    bits of a (5, h) handle given the same coefficients. (Equal bits are necessary, not sufficient: the terms left out multiply
+    coefficients that are exactly 0. The handle exposes no count of launches per instantiation.)"""
+    D = 17
+    vol = volume(D)
+    ref = Restated(oracle, vol, 5, 4)
+    small = Restated(oracle, vol, 5, h2)
+    assert ref.terms[:small.vec] == small.terms
+    x = coefficients(ref, 5 + D, 1.5)
+    xs = np.zeros(small.nvars)
+    for d in range(3):
+        x[d * ref.vec + small.vec:(d + 1) * ref.vec] = 0.0
+        xs[d * small.vec:(d + 1) * small.vec] = x[d * ref.vec:d * ref.vec + small.vec]
+    assert np.all(x[:small.vec] != 0)
+    _check_projection(gpu, ref, vol, GENERIC, x)
+    P54, s54 = _raw(gpu, ref, vol, GENERIC, x)
+    P5h, s5h = _raw(gpu, small, vol, GENERIC, xs)
+    assert np.array_equal(P54, P5h) and np.array_equal(s54[:3], s5h[:3])
+
+
+def test_projection_second_lap_of_the_totals(gpu):
+    """D = 260: 265 workgroups per row, so k_asa_cost adds the partials in two laps. Identity pose, no coefficients, a volume of small
+    integers: P_raw is the column sum over r^2 < 130^2 and sumVd, count are integers, all exact in any order of addition"""
+    xa, ctx, torch = gpu
+    D = shapes.LAP
+    c = D // 2
+    assert shapes.tiles(D) == 265 and shapes.laps(shapes.tiles(D)) == 2
+    vol = np.random.default_rng(D).integers(-2, 5, (D, D, D)).astype(np.float32)
+    q = np.arange(D) - c
+    ij2 = (q * q)[:, None] + (q * q)[None, :]
+    want, count = np.zeros((D, D)), 0
+    for k in range(D):                                   # the reference's k-outer loop, from index vectors: no D^3 grids
+        ball = ij2 + q[k] * q[k] < c * c
+        want += np.where(ball, vol[k], 0.0)
+        count += int(ball.sum())
+    h = xa.AngularSphAlignment(ctx, torch.from_numpy(vol).cuda(), capacity=1, l1=3, l2=2)
+    assert h.RDef == c
+    img = np.zeros((1, D, D), np.float32)
+    img[0, c, c] = 1
+    h.load(img, [{}])
+    cost = h.cost([0], np.zeros((1, h.nvars)))[0]
+    Praw, _, _, sums = h.last(0)
+    Praw = Praw.cpu().numpy()
+    print(f"D {D}: count {sums[2]:.0f} vs {count}, sumVd {sums[0]:.0f} vs {want.sum():.0f}, modg {sums[1]}, cost {cost}")
+    assert np.array_equal(Praw, want)
+    assert sums[2] == count and sums[0] == want.sum() and sums[1] == 0.0
+    assert want.reshape(-1)[256 * 256:].any()            # the partials of the second lap (the columns from 65536 on) are not zeros
+    assert cost < 1e30
+
+
 # ------------------------------------------------------------------ 2. the cost
 COST_CASES = {
     "plain": dict(),
@@ -273,6 +366,16 @@ COST_CASES = {
 @pytest.mark.parametrize("case", sorted(COST_CASES))
 @pytest.mark.parametrize("D", SIZES)
 def test_cost(gpu, oracle, D, case):
+    _check_cost(gpu, oracle, D, case)
+
+
+@pytest.mark.parametrize("case", ["plain", "ctf", "flip", "shift_out_of_frame"])
+@pytest.mark.parametrize("D", shapes.ASA_TILES)
+def test_cost_seven_tiles(gpu, oracle, D, case):
+    _check_cost(gpu, oracle, D, case)
+
+
+def _check_cost(gpu, oracle, D, case):
     xa = gpu[0]
     c = COST_CASES[case]
     vol = volume(D)
@@ -344,7 +447,7 @@ def _mixed_rows(gpu, oracle, D):
     X[4, 2:ref.vec] = X[4, ref.vec + 2:2 * ref.vec] = X[4, 2 * ref.vec + 2:3 * ref.vec] = 0
     for q in range(7):
         X[q, 3 * ref.vec:] = np.random.default_rng(80 + q).uniform(-1, 1, 8) * (1, 1, 2, 2, 2, 100, 100, 3)
-    return vol, ref, imgs, load, part, X
+    return vol, ref, imgs, load, part, X, rows
 
 
 def _call(h, part, X):
@@ -357,7 +460,7 @@ def _call(h, part, X):
 
 @pytest.mark.parametrize("D", SIZES)
 def test_batch_independence_and_repeatability(gpu, oracle, D):
-    vol, ref, imgs, load, part, X = _mixed_rows(gpu, oracle, D)
+    vol, ref, imgs, load, part, X, _ = _mixed_rows(gpu, oracle, D)
     handles = {}
     for capacity in (3, 7, 8):
         handles[capacity] = handle(gpu, ref, vol, capacity=capacity)
@@ -382,6 +485,37 @@ def test_batch_independence_and_repeatability(gpu, oracle, D):
         assert np.array_equal(cost, cost0[a:a + 3])
         for r, v in sums.items():
             assert np.array_equal(v, sums0[a + r])
+
+
+def test_six_hundred_rows_in_one_step(gpu, oracle):
+    """grid.y = 600 in k_asa_project, 600 workgroups of k_asa_cost and 9600 lines in a transform: the mixed rows, cycled. Every row's
+    cost and sums are the bits of the same row in a step of 7; 12 rows, the first and the last among them, against the restatement"""
+    D, m = shapes.ASA_ROWS
+    vol, ref, imgs, load, part7, X7, rows = _mixed_rows(gpu, oracle, D)
+    # row 0 has no coefficients, so its rotation leaves the origin voxel at exactly (0, 0, 0), which the restatement's margin refuses:
+    # the constant term moves it, and the row still runs the (L1, 0) instantiation
+    X7[0, [0, ref.vec, 2 * ref.vec]] = (0.31, -0.27, 0.43)
+    part, X = np.resize(part7, m), np.resize(X7, (m, ref.nvars))
+    assert np.array_equal(X[597], X7[597 % 7]) and part[599] == part7[599 % 7]
+    big, small = handle(gpu, ref, vol, capacity=m), handle(gpu, ref, vol, capacity=7)
+    big.load(imgs, load)
+    small.load(imgs, load)
+    cost = big.cost(part, X)
+    assert big.stats()["steps"] == 1 and big.stats()["rows"] == m
+    sums = np.array([big.last(r)[3] for r in range(m)])
+    cost7, sums7 = _call(small, part7, X7)
+    assert np.array_equal(small.cost(part, X), cost) and small.stats()["steps"] == -(-m // 7)
+    for r in range(m):
+        assert cost[r] == cost7[r % 7] and np.array_equal(sums[r], sums7[r % 7]), r
+    sampled = sorted({0, m - 1} | set(np.random.default_rng(m).choice(np.arange(1, m - 1), 10, replace=False).tolist()))
+    assert len(sampled) == 12
+    want = {}
+    for r in sampled:
+        q = r % 7
+        if q not in want:
+            want[q] = ref.cost(lowpass(imgs[part7[q]], ref.w1), rows[part7[q]], X7[q])
+        print(f"row {r}: cost {cost[r]:.15g} vs {want[q]:.15g} (difference {abs(cost[r] - want[q]):.3g})")
+        assert abs(cost[r] - want[q]) <= 1e-9
 
 
 # ------------------------------------------------------------------ 5. the search

@@ -9,11 +9,13 @@ Margins. The contract is discontinuous where a projected coordinate has fraction
 sumMw crosses 0 (Idiff and Iws switch on). The restatement asserts that no splatted voxel is within MARGIN = 1e-9 of the first, and,
 whenever the volume is updated, that every pixel a backward tap can reach (the disc of radius RDef + max|g| + 1) has
 sumMw >= 1e-9 max(sumMw). With both, no voxel and no pixel is exempted from a comparison of V. Idiff, Iws and the error are compared over
-the pixels above that margin, a set that is asserted to be the whole image at D = 16, 17 with RDef = D / 2 and sigma = 2.
+the pixels above that margin, a set that is asserted to be the whole image at D = 16, 17 with RDef = D / 2 and sigma = 2, and wherever
+the error value is compared (compare_forward compares it only then; at D = 80 and 260 test_error_where_it_is_exact makes it so).
 
 Tolerances. A pixel of P or W is a sum of at most ~2 D terms (the voxels of a column through the ball, spread over the pixels next to
 it), each a product of a weight and gw = (1 - a)(1 - b) whose position carries a few ulp of the rotation, the basis and the sums of g:
-relative to the plane's maximum that is at most 2 D x a few x 2.2e-16 < 1e-13 at D = 33, in whatever order the atomics arrive. The
+relative to the plane's maximum that is at most 2 D x a few x 2.2e-16 < 1e-13 at D = 33 and < 1e-12 at D = 260, the largest size
+here (tests/zernike_shapes.py lists the sizes past 33 and what each is there for), in whatever order the atomics arrive. The
 transform pair adds a few ulp times log2 of the size. 1e-10 x the plane's maximum, the tolerance of the sibling tests, is three orders
 above that bound; the volume after n updates is held to n x 1e-10 x max|V|, every update adding a quotient of two such planes. A case that
 needs more has a cause to be found.
@@ -28,6 +30,7 @@ import numpy as np
 import pytest
 
 from tests import xmipp_io
+from tests import zernike_shapes as shapes
 from tests.test_volume_deform_sph_host import blobs, terms_ref, zsh_ref
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +40,7 @@ from tests.test_gpu_continuous_assign2 import CTF, ctf_and_envelope  # noqa: E40
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROG = os.path.join(ROOT, "xmipp3_amd", "bin", "xmipp_forward_art_zernike3d")
 SIZES = [16, 17, 33]
+TILED = SIZES + list(shapes.FAZ_TILES)      # and the sizes with LDS tiles inside the image and across each of its edges
 MARGIN = 1e-9
 TOL = 1e-10
 MIN_CTF = 0.05
@@ -344,6 +348,93 @@ def test_forward_exact(gpu, oracle, D):
     compare_forward(f"exact D {D}", got, want, whole=D in (16, 17))
 
 
+def _flat(D, sigma=(2.0,), lam=0.01):
+    """steps 3 and 5 alone: an Art without its D^3 grids, for filter() and residual()"""
+    a = Art.__new__(Art)
+    a.D, a.sigma, a.lam = D, [float(s) for s in sigma], lam
+    return a
+
+
+@pytest.mark.parametrize("D", shapes.FAZ_EXACT)
+def test_error_where_it_is_exact(gpu, oracle, D):
+    """a file mask of ones inside a ball that covers the cube (RDef = D), identity rotation, no deformation, V of small integers: raw P
+    is the column sum and raw W is D in every pixel, bit for bit, every pixel is above the margin, and the error is compared. At D = 260
+    k_faz_errors adds 265 partials in two laps and N = 67600; the expectation comes from the column sums and the 2-D steps alone"""
+    xa, ctx, _ = gpu
+    assert 3 * (D // 2) ** 2 < D * D
+    rng = np.random.default_rng(D)
+    V0 = rng.integers(-3, 4, (D, D, D)).astype(np.float64)
+    img = rng.standard_normal((D, D)).astype(np.float32) * 10
+    ones = np.ones((D, D, D), np.int32)
+    flat = _flat(D)
+    P, W = V0.sum(axis=0)[None], np.full((1, D, D), float(D))
+    Pf, Wf = flat.filter(P, W)
+    Idiff, Iws, diff, sumMw = flat.residual(img.astype(np.float64), Pf, Wf)
+    safe = np.abs(sumMw) >= MARGIN * np.abs(sumMw).max()
+    assert safe.all() and (sumMw > 0).all()
+    on = safe & (sumMw > 0)
+    want = dict(P_raw=P, W_raw=W, P=Pf, W=Wf, Idiff=Idiff, Iws=Iws, diff=diff, sumMw=sumMw, safe=safe, error=float(np.sqrt((diff[on] ** 2).sum() / on.sum())))
+    if D < 100:                                                # the same through the whole restatement, where its grids are small
+        ref = Art(oracle, D, V0=V0, maskf=ones, RDef=float(D), use_zernike=False)
+        assert (ref.maskf == 1).all()
+        full = ref.forward(ref.particle(img, {}), ref.rotations({})[0], None)
+        for name in ("P_raw", "W_raw", "P", "W", "Idiff", "Iws"):
+            assert np.array_equal(full[name], want[name]), name
+        assert full["error"] == want["error"] and full["safe"].all()
+    else:
+        assert shapes.tiles(D) == 265 and shapes.laps(shapes.tiles(D)) == 2 and D * D > 65536
+    h = xa.ForwardArtZernike3D(ctx, D, volume=V0, maskf=ones, sigma=flat.sigma, RDef=float(D), lam=flat.lam, use_zernike=0)
+    assert h.nbricks == shapes.brick_grid(D) ** 3
+    h.load(img[None], [{}])
+    got = h.forward(0)
+    assert np.array_equal(got["P_raw"].cpu().numpy(), P) and np.array_equal(got["W_raw"].cpu().numpy(), W)
+    assert np.array_equal(got["particle"].cpu().numpy(), img.astype(np.float64))
+    compare_forward(f"exact error D {D}", got, want, whole=True)
+    # the same value through a sweep, whose partials lie at the first slot
+    err = h.sweep(0, 1)
+    print(f"exact error D {D}: sweep {err[0, 0]:.15g} vs {want['error']:.15g}")
+    assert abs(err[0, 0] - want["error"]) <= TOL * np.abs(diff).max()
+
+
+def test_load_seam(gpu, oracle):
+    """16384 + 6 images of 32 x 32: two chunks of faz_load. The first holds no CTF and is not filtered: its images come back bit for bit
+    (but the last, which is shifted). The second holds one CTF, so all six of its images pass through the transform pair"""
+    D, n = shapes.SEAM_D, shapes.SEAM_N
+    first = shapes.load_chunks(D, n)[0]
+    assert first == 16384 and n - first == 6
+    ref = Art(oracle, D, use_zernike=False, use_ctf=True)
+    idx = np.arange(n)
+    base = (blobs((1, D, D), seed=3 + D)[0] * 10).astype(np.float32)
+    imgs = base[None] * (1 + (idx % 97) / 97.0)[:, None, None].astype(np.float32)
+    imgs[idx, (idx // D) % D, idx % D] += (1 + idx / n).astype(np.float32)      # every image is distinct
+    assert len({im.tobytes() for im in imgs[::61]}) == len(imgs[::61]) and len({im.tobytes() for im in imgs[first - 3:]}) == 9
+    rows = [{} for _ in range(n)]
+    rows[first - 1] = dict(shift_x=1.6, shift_y=-2.3)
+    rows[first + 1] = dict(shift_x=-0.7, shift_y=1.2)
+    rows[first + 2] = dict(flip=1)
+    rows[first + 3] = dict(ctf=dict(CTF))
+    h = handle(gpu, ref)
+    h.load(imgs, load_rows(gpu, rows))
+
+    def particle(i):
+        return h.forward(i)["particle"].cpu().numpy()
+    drawn = np.random.default_rng(n).choice(np.arange(2, first - 2), 12, replace=False).tolist()
+    for i in [0, 1, first // 2 - 1, first - 2] + drawn:
+        assert np.array_equal(particle(i), imgs[i].astype(np.float64)), i
+    worst = 0.0
+    for i in range(first - 1, n):
+        got, want = particle(i), ref.particle(imgs[i], rows[i])
+        err, scale = np.abs(got - want).max(), np.abs(want).max()
+        worst = max(worst, err / scale)
+        print(f"load seam image {i} {rows[i] and sorted(rows[i])}: max {scale:.6g}, error {err:.3g}")
+        assert err <= TOL * scale, i
+    print(f"load seam: worst relative error {worst:.3g}")
+    assert not np.array_equal(particle(first), imgs[first].astype(np.float64))          # the chunk was filtered
+    assert np.abs(particle(first) - imgs[first]).max() <= TOL * np.abs(imgs[first]).max()
+    unfiltered = imgs[first + 3].astype(np.float64)
+    assert np.abs(particle(first + 3) - unfiltered).max() > 1e-3 * np.abs(unfiltered).max()
+
+
 @pytest.mark.parametrize("degrees", [(1, 0), (2, 1), (3, 2), (5, 4), (0, 0)])
 @pytest.mark.parametrize("D", SIZES)
 def test_forward_generic(gpu, oracle, D, degrees):
@@ -352,7 +443,25 @@ def test_forward_generic(gpu, oracle, D, degrees):
     run_forward(gpu, ref, GENERIC, coefficients(ref, 5 + D, 1.5), V0=ref.V.copy(), whole=D in (16, 17), tag=f"generic D {D} {degrees}")
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D,degrees", [(65, (3, 2)), (65, (5, 4)), (80, (3, 2))])
+def test_forward_generic_whole_tiles(gpu, oracle, D, degrees):
+    """48 x 48 tiles that lie wholly inside the image (8 at D = 65, 23 at D = 80) and tiles across each of its edges
+    (tests/test_zernike_shapes.py counts them for this case); at D = 80, 117 of the 125 bricks are listed"""
+    ref = Art(oracle, D, *degrees, V0=volume(D))
+    h, _, want = run_forward(gpu, ref, GENERIC, coefficients(ref, 5 + D, 1.5), V0=ref.V.copy(), tag=f"generic D {D} {degrees}")
+    assert h.nbricks == len(shapes.bricks(ref.maskf)) == {65: 67, 80: 117}[D]
+    assert int(want["safe"].sum()) == {(65, (3, 2)): 4208, (65, (5, 4)): 4205, (80, (3, 2)): 6377}[D, degrees]      # the pixels compared in Idiff, Iws
+
+
+@pytest.mark.parametrize("degrees", shapes.PAIRS)
+def test_forward_every_instantiation(gpu, oracle, degrees):
+    """the 19 compiled (L1, L2) pairs of the dispatch table, each unrolled on its own"""
+    D = 17
+    ref = Art(oracle, D, *degrees, V0=volume(D))
+    run_forward(gpu, ref, GENERIC, coefficients(ref, 5 + D, 1.5), V0=ref.V.copy(), whole=True, tag=f"pair D {D} {degrees}")
+
+
+@pytest.mark.parametrize("D", TILED)
 def test_forward_no_deformation(gpu, oracle, D):
     ref = Art(oracle, D, V0=volume(D), use_zernike=False)
     run_forward(gpu, ref, GENERIC, None, V0=ref.V.copy(), whole=D in (16, 17), tag=f"no deformation D {D}")
@@ -369,12 +478,22 @@ def test_forward_effective_l2(gpu, oracle, D):
     run_forward(gpu, ref, GENERIC, coef, V0=ref.V.copy(), whole=D in (16, 17), tag=f"effective l2 D {D}")
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_forward_step_2(gpu, oracle, D):
     ref = Art(oracle, D, V0=volume(D), step=2)
     _, got, want = run_forward(gpu, ref, GENERIC, coefficients(ref, 9 + D, 1.5), V0=ref.V.copy(), tag=f"step 2 D {D}")
     full = Art(oracle, D, V0=volume(D)).splat(ref.rotations(GENERIC)[0], coefficients(ref, 9 + D, 1.5))[1]
     assert 0 < want["W_raw"].sum() < 0.5 * full.sum()          # an eighth of the voxels, each with a wider footprint weight
+
+
+@pytest.mark.parametrize("D", shapes.FAZ_TILES)
+def test_forward_step_3(gpu, oracle, D):
+    """a lattice that does not line up with the 16-voxel bricks: the first lattice plane of a brick is at offset 0, 2 or 1"""
+    ref = Art(oracle, D, V0=volume(D), step=3)
+    assert shapes.BRICK % 3 != 0 and {(b * shapes.BRICK) % 3 for b in range(shapes.brick_grid(D))} == {0, 1, 2}
+    h, got, want = run_forward(gpu, ref, GENERIC, coefficients(ref, 9 + D, 1.5), V0=ref.V.copy(), tag=f"step 3 D {D}")
+    assert h.nbricks == len(shapes.bricks(ref.maskf, 3))
+    assert int(ref.lattice.sum()) == (-(-D // 3)) ** 3 and want["W_raw"].sum() > 0
 
 
 @pytest.mark.parametrize("D", SIZES)
@@ -388,7 +507,7 @@ def test_forward_file_mask(gpu, oracle, D):
     run_forward(gpu, ref, GENERIC, coefficients(ref, 11 + D, 1.2), V0=ref.V.copy(), maskf=mask, tag=f"file mask D {D}")
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_forward_two_sigmas(gpu, oracle, D):
     """maskF holds both sigmas and one value that matches neither: those voxels are skipped"""
     k, i, j = np.meshgrid(*(np.arange(D) - D // 2,) * 3, indexing="ij")
@@ -399,7 +518,7 @@ def test_forward_two_sigmas(gpu, oracle, D):
     assert want["W_raw"][0].any() and want["W_raw"][1].any() and want["W_raw"].sum() < one.sum()
 
 
-@pytest.mark.parametrize("D", SIZES)
+@pytest.mark.parametrize("D", TILED)
 def test_forward_large_coefficients(gpu, oracle, D):
     """displacements of up to 9 voxels push voxels out of the 48 x 48 tile's centre, and out of the image"""
     ref = Art(oracle, D, V0=volume(D))
@@ -473,8 +592,8 @@ def test_particle_preparation(gpu, oracle, D, case):
 
 
 # ------------------------------------------------------------------ 3. updates
-def _update_case(oracle, D, sym=()):
-    """non-zero weights of every regulariser, maskB different from maskF, V with both signs and exact zeros"""
+def _update_case(oracle, D, sym=(), n=6):
+    """non-zero weights of every regulariser, maskB different from maskF, V with both signs and exact zeros; n images"""
     V0 = volume(D) - 0.2
     k, i, j = np.meshgrid(*(np.arange(D) - D // 2,) * 3, indexing="ij")
     V0[(k + 2 * i + 3 * j) % 4 == 0] = 0.0
@@ -482,8 +601,8 @@ def _update_case(oracle, D, sym=()):
     maskb[(np.abs(k) <= 1) & (np.abs(i) <= 1)] = 0
     ref = Art(oracle, D, 3, 2, V0=V0, maskb=maskb, lam=0.05, ltv=2e-2, ltk=3e-2, ll1=4e-2, lst=5e-2, sym=sym)
     assert (ref.V > 0).any() and (ref.V < 0).any() and (ref.V[ref.maskb != 0] == 0).any() and not np.array_equal(ref.maskb, ref.maskf)
-    coefs = np.array([coefficients(ref, 40 + q, 1.0 + 0.1 * q) for q in range(6)])
-    imgs = np.array([particle_image(ref, POSES[q], coefs[q], seed=60 + q) for q in range(6)])
+    coefs = np.array([coefficients(ref, 40 + q, 1.0 + 0.1 * q) for q in range(n)])
+    imgs = np.array([particle_image(ref, POSES[q], coefs[q], seed=60 + q) for q in range(n)])
     return ref, V0, maskb, coefs, imgs
 
 
@@ -534,6 +653,29 @@ def test_sweep_of_six_and_repeatability(gpu, oracle, D):
     _check_volume(f"sweep D {D}", vols[0], states[5], 6)
     # stale Dl1 entries matter: without them the restatement ends elsewhere
     _check_volume(f"repeat D {D}", vols[1], vols[0], 6)
+
+
+@pytest.mark.parametrize("D", shapes.FAZ_TILES)
+def test_sweep_of_two_whole_tiles(gpu, oracle, D):
+    """two updates where tiles lie inside the image and k_faz_back reads it over more than one brick's footprint: V after each update,
+    and a second handle from the same state. The restatement asserts its margin and the backward disc's weights for both updates. The
+    pixels above the margin are not the whole image at these sizes, so the error value is not compared (test_error_where_it_is_exact)"""
+    ref, V0, maskb, coefs, imgs = _update_case(oracle, D, n=2)
+    states = []
+    for q in range(2):
+        ref.update(ref.particle(imgs[q], POSES[q]), POSES[q], coefs[q])
+        states.append(ref.V.copy())
+    vols = []
+    for _ in range(2):
+        h = handle(gpu, ref, V0=V0, maskb=maskb)
+        h.load(imgs, load_rows(gpu, POSES[:2]), coefs)
+        for q in range(2):
+            h.sweep(q, 1)
+            vols.append(h.get_volume())
+            if len(vols) <= 2:
+                _check_volume(f"sweep of two D {D}, update {q + 1}", vols[-1], states[q], q + 1)
+    assert not np.array_equal(states[1], states[0]) and np.array_equal(states[1][maskb == 0], V0[maskb == 0])
+    _check_volume(f"repeat D {D}", vols[3], vols[1], 2)
 
 
 def test_symmetry_c2(gpu, oracle):

@@ -198,6 +198,35 @@ def test_segment_size_moves_the_last_bits_only(gpu):
         assert np.abs(out[seg][0] - out[64][0]).max() <= 1e-13 * np.abs(out[64][0]).max()
 
 
+def test_timed_run_changes_no_byte(gpu):
+    """set_timing(True) puts a wait after every stage: load and directional return the same bytes, the stages report times (SMALL is no
+    cube: the 3DFSC's stays 0), and set_timing resets them"""
+    xa, ctx, torch = gpu
+    h1, h2, m = (torch.from_numpy(a).cuda() for a in inputs(SMALL))
+    dirs = directions("level2")
+    cosA, aux = R.cone(ANGLE)
+    f = xa.FSO(ctx, SMALL, seg=SEG[SMALL])
+
+    def run():
+        return [a.tobytes() for a in f.load(h1, h2, m) + f.directional(dirs, cosA, aux)]
+
+    out = run()
+    assert set(f.stage_ms().values()) == {0.0}                  # an untimed run reports nothing
+    f.set_timing(True)
+    out_t = run()
+    ms = f.stage_ms()
+    print(f"stage ms: {ms}")
+    assert out_t == out
+    assert list(ms) == list(xa.FSO.STAGES) and len(ms) == 5
+    assert all(v >= 0.0 for v in ms.values()) and sum(ms.values()) > 0.0
+    assert all(ms[k] > 0.0 for k in ("transforms", "layout", "cones", "segment_reduce"))
+    f.set_timing(False)
+    assert set(f.stage_ms().values()) == {0.0}
+    assert run() == out
+    assert set(f.stage_ms().values()) == {0.0}
+    f.close()
+
+
 # ---------------------------------------------------------------- threshold decisions
 def check_decisions(got, exp, ndir, what):
     """got, exp: (fsc, resolution, fso, bingham) of the device sums and of the restatement"""

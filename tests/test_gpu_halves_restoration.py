@@ -403,6 +403,83 @@ def test_difference_of_equal_halves(gpu):
         assert np.array_equal(got, (V + V) * 0.5)
 
 
+# ---------------------------------------------------------------- the handle
+def test_timed_filter_bank_changes_no_byte(gpu):
+    """set_timing(True) puts four events and a wait into every band: the three outputs keep their bytes and band_timing reports the
+    bands and three times. filter_bank resets them, set_timing does not"""
+    xa, ctx, torch = gpu
+    shape = (33, 40, 36)
+    d1, d2 = (torch.from_numpy(v).cuda() for v in halves(shape))
+    h = xa.HalvesRestoration(ctx, shape)
+
+    def run():
+        h.load(d1, d2)
+        h.filter_bank(0.04, 0.5, 1, 3.0)
+        return [_np(h.output(name)).tobytes() for name in ("filterBank", "restored1", "restored2")]
+
+    out = run()
+    bands, ms = h.band_timing()
+    assert bands == 25 and not ms.any()                         # w = 0, 0.02 .. < 0.5; an untimed run reports no time
+    h.set_timing(True)
+    out_t = run()
+    bands_t, ms_t = h.band_timing()
+    print(f"{bands_t} bands, transforms / cdf / weights ms: {ms_t}")
+    assert out_t == out and bands_t == bands
+    assert ms_t.shape == (3,) and (ms_t >= 0).all() and ms_t.sum() > 0
+    h.set_timing(False)
+    assert np.array_equal(h.band_timing()[1], ms_t)             # the switch alone resets nothing
+    assert run() == out
+    bands_u, ms_u = h.band_timing()
+    assert bands_u == bands and not ms_u.any()
+    h.close()
+
+
+def test_wrong_tensor_is_refused(gpu):
+    """a tensor of another shape or type, or one that is not contiguous, is an XhError before its pointer reaches the library: for the
+    volumes, and for the int32 masks, which a float64 tensor of the right shape is not"""
+    xa, ctx, torch = gpu
+    shape = (16, 18, 20)
+    Z, Y, X = shape
+    dv = torch.from_numpy(halves(shape)[0]).cuda()
+    dm = torch.from_numpy(xa.halves_circular_mask(shape, -5)).cuda()
+    h = xa.HalvesRestoration(ctx, shape)
+    h.load(dv, dv)
+
+    def wrong(good):
+        other = torch.float32 if good.dtype == torch.float64 else torch.float64
+        return [torch.zeros((Z, Y, X - 2), dtype=good.dtype, device="cuda"), good.to(other),
+                torch.zeros((Z, Y, 2 * X), dtype=good.dtype, device="cuda")[:, :, ::2]]
+
+    for bad in wrong(dv):
+        for call in (lambda: h.load(bad, dv), lambda: h.load(dv, bad), lambda: h.rfft(bad), lambda: h.cdf(bad), lambda: h.cdf(dv, bad)):
+            with pytest.raises(xa.XhError, match="HalvesRestoration: the volume"):
+                call()
+    for bad in wrong(dm) + [dv]:
+        for call in (lambda: h.denoise(1, bad), lambda: h.difference(1, 1.5, bad), lambda: h.cdf(dv, mask=bad)):
+            with pytest.raises(xa.XhError, match="HalvesRestoration: the mask"):
+                call()
+    with pytest.raises(xa.XhError, match="int32"):
+        h.denoise(1, dv)
+    h.denoise(1, dm)                                            # the handle still works
+    h.close()
+
+
+def test_close_with_work_in_flight(gpu):
+    """close() right behind a launch: the handle waits for its stream before its buffers and events go"""
+    xa, ctx, torch = gpu
+    shape = (33, 40, 36)
+    d1, d2 = (torch.from_numpy(v).cuda() for v in halves(shape))
+    h = xa.HalvesRestoration(ctx, shape)
+    h.load(d1, d2)
+    h.denoise(1)
+    h.close()
+    assert h.h is None
+    h2 = _handle(gpu, *halves(shape))                           # the context is in order: the next handle computes
+    h2.denoise(1)
+    e1, _ = denoise(*halves(shape), 1)
+    _close(_np(h2.output("restored1")), e1)
+
+
 # ---------------------------------------------------------------- stages past the grid cap
 # Every per-voxel kernel and reduction runs on min(ceil(NF / 256), 4 CUs) workgroups of 256 and walks the rest in a grid-stride loop.
 # (81, 80, 82): NF = 81 * 80 * 42 = 272 160 half-spectrum elements and N = 531 360 voxels, between one and two passes of 1024 threads

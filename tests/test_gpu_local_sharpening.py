@@ -310,6 +310,28 @@ def test_two_runs_give_the_same_bytes(gpu):
     assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes() and la == lb and ia == ib
 
 
+def test_timed_run_changes_no_byte(gpu):
+    """set_timing(True) puts a wait after every stage: the map, lambda and the records keep their bytes, the five stages report times,
+    and set_timing resets them"""
+    xa = gpu[0]
+    m = loaded(gpu, SHAPES[0])
+    out, lam, its = m.run(0.5, 3)
+    assert set(m.stage_ms().values()) == {0.0}                  # an untimed run reports nothing
+    m.set_timing(True)
+    out_t, lam_t, its_t = m.run(0.5, 3)
+    ms = m.stage_ms()
+    print(f"stage ms: {ms}")
+    assert out_t.cpu().numpy().tobytes() == out.cpu().numpy().tobytes() and lam_t == lam and its_t == its
+    assert list(ms) == list(xa.LocalDeblur.STAGES) and len(ms) == 5
+    assert all(v >= 0.0 for v in ms.values()) and sum(ms.values()) > 0.0
+    m.set_timing(False)
+    assert set(m.stage_ms().values()) == {0.0}
+    out_u, lam_u, its_u = m.run(0.5, 3)
+    assert out_u.cpu().numpy().tobytes() == out.cpu().numpy().tobytes() and lam_u == lam and its_u == its
+    assert set(m.stage_ms().values()) == {0.0}
+    m.close()
+
+
 def test_two_iterations_past_the_grid_cap(gpu, big):
     """four operators at BIG with a fixed lambda (a 50-iteration run at this size belongs to no test), and the same bytes twice"""
     ref = ref_run(big, 0.5, 2)

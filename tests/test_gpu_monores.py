@@ -300,20 +300,20 @@ CASES = {
 _E2E = {}
 
 
-def e2e_inputs(name):
+def e2e_inputs(name, shape=SHAPE, r_prot=R_PROT, r_noise=R_NOISE):
     c = CASES[name]
     seed = 1
-    sig = R.synth_map(SHAPE, seed)
-    sig[R.r2_map(SHAPE) > R_PROT * R_PROT] = 0.0
+    sig = R.synth_map(shape, seed)
+    sig[R.r2_map(shape) > r_prot * r_prot] = 0.0
     if c["halves"]:
-        v1 = sig + R.noise_in_sphere(SHAPE, seed + 100, 0.21, R_NOISE)
-        v2 = sig + R.noise_in_sphere(SHAPE, seed + 200, 0.21, R_NOISE)
+        v1 = sig + R.noise_in_sphere(shape, seed + 100, 0.21, r_noise)
+        v2 = sig + R.noise_in_sphere(shape, seed + 200, 0.21, r_noise)
     else:
-        v1, v2 = sig + R.noise_in_sphere(SHAPE, seed + 100, 0.15, R_NOISE), None
-    mask = R.protein_mask(SHAPE, R_PROT)
+        v1, v2 = sig + R.noise_in_sphere(shape, seed + 100, 0.15, r_noise), None
+    mask = R.protein_mask(shape, r_prot)
     excl = None
     if c.get("excl"):
-        excl = np.zeros(SHAPE, np.int32)
+        excl = np.zeros(shape, np.int32)
         excl[10:16, 12:20, 14:22] = 1
     # what the program reads from files: float32 values
     v1 = v1.astype(np.float32).astype(np.float64)
@@ -403,6 +403,80 @@ def test_two_runs_give_the_same_bytes(gpu):
         for key in ("refined_mask", "chimera", "resolution_map"):
             assert a[key].cpu().numpy().tobytes() == b[key].cpu().numpy().tobytes(), (name, key)
         assert a["steps"] == b["steps"] and a["stop"] == b["stop"]
+
+
+def test_timed_run_changes_no_byte(gpu):
+    """set_timing(True) records events around the stages and reads them after the step's own wait: the maps and the records keep their
+    bytes and the seven stages report times (every step of this sweep assigns, the restatement says). run resets the times,
+    set_timing does not"""
+    xa, ctx, torch = gpu
+    shape = SMALL[0]
+    v1, _, mask, _, kw = e2e_inputs("single", shape, 5, 8)
+    ref = R.run(v1, mask, **kw)
+    assert len(ref["steps"]) >= 6 and all(s["assigned"] for s in ref["steps"])
+    dv, dm = torch.from_numpy(v1).cuda(), torch.from_numpy(mask).cuda()
+    m = xa.MonoRes(ctx, shape)
+    keys = ("refined_mask", "chimera", "resolution_map")
+
+    def run():
+        out = m.run(dv, dm, sampling=kw["sampling"], max_res=kw["maxRes"], step=kw["freq_step"], significance=kw["significance"])
+        return [out[k].cpu().numpy().tobytes() for k in keys], out["steps"], out["stop"]
+
+    out = run()
+    assert len(out[1]) == len(ref["steps"])
+    assert set(m.stage_ms().values()) == {0.0}                  # an untimed run reports nothing
+    m.set_timing(True)
+    out_t = run()
+    ms = m.stage_ms()
+    print(f"stage ms: {ms}")
+    assert out_t == out
+    assert list(ms) == list(xa.MonoRes.STAGES) and len(ms) == 7
+    assert all(v >= 0.0 for v in ms.values()) and sum(ms.values()) > 0.0
+    m.set_timing(False)
+    assert m.stage_ms() == ms                                   # the switch alone resets nothing
+    assert run() == out
+    assert set(m.stage_ms().values()) == {0.0}
+    m.close()
+
+
+def _wrong_tensors(torch, shape, good):
+    """what a volume handle refuses in place of `good`: another shape, another type, a view that is not contiguous"""
+    Z, Y, X = shape
+    other = torch.float32 if good.dtype == torch.float64 else torch.float64
+    return {"shape": torch.zeros((Z, Y, X - 2), dtype=good.dtype, device="cuda"), "type": good.to(other),
+            "view": torch.zeros((Z, Y, 2 * X), dtype=good.dtype, device="cuda")[:, :, ::2]}
+
+
+def test_wrong_tensor_is_refused(gpu):
+    """a tensor of another shape or type, or one that is not contiguous, is an XhError before its pointer reaches the library: for the
+    volumes, and for the int32 masks, which a float64 tensor of the right shape is not"""
+    xa, ctx, torch = gpu
+    shape = SMALL[0]
+    v1, _, mask, _, _ = e2e_inputs("single", shape, 5, 8)
+    dv, dm = torch.from_numpy(v1).cuda(), torch.from_numpy(mask).cuda()
+    m = xa.MonoRes(ctx, shape)
+    for what, bad in _wrong_tensors(torch, shape, dv).items():
+        assert tuple(bad.shape) == shape or what == "shape"
+        with pytest.raises(xa.XhError, match="MonoRes: the volume"):
+            m.run(bad, dm, max_res=10.0)
+        with pytest.raises(xa.XhError, match="MonoRes: the second half"):
+            m.run(dv, dm, vol2=bad, max_res=10.0)
+        with pytest.raises(xa.XhError, match="MonoRes: the volume"):
+            m.amplitude(bad, 0.25, 0.2, 0.3)
+        with pytest.raises(xa.XhError, match="MonoRes: the volume"):
+            m.gaussian(bad, 3.0)
+        with pytest.raises(xa.XhError, match="MonoRes: the volume"):
+            m.shell_sums(bad)
+    for what, bad in _wrong_tensors(torch, shape, dm).items():
+        with pytest.raises(xa.XhError, match="MonoRes: the mask"):
+            m.run(dv, bad, max_res=10.0)
+        with pytest.raises(xa.XhError, match="MonoRes: the exclusion mask"):
+            m.run(dv, dm, mask_excl=bad, max_res=10.0)
+        with pytest.raises(xa.XhError, match="MonoRes: the mask"):
+            m.statistics(dv, bad)
+    with pytest.raises(xa.XhError, match="int32"):
+        m.run(dv, dv, max_res=10.0)
+    m.close()
 
 
 def test_refusals(gpu):

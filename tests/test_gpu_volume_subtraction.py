@@ -247,6 +247,29 @@ def test_two_runs_give_the_same_bytes(gpu, shape, radavg, cut):
     assert a.tobytes() == b.tobytes()
 
 
+def test_timed_run_changes_no_byte(gpu):
+    """set_timing(True) puts a wait after every stage: the adjusted volume keeps its bytes, the four stages report times (radavg and a
+    cut-off frequency: all four run), and set_timing resets them"""
+    xa = gpu[0]
+    shape = (36, 30, 25)
+    dv = dev(gpu, target(shape))
+    h = handle(gpu, shape, radavg=True)
+    out = h.adjust(dv, 3, 1.0, True, CUT).cpu().numpy()
+    assert set(h.stage_ms().values()) == {0.0}                  # an untimed run reports nothing
+    h.set_timing(True)
+    out_t = h.adjust(dv, 3, 1.0, True, CUT).cpu().numpy()
+    ms = h.stage_ms()
+    print(f"stage ms: {ms}")
+    assert out_t.tobytes() == out.tobytes()
+    assert list(ms) == list(xa.VolumeSubtraction.STAGES) and len(ms) == 4
+    assert all(v > 0.0 for v in ms.values())
+    h.set_timing(False)
+    assert set(h.stage_ms().values()) == {0.0}
+    assert h.adjust(dv, 3, 1.0, True, CUT).cpu().numpy().tobytes() == out.tobytes()
+    assert set(h.stage_ms().values()) == {0.0}
+    h.close()
+
+
 @pytest.mark.parametrize("radavg", [False, True])
 def test_one_reference_serves_two_volumes(gpu, radavg):
     shape = (36, 30, 25)

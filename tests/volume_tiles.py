@@ -33,7 +33,7 @@ def plan_M(n):
 
 
 def plan_lpb(n, budget=64 * 1024, max_lines=8):
-    """xh_plan_lpb (xh_plan.h) as ldb_filter (xh_ldb.hip) and mn_yz_inverse (xh_mono.hip) call it: 64 KiB, at most 8 lines"""
+    """xh_plan_lpb (xh_plan.h) as ldb_filter (xh_ldb.hip) and fft3d_yz (xh_fft3d.h, the batch of four of xh_mono.hip) call it: 64 KiB, at most 8 lines"""
     return max(1, min(max_lines, budget // (CD * plan_M(n))))
 
 

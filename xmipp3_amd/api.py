@@ -122,6 +122,52 @@ class _Handle:
             pass
 
 
+class _StageTimes:
+    """set_timing / stage_ms of a handle whose entry points are xh_<_PREFIX>_set_timing and xh_<_PREFIX>_stage_ms; STAGES names what
+    the second fills, in order."""
+
+    _PREFIX = None
+    STAGES = ()
+
+    def set_timing(self, on=True):
+        """runs record their stages (the benchmark's switch)"""
+        check(getattr(lib(), f"xh_{self._PREFIX}_set_timing")(self.h, int(bool(on))))
+
+    def stage_ms(self):
+        """milliseconds per stage of the timed runs, a dict in the order of STAGES"""
+        ms = np.zeros(len(self.STAGES))
+        check(getattr(lib(), f"xh_{self._PREFIX}_stage_ms")(self.h, _np_ptr(ms)))
+        return dict(zip(self.STAGES, ms))
+
+
+class _VolumeHandle(_Handle):
+    """A handle on one [Z, Y, X] box, made by xh_<_PREFIX>_create(ctx, Z, Y, X, *args, &h): the shape, new volumes of it, and the check
+    every tensor passes before its pointer reaches the library."""
+
+    _PREFIX = None
+    _WHAT = "volume"
+
+    def __init__(self, ctx, shape, *args):
+        self.ctx = ctx
+        self.shape = tuple(int(s) for s in shape)
+        assert len(self.shape) == 3
+        h = C.c_void_p()
+        check(getattr(lib(), f"xh_{self._PREFIX}_create")(ctx.h, *self.shape, *args, C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _vol(self, t, what=None, dtype=None, shape=None):
+        dtype, shape = dtype or _torch().float64, shape or self.shape
+        name, what = type(self).__name__, what or self._WHAT
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise XhError(f"{name}: the {what} must be a contiguous {str(dtype).split('.')[-1]} cuda tensor")
+        if tuple(t.shape) != shape:
+            raise XhError(f"{name}: the {what} has shape {tuple(t.shape)}, the handle {shape}")
+        return t
+
+    def _new(self):
+        return _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+
+
 def _ptr(t, dtype=None):
     if t is None:
         return None
@@ -706,30 +752,17 @@ class AlignSignificant(_Handle):
         return out
 
 
-class HalvesRestoration(_Handle):
+class HalvesRestoration(_VolumeHandle):
     """The device side of xmipp_volume_halves_restoration (VolumeHalvesRestorator<double>): two half maps [Z, Y, X] float64 restored in
     place by denoise, deconvolve, filter_bank and difference, in that order, as the reference's apply runs them."""
 
     _destroy = "xh_halves_destroy"
+    _PREFIX = "halves"
 
     OUTPUTS = ("restored1", "restored2", "filterBank", "deconvolved", "convolved", "avgDiff")
 
-    def __init__(self, ctx, shape):
-        self.ctx = ctx
-        self.shape = tuple(int(s) for s in shape)
-        assert len(self.shape) == 3
-        h = C.c_void_p()
-        check(lib().xh_halves_create(ctx.h, *self.shape, C.byref(h)))
-        super().__init__(ctx, h)
-
-    def _vol(self, t, dtype=None):
-        torch = _torch()
-        dtype = dtype or torch.float64
-        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == self.shape, (t.shape, t.dtype)
-        return t
-
     def _mask(self, mask):
-        return None if mask is None else _ptr(self._vol(mask, _torch().int32))
+        return None if mask is None else _ptr(self._vol(mask, "mask", _torch().int32))
 
     def load(self, v1, v2):
         check(lib().xh_halves_load(self.h, _ptr(self._vol(v1)), _ptr(self._vol(v2))))
@@ -751,8 +784,7 @@ class HalvesRestoration(_Handle):
 
     def output(self, name):
         """one of OUTPUTS as a new device tensor, or None where its stage did not run"""
-        torch = _torch()
-        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        out = self._new()
         present = C.c_int32()
         check(lib().xh_halves_output(self.h, self.OUTPUTS.index(name), _ptr(out), C.byref(present)))
         return out if present.value else None
@@ -778,7 +810,7 @@ class HalvesRestoration(_Handle):
         torch = _torch()
         Z, Y, X = self.shape
         assert F.is_cuda and F.dtype == torch.complex128 and F.is_contiguous() and tuple(F.shape) == (Z, Y, X // 2 + 1)
-        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        out = self._new()
         check(lib().xh_halves_fft_c2r(self.h, _ptr(F), _ptr(out), float(scale)))
         return out
 
@@ -814,28 +846,15 @@ def halves_binary_mask(values):
     check(lib().xh_halves_binary_mask(_np_ptr(v), v.size, _np_ptr(m)))
     return m
 
-class MonoRes(_Handle):
+class MonoRes(_StageTimes, _VolumeHandle):
     """The device side of xmipp_resolution_monogenic_signal (MonoRes): the local resolution map of a volume, or of two half maps,
     [Z, Y, X] float64 tensors on the device; masks are int32 tensors."""
 
     _destroy = "xh_mono_destroy"
+    _PREFIX = "mono"
 
     STOP = {1: "range", 2: "mask_done", 3: "no_points", 4: "low_signal", 5: "ztest", 6: "min_res"}
     STAGES = ("split", "inverse", "rows", "smooth", "stats", "select", "assign")
-
-    def __init__(self, ctx, shape):
-        self.ctx = ctx
-        self.shape = tuple(int(s) for s in shape)
-        assert len(self.shape) == 3
-        h = C.c_void_p()
-        check(lib().xh_mono_create(ctx.h, *self.shape, C.byref(h)))
-        super().__init__(ctx, h)
-
-    def _vol(self, t, dtype=None):
-        torch = _torch()
-        dtype = dtype or torch.float64
-        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == self.shape, (t.shape, t.dtype)
-        return t
 
     def run(self, vol, mask, vol2=None, mask_excl=None, sampling=1.0, min_res=30.0, max_res=1.0, step=0.25, significance=0.95, gaussian=False,
             noise_only_in_halves=False, max_steps=4096):
@@ -849,12 +868,11 @@ class MonoRes(_Handle):
         prm.gaussian, prm.noise_only_in_halves = int(bool(gaussian)), int(bool(noise_only_in_halves))
         steps = (MonoStep * int(max_steps))()
         n, stop = C.c_int32(), C.c_int32()
-        mean = torch.empty(self.shape, dtype=torch.float64, device="cuda") if vol2 is not None else None
+        mean = self._new() if vol2 is not None else None
         refined = torch.empty(self.shape, dtype=torch.int32, device="cuda")
-        chimera = torch.empty(self.shape, dtype=torch.float64, device="cuda")
-        resmap = torch.empty(self.shape, dtype=torch.float64, device="cuda")
-        check(lib().xh_mono_run(self.h, _ptr(self._vol(vol)), None if vol2 is None else _ptr(self._vol(vol2)), _ptr(self._vol(mask, torch.int32)),
-                                None if mask_excl is None else _ptr(self._vol(mask_excl, torch.int32)), C.byref(prm), C.cast(steps, C.c_void_p), int(max_steps),
+        chimera, resmap = self._new(), self._new()
+        check(lib().xh_mono_run(self.h, _ptr(self._vol(vol)), None if vol2 is None else _ptr(self._vol(vol2, "second half")), _ptr(self._vol(mask, "mask", torch.int32)),
+                                None if mask_excl is None else _ptr(self._vol(mask_excl, "exclusion mask", torch.int32)), C.byref(prm), C.cast(steps, C.c_void_p), int(max_steps),
                                 C.byref(n), C.byref(stop), _ptr(mean), _ptr(refined), _ptr(chimera), _ptr(resmap)))
         recs = []
         for k in range(min(n.value, int(max_steps))):
@@ -874,8 +892,7 @@ class MonoRes(_Handle):
 
     def amplitude(self, vol, freq, freqH, freqL, banded=True):
         """amplitudeMonoSig3D_LPF (banded) or monogenicAmplitude_3D_Fourier of a map, as a new device tensor"""
-        torch = _torch()
-        out = torch.empty(self.shape, dtype=torch.float64, device="cuda")
+        out = self._new()
         check(lib().xh_mono_amplitude(self.h, _ptr(self._vol(vol)), float(freq), float(freqH), float(freqL), int(bool(banded)), _ptr(out)))
         return out
 
@@ -888,7 +905,7 @@ class MonoRes(_Handle):
     def statistics(self, ampS, mask, ampN=None, significance=0.95):
         from ._lib import MonoStats
         st = MonoStats()
-        check(lib().xh_mono_statistics(self.h, _ptr(self._vol(ampS)), None if ampN is None else _ptr(self._vol(ampN)), _ptr(self._vol(mask, _torch().int32)),
+        check(lib().xh_mono_statistics(self.h, _ptr(self._vol(ampS, "amplitude")), None if ampN is None else _ptr(self._vol(ampN, "noise amplitude")), _ptr(self._vol(mask, "mask", _torch().int32)),
                                        float(significance), C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
@@ -913,14 +930,6 @@ class MonoRes(_Handle):
         s, s2, n = np.zeros(ns), np.zeros(ns), np.zeros(ns)
         check(lib().xh_mono_shell_sums(self.h, _ptr(self._vol(vol)), _np_ptr(s), _np_ptr(s2), _np_ptr(n)))
         return s, s2, n
-
-    def set_timing(self, on):
-        check(lib().xh_mono_set_timing(self.h, int(bool(on))))
-
-    def stage_ms(self):
-        ms = np.zeros(len(self.STAGES))
-        check(lib().xh_mono_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms))
 
 
 def mono_icdf_gauss(p):
@@ -964,29 +973,17 @@ def mono_num_shells(shape):
     return out.value
 
 
-class LocalDeblur(_Handle):
+class LocalDeblur(_StageTimes, _VolumeHandle):
     """The device side of xmipp_volume_local_sharpening (LocalDeblur): sharpens a volume with its local resolution map, [Z, Y, X] float64
     tensors on the device. batch: the band spectra held at once (rounded up to an even number; any value gives the same bytes)."""
 
     _destroy = "xh_ldb_destroy"
+    _PREFIX = "ldb"
 
     STAGES = ("forward", "split", "yz", "rows", "finish")
 
     def __init__(self, ctx, shape, batch=8):
-        self.ctx = ctx
-        self.shape = tuple(int(s) for s in shape)
-        assert len(self.shape) == 3
-        h = C.c_void_p()
-        check(lib().xh_ldb_create(ctx.h, *self.shape, int(batch), C.byref(h)))
-        super().__init__(ctx, h)
-
-    def _vol(self, t, what="volume"):
-        torch = _torch()
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise XhError(f"LocalDeblur: the {what} must be a contiguous float64 cuda tensor")
-        if tuple(t.shape) != self.shape:
-            raise XhError(f"LocalDeblur: the {what} has shape {tuple(t.shape)}, the handle {self.shape}")
-        return t
+        super().__init__(ctx, shape, int(batch))
 
     def load(self, vol, resmap, sampling=1.0, K=0.025):
         """produceSideInfo: the volume and its resolution map (both are copied)"""
@@ -1004,13 +1001,13 @@ class LocalDeblur(_Handle):
 
     def resmap(self):
         """the resolution map as load left it (clamped)"""
-        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        out = self._new()
         check(lib().xh_ldb_resmap(self.h, _ptr(out)))
         return out
 
     def localfilter(self, v):
         """localfiltering of a volume, as a new device tensor"""
-        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        out = self._new()
         check(lib().xh_ldb_localfilter(self.h, _ptr(self._vol(v)), _ptr(out)))
         return out
 
@@ -1020,18 +1017,10 @@ class LocalDeblur(_Handle):
         cap = max(int(niter), 1)
         recs = (LdbIter * cap)()
         n, stopped, lout = C.c_int32(), C.c_int32(), C.c_double()
-        out = _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
+        out = self._new()
         check(lib().xh_ldb_run(self.h, float(lam), int(niter), C.cast(recs, C.c_void_p), cap, C.byref(n), C.byref(stopped), C.byref(lout), _ptr(out)))
         its = [{"norm": r.norm, "porc": r.porc, "subst": r.subst, "lambda": r.lambda_, "stop": bool(r.stop)} for r in recs[:n.value]]
         return out, lout.value, its
-
-    def set_timing(self, on):
-        check(lib().xh_ldb_set_timing(self.h, int(bool(on))))
-
-    def stage_ms(self):
-        ms = np.zeros(len(self.STAGES))
-        check(lib().xh_ldb_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms))
 
 
 def ldb_bands(zsize, sampling, max_res):
@@ -1044,31 +1033,20 @@ def ldb_bands(zsize, sampling, max_res):
     return [(r[0], r[1], r[2], int(r[3])) for r in b]
 
 
-class FSO(_Handle):
+class FSO(_StageTimes, _VolumeHandle):
     """The device side of xmipp_resolution_fso: global FSC, directional FSCs through Gaussian-weighted cones, FSO curve, 3DFSC of two
     half maps, [Z, Y, X] float64 tensors on the device. seg: the sorted coefficients a workgroup of the cone stage takes (0: the
     default); any value gives sums that differ in the last bits only, and the same bytes on every run."""
 
     _destroy = "xh_fso_destroy"
+    _PREFIX = "fso"
+    _WHAT = "half map"
 
     STAGES = ("transforms", "layout", "cones", "segment_reduce", "threedfsc")
 
     def __init__(self, ctx, shape, seg=0):
-        self.ctx = ctx
-        self.shape = tuple(int(s) for s in shape)
-        assert len(self.shape) == 3
+        super().__init__(ctx, shape, int(seg))
         self.L = self.shape[2] // 2 + 1
-        h = C.c_void_p()
-        check(lib().xh_fso_create(ctx.h, *self.shape, int(seg), C.byref(h)))
-        super().__init__(ctx, h)
-
-    def _vol(self, t, what="half map"):
-        torch = _torch()
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise XhError(f"FSO: the {what} must be a contiguous float64 cuda tensor")
-        if tuple(t.shape) != self.shape:
-            raise XhError(f"FSO: the {what} has shape {tuple(t.shape)}, the handle {self.shape}")
-        return t
 
     def load(self, half1, half2, mask=None):
         """the transforms and the shell-sorted layout. Returns (sums [L, 3]: num, den1, den2 of the global FSC in fp64, the shells'
@@ -1107,7 +1085,7 @@ class FSO(_Handle):
             raise XhError(f"FSO: the directional FSCs have shape {fsc.shape}, expected {(len(dirs), self.L)}")
         Z, Y, X = self.shape
         half = torch.empty((Z, Y, X // 2 + 1), dtype=torch.float64, device="cuda")
-        out = torch.empty(self.shape, dtype=torch.float64, device="cuda") if full else None
+        out = self._new() if full else None
         check(lib().xh_fso_threedfsc(self.h, _np_ptr(dirs), len(dirs), float(cos_angle), float(aux), _np_ptr(fsc), _ptr(half), _ptr(out)))
         return half, out
 
@@ -1131,44 +1109,20 @@ class FSO(_Handle):
             out["threedfsc_half"], out["threedfsc_full"] = self.threedfsc(dirs, cos_angle, aux, fsc)
         return out
 
-    def set_timing(self, on):
-        check(lib().xh_fso_set_timing(self.h, int(bool(on))))
 
-    def stage_ms(self):
-        ms = np.zeros(len(self.STAGES))
-        check(lib().xh_fso_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms))
-
-
-class VolumeSubtraction(_Handle):
+class VolumeSubtraction(_StageTimes, _VolumeHandle):
     """The device side of xmipp_volume_subtraction: a volume is adjusted to a reference by projections onto convex sets, and the
     reference minus the adjusted volume is formed inside a mask. [Z, Y, X] float64 tensors on the device; spectra are [Z, Y, X // 2 + 1]."""
 
     _destroy = "xh_vsub_destroy"
+    _PREFIX = "vsub"
 
     STAGES = ("transforms", "spectrum", "real", "filter")
     ENERGIES = ("amplitude", "minmax", "mask", "phase", "nonneg", "scale", "filter")
 
     def __init__(self, ctx, shape):
-        self.ctx = ctx
-        self.shape = tuple(int(s) for s in shape)
-        assert len(self.shape) == 3
+        super().__init__(ctx, shape)
         self.half_shape = self.shape[:2] + (self.shape[2] // 2 + 1,)
-        h = C.c_void_p()
-        check(lib().xh_vsub_create(ctx.h, *self.shape, C.byref(h)))
-        super().__init__(ctx, h)
-
-    def _vol(self, t, what="volume", shape=None):
-        torch = _torch()
-        shape = shape or self.shape
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise XhError(f"VolumeSubtraction: the {what} must be a contiguous float64 cuda tensor")
-        if tuple(t.shape) != shape:
-            raise XhError(f"VolumeSubtraction: the {what} has shape {tuple(t.shape)}, the handle {shape}")
-        return t
-
-    def _new(self):
-        return _torch().empty(self.shape, dtype=_torch().float64, device="cuda")
 
     def set_reference(self, v1, mask=None, radavg=False):
         """the reference volume and the mask (None: ones; the product of both masks, as the reference uses a mask only when it has
@@ -1191,7 +1145,7 @@ class VolumeSubtraction(_Handle):
     def radial_mean(self, mag):
         """radialAverage of a magnitude [Z, Y, X // 2 + 1], as a numpy array [nbins]"""
         out = np.zeros(vsub_radial_bins(self.shape)[0])
-        check(lib().xh_vsub_radial_mean(self.h, _ptr(self._vol(mag, "magnitude", self.half_shape)), _np_ptr(out)))
+        check(lib().xh_vsub_radial_mean(self.h, _ptr(self._vol(mag, "magnitude", shape=self.half_shape)), _np_ptr(out)))
         return out
 
     def quotient(self, v):
@@ -1234,14 +1188,6 @@ class VolumeSubtraction(_Handle):
         check(lib().xh_vsub_subtract(self.h, _ptr(self._vol(v1_raw, "reference")), _ptr(self._vol(vadj, "adjusted volume")),
                                      _ptr(self._vol(masksub, "subtraction mask")), float(cut_freq), _ptr(v1f), _ptr(out)))
         return out, v1f
-
-    def set_timing(self, on):
-        check(lib().xh_vsub_set_timing(self.h, int(bool(on))))
-
-    def stage_ms(self):
-        ms = np.zeros(len(self.STAGES))
-        check(lib().xh_vsub_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms))
 
 
 def vsub_radial_bins(shape):
@@ -1654,7 +1600,7 @@ def sub_choose(sumY, sumY2, sumE0, sumE1, cells):
     return out[0], int(out[1]), out[2]
 
 
-class SubtractProjection(_Handle):
+class SubtractProjection(_StageTimes, _Handle):
     """Device side of xmipp_subtract_projection (reconstruction/subtract_projection.cpp). vol, roi (--mask_roi) and mask (--mask): host
     arrays [D, D, D]; params: sampling, max_resolution, padding, cirmaskrad, subtract, real_space, ignore_ctf, boost, non_negative."""
 
@@ -1713,15 +1659,8 @@ class SubtractProjection(_Handle):
         names = [f[0] for f in SubResult._fields_ if f[0] != "pad_"]
         return out, [{k: getattr(r, k) for k in names} for r in res[:self.n]]
 
+    _PREFIX = "sub"
     STAGES = ("projection", "ctf", "masks", "prepare_spectra", "sums_fit", "models", "output")
-
-    def set_timing(self, on=True):
-        check(lib().xh_sub_set_timing(self.h, int(bool(on))))
-
-    def stage_ms(self):
-        ms = np.empty(len(self.STAGES))
-        check(lib().xh_sub_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms.tolist()))
 
     def last(self, index):
         """The planes of particle `index` of the last chunk (host arrays), its sums [maxwi + 1, 4] and its betas."""
@@ -1942,7 +1881,7 @@ def faz_save_schedule(n, save_iter):
     return out
 
 
-class ForwardArtZernike3D(_Handle):
+class ForwardArtZernike3D(_StageTimes, _Handle):
     """Device side of xmipp_forward_art_zernike3d: ART reconstruction of the undeformed volume of side D from particles with a pose and
     Zernike3D coefficients. volume: float64 [D, D, D] (numpy; None: zeros); maskf / maskb: int32 [D, D, D] (numpy; None: the sphere of
     radius RDef); sigma: the Gaussian sigmas; sym: [nsym, 3, 3] right matrices of the symmetry group without the identity. Keyword
@@ -2035,17 +1974,8 @@ class ForwardArtZernike3D(_Handle):
         assert v.shape == (self.D,) * 3
         check(lib().xh_faz_set_volume(self.h, _np_ptr(v)))
 
-    STAGES = ("splat", "filter", "residual", "regulariser", "backward")
-
-    def set_timing(self, on=True):
-        """sweeps record events around their stages (the benchmark's switch)"""
-        check(lib().xh_faz_set_timing(self.h, int(bool(on))))
-
-    def stage_ms(self):
-        """milliseconds per stage of the last timed sweep, summed over its presentations"""
-        ms = np.zeros(len(self.STAGES))
-        check(lib().xh_faz_stage_ms(self.h, _np_ptr(ms)))
-        return dict(zip(self.STAGES, ms))
+    _PREFIX = "faz"
+    STAGES = ("splat", "filter", "residual", "regulariser", "backward")      # of the last timed sweep, summed over its presentations
 
 
 class ProjectionMatcher(_Handle):

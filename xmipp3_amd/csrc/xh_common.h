@@ -104,6 +104,30 @@ struct XhPinned {
 // frees b, then allocates `bytes` of page-locked memory
 int xh_pinned_alloc(xh_ctx *ctx, XhPinned &b, size_t bytes);
 
+// A HIP event with one owner, the third of the family: move-only, destroyed by its destructor, which like XhPinned's runs after the body of
+// the handle's destructor has synchronised the stream. A handle holds one, an array or a vector of them; a failed create leaks none.
+struct XhEvent {
+    hipEvent_t e = nullptr;
+    XhEvent() = default;
+    XhEvent(const XhEvent &) = delete;
+    XhEvent &operator=(const XhEvent &) = delete;
+    XhEvent(XhEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+    XhEvent &operator=(XhEvent &&o) noexcept
+    {
+        std::swap(e, o.e);      // o's destructor destroys what this held
+        return *this;
+    }
+    ~XhEvent() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+// destroys what ev held, then creates an event; timed false: hipEventDisableTiming, an event that only orders
+static inline int xh_event_create(XhEvent &ev, bool timed = true)
+{
+    ev = XhEvent();
+    XH_HIP(hipEventCreateWithFlags(&ev.e, timed ? hipEventDefault : hipEventDisableTiming));
+    return XH_OK;
+}
+
 // a grow-only device buffer that lives with a 2-D transform plan (frame-after-frame callers: dose filter, binning)
 int xh_fft2d_user_scratch(xh_fft2d *f, size_t bytes, void **p);
 int xh_fft2d_rows_of_real_pairs(xh_fft2d *f, const float *d_frame, const float *d_dark, const float *d_gain, int Y, float *d_work, int *n1, int *n2);

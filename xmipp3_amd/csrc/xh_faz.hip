@@ -321,25 +321,6 @@ k_faz_shift(const double *__restrict__ in, const double *__restrict__ rows, int 
 namespace {
 // the stages a timed sweep reports (xh_faz_stage_ms)
 enum { FAZ_T_SPLAT, FAZ_T_FILTER, FAZ_T_RESIDUAL, FAZ_T_REGULARISER, FAZ_T_BACK, FAZ_NT };
-
-// the events of one timed sweep, FAZ_NT + 1 per presentation: one owner, destroyed with it
-struct FazEvents {
-    std::vector<hipEvent_t> e;
-    FazEvents() = default;
-    FazEvents(const FazEvents &) = delete;
-    FazEvents &operator=(const FazEvents &) = delete;
-    ~FazEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-    int create(size_t n)
-    {
-        e.reserve(n);
-        for (size_t k = 0; k < n; ++k) {
-            hipEvent_t x;
-            XH_HIP(hipEventCreate(&x));
-            e.push_back(x);
-        }
-        return XH_OK;
-    }
-};
 }  // namespace
 
 struct xh_faz {
@@ -367,7 +348,7 @@ struct xh_faz {
 namespace {
 // steps 2-5 for presentation s of image img; partials: where the residual's block partials go; ev (nullable): the presentation's
 // FAZ_NT + 1 events, of which [0 .. FAZ_T_RESIDUAL + 1) are recorded here
-int faz_forward(xh_faz *h, int img, int s, double *partials, const hipEvent_t *ev = nullptr)
+int faz_forward(xh_faz *h, int img, int s, double *partials, const XhEvent *ev = nullptr)
 {
     xh_ctx *ctx = h->ctx;
     const int S = h->nsigma, D = h->D;
@@ -405,7 +386,7 @@ int faz_forward(xh_faz *h, int img, int s, double *partials, const hipEvent_t *e
 }
 
 // steps 6-7 for presentation s of image img; ev as in faz_forward, [FAZ_T_BACK, FAZ_NT] are recorded here
-int faz_backward(xh_faz *h, int img, int s, const hipEvent_t *ev = nullptr)
+int faz_backward(xh_faz *h, int img, int s, const XhEvent *ev = nullptr)
 {
     xh_ctx *ctx = h->ctx;
     const int D = h->D;
@@ -718,11 +699,11 @@ int xh_faz_sweep(xh_faz *h, int32_t first, int32_t count, double *h_errors)
     XH_HIP(hipSetDevice(ctx->device));
     double *partials = (double *)h->d_partials.p;
     const int per = h->per;
-    FazEvents events;
-    if (h->timing) XH_TRY(events.create((size_t)(FAZ_NT + 1) * count * per));
+    std::vector<XhEvent> events(h->timing ? (size_t)(FAZ_NT + 1) * count * per : 0);      // of this sweep, FAZ_NT + 1 per presentation
+    for (XhEvent &e : events) XH_TRY(xh_event_create(e));
     for (int k = 0; k < count; ++k)
         for (int s = 0; s < per; ++s) {
-            const hipEvent_t *ev = h->timing ? &events.e[(size_t)(FAZ_NT + 1) * ((size_t)k * per + s)] : nullptr;
+            const XhEvent *ev = h->timing ? &events[(size_t)(FAZ_NT + 1) * ((size_t)k * per + s)] : nullptr;
             XH_TRY(faz_forward(h, first + k, s, partials + (size_t)2 * h->tiles * ((size_t)k * per + s), ev));
             XH_TRY(faz_backward(h, first + k, s, ev));
         }
@@ -734,7 +715,7 @@ int xh_faz_sweep(xh_faz *h, int32_t first, int32_t count, double *h_errors)
         for (size_t p = 0; p < (size_t)count * per; ++p)
             for (int t = 0; t < FAZ_NT; ++t) {
                 float ms = 0.f;
-                XH_HIP(hipEventElapsedTime(&ms, events.e[(FAZ_NT + 1) * p + t], events.e[(FAZ_NT + 1) * p + t + 1]));
+                XH_HIP(hipEventElapsedTime(&ms, events[(FAZ_NT + 1) * p + t], events[(FAZ_NT + 1) * p + t + 1]));
                 h->stage_ms[t] += ms;
             }
     }

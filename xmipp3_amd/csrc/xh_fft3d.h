@@ -1,7 +1,8 @@
 // xh_fft3d.h -- fp64 3-D real transforms of any size (line FFTs of xh_plan.h) in FFTW layout: real [Z][Y][X] <-> half spectrum
 // [Z][Y][X/2+1]. Both directions are un-normalised, as FFTW's and cuFFT's plans are; a caller that wants the 1/N of an inverse passes it
 // as `scale`, which multiplies each result once, the same single rounding as a separate pass over the output.
-// Used by xh_fsc.hip (forward), xh_halves.hip and xh_vds.hip (both).
+// Used by xh_fsc.hip (forward), xh_vds.hip (both, a plan per call) and, through the handle part of xh_volume.h, by the whole-volume
+// programs listed there.
 #ifndef XH_FFT3D_H
 #define XH_FFT3D_H
 #include "xh_common.h"
@@ -61,22 +62,22 @@ k_fft3d_rows_c2r(const xh_cd *__restrict__ in, double *__restrict__ out, XhPlan<
     }
 }
 
-// y and z lines of a half spectrum, in place
+// y and z lines of nb half spectra that lie one after the other, in place
 template <bool INV>
-int fft3d_yz(xh_ctx *ctx, xh_cd *F, int Z, int Y, int xh, const XhPlan<double> &py, const XhPlan<double> &pz)
+int fft3d_yz(xh_ctx *ctx, xh_cd *F, int Z, int Y, int xh, const XhPlan<double> &py, const XhPlan<double> &pz, int nb = 1)
 {
-    if (Y > 1) {   // y lines: (k,j) -> offset k*Y*xh + j, element stride xh
+    if (Y > 1) {   // y lines: (b,k,j) -> offset (b*Z + k)*Y*xh + j, element stride xh
         const int lpb = xh_plan_lpb(py, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << py.logM, nlines = (size_t)Z * xh;
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << py.logM, nlines = (size_t)nb * Z * xh;
         hipLaunchKernelGGL((xh_k_fft_lines<double, INV>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, py,
                            nlines, (size_t)xh, (size_t)Y * xh, (size_t)1, (size_t)xh, lpb);
         XH_LAUNCH_CHECK();
     }
-    if (Z > 1) {   // z lines: (i,j) -> offset i*xh + j, element stride Y*xh
+    if (Z > 1) {   // z lines: (b,i,j) -> offset b*Z*Y*xh + i*xh + j, element stride Y*xh
         const int lpb = xh_plan_lpb(pz, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << pz.logM, nlines = (size_t)Y * xh;
+        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << pz.logM, nlines = (size_t)nb * Y * xh;
         hipLaunchKernelGGL((xh_k_fft_lines<double, INV>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, ctx->stream, F, pz,
-                           nlines, nlines, (size_t)0, (size_t)1, (size_t)Y * xh, lpb);
+                           nlines, (size_t)Y * xh, (size_t)Z * Y * xh, (size_t)1, (size_t)Y * xh, lpb);
         XH_LAUNCH_CHECK();
     }
     return XH_OK;

@@ -34,7 +34,7 @@
 // Deviation: the sums are fp64 where the reference's float den1 den2 (:468) can overflow on un-normalised spectra.
 // Refused: a side below 8 or above 1024; an odd X beside an even Y or Z (a coefficient with f = 0.5 exactly has shell round(X / 2) = X / 2 + 1,
 // one past the reference's arrays); the 3DFSC of a box that is not cubic (createFullFourier passes (X, Y, Z) to a (Z, Y, X) resize).
-#include "xh_fft3d.h"
+#include "xh_volume.h"
 #include "xh_reduce.h"
 #include <algorithm>
 #include <array>
@@ -45,9 +45,6 @@
 
 namespace {
 
-#define FSO_LOOP(n, N) for (size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x; n < (N); n += (size_t)gridDim.x * blockDim.x)
-
-struct FsoDims { int Z, Y, X, xh; };
 struct FsoSeg { int start, len; };
 struct FsoCoef { float x, y, z, r, a, b; };   // a staged coefficient of the cone kernel
 
@@ -61,11 +58,10 @@ enum { FSO_T_TRANSFORMS = 0, FSO_T_LAYOUT, FSO_T_CONES, FSO_T_SEGREDUCE, FSO_T_3
 __device__ __forceinline__ double fso_axis(int idx, int size) { return idx == 0 ? DBL_MIN : d_digfreq(idx, size); }
 
 // raster element e of the half spectrum: is it kept (:173-193, :284), and its shell (:288), axis frequencies and 1 / f (:179)
-__device__ __forceinline__ bool fso_elem(size_t e, FsoDims d, int &shell, double &uz, double &uy, double &ux, double &iun)
+__device__ __forceinline__ bool fso_elem(size_t e, XhDims d, int &shell, double &uz, double &uy, double &ux, double &iun)
 {
-    const int j = (int)(e % d.xh);
-    const size_t r = e / d.xh;
-    const int i = (int)(r % d.Y), k = (int)(r / d.Y);
+    int k, i, j;
+    xh_kij(e, d, k, i, j);
     uz = fso_axis(k, d.Z); uy = fso_axis(i, d.Y); ux = fso_axis(j, d.X);
     const double uz2 = uz * uz;
     const double uz2y2 = uz2 + uy * uy;
@@ -82,14 +78,14 @@ __device__ __forceinline__ bool fso_elem(size_t e, FsoDims d, int &shell, double
 // prepareData :1013-1024
 __global__ void __launch_bounds__(256) k_fso_mask(const double *__restrict__ v, const double *__restrict__ m, double *__restrict__ out, size_t N)
 {
-    FSO_LOOP(n, N) out[n] = v[n] * m[n];
+    XH_GRID_LOOP(n, N) out[n] = v[n] * m[n];
 }
 
 // one wave per chunk. FILL false: counts [L][nchunks] <- the kept elements of the chunk per shell. FILL true: counts holds the first slot
 // of (shell, chunk); the wave hands out the slots in raster order and writes the layout
 template <bool FILL>
 __global__ void __launch_bounds__(64)
-k_fso_layout(const xh_cd *__restrict__ F1, const xh_cd *__restrict__ F2, size_t NF, FsoDims d, int L, int nchunks, int *__restrict__ counts,
+k_fso_layout(const xh_cd *__restrict__ F1, const xh_cd *__restrict__ F2, size_t NF, XhDims d, int L, int nchunks, int *__restrict__ counts,
              float *__restrict__ fx, float *__restrict__ fy, float *__restrict__ fz, int *__restrict__ freqidx, int *__restrict__ arr2indx,
              float *__restrict__ rz, float *__restrict__ a1, float *__restrict__ a2)
 {
@@ -278,7 +274,7 @@ k_fso_threed(const float *__restrict__ fx, const float *__restrict__ fy, const f
 }
 
 // the two fixes of the empty lines (:1521-1539): column 0 takes column 1 on the rows i > Y / 2 of every plane, then on row 0 of every plane
-__global__ void __launch_bounds__(256) k_fso_line_fix(double *__restrict__ half, FsoDims d)
+__global__ void __launch_bounds__(256) k_fso_line_fix(double *__restrict__ half, XhDims d)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= d.Z * d.Y) return;
@@ -290,7 +286,7 @@ __global__ void __launch_bounds__(256) k_fso_line_fix(double *__restrict__ half,
 }
 
 // getCompleteFourier (:1277-1293) and CenterFFT(.., true) (:1302): the completed element (k, i, j) lands at ((k + Z / 2) % Z, ..)
-__global__ void __launch_bounds__(256) k_fso_full(const double *__restrict__ half, double *__restrict__ full, FsoDims d)
+__global__ void __launch_bounds__(256) k_fso_full(const double *__restrict__ half, double *__restrict__ full, XhDims d)
 {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)d.Z * d.Y * d.X) return;
@@ -361,49 +357,16 @@ double fso_round4(double v) { return std::round(v * 1e4) / 1e4; }
 
 }  // namespace
 
-struct xh_fso {
-    xh_ctx *ctx = nullptr;
-    FsoDims d = {};
-    size_t N = 0, NF = 0;
+struct xh_fso : XhVolume {
     int L = 0, seg = 0, nchunks = 0, ncomps = 0, nseg = 0;
-    XhFft3d fft;
     XhBuf F1, F2, work, counts, total, cumpos, sums, fx, fy, fz, freqidx, arr2indx, rz, a1, a2, segs, segfirst, dirs, lane_dir, part, pcount, dsums, dcounts, fsc;
     std::vector<int> hcumpos;
-    hipEvent_t ev[2] = {};
-    bool timing = false, loaded = false;
-    double ms[FSO_NT] = {};
-    ~xh_fso()
-    {
-        if (ctx) {
-            (void)hipSetDevice(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    XhLapTimer<FSO_NT> tm;
+    bool loaded = false;
+    ~xh_fso() { finish(); }
 };
 
 namespace {
-
-float *fp(XhBuf &b) { return (float *)b.p; }
-int *ip(XhBuf &b) { return (int *)b.p; }
-
-// timing: the time since the last lap goes to `stage` (one wait per lap: the benchmark's switch)
-int fso_lap_start(xh_fso *h)
-{
-    if (h->timing) XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
-int fso_lap(xh_fso *h, int stage)
-{
-    if (!h->timing) return XH_OK;
-    XH_HIP(hipEventRecord(h->ev[1], h->ctx->stream));
-    XH_HIP(hipEventSynchronize(h->ev[1]));
-    float ms = 0;
-    XH_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms[stage] += ms;
-    XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
 
 int fso_check_cone(const char *who, const xh_fso *h, const float *h_dirs, int ndir, float cosAngle, float aux)
 {
@@ -574,13 +537,8 @@ int xh_fso_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t seg, xh_
     XH_CHECK(!((X & 1) && (!(Y & 1) || !(Z & 1))), XH_ERR_UNSUPPORTED,
              "xh_fso_create: an odd X = %d beside an even Y or Z: a coefficient at f = 0.5 has shell X / 2 + 1, one past the shells", X);
     XH_CHECK(seg <= FSO_SEG_MAX, XH_ERR_ARG, "xh_fso_create: a segment of %d coefficients (at most %d; 0: the default)", seg, FSO_SEG_MAX);
-    XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_fso> h(new xh_fso);
-    h->ctx = ctx;
-    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
-    h->d = FsoDims{Z, Y, X, X / 2 + 1};
-    h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->d.xh;
+    XH_TRY(h->init(ctx, Z, Y, X));
     h->L = X / 2 + 1;
     h->seg = seg > 0 ? seg : FSO_SEG_DEFAULT;
     h->nchunks = (int)((h->NF + FSO_CHUNK - 1) / FSO_CHUNK);
@@ -591,9 +549,7 @@ int xh_fso_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t seg, xh_
     XH_TRY(xh_buf_alloc(ctx, h->cumpos, sizeof(int) * (h->L + 1)));
     XH_TRY(xh_buf_alloc(ctx, h->segfirst, sizeof(int) * (h->L + 1)));
     XH_TRY(xh_buf_alloc(ctx, h->sums, sizeof(double) * 3 * h->L));
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &x : h->ev) if (e == hipSuccess) e = hipEventCreate(&x);
-    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_fso_create: %s", hipGetErrorString(e));
+    XH_TRY(h->tm.create(ctx));
     *out = h.release();
     return XH_OK;
 }
@@ -609,20 +565,20 @@ int xh_fso_load(xh_fso *h, const double *d_half1, const double *d_half2, const d
     XH_CHECK(h && d_half1 && d_half2 && h_sums, XH_ERR_ARG, "xh_fso_load: null argument");
     XH_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
-    const FsoDims d = h->d;
+    const XhDims d = h->d;
     const int L = h->L, nchunks = h->nchunks;
     h->loaded = false;
-    XH_TRY(fso_lap_start(h));
+    XH_TRY(h->tm.start());
     // prepareData :1013-1024 and run :1324-1325; xmippCore's forward transform carries the 1 / N
     const double *in[2] = {d_half1, d_half2};
     xh_cd *F[2] = {(xh_cd *)h->F1.p, (xh_cd *)h->F2.p};
     if (d_mask) XH_TRY(xh_buf_reserve(h->ctx, h->work, sizeof(double) * h->N));
-    const unsigned gridN = (unsigned)std::max<size_t>(1, std::min<size_t>((h->N + 255) / 256, (size_t)h->ctx->num_cus * 4));
+    const unsigned gridN = xh_grid256(h->N, h->ctx->num_cus, 4);
     for (int m = 0; m < 2; ++m) {
         if (d_mask) XH_LAUNCH256(h->ctx, k_fso_mask, gridN, in[m], d_mask, (double *)h->work.p, h->N);
         XH_TRY(h->fft.r2c(d_mask ? (const double *)h->work.p : in[m], F[m], 1.0 / (double)h->N));
     }
-    XH_TRY(fso_lap(h, FSO_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(FSO_T_TRANSFORMS));
     // the layout: count, scan, cumpos on the host (it cuts the segments from it as well), fill
     const size_t lds = sizeof(int) * L;
     hipLaunchKernelGGL(k_fso_layout<false>, dim3(nchunks), dim3(64), lds, st, (const xh_cd *)F[0], (const xh_cd *)F[1], h->NF, d, L, nchunks, ip(h->counts), nullptr, nullptr,
@@ -658,7 +614,7 @@ int xh_fso_load(xh_fso *h, const double *d_half1, const double *d_half2, const d
     XH_LAUNCH256(h->ctx, k_fso_shell_sums, L, (const xh_cd *)F[0], (const xh_cd *)F[1], (const int *)h->arr2indx.p, (const int *)h->cumpos.p, (double *)h->sums.p);
     XH_HIP(hipMemcpyAsync(h_sums, h->sums.p, sizeof(double) * 3 * L, hipMemcpyDeviceToHost, st));
     XH_HIP(hipStreamSynchronize(st));
-    XH_TRY(fso_lap(h, FSO_T_LAYOUT));
+    XH_TRY(h->tm.lap(FSO_T_LAYOUT));
     if (h_shell_count)
         for (int s = 0; s < L; ++s) h_shell_count[s] = total[s];
     if (ncomps) *ncomps = h->ncomps;
@@ -717,7 +673,7 @@ int xh_fso_directional(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAn
         });
     XH_TRY(xh_buf_reserve(h->ctx, h->lane_dir, sizeof(int) * ndir));
     XH_HIP(hipMemcpyAsync(h->lane_dir.p, lane_dir.data(), sizeof(int) * ndir, hipMemcpyHostToDevice, st));
-    XH_TRY(fso_lap_start(h));
+    XH_TRY(h->tm.start());
     if (nseg > 0) {
         const int threads = 64 * ((ndir + 63) / 64);
         hipLaunchKernelGGL(k_fso_cones, dim3(nseg), dim3(threads), sizeof(FsoCoef) * h->seg, st, (const float *)h->fx.p, (const float *)h->fy.p, (const float *)h->fz.p,
@@ -725,14 +681,14 @@ int xh_fso_directional(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAn
                            cosAngle, aux, (double *)h->part.p, ip(h->pcount));
         XH_LAUNCH_CHECK();
     }
-    XH_TRY(fso_lap(h, FSO_T_CONES));
+    XH_TRY(h->tm.lap(FSO_T_CONES));
     XH_LAUNCH256(h->ctx, k_fso_seg_reduce, (unsigned)((cells + 255) / 256), (const double *)h->part.p, (const int *)h->pcount.p, (const int *)h->segfirst.p, L, ndir,
                  (double *)h->dsums.p, (long long *)h->dcounts.p);
     std::vector<long long> counts(cells);
     XH_HIP(hipMemcpyAsync(h_sums, h->dsums.p, sizeof(double) * 3 * cells, hipMemcpyDeviceToHost, st));
     XH_HIP(hipMemcpyAsync(counts.data(), h->dcounts.p, sizeof(long long) * cells, hipMemcpyDeviceToHost, st));
     XH_HIP(hipStreamSynchronize(st));
-    XH_TRY(fso_lap(h, FSO_T_SEGREDUCE));
+    XH_TRY(h->tm.lap(FSO_T_SEGREDUCE));
     for (int dir = 0; dir < ndir; ++dir) {
         int64_t c = 0;
         for (int s = 0; s < L; ++s) c += counts[(size_t)dir * L + s];
@@ -745,7 +701,7 @@ int xh_fso_threedfsc(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngl
 {
     XH_TRY(fso_check_cone("xh_fso_threedfsc", h, h_dirs, ndir, cosAngle, aux));
     XH_CHECK(h_fsc && d_half, XH_ERR_ARG, "xh_fso_threedfsc: null argument");
-    const FsoDims d = h->d;
+    const XhDims d = h->d;
     XH_CHECK(d.Z == d.Y && d.Y == d.X, XH_ERR_UNSUPPORTED, "xh_fso_threedfsc: the 3DFSC needs a cubic box, this one is %d x %d x %d", d.Z, d.Y, d.X);
     XH_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
@@ -754,7 +710,7 @@ int xh_fso_threedfsc(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngl
     XH_TRY(xh_buf_reserve(h->ctx, h->fsc, sizeof(float) * (size_t)ndir * L));
     XH_HIP(hipMemcpyAsync(h->dirs.p, h_dirs, sizeof(float) * 3 * ndir, hipMemcpyHostToDevice, st));
     XH_HIP(hipMemcpyAsync(h->fsc.p, h_fsc, sizeof(float) * (size_t)ndir * L, hipMemcpyHostToDevice, st));
-    XH_TRY(fso_lap_start(h));
+    XH_TRY(h->tm.start());
     XH_HIP(hipMemsetAsync(d_half, 0, sizeof(double) * h->NF, st));
     hipLaunchKernelGGL(k_fso_threed, dim3((unsigned)((h->ncomps + 255) / 256)), dim3(256), sizeof(float) * 3 * ndir, st, (const float *)h->fx.p, (const float *)h->fy.p,
                        (const float *)h->fz.p, (const int *)h->freqidx.p, (const int *)h->arr2indx.p, h->ncomps, (const float *)h->dirs.p, ndir, (const float *)h->fsc.p, L,
@@ -763,22 +719,21 @@ int xh_fso_threedfsc(xh_fso *h, const float *h_dirs, int32_t ndir, float cosAngl
     XH_LAUNCH256(h->ctx, k_fso_line_fix, (unsigned)((d.Z * d.Y + 255) / 256), d_half, d);
     if (d_full) XH_LAUNCH256(h->ctx, k_fso_full, (unsigned)((h->N + 255) / 256), (const double *)d_half, d_full, d);
     XH_HIP(hipStreamSynchronize(st));     // the host arrays were copied from
-    XH_TRY(fso_lap(h, FSO_T_3DFSC));
+    XH_TRY(h->tm.lap(FSO_T_3DFSC));
     return XH_OK;
 }
 
 int xh_fso_set_timing(xh_fso *h, int32_t on)
 {
     XH_CHECK(h, XH_ERR_ARG, "xh_fso_set_timing: null handle");
-    h->timing = on != 0;
-    for (double &t : h->ms) t = 0;
+    h->tm.set(on != 0);
     return XH_OK;
 }
 
 int xh_fso_stage_ms(const xh_fso *h, double *h_ms)
 {
     XH_CHECK(h && h_ms, XH_ERR_ARG, "xh_fso_stage_ms: null argument");
-    for (int i = 0; i < FSO_NT; ++i) h_ms[i] = h->ms[i];
+    h->tm.read(h_ms);
     return XH_OK;
 }
 

@@ -27,7 +27,7 @@
 //  - An empty mask and a filter bank whose step (1 - overlap) is not positive are refused (the reference reads out of bounds / loops
 //    forever).
 // The reference's power(double, int) truncates weightPower to an integer before pow; so does this file.
-#include "xh_fft3d.h"
+#include "xh_volume.h"
 #include "xh_reduce.h"
 #include <cmath>
 
@@ -92,7 +92,6 @@ __device__ __forceinline__ void hv_load_tabs(double *s, const CdfDev *cd, int nt
     __syncthreads();
 }
 
-#define HV_LOOP(n, N) for (size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x; n < (N); n += (size_t)gridDim.x * blockDim.x)
 
 // ---------------------------------------------------------------- CDF by radix select
 __global__ void __launch_bounds__(256) k_cdf_init(CdfDev *cd, unsigned long long N)
@@ -118,7 +117,7 @@ k_cdf_first(const double *__restrict__ a, const double *__restrict__ b, const in
     __shared__ unsigned int h[1 << HV_W0];
     for (int i = threadIdx.x; i < (1 << HV_W0); i += blockDim.x) h[i] = 0;
     __syncthreads();
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         double v;
         if (MODE == 0) v = a[n] * a[n];
         else { const double d = a[n] - b[n]; v = mult * d * d; }
@@ -143,7 +142,7 @@ k_cdf_pass(const unsigned long long *__restrict__ keys, size_t N, int b, int w, 
     __syncthreads();
     const unsigned long long lo = pre[0], hi = pre[P - 1];
     const unsigned dmask = (1u << w) - 1;
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const unsigned long long k = keys[n], top = k >> (64 - b);
         if (top < lo || top > hi) continue;
         int l = 0, r = P - 1;
@@ -229,7 +228,7 @@ __global__ void __launch_bounds__(256) k_cdf_finish(CdfDev *cd, int slot)
 __global__ void __launch_bounds__(256)
 k_avg_positivity(const double *__restrict__ V1, const double *__restrict__ V2, const int *__restrict__ mask, double *__restrict__ S, size_t N)
 {
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double val = 0.5 * (V1[n] + V2[n]);
         S[n] = (val <= 0 || (mask && mask[n] == 0)) ? 0.0 : val;
     }
@@ -237,7 +236,7 @@ k_avg_positivity(const double *__restrict__ V1, const double *__restrict__ V2, c
 
 __global__ void __launch_bounds__(256) k_filter_s(xh_cd *__restrict__ F, int Z, int Y, int X, int xh)
 {
-    HV_LOOP(e, (size_t)Z * Y * xh) {
+    XH_GRID_LOOP(e, (size_t)Z * Y * xh) {
         if (hv_r2(e, Y, X, Z, xh) > 0.25) F[e] = xh_cd{0.0, 0.0};
     }
 }
@@ -247,7 +246,7 @@ __global__ void __launch_bounds__(256) k_mask_noise(double *__restrict__ V, cons
     __shared__ double s[HV_NSTEPS + 2 * HV_NR];
     hv_load_tabs(s, cd, 2);
     const double *tS = s + HV_NSTEPS, *tN = s + HV_NSTEPS + HV_NR;
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double v = V[n], e = v * v;
         double pN = hv_cdf_prob(e, tN, s);
         if (pN < 1) {
@@ -260,7 +259,7 @@ __global__ void __launch_bounds__(256) k_mask_noise(double *__restrict__ V, cons
 __global__ void __launch_bounds__(256)
 k_deconvolve(xh_cd *__restrict__ fVol, xh_cd *__restrict__ fV1, xh_cd *__restrict__ fV2, double K1, double K2, double lambda, int Z, int Y, int X, int xh)
 {
-    HV_LOOP(e, (size_t)Z * Y * xh) {
+    XH_GRID_LOOP(e, (size_t)Z * Y * xh) {
         const double R2n = hv_r2(e, Y, X, Z, xh);
         if (R2n <= 0.25) {
             double H1 = exp(K1 * R2n), H2 = exp(K2 * R2n);
@@ -276,7 +275,7 @@ k_deconvolve(xh_cd *__restrict__ fVol, xh_cd *__restrict__ fV1, xh_cd *__restric
 
 __global__ void __launch_bounds__(256) k_convolve(xh_cd *__restrict__ F, double K, int Z, int Y, int X, int xh)
 {
-    HV_LOOP(e, (size_t)Z * Y * xh) {
+    XH_GRID_LOOP(e, (size_t)Z * Y * xh) {
         const double R2n = hv_r2(e, Y, X, Z, xh);
         if (R2n <= 0.25) {
             const double g = exp(K * R2n);
@@ -288,7 +287,7 @@ __global__ void __launch_bounds__(256) k_convolve(xh_cd *__restrict__ F, double 
 __global__ void __launch_bounds__(256)
 k_band(const xh_cd *__restrict__ fV, xh_cd *__restrict__ out, double w2, double w2Step, int Z, int Y, int X, int xh)
 {
-    HV_LOOP(e, (size_t)Z * Y * xh) {
+    XH_GRID_LOOP(e, (size_t)Z * Y * xh) {
         const double R2n = hv_r2(e, Y, X, Z, xh);
         out[e] = (R2n >= w2 && R2n < w2Step) ? fV[e] : xh_cd{0.0, 0.0};
     }
@@ -302,7 +301,7 @@ k_weights(const double *__restrict__ Vf1, const double *__restrict__ Vf2, double
     hv_load_tabs(s, cd, 1);
     const double *t = s + HV_NSTEPS;
     const double ipow = (double)(int)weightPower;     // power(double, int)
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double f1 = Vf1[n], e1 = f1 * f1, w1 = hv_cdf_prob(e1, t, s);
         const double f2 = Vf2[n], e2 = f2 * f2, w2 = hv_cdf_prob(e2, t, s);
         double weight = 0;
@@ -322,13 +321,13 @@ k_weights(const double *__restrict__ Vf1, const double *__restrict__ Vf2, double
 
 __global__ void __launch_bounds__(256) k_scale3(double *__restrict__ a, double *__restrict__ b, double *__restrict__ c, double f, size_t N)
 {
-    HV_LOOP(n, N) { a[n] = a[n] * f; b[n] = b[n] * f; c[n] = c[n] * f; }
+    XH_GRID_LOOP(n, N) { a[n] = a[n] * f; b[n] = b[n] * f; c[n] = c[n] * f; }
 }
 
 __global__ void __launch_bounds__(256)
 k_difference(double *__restrict__ V1, double *__restrict__ V2, const double *__restrict__ S, const double *__restrict__ D, double k, size_t N)
 {
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double Nn = D[n];
         const double w = (isinf(k) && Nn == 0) ? 0.0 : exp(k * Nn * Nn);
         const double s = S[n];
@@ -344,7 +343,7 @@ k_sigma_cost(const xh_cd *__restrict__ fVol, const xh_cd *__restrict__ fV1, cons
              int Z, int Y, int X, int xh, double *__restrict__ partials)
 {
     double acc[1] = {0.0};
-    HV_LOOP(e, (size_t)Z * Y * xh) {
+    XH_GRID_LOOP(e, (size_t)Z * Y * xh) {
         const double R2n = hv_r2(e, Y, X, Z, xh);
         if (R2n <= 0.25) {
             const double H1 = exp(K1 * R2n), H2 = exp(K2 * R2n);
@@ -363,7 +362,7 @@ k_diff_avg(const double *__restrict__ V1, const double *__restrict__ V2, double 
            size_t N, double *__restrict__ partials)
 {
     double acc[2] = {0.0, 0.0};
-    HV_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double a = V1[n], b = V2[n], d = a - b;
         D[n] = d;
         S[n] = (a + b) * 0.5;
@@ -375,7 +374,7 @@ k_diff_avg(const double *__restrict__ V1, const double *__restrict__ V2, double 
 __global__ void __launch_bounds__(256) k_mask_count(const int *__restrict__ mask, size_t N, double *__restrict__ partials)
 {
     double acc[1] = {0.0};
-    HV_LOOP(n, N) acc[0] += mask[n] != 0 ? 1.0 : 0.0;
+    XH_GRID_LOOP(n, N) acc[0] += mask[n] != 0 ? 1.0 : 0.0;
     xh_block_partials(acc, partials);
 }
 
@@ -384,31 +383,22 @@ __global__ void __launch_bounds__(256) k_mask_count(const int *__restrict__ mask
 // ---------------------------------------------------------------- the handle
 enum { HV_OUT_RESTORED1 = 0, HV_OUT_RESTORED2, HV_OUT_FILTERBANK, HV_OUT_DECONVOLVED, HV_OUT_CONVOLVED, HV_OUT_AVGDIFF, HV_NOUT };
 
-struct xh_halves {
-    xh_ctx *ctx = nullptr;
-    size_t N = 0, NF = 0;
+struct xh_halves : XhVolume {
     unsigned grid = 0;                       // per-voxel kernels and reductions
     unsigned gridPass = 0;                   // CDF histogram passes (53 KB of LDS each)
-    XhFft3d fft;
     XhBuf V1, V2, S, B2, B3, keys, C1, C2, C3, cdf, partials, result;
     XhBuf out[4];                            // filter bank, deconvolved, convolved, average difference
     bool loaded = false, has[HV_NOUT] = {};
     bool timing = false;
-    hipEvent_t ev[4] = {};
+    XhEvent ev[4];
     double band_ms[3] = {0, 0, 0};
     int bands = 0;
     int costRc = XH_OK;
-    ~xh_halves()
-    {
-        if (ctx) (void)hipSetDevice(ctx->device);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    ~xh_halves() { finish(); }
 };
 
 namespace {
 
-double *dp(XhBuf &b) { return (double *)b.p; }
-xh_cd *cp(XhBuf &b) { return (xh_cd *)b.p; }
 CdfDev *cdfp(xh_halves *h) { return (CdfDev *)h->cdf.p; }
 
 // sum of NC partial rows -> NC doubles on the host (synchronous)
@@ -471,14 +461,10 @@ int xh_halves_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_halves **o
     XH_CHECK(ctx && out, XH_ERR_ARG, "xh_halves_create: null argument");
     XH_CHECK(Z >= 1 && Y >= 1 && X >= 2, XH_ERR_ARG, "xh_halves_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_halves_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
-    XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_halves> h(new xh_halves);
-    h->ctx = ctx;
-    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
-    h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->fft.xh;
-    h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->NF + 255) / 256, (size_t)ctx->num_cus * 4));
-    h->gridPass = (unsigned)std::max<size_t>(1, std::min<size_t>((h->N + 255) / 256, (size_t)ctx->num_cus * 2));
+    XH_TRY(h->init(ctx, Z, Y, X));
+    h->grid = xh_grid256(h->NF, ctx->num_cus, 4);
+    h->gridPass = xh_grid256(h->N, ctx->num_cus, 2);
     const size_t vb = sizeof(double) * h->N, fb = sizeof(xh_cd) * h->NF;
     for (XhBuf *b : {&h->V1, &h->V2, &h->S, &h->B2, &h->B3, &h->keys, &h->out[0], &h->out[1], &h->out[2], &h->out[3]}) XH_TRY(xh_buf_alloc(ctx, *b, vb));
     for (XhBuf *b : {&h->C1, &h->C2, &h->C3}) XH_TRY(xh_buf_alloc(ctx, *b, fb));
@@ -490,8 +476,8 @@ int xh_halves_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_halves **o
     XH_CHECK(prob.size() == HV_NSTEPS, XH_ERR_STATE, "xh_halves_create: %zu CDF steps", prob.size());
     hipError_t e = hipMemset(h->cdf.p, 0, sizeof(CdfDev));
     if (e == hipSuccess) e = hipMemcpy((char *)h->cdf.p + offsetof(CdfDev, prob), prob.data(), sizeof(double) * HV_NSTEPS, hipMemcpyHostToDevice);
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
     XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_halves_create: %s", hipGetErrorString(e));
+    for (XhEvent &x : h->ev) XH_TRY(xh_event_create(x));
     *out = h.release();
     return XH_OK;
 }

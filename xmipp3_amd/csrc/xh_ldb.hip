@@ -39,16 +39,12 @@
 //  - a sampling rate with 2 sampling - 0.2 <= 0 (wL of the first band);
 //  - a resolution map with no voxel >= 2 sampling (norm = 0, porc = 0 / 0), or with a maximum that is not finite;
 //  - Niter < 1 (the sharpened map is never assigned).
-#include "xh_fft3d.h"
+#include "xh_volume.h"
 #include "xh_reduce.h"
 #include <cmath>
 #include <cstring>
 
 namespace {
-
-#define LDB_LOOP(n, N) for (size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x; n < (N); n += (size_t)gridDim.x * blockDim.x)
-
-struct LdbDims { int Z, Y, X, xh; };
 
 // one resolution band: the filter's constants and the table of the lines that can be non-zero
 struct LdbBand {
@@ -62,7 +58,7 @@ constexpr double LDB_STEP = 0.2;
 enum { LDB_T_FORWARD = 0, LDB_T_SPLIT, LDB_T_YZ, LDB_T_ROWS, LDB_T_FINISH, LDB_NT };
 
 // produceSideInfo :81-102: sqrt((uz^2 + uy^2) + ux^2), 1e-38 at the origin
-__device__ __forceinline__ double ldb_un(int k, int i, int j, LdbDims d)
+__device__ __forceinline__ double ldb_un(int k, int i, int j, XhDims d)
 {
     if (k == 0 && i == 0 && j == 0) return 1e-38;
     const double uz = d_digfreq(k, d.Z), uy = d_digfreq(i, d.Y), ux = d_digfreq(j, d.X);
@@ -83,7 +79,7 @@ k_ldb_side(double *__restrict__ res, const double *__restrict__ vol, size_t N, d
 {
     double acc[3] = {0, 0, 0};
     unsigned long long mx = 0;
-    LDB_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         double r = res[n];
         if (r > 1e-38) mx = max(mx, (unsigned long long)__double_as_longlong(r));
         if (r < twoS && r > 0) {
@@ -103,7 +99,7 @@ k_ldb_side(double *__restrict__ res, const double *__restrict__ vol, size_t N, d
 __global__ void __launch_bounds__(256)
 k_ldb_lastweight(const double *__restrict__ res, double *__restrict__ lw, size_t N, const LdbBand *__restrict__ bands, int nbands, double twoS, double K)
 {
-    LDB_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double r = res[n];
         double s = 0;
         if (!(r < twoS))
@@ -115,12 +111,11 @@ k_ldb_lastweight(const double *__restrict__ res, double *__restrict__ lw, size_t
 // ---------------------------------------------------------------- one batch of bands
 // bandPassFilterFunction :189-206 for the bands b0 .. b0 + nb - 1: F -> FB[s], columns j < jcount only
 __global__ void __launch_bounds__(256)
-k_ldb_split(const xh_cd *__restrict__ F, xh_cd *__restrict__ FB, size_t NF, LdbDims d, const LdbBand *__restrict__ bands, int b0, int nb)
+k_ldb_split(const xh_cd *__restrict__ F, xh_cd *__restrict__ FB, size_t NF, XhDims d, const LdbBand *__restrict__ bands, int b0, int nb)
 {
-    LDB_LOOP(e, NF) {
-        const int j = (int)(e % d.xh);
-        const size_t r = e / d.xh;
-        const int i = (int)(r % d.Y), k = (int)(r / d.Y);
+    XH_GRID_LOOP(e, NF) {
+        int k, i, j;
+        xh_kij(e, d, k, i, j);
         const double un = ldb_un(k, i, j, d);
         xh_cd f = xh_cd{0.0, 0.0};
         bool have = false;
@@ -142,7 +137,7 @@ k_ldb_split(const xh_cd *__restrict__ F, xh_cd *__restrict__ FB, size_t NF, LdbD
 // Line l of band s: PASS 0 (a, j) with a < kcount standing for k = a (a <= kmax) or Z - (kcount - a); PASS 1 (i, j); j < jcount
 template <int PASS>
 __global__ void __launch_bounds__(256)
-k_ldb_lines(xh_cd *__restrict__ FB, XhPlan<double> plan, const LdbBand *__restrict__ bands, int b0, int nb, LdbDims d, size_t NF, int lpb)
+k_ldb_lines(xh_cd *__restrict__ FB, XhPlan<double> plan, const LdbBand *__restrict__ bands, int b0, int nb, XhDims d, size_t NF, int lpb)
 {
     extern __shared__ __align__(16) unsigned char ldb_lines_smem[];
     __shared__ long long base[LDB_MAX_LPB];
@@ -260,7 +255,7 @@ __device__ __forceinline__ double ldb_div(double v, double lw) { return lw > 0 ?
 
 __global__ void __launch_bounds__(256) k_ldb_divide(const double *__restrict__ acc, const double *__restrict__ lw, double *__restrict__ out, size_t N)
 {
-    LDB_LOOP(n, N) out[n] = ldb_div(acc[n], lw[n]);
+    XH_GRID_LOOP(n, N) out[n] = ldb_div(acc[n], lw[n]);
 }
 
 // the first operator of an iteration (:320-341): op = acc / lastweight, filt = Vorig - op, partial sums of op^2 and Vorig^2
@@ -269,7 +264,7 @@ k_ldb_first(const double *__restrict__ acc, const double *__restrict__ lw, const
             double *__restrict__ partials)
 {
     double s[2] = {0, 0};
-    LDB_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double op = ldb_div(acc[n], lw[n]), v = vorig[n];
         filt[n] = v - op;
         s[0] += op * op;
@@ -282,7 +277,7 @@ k_ldb_first(const double *__restrict__ acc, const double *__restrict__ lw, const
 __global__ void __launch_bounds__(256)
 k_ldb_second(const double *__restrict__ acc, const double *__restrict__ lw, const double *vk, double *sharp, size_t N, double lambda, double floorv)
 {
-    LDB_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double f = ldb_div(acc[n], lw[n]);
         const double t = lambda * f;
         double v = vk[n] + t;
@@ -340,71 +335,39 @@ void ldb_band_table(LdbBand &b, int Z, int X, int xh)
 
 }  // namespace
 
-struct xh_ldb {
-    xh_ctx *ctx = nullptr;
-    LdbDims d = {};
-    size_t N = 0, NF = 0;
+struct xh_ldb : XhVolume {
     unsigned grid = 0;
     int nbuf = 2, rpb = 1, ppc = 1;
-    XhFft3d fft;
     XhBuf F, FB, Vorig, res, lw, acc, filt, sharp, bands, partials, result, maxbits;
     XhPinned host;
-    hipEvent_t ev[2] = {}, evRec = nullptr;
-    bool timing = false, loaded = false;
-    double ms[LDB_NT] = {};
+    XhLapTimer<LDB_NT> tm;
+    XhEvent evRec;
+    bool loaded = false;
     std::vector<LdbBand> list;
     double sampling = 1, K = 0.025, maxRes = 0, desvOutside = 0;
     int64_t noutside = 0;
-    ~xh_ldb()
-    {
-        if (ctx) {
-            (void)hipSetDevice(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (evRec) (void)hipEventDestroy(evRec);
-    }
+    ~xh_ldb() { finish(); }
 };
 
 namespace {
 
-double *dp(XhBuf &b) { return (double *)b.p; }
-xh_cd *cp(XhBuf &b) { return (xh_cd *)b.p; }
 const LdbBand *bp(xh_ldb *h) { return (const LdbBand *)h->bands.p; }
-
-// timing: the time since the last lap goes to `stage` (one wait per lap: the benchmark's switch)
-int ldb_lap_start(xh_ldb *h)
-{
-    if (h->timing) XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
-int ldb_lap(xh_ldb *h, int stage)
-{
-    if (!h->timing) return XH_OK;
-    XH_HIP(hipEventRecord(h->ev[1], h->ctx->stream));
-    XH_HIP(hipEventSynchronize(h->ev[1]));
-    float ms = 0;
-    XH_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms[stage] += ms;
-    XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
 
 // L without its division: the weighted band sum of d_in into h->acc
 int ldb_filter(xh_ldb *h, const double *d_in)
 {
     hipStream_t st = h->ctx->stream;
-    const LdbDims d = h->d;
+    const XhDims d = h->d;
     const int nbands = (int)h->list.size();
-    XH_TRY(ldb_lap_start(h));
+    XH_TRY(h->tm.start());
     XH_TRY(h->fft.r2c(d_in, cp(h->F), 1.0 / (double)h->N));
-    XH_TRY(ldb_lap(h, LDB_T_FORWARD));
+    XH_TRY(h->tm.lap(LDB_T_FORWARD));
     const XhPlan<double> &py = h->fft.py.plan, &pz = h->fft.pz.plan, &px = h->fft.px.plan;
     const int lpy = xh_plan_lpb(py, 64 * 1024, LDB_MAX_LPB), lpz = xh_plan_lpb(pz, 64 * 1024, LDB_MAX_LPB);
     for (int b0 = 0; b0 < nbands; b0 += h->nbuf) {
         const int nb = std::min(h->nbuf, nbands - b0);
         XH_LAUNCH256(h->ctx, k_ldb_split, h->grid, (const xh_cd *)h->F.p, cp(h->FB), h->NF, d, bp(h), b0, nb);
-        XH_TRY(ldb_lap(h, LDB_T_SPLIT));
+        XH_TRY(h->tm.lap(LDB_T_SPLIT));
         size_t ny = 0, nz = 0;
         for (int b = b0; b < b0 + nb; ++b) {
             ny += (size_t)h->list[b].kcount * h->list[b].jcount;
@@ -416,13 +379,13 @@ int ldb_filter(xh_ldb *h, const double *d_in)
         hipLaunchKernelGGL(k_ldb_lines<1>, dim3((unsigned)((nz + lpz - 1) / lpz)), dim3(256), ((size_t)lpz * sizeof(xh_cd)) << pz.logM, st, cp(h->FB), pz, bp(h), b0, nb, d,
                            h->NF, lpz);
         XH_LAUNCH_CHECK();
-        XH_TRY(ldb_lap(h, LDB_T_YZ));
+        XH_TRY(h->tm.lap(LDB_T_YZ));
         const size_t nrows = (size_t)d.Z * d.Y;
         const size_t smem = ((size_t)h->rpb * h->ppc * sizeof(xh_cd)) << px.logM;
         hipLaunchKernelGGL(k_ldb_rows, dim3((unsigned)((nrows + h->rpb - 1) / h->rpb)), dim3(256), smem, st, (const xh_cd *)h->FB.p, (const double *)h->res.p, dp(h->acc),
                            bp(h), px, nrows, h->NF, d.X, d.xh, h->rpb, h->ppc, b0, nb, b0 == 0 ? 1 : 0, 2 * h->sampling, h->K);
         XH_LAUNCH_CHECK();
-        XH_TRY(ldb_lap(h, LDB_T_ROWS));
+        XH_TRY(h->tm.lap(LDB_T_ROWS));
     }
     return XH_OK;
 }
@@ -449,14 +412,9 @@ int xh_ldb_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t batch, x
     XH_CHECK(Z >= 2 && Y >= 2 && X >= 2, XH_ERR_ARG, "xh_ldb_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_ldb_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
     XH_CHECK(batch >= 1 && batch <= 64, XH_ERR_ARG, "xh_ldb_create: a batch of %d bands (1 .. 64)", batch);
-    XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_ldb> h(new xh_ldb);
-    h->ctx = ctx;
-    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
-    h->d = LdbDims{Z, Y, X, X / 2 + 1};
-    h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->d.xh;
-    h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->NF + 255) / 256, (size_t)ctx->num_cus * 4));
+    XH_TRY(h->init(ctx, Z, Y, X));
+    h->grid = xh_grid256(h->NF, ctx->num_cus, 4);
     h->nbuf = (batch + 1) & ~1;
     const size_t lineBytes = sizeof(xh_cd) << h->fft.px.plan.logM;
     XH_CHECK(lineBytes <= 64 * 1024, XH_ERR_UNSUPPORTED, "xh_ldb_create: a row of %d points does not fit the LDS of the row kernel", X);
@@ -471,10 +429,8 @@ int xh_ldb_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t batch, x
     XH_TRY(xh_buf_alloc(ctx, h->result, sizeof(double) * 4));
     XH_TRY(xh_buf_alloc(ctx, h->maxbits, sizeof(unsigned long long)));
     XH_TRY(xh_pinned_alloc(ctx, h->host, sizeof(double) * 8));
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &x : h->ev) if (e == hipSuccess) e = hipEventCreate(&x);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evRec, hipEventDisableTiming);
-    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_ldb_create: %s", hipGetErrorString(e));
+    XH_TRY(h->tm.create(ctx));
+    XH_TRY(xh_event_create(h->evRec, false));
     *out = h.release();
     return XH_OK;
 }
@@ -561,7 +517,7 @@ int xh_ldb_localfilter(xh_ldb *h, const double *d_in, double *d_out)
     XH_HIP(hipSetDevice(h->ctx->device));
     XH_TRY(ldb_filter(h, d_in));
     XH_LAUNCH256(h->ctx, k_ldb_divide, h->grid, (const double *)h->acc.p, (const double *)h->lw.p, d_out, h->N);
-    XH_TRY(ldb_lap(h, LDB_T_FINISH));
+    XH_TRY(h->tm.lap(LDB_T_FINISH));
     return XH_OK;
 }
 
@@ -577,7 +533,7 @@ int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, in
     const size_t N = h->N;
     *n_iters = 0;
     *stopped = 0;
-    for (double &t : h->ms) t = 0;
+    h->tm.zero();
     double lastnorm = 0, lastporc = 1, normOrig = 0;
     int bool1 = 1;
     const double floorv = -4 * h->desvOutside;
@@ -589,7 +545,7 @@ int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, in
         XH_LAUNCH256(h->ctx, xh_k_reduce_final, 1, (const double *)h->partials.p, (int)h->grid, 2, dp(h->result));
         XH_HIP(hipMemcpyAsync(hp, h->result.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
         XH_HIP(hipEventRecord(h->evRec, st));
-        XH_TRY(ldb_lap(h, LDB_T_FINISH));
+        XH_TRY(h->tm.lap(LDB_T_FINISH));
         // :367-368: the second operator does not need the record
         XH_TRY(ldb_filter(h, (const double *)h->filt.p));
         XH_HIP(hipEventSynchronize(h->evRec));
@@ -605,7 +561,7 @@ int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, in
         // :370-389
         XH_LAUNCH256(h->ctx, k_ldb_second, h->grid, (const double *)h->acc.p, (const double *)h->lw.p, i == 1 ? (const double *)h->Vorig.p : (const double *)h->sharp.p,
                      dp(h->sharp), N, lambda, floorv);
-        XH_TRY(ldb_lap(h, LDB_T_FINISH));
+        XH_TRY(h->tm.lap(LDB_T_FINISH));
         xh_ldb_iter rec;
         std::memset(&rec, 0, sizeof(rec));
         rec.norm = norm; rec.porc = porc; rec.subst = subst; rec.lambda = lambda; rec.stop = bool1 == 2 ? 1 : 0;
@@ -622,15 +578,14 @@ int xh_ldb_run(xh_ldb *h, double lambda, int32_t niter, xh_ldb_iter *h_iters, in
 int xh_ldb_set_timing(xh_ldb *h, int32_t on)
 {
     XH_CHECK(h, XH_ERR_ARG, "xh_ldb_set_timing: null handle");
-    h->timing = on != 0;
-    for (double &t : h->ms) t = 0;
+    h->tm.set(on != 0);
     return XH_OK;
 }
 
 int xh_ldb_stage_ms(const xh_ldb *h, double *h_ms)
 {
     XH_CHECK(h && h_ms, XH_ERR_ARG, "xh_ldb_stage_ms: null argument");
-    for (int i = 0; i < LDB_NT; ++i) h_ms[i] = h->ms[i];
+    h->tm.read(h_ms);
     return XH_OK;
 }
 

@@ -40,17 +40,13 @@
 //  - the median of post-processing: the reference counts N with >= and copies with >, leaving zeros where a value equals the bound; the
 //    zeros are counted in, not stored.
 // icdf_gauss (xmippCore, not in the tree) is restated as Abramowitz-Stegun 26.2.23 (parity unpinned).
-#include "xh_fft3d.h"
+#include "xh_volume.h"
 #include "xh_reduce.h"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
 namespace {
-
-#define MN_LOOP(n, N) for (size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x; n < (N); n += (size_t)gridDim.x * blockDim.x)
-
-struct MnDims { int Z, Y, X, xh; };
 
 constexpr int MN_W = 11;                 // select: digit width
 constexpr int MN_BINS = 1 << MN_W;
@@ -67,7 +63,7 @@ struct MnSel {
 __device__ __forceinline__ double mn_axis(int idx, int size) { return idx == 0 ? 1e-38 : d_digfreq(idx, size); }
 
 // fourierFreqs_3D (:174-199): 1 / sqrt(u2), 1e38 at the origin
-__device__ __forceinline__ double mn_iu(int k, int i, int j, MnDims d)
+__device__ __forceinline__ double mn_iu(int k, int i, int j, XhDims d)
 {
     if (k == 0 && i == 0 && j == 0) return 1e38;
     const double uz = d_digfreq(k, d.Z), uy = d_digfreq(i, d.Y), ux = d_digfreq(j, d.X);
@@ -77,19 +73,11 @@ __device__ __forceinline__ double mn_iu(int k, int i, int j, MnDims d)
     return 1 / sqrt(u2);
 }
 
-__device__ __forceinline__ void mn_kij(size_t e, MnDims d, int &k, int &i, int &j)
-{
-    j = (int)(e % d.xh);
-    const size_t r = e / d.xh;
-    i = (int)(r % d.Y);
-    k = (int)(r / d.Y);
-}
-
 // ---------------------------------------------------------------- side info
 // V = 0.5 (V1 + V2), noise = (V1 - V2) / 2 (produceSideInfo :101-105)
 __global__ void __launch_bounds__(256) k_mn_mean_diff(const double *__restrict__ V1, const double *__restrict__ V2, double *__restrict__ V, double *__restrict__ Nz, size_t N)
 {
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double a = V1[n], b = V2[n];
         V[n] = 0.5 * (a + b);
         Nz[n] = (a - b) / 2;
@@ -98,10 +86,10 @@ __global__ void __launch_bounds__(256) k_mn_mean_diff(const double *__restrict__
 
 // proteinRadiusVolumeAndShellStatistics (:36-55): the largest R2 of a voxel equal to 1 and their number. Integer atomics: any order
 // gives the same result
-__global__ void __launch_bounds__(256) k_mn_radius(const int *__restrict__ mask, MnDims d, unsigned long long *__restrict__ out)
+__global__ void __launch_bounds__(256) k_mn_radius(const int *__restrict__ mask, XhDims d, unsigned long long *__restrict__ out)
 {
     unsigned long long r2max = 0, cnt = 0;
-    MN_LOOP(n, (size_t)d.Z * d.Y * d.X) {
+    XH_GRID_LOOP(n, (size_t)d.Z * d.Y * d.X) {
         if (mask[n] == 1) {
             const long long j = (long long)(n % d.X) - d.X / 2;
             const size_t r = n / d.X;
@@ -126,7 +114,7 @@ __device__ __forceinline__ long long mn_isqrt(long long n)
 
 // findCliffValue's shells (:75-94) in one pass: workgroup kk takes plane kk, thread t the shells t, t + 256, ..: it walks its ring of the
 // plane row by row, x ascending, so every sum has a fixed order. part [Z][3][nshell]: sum, sum2, N
-__global__ void __launch_bounds__(256) k_mn_shell_planes(const double *__restrict__ V, MnDims d, int nshell, double *__restrict__ part)
+__global__ void __launch_bounds__(256) k_mn_shell_planes(const double *__restrict__ V, XhDims d, int nshell, double *__restrict__ part)
 {
     const int kk = blockIdx.x;
     const long long k = kk - d.Z / 2, k2 = k * k;
@@ -167,9 +155,9 @@ __global__ void __launch_bounds__(256) k_mn_shell_final(const double *__restrict
 }
 
 // findCliffValue :119-124: voxels at or beyond raux are -1
-__global__ void __launch_bounds__(256) k_mn_cliff_mask(int *__restrict__ mask, MnDims d, double raux2)
+__global__ void __launch_bounds__(256) k_mn_cliff_mask(int *__restrict__ mask, XhDims d, double raux2)
 {
-    MN_LOOP(n, (size_t)d.Z * d.Y * d.X) {
+    XH_GRID_LOOP(n, (size_t)d.Z * d.Y * d.X) {
         const long long j = (long long)(n % d.X) - d.X / 2;
         const size_t r = n / d.X;
         const long long i = (long long)(r % d.Y) - d.Y / 2, k = (long long)(r / d.Y) - d.Z / 2;
@@ -181,7 +169,7 @@ __global__ void __launch_bounds__(256) k_mn_cliff_mask(int *__restrict__ mask, M
 // excludeArea (:169-200) with excl, the --noiseonlyinhalves relabelling (:143-150) without
 __global__ void __launch_bounds__(256) k_mn_exclude(int *__restrict__ mask, const int *__restrict__ excl, int halves, int noiseOnly, size_t N)
 {
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         int m = mask[n];
         if (excl) {
             if (halves) {
@@ -199,11 +187,11 @@ __global__ void __launch_bounds__(256) k_mn_exclude(int *__restrict__ mask, cons
 // amplitudeMonoSig3D_LPF :295-373 (BAND) and monogenicAmplitude_3D_Fourier :591-648: F -> F4 = [V, Rx, Ry, Rz]
 template <bool BAND>
 __global__ void __launch_bounds__(256)
-k_mn_split(const xh_cd *__restrict__ F, xh_cd *__restrict__ F4, size_t NF, MnDims d, double freq, double freqH, double ideltal)
+k_mn_split(const xh_cd *__restrict__ F, xh_cd *__restrict__ F4, size_t NF, XhDims d, double freq, double freqH, double ideltal)
 {
-    MN_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         int k, i, j;
-        mn_kij(e, d, k, i, j);
+        xh_kij(e, d, k, i, j);
         const double iun = mn_iu(k, i, j, d);
         xh_cd f = xh_cd{0.0, 0.0}, aux = xh_cd{0.0, 0.0};
         bool in = true;
@@ -265,12 +253,12 @@ k_mn_rows_amp(const xh_cd *__restrict__ F4, double *__restrict__ amp, XhPlan<dou
 }
 
 // the low-pass tail (:390-406)
-__global__ void __launch_bounds__(256) k_mn_lowpass(xh_cd *__restrict__ F, size_t NF, MnDims d, double freq, double freqL)
+__global__ void __launch_bounds__(256) k_mn_lowpass(xh_cd *__restrict__ F, size_t NF, XhDims d, double freq, double freqL)
 {
     const double raised_w = 3.14159265358979323846 / (freqL - freq);
-    MN_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         int k, i, j;
-        mn_kij(e, d, k, i, j);
+        xh_kij(e, d, k, i, j);
         const double un = 1.0 / mn_iu(k, i, j, d);
         if (freqL >= un && un >= freq) {
             if (freqL != freq) {
@@ -282,12 +270,12 @@ __global__ void __launch_bounds__(256) k_mn_lowpass(xh_cd *__restrict__ F, size_
 }
 
 // realGaussianFilter's mask (data/fourier_filter.cpp :438 through generateMask :664-676)
-__global__ void __launch_bounds__(256) k_mn_gauss(xh_cd *__restrict__ F, size_t NF, MnDims d, double sigma)
+__global__ void __launch_bounds__(256) k_mn_gauss(xh_cd *__restrict__ F, size_t NF, XhDims d, double sigma)
 {
     const double PI = 3.14159265358979323846;
-    MN_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         int k, i, j;
-        mn_kij(e, d, k, i, j);
+        xh_kij(e, d, k, i, j);
         const double wx = d_digfreq(j, d.X), wy = d_digfreq(i, d.Y), wz = d_digfreq(k, d.Z);
         double sum = wx * wx;
         sum += wy * wy;
@@ -304,7 +292,7 @@ __global__ void __launch_bounds__(256)
 k_mn_stats(const double *__restrict__ ampS, const double *__restrict__ ampN, const int *__restrict__ mask, size_t N, int halves, double *__restrict__ partials)
 {
     double acc[6] = {0, 0, 0, 0, 0, 0};
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const int m = mask[n];
         if (m >= 1) {
             const double a = ampS[n];
@@ -368,7 +356,7 @@ k_mn_sel_pass(const double *__restrict__ vals, const int *__restrict__ mask, siz
     const unsigned long long prefix = sel->prefix;
     const unsigned dmask = (1u << w) - 1;
     unsigned last = 0, cnt = 0;
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double v = vals[n];
         if (!mn_in_set(mode, mask, n, v, t)) continue;
         const unsigned long long key = mn_key(v);
@@ -420,7 +408,7 @@ __global__ void k_mn_sel_finish(MnSel *sel) { sel->value = mn_unkey(sel->prefix)
 __global__ void __launch_bounds__(256)
 k_mn_assign(const double *__restrict__ amp, int *__restrict__ mask, double *__restrict__ res, size_t N, double thr, double resolution, double resolution_2, int drop)
 {
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         int m = mask[n];
         if (m >= 1) {
             if (amp[n] > thr) {
@@ -442,7 +430,7 @@ k_mn_assign(const double *__restrict__ amp, int *__restrict__ mask, double *__re
 __global__ void __launch_bounds__(256) k_mn_refine(const double *__restrict__ amp, int *__restrict__ mask, size_t N, double thr, unsigned long long *__restrict__ out)
 {
     unsigned long long c = 0;
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         if (mask[n] >= 1) {
             if (amp[n] < thr) mask[n] = 0;
             else ++c;
@@ -454,14 +442,14 @@ __global__ void __launch_bounds__(256) k_mn_refine(const double *__restrict__ am
 // run :466-475 / :541-550
 __global__ void __launch_bounds__(256) k_mn_relabel(const double *__restrict__ res, int *__restrict__ mask, size_t N)
 {
-    MN_LOOP(n, N) mask[n] = res[n] == 0 ? 0 : 1;
+    XH_GRID_LOOP(n, N) mask[n] = res[n] == 0 ? 0 : 1;
 }
 
 // postProcessingLocalResolutions :270-274 and the values copied at :280-282: out[0] counts >= bound, out[1] counts > bound
 __global__ void __launch_bounds__(256) k_mn_post_count(const double *__restrict__ filt, size_t N, double bound, unsigned long long *__restrict__ out)
 {
     unsigned long long ge = 0, gt = 0;
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double v = filt[n];
         if (v >= bound) ++ge;
         if (v > bound) ++gt;
@@ -473,7 +461,7 @@ __global__ void __launch_bounds__(256) k_mn_post_count(const double *__restrict_
 // :290-299
 __global__ void __launch_bounds__(256) k_mn_post_fill(double *__restrict__ filt, int *__restrict__ mask, size_t N, double last_res, double filling)
 {
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         if (filt[n] < last_res) { filt[n] = filling; mask[n] = 0; }
         else mask[n] = 1;
     }
@@ -484,7 +472,7 @@ __global__ void __launch_bounds__(256)
 k_mn_post_out(const double *__restrict__ filt, const double *__restrict__ res, const int *__restrict__ mask, size_t N, double nyquist, double *__restrict__ chimera,
               double *__restrict__ resmap)
 {
-    MN_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         double v = filt[n];
         const int m = mask[n];
         if (m > 0) {
@@ -510,59 +498,22 @@ double mn_idx2freq(int idx, int size) { return size <= 1 ? 0.0 : (double)(idx <=
 
 }  // namespace
 
-struct xh_mono {
-    xh_ctx *ctx = nullptr;
-    MnDims d = {};
-    size_t N = 0, NF = 0;
+struct xh_mono : XhVolume {
     unsigned grid = 0;
     int nshell = 0, rpb = 1;
-    XhFft3d fft;
     XhBuf FV, FN, F4, V, Nz, ampS, ampN, mask, res, filt, shellPart, shellOut, partials, result, sel, counts;
     XhPinned host;                               // 6 sums, the select's record, 2 counters
-    hipEvent_t ev[2][5] = {}, evs[6] = {};
+    XhEvent ev[2][5], evs[6];
     bool timing = false;
     double ms[MN_NT] = {};
     int32_t radius = 0, radiuslimit = 0;
     int64_t nvox = 0;
-    ~xh_mono()
-    {
-        if (ctx) {
-            (void)hipSetDevice(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-        for (auto &r : ev) for (hipEvent_t e : r) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    }
+    ~xh_mono() { finish(); }
 };
 
 namespace {
 
-double *dp(XhBuf &b) { return (double *)b.p; }
-xh_cd *cp(XhBuf &b) { return (xh_cd *)b.p; }
-int *ip(XhBuf &b) { return (int *)b.p; }
 MnSel *selp(xh_mono *h) { return (MnSel *)h->sel.p; }
-
-// y and z line passes of nb inverse transforms that lie one after the other
-int mn_yz_inverse(xh_mono *h, xh_cd *F, int nb)
-{
-    const MnDims d = h->d;
-    const XhPlan<double> &py = h->fft.py.plan, &pz = h->fft.pz.plan;
-    {
-        const int lpb = xh_plan_lpb(py, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << py.logM, nlines = (size_t)nb * d.Z * d.xh;
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, h->ctx->stream, F, py, nlines, (size_t)d.xh,
-                           (size_t)d.Y * d.xh, (size_t)1, (size_t)d.xh, lpb);
-        XH_LAUNCH_CHECK();
-    }
-    {
-        const int lpb = xh_plan_lpb(pz, 64 * 1024, 8);
-        const size_t smem = ((size_t)lpb * sizeof(xh_cd)) << pz.logM, nlines = (size_t)nb * d.Y * d.xh;
-        hipLaunchKernelGGL((xh_k_fft_lines<double, true>), dim3((unsigned)((nlines + lpb - 1) / lpb)), dim3(256), smem, h->ctx->stream, F, pz, nlines,
-                           (size_t)d.Y * d.xh, (size_t)d.Z * d.Y * d.xh, (size_t)1, (size_t)d.Y * d.xh, lpb);
-        XH_LAUNCH_CHECK();
-    }
-    return XH_OK;
-}
 
 // the monogenic amplitude of spectrum F into d_amp: the sweep's form (band, low-pass tail) or monogenicAmplitude_3D_Fourier's. tslot:
 // which event row records the stages when timing is on
@@ -570,12 +521,12 @@ int mn_amplitude(xh_mono *h, const xh_cd *F, double freq, double freqH, double f
 {
     hipStream_t st = h->ctx->stream;
     const bool tm = h->timing && tslot >= 0;
-    hipEvent_t *ev = h->ev[tslot < 0 ? 0 : tslot];
+    XhEvent *ev = h->ev[tslot < 0 ? 0 : tslot];
     if (tm) XH_HIP(hipEventRecord(ev[0], st));
     if (banded) XH_LAUNCH256(h->ctx, k_mn_split<true>, h->grid, F, cp(h->F4), h->NF, h->d, freq, freqH, 3.14159265358979323846 / (freq - freqH));
     else XH_LAUNCH256(h->ctx, k_mn_split<false>, h->grid, F, cp(h->F4), h->NF, h->d, 0.0, 0.0, 0.0);
     if (tm) XH_HIP(hipEventRecord(ev[1], st));
-    XH_TRY(mn_yz_inverse(h, cp(h->F4), 4));
+    XH_TRY(fft3d_yz<true>(h->ctx, cp(h->F4), h->d.Z, h->d.Y, h->d.xh, h->fft.py.plan, h->fft.pz.plan, 4));
     if (tm) XH_HIP(hipEventRecord(ev[2], st));
     {
         const size_t nrows = (size_t)h->d.Z * h->d.Y;
@@ -769,14 +720,9 @@ int xh_mono_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_mono **out)
     XH_CHECK(ctx && out, XH_ERR_ARG, "xh_mono_create: null argument");
     XH_CHECK(Z >= 2 && Y >= 2 && X >= 2, XH_ERR_ARG, "xh_mono_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_mono_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
-    XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_mono> h(new xh_mono);
-    h->ctx = ctx;
-    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
-    h->d = MnDims{Z, Y, X, X / 2 + 1};
-    h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->d.xh;
-    h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->NF + 255) / 256, (size_t)ctx->num_cus * 4));
+    XH_TRY(h->init(ctx, Z, Y, X));
+    h->grid = xh_grid256(h->NF, ctx->num_cus, 4);
     const size_t rowBytes = (2 * sizeof(xh_cd)) << h->fft.px.plan.logM;     // the two complex lines of a row
     XH_CHECK(rowBytes <= 64 * 1024, XH_ERR_UNSUPPORTED, "xh_mono_create: a row of %d points does not fit the LDS of the amplitude kernel", X);
     h->rpb = (int)std::max<size_t>(1, std::min<size_t>(8, 32 * 1024 / rowBytes));
@@ -794,10 +740,8 @@ int xh_mono_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_mono **out)
     XH_TRY(xh_buf_alloc(ctx, h->sel, sizeof(MnSel)));
     XH_TRY(xh_buf_alloc(ctx, h->counts, sizeof(unsigned long long) * 2));
     XH_TRY(xh_pinned_alloc(ctx, h->host, sizeof(double) * 32));
-    hipError_t e = hipSuccess;
-    for (auto &r : h->ev) for (hipEvent_t &x : r) if (e == hipSuccess) e = hipEventCreate(&x);
-    for (hipEvent_t &x : h->evs) if (e == hipSuccess) e = hipEventCreate(&x);
-    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_mono_create: %s", hipGetErrorString(e));
+    for (auto &r : h->ev) for (XhEvent &x : r) XH_TRY(xh_event_create(x));
+    for (XhEvent &x : h->evs) XH_TRY(xh_event_create(x));
     *out = h.release();
     return XH_OK;
 }

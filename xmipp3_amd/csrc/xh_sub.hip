@@ -350,7 +350,7 @@ struct xh_sub {
     XhBuf d_Praw, d_P, d_Pc, d_Pmask, d_M, d_iM, d_I2, d_b, d_F, d_Fpad, d_S, d_beta, d_res, d_out;
     std::vector<double> rows;                                // host copy of the rows
     std::vector<double> ang, off;                            // per particle: angles [3], roffset [2]
-    std::vector<hipEvent_t> ev;                              // kSubStages + 1 events while timing is on
+    std::vector<XhEvent> ev;                                 // kSubStages + 1 events while timing is on
     double stage_ms[kSubStages] = {};                        // of the last timed run, summed over its chunks
     ~xh_sub()
     {
@@ -361,7 +361,6 @@ struct xh_sub {
         if (rspV) xh_rsp_destroy(rspV);
         if (rspRoi) xh_rsp_destroy(rspRoi);
         if (rspMask) xh_rsp_destroy(rspMask);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
 };
 
@@ -653,14 +652,11 @@ int xh_sub_set_timing(xh_sub *h, int32_t on)
     XH_CHECK(h, XH_ERR_ARG, "xh_sub_set_timing: null handle");
     XH_HIP(hipSetDevice(h->ctx->device));
     if (on && h->ev.empty()) {
-        for (int k = 0; k <= kSubStages; ++k) {
-            hipEvent_t e;
-            XH_HIP(hipEventCreate(&e));
-            h->ev.push_back(e);
-        }
+        std::vector<XhEvent> ev(kSubStages + 1);
+        for (XhEvent &e : ev) XH_TRY(xh_event_create(e));
+        h->ev.swap(ev);
     } else if (!on) {
         XH_HIP(hipStreamSynchronize(h->ctx->stream));
-        for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
         h->ev.clear();
     }
     return XH_OK;

@@ -31,16 +31,12 @@
 //  - --radavg on a box whose largest octant bin round(w X) reaches the number of bins (radial_mean is written past its end);
 //  - stddev(V) == 0 after a phase step (:403), and a reference whose masked, clipped volume is constant;
 //  - lambda outside [0, 1], cutFreq outside [0, 0.5], a negative iteration count or sigma.
-#include "xh_fft3d.h"
+#include "xh_volume.h"
 #include "xh_reduce.h"
 #include <cmath>
 #include <cstring>
 
 namespace {
-
-#define VS_LOOP(n, N) for (size_t n = (size_t)blockIdx.x * blockDim.x + threadIdx.x; n < (N); n += (size_t)gridDim.x * blockDim.x)
-
-struct VsDims { int Z, Y, X, xh; };
 
 constexpr double VS_PI = 3.14159265358979323846;
 constexpr double VS_RAISED_W = 0.02;   // createFilter :280
@@ -75,7 +71,7 @@ __global__ void __launch_bounds__(256)
 k_vs_prepare(const double *__restrict__ in, const double *__restrict__ mask, double *__restrict__ out, size_t N, double *__restrict__ partials)
 {
     double s[2] = {0, 0};
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         double v = in[n];
         if (mask) v *= mask[n];
         v = vs_nonneg(v);
@@ -91,7 +87,7 @@ __global__ void __launch_bounds__(256) k_vs_minmax(const double *__restrict__ v,
 {
     __shared__ double lo[256], hi[256];
     double a = v[0], b = v[0];
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double x = v[n];
         a = x < a ? x : a;
         b = x > b ? x : b;
@@ -115,7 +111,7 @@ __global__ void __launch_bounds__(256) k_vs_minmax(const double *__restrict__ v,
 // POCSMinMax and POCSmask (:380, :385) in one pass; mask null: ones
 __global__ void __launch_bounds__(256) k_vs_clip_mask(double *__restrict__ v, const double *__restrict__ mask, size_t N, double lo, double hi)
 {
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         double x = vs_clip(v[n], lo, hi);
         if (mask) x *= mask[n];
         v[n] = x;
@@ -126,7 +122,7 @@ __global__ void __launch_bounds__(256) k_vs_clip_mask(double *__restrict__ v, co
 __global__ void __launch_bounds__(256) k_vs_nonneg_moments(double *__restrict__ v, size_t N, double *__restrict__ partials)
 {
     double s[2] = {0, 0};
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double x = vs_nonneg(v[n]);
         v[n] = x;
         s[0] += x;
@@ -138,7 +134,7 @@ __global__ void __launch_bounds__(256) k_vs_nonneg_moments(double *__restrict__ 
 // V *= std1 / std2 (:403) on its way out
 __global__ void __launch_bounds__(256) k_vs_scale(const double *__restrict__ v, double *__restrict__ out, size_t N, double f)
 {
-    VS_LOOP(n, N) out[n] = v[n] * f;
+    XH_GRID_LOOP(n, N) out[n] = v[n] * f;
 }
 
 // the sums behind computeEnergy (:205-211) of the steps between two states in memory, read only. prev fprev is the state before, cur the
@@ -152,7 +148,7 @@ k_vs_energy(const double *__restrict__ prev, double fprev, const double *__restr
             double *__restrict__ partials)
 {
     double s[3] = {0, 0, 0};
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double x = cur[n];
         if (mode == VS_E_SCALE) {
             const double d = x - x * fprev;
@@ -180,7 +176,7 @@ k_vs_energy(const double *__restrict__ prev, double fprev, const double *__restr
 __global__ void __launch_bounds__(256)
 k_vs_subtract(const double *__restrict__ v1, const double *__restrict__ v1f, const double *__restrict__ v, const double *__restrict__ m, double *__restrict__ out, size_t N)
 {
-    VS_LOOP(n, N) {
+    XH_GRID_LOOP(n, N) {
         const double f = v1f[n], mk = m[n];
         const double a = v1[n] * (1 - mk);
         const double mn = v[n] < f ? v[n] : f;   // std::min(V, V1F)
@@ -193,13 +189,13 @@ k_vs_subtract(const double *__restrict__ v1, const double *__restrict__ v1f, con
 // FFT_magnitude: std::abs of every coefficient
 __global__ void __launch_bounds__(256) k_vs_magnitude(const xh_cd *__restrict__ F, double *__restrict__ mag, size_t NF)
 {
-    VS_LOOP(e, NF) mag[e] = hypot(F[e].x, F[e].y);
+    XH_GRID_LOOP(e, NF) mag[e] = hypot(F[e].x, F[e].y);
 }
 
 // extractPhase :197-203, and the magnitude when mag is not null
 __global__ void __launch_bounds__(256) k_vs_extract_phase(const xh_cd *__restrict__ F, xh_cd *__restrict__ P, double *__restrict__ mag, size_t NF)
 {
-    VS_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         const xh_cd f = F[e];
         const double phi = atan2(f.y, f.x);
         P[e] = xh_cd{cos(phi), sin(phi)};
@@ -210,7 +206,7 @@ __global__ void __launch_bounds__(256) k_vs_extract_phase(const xh_cd *__restric
 // POCSFourierAmplitude :138-147
 __global__ void __launch_bounds__(256) k_vs_amplitude(xh_cd *__restrict__ F, const double *__restrict__ v1mag, size_t NF, double l)
 {
-    VS_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         const xh_cd f = F[e];
         const double mod = hypot(f.x, f.y);
         if (mod > 1e-10) {
@@ -221,12 +217,11 @@ __global__ void __launch_bounds__(256) k_vs_amplitude(xh_cd *__restrict__ F, con
 }
 
 // POCSFourierAmplitudeRadAvg :149-177
-__global__ void __launch_bounds__(256) k_vs_amplitude_radavg(xh_cd *__restrict__ F, const double *__restrict__ rq, int nbins, size_t NF, VsDims d, double l)
+__global__ void __launch_bounds__(256) k_vs_amplitude_radavg(xh_cd *__restrict__ F, const double *__restrict__ rq, int nbins, size_t NF, XhDims d, double l)
 {
-    VS_LOOP(e, NF) {
-        const int j = (int)(e % d.xh);
-        const size_t r = e / d.xh;
-        const int i = (int)(r % d.Y), k = (int)(r / d.Y);
+    XH_GRID_LOOP(e, NF) {
+        int k, i, j;
+        xh_kij(e, d, k, i, j);
         const double w = vs_w_fast(k, i, j, d.Z, d.Y, d.X);
         const int iw = min((int)floor(w * d.X), nbins - 1);
         const double g = (1 - l) + l * rq[iw];
@@ -238,19 +233,18 @@ __global__ void __launch_bounds__(256) k_vs_amplitude_radavg(xh_cd *__restrict__
 // POCSFourierPhase :189-194
 __global__ void __launch_bounds__(256) k_vs_phase(xh_cd *__restrict__ F, const xh_cd *__restrict__ P, size_t NF)
 {
-    VS_LOOP(e, NF) {
+    XH_GRID_LOOP(e, NF) {
         const double mod = hypot(F[e].x, F[e].y);
         F[e] = xh_cd{mod * P[e].x, mod * P[e].y};
     }
 }
 
 // FourierFilter LOWPASS (fourier_filter.cpp:423-439): RAISED_COSINE with w1 = cut (GAUSS false) or REALGAUSSIAN with w1 = cut (GAUSS true)
-template <bool GAUSS> __global__ void __launch_bounds__(256) k_vs_lowpass(xh_cd *__restrict__ F, size_t NF, VsDims d, double cut)
+template <bool GAUSS> __global__ void __launch_bounds__(256) k_vs_lowpass(xh_cd *__restrict__ F, size_t NF, XhDims d, double cut)
 {
-    VS_LOOP(e, NF) {
-        const int j = (int)(e % d.xh);
-        const size_t r = e / d.xh;
-        const int i = (int)(r % d.Y), k = (int)(r / d.Y);
+    XH_GRID_LOOP(e, NF) {
+        int k, i, j;
+        xh_kij(e, d, k, i, j);
         const double wx = d_digfreq(j, d.X), wy = d_digfreq(i, d.Y), wz = d_digfreq(k, d.Z);
         const double absw = sqrt(wx * wx + wy * wy + wz * wz);
         double m;
@@ -264,7 +258,7 @@ template <bool GAUSS> __global__ void __launch_bounds__(256) k_vs_lowpass(xh_cd 
 
 // ---------------------------------------------------------------- radial mean
 // the runs of one octant row (k, i): a row per workgroup and lap. slots [nrows][xq], zeroed before
-__global__ void __launch_bounds__(256) k_vs_radial_rows(const double *__restrict__ mag, double *__restrict__ slots, VsDims d)
+__global__ void __launch_bounds__(256) k_vs_radial_rows(const double *__restrict__ mag, double *__restrict__ slots, XhDims d)
 {
     const int zq = d.Z / 2, yq = d.Y / 2, xq = d.X / 2;
     const int nrows = zq * yq;
@@ -284,7 +278,7 @@ __global__ void __launch_bounds__(256) k_vs_radial_rows(const double *__restrict
 }
 
 // bin b = blockIdx.x: the rows in row order, then the tree
-__global__ void __launch_bounds__(256) k_vs_radial_bins(const double *__restrict__ slots, double *__restrict__ sums, VsDims d)
+__global__ void __launch_bounds__(256) k_vs_radial_bins(const double *__restrict__ slots, double *__restrict__ sums, XhDims d)
 {
     __shared__ double red[1][256];
     const int zq = d.Z / 2, yq = d.Y / 2, xq = d.X / 2;
@@ -311,53 +305,21 @@ int vs_max_bin(int Z, int Y, int X) { return vs_bin_round(Z / 2 - 1, Y / 2 - 1, 
 
 }  // namespace
 
-struct xh_vsub {
-    xh_ctx *ctx = nullptr;
-    VsDims d = {};
-    size_t N = 0, NF = 0;
+struct xh_vsub : XhVolume {
     unsigned grid = 0;
     int nbins = 0;
-    XhFft3d fft;
     XhBuf F, P, v1mag, mag, mask, V, prev, tmp, slots, binsums, rq, partials, result, energies;
     XhPinned host;
-    hipEvent_t ev[2] = {};
-    bool timing = false, haveRef = false, haveMask = false, haveRadial = false, havePhase = false;
-    double ms[VS_NT] = {};
+    XhLapTimer<VS_NT> tm;
+    bool haveRef = false, haveMask = false, haveRadial = false, havePhase = false;
     double v1min = 0, v1max = 0, std1 = 0;
     std::vector<double> count, meanV1, meanV, quotient;
-    ~xh_vsub()
-    {
-        if (ctx) {
-            (void)hipSetDevice(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-        }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    ~xh_vsub() { finish(); }
 };
 
 namespace {
 
-double *dp(XhBuf &b) { return (double *)b.p; }
-xh_cd *cp(XhBuf &b) { return (xh_cd *)b.p; }
 const double *maskp(xh_vsub *h) { return h->haveMask ? (const double *)h->mask.p : nullptr; }
-
-// timing: the time since the last lap goes to `stage` (one wait per lap: the benchmark's switch)
-int vs_lap_start(xh_vsub *h)
-{
-    if (h->timing) XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
-int vs_lap(xh_vsub *h, int stage)
-{
-    if (!h->timing) return XH_OK;
-    XH_HIP(hipEventRecord(h->ev[1], h->ctx->stream));
-    XH_HIP(hipEventSynchronize(h->ev[1]));
-    float ms = 0;
-    XH_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms[stage] += ms;
-    XH_HIP(hipEventRecord(h->ev[0], h->ctx->stream));
-    return XH_OK;
-}
 
 // computeStddev from the sum and the sum of squares
 double vs_stddev(double sum, double sum2, double N)
@@ -366,7 +328,7 @@ double vs_stddev(double sum, double sum2, double N)
     return N > 1 ? std::sqrt(std::fabs(sum2 / N - avg * avg) * N / (N - 1)) : 0.0;
 }
 
-int vs_check_radavg(const VsDims &d)
+int vs_check_radavg(const XhDims &d)
 {
     const int nb = vs_num_bins(d.Z, d.Y, d.X), mb = vs_max_bin(d.Z, d.Y, d.X);
     XH_CHECK(d.Z >= 2 && d.Y >= 2 && d.X >= 2 && nb >= 1 && mb < nb, XH_ERR_UNSUPPORTED,
@@ -379,7 +341,7 @@ int vs_check_radavg(const VsDims &d)
 int vs_radial_mean(xh_vsub *h, const double *d_mag, std::vector<double> &mean)
 {
     XH_TRY(vs_check_radavg(h->d));
-    const VsDims d = h->d;
+    const XhDims d = h->d;
     const int zq = d.Z / 2, yq = d.Y / 2, xq = d.X / 2, nrows = zq * yq, nb = h->nbins;
     if (h->count.empty()) {
         h->count.assign(nb, 0.0);
@@ -416,11 +378,11 @@ void vs_quotient(const std::vector<double> &m1, const std::vector<double> &m2, s
 // the phase of d_v's transform (:434) and, with radavg, the quotient table of its magnitude against the reference's (:436-437)
 int vs_target(xh_vsub *h, const double *d_v, bool radavg)
 {
-    XH_TRY(vs_lap_start(h));
+    XH_TRY(h->tm.start());
     XH_TRY(h->fft.r2c(d_v, cp(h->F), 1.0 / (double)h->N));
-    XH_TRY(vs_lap(h, VS_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(VS_T_TRANSFORMS));
     XH_LAUNCH256(h->ctx, k_vs_extract_phase, h->grid, (const xh_cd *)h->F.p, cp(h->P), radavg ? dp(h->mag) : (double *)nullptr, h->NF);
-    XH_TRY(vs_lap(h, VS_T_SPECTRUM));
+    XH_TRY(h->tm.lap(VS_T_SPECTRUM));
     h->havePhase = true;
     if (radavg) {
         XH_CHECK(h->haveRadial, XH_ERR_STATE, "volume subtraction: the reference was set without its radial mean");
@@ -428,7 +390,7 @@ int vs_target(xh_vsub *h, const double *d_v, bool radavg)
         vs_quotient(h->meanV1, h->meanV, h->quotient);
         XH_HIP(hipMemcpyAsync(h->rq.p, h->quotient.data(), sizeof(double) * h->nbins, hipMemcpyHostToDevice, h->ctx->stream));
         XH_HIP(hipStreamSynchronize(h->ctx->stream));
-        XH_TRY(vs_lap_start(h));
+        XH_TRY(h->tm.start());
     }
     return XH_OK;
 }
@@ -455,28 +417,28 @@ int vs_iteration(xh_vsub *h, double lambda, bool radavg, double cutFreq, double 
     hipStream_t st = h->ctx->stream;
     const double iN = 1.0 / (double)h->N;
     double *V = dp(h->V), *prev = dp(h->prev);
-    XH_TRY(vs_lap_start(h));
+    XH_TRY(h->tm.start());
     // :365-375
     XH_TRY(h->fft.r2c(V, cp(h->F), *pending * iN));
-    XH_TRY(vs_lap(h, VS_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(VS_T_TRANSFORMS));
     if (radavg) XH_LAUNCH256(h->ctx, k_vs_amplitude_radavg, h->grid, cp(h->F), (const double *)h->rq.p, h->nbins, h->NF, h->d, lambda);
     else XH_LAUNCH256(h->ctx, k_vs_amplitude, h->grid, cp(h->F), (const double *)h->v1mag.p, h->NF, lambda);
-    XH_TRY(vs_lap(h, VS_T_SPECTRUM));
+    XH_TRY(h->tm.lap(VS_T_SPECTRUM));
     if (e) XH_HIP(hipMemcpyAsync(prev, V, h->V.bytes, hipMemcpyDeviceToDevice, st));
     XH_TRY(h->fft.c2r(cp(h->F), V, 1.0));
-    XH_TRY(vs_lap(h, VS_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(VS_T_TRANSFORMS));
     // :376-389
     if (e) XH_TRY(vs_energy(h, prev, *pending, V, VS_E_AMP_CLIP_MASK, e));
     XH_LAUNCH256(h->ctx, k_vs_clip_mask, h->grid, V, maskp(h), h->N, h->v1min, h->v1max);
-    XH_TRY(vs_lap(h, VS_T_REAL));
+    XH_TRY(h->tm.lap(VS_T_REAL));
     // :390-392
     XH_TRY(h->fft.r2c(V, cp(h->F), iN));
-    XH_TRY(vs_lap(h, VS_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(VS_T_TRANSFORMS));
     XH_LAUNCH256(h->ctx, k_vs_phase, h->grid, cp(h->F), (const xh_cd *)h->P.p, h->NF);
-    XH_TRY(vs_lap(h, VS_T_SPECTRUM));
+    XH_TRY(h->tm.lap(VS_T_SPECTRUM));
     if (e) XH_HIP(hipMemcpyAsync(prev, V, h->V.bytes, hipMemcpyDeviceToDevice, st));
     XH_TRY(h->fft.c2r(cp(h->F), V, 1.0));
-    XH_TRY(vs_lap(h, VS_T_TRANSFORMS));
+    XH_TRY(h->tm.lap(VS_T_TRANSFORMS));
     // :393-403
     if (e) XH_TRY(vs_energy(h, prev, 1.0, V, VS_E_PHASE_NONNEG, e + 3));
     XH_LAUNCH256(h->ctx, k_vs_nonneg_moments, h->grid, V, h->N, dp(h->partials));
@@ -485,7 +447,7 @@ int vs_iteration(xh_vsub *h, double lambda, bool radavg, double cutFreq, double 
     const double std2 = vs_stddev(hp[0], hp[1], (double)h->N);
     XH_CHECK(std2 > 0 && std::isfinite(std2), XH_ERR_ARG, "volume subtraction: stddev(V) = %g after the phase step: std1 / stddev(V) is undefined", std2);
     *pending = h->std1 / std2;
-    XH_TRY(vs_lap(h, VS_T_REAL));
+    XH_TRY(h->tm.lap(VS_T_REAL));
     if (e) XH_TRY(vs_energy(h, V, *pending, V, VS_E_SCALE, e + 6));
     // :409-417
     if (cutFreq != 0) {
@@ -495,7 +457,7 @@ int vs_iteration(xh_vsub *h, double lambda, bool radavg, double cutFreq, double 
         XH_TRY(h->fft.c2r(cp(h->F), V, 1.0));
         if (e) XH_TRY(vs_energy(h, prev, *pending, V, VS_E_FILTER, e + 9));
         *pending = 1.0;
-        XH_TRY(vs_lap(h, VS_T_FILTER));
+        XH_TRY(h->tm.lap(VS_T_FILTER));
     }
     return XH_OK;
 }
@@ -510,9 +472,9 @@ int vs_iterate(xh_vsub *h, int32_t iter, double lambda, bool radavg, double cutF
     }
     double pending = 1.0;
     for (int32_t n = 0; n < iter; ++n) XH_TRY(vs_iteration(h, lambda, radavg, cutFreq, &pending, energies ? dp(h->energies) + 12 * (size_t)n : nullptr));
-    XH_TRY(vs_lap_start(h));
+    XH_TRY(h->tm.start());
     XH_LAUNCH256(h->ctx, k_vs_scale, h->grid, (const double *)h->V.p, d_out, h->N, pending);
-    XH_TRY(vs_lap(h, VS_T_REAL));
+    XH_TRY(h->tm.lap(VS_T_REAL));
     if (energies && iter > 0) {
         std::vector<double> s(12 * (size_t)iter);
         XH_HIP(hipMemcpyAsync(s.data(), h->energies.p, sizeof(double) * s.size(), hipMemcpyDeviceToHost, st));
@@ -556,15 +518,10 @@ int xh_vsub_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_vsub **out)
     XH_CHECK(ctx && out, XH_ERR_ARG, "xh_vsub_create: null argument");
     XH_CHECK(Z >= 2 && Y >= 2 && X >= 2, XH_ERR_ARG, "xh_vsub_create: bad size %d x %d x %d", Z, Y, X);
     XH_CHECK(Z <= 1024 && Y <= 1024 && X <= 1024, XH_ERR_UNSUPPORTED, "xh_vsub_create: sizes above 1024 are not supported (%d x %d x %d)", Z, Y, X);
-    XH_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<xh_vsub> h(new xh_vsub);
-    h->ctx = ctx;
-    XH_TRY(xh_fft3d_create(ctx, Z, Y, X, h->fft));
-    h->d = VsDims{Z, Y, X, X / 2 + 1};
-    h->N = (size_t)Z * Y * X;
-    h->NF = (size_t)Z * Y * h->d.xh;
+    XH_TRY(h->init(ctx, Z, Y, X));
     h->nbins = vs_num_bins(Z, Y, X);
-    h->grid = (unsigned)std::max<size_t>(1, std::min<size_t>((h->N + 255) / 256, (size_t)ctx->num_cus * 8));
+    h->grid = xh_grid256(h->N, ctx->num_cus, 8);
     const size_t vb = sizeof(double) * h->N, fb = sizeof(xh_cd) * h->NF;
     for (XhBuf *b : {&h->mask, &h->V, &h->prev, &h->tmp}) XH_TRY(xh_buf_alloc(ctx, *b, vb));
     for (XhBuf *b : {&h->F, &h->P}) XH_TRY(xh_buf_alloc(ctx, *b, fb));
@@ -572,9 +529,7 @@ int xh_vsub_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_vsub **out)
     XH_TRY(xh_buf_alloc(ctx, h->partials, sizeof(double) * 3 * h->grid));
     XH_TRY(xh_buf_alloc(ctx, h->result, sizeof(double) * 4));
     XH_TRY(xh_pinned_alloc(ctx, h->host, sizeof(double) * 8));
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &x : h->ev) if (e == hipSuccess) e = hipEventCreate(&x);
-    XH_CHECK(e == hipSuccess, XH_ERR_HIP, "xh_vsub_create: %s", hipGetErrorString(e));
+    XH_TRY(h->tm.create(ctx));
     *out = h.release();
     return XH_OK;
 }
@@ -680,11 +635,11 @@ int xh_vsub_adjust(xh_vsub *h, const double *d_V, int32_t iter, double lambda, i
     XH_CHECK(h->haveRef, XH_ERR_STATE, "xh_vsub_adjust: no reference is set");
     XH_TRY(vs_check_options("xh_vsub_adjust", iter, lambda, cutFreq));
     XH_HIP(hipSetDevice(h->ctx->device));
-    for (double &t : h->ms) t = 0;
+    h->tm.zero();
     // :430-431
-    XH_TRY(vs_lap_start(h));
+    XH_TRY(h->tm.start());
     XH_LAUNCH256(h->ctx, k_vs_prepare, h->grid, d_V, maskp(h), dp(h->V), h->N, dp(h->partials));
-    XH_TRY(vs_lap(h, VS_T_REAL));
+    XH_TRY(h->tm.lap(VS_T_REAL));
     if (iter > 0) XH_TRY(vs_target(h, (const double *)h->V.p, radavg != 0));
     return vs_iterate(h, iter, lambda, radavg != 0, cutFreq, h_energies, d_out);
 }
@@ -726,15 +681,14 @@ int xh_vsub_subtract(xh_vsub *h, const double *d_V1_raw, const double *d_Vadj, c
 int xh_vsub_set_timing(xh_vsub *h, int32_t on)
 {
     XH_CHECK(h, XH_ERR_ARG, "xh_vsub_set_timing: null handle");
-    h->timing = on != 0;
-    for (double &t : h->ms) t = 0;
+    h->tm.set(on != 0);
     return XH_OK;
 }
 
 int xh_vsub_stage_ms(const xh_vsub *h, double *h_ms)
 {
     XH_CHECK(h && h_ms, XH_ERR_ARG, "xh_vsub_stage_ms: null argument");
-    for (int i = 0; i < VS_NT; ++i) h_ms[i] = h->ms[i];
+    h->tm.read(h_ms);
     return XH_OK;
 }
 

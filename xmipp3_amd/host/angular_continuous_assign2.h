@@ -85,13 +85,7 @@ public:
         prm.same_defocus = checkParam("--sameDefocus");
         fnResiduals = checkParam("--oresiduals") ? getParam("--oresiduals") : std::string();
         fnProjections = checkParam("--oprojections") ? getParam("--oprojections") : std::string();
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         batch = std::max(1, (int)getIntParam("--batch"));
         if (!(prm.optimize_gray || prm.optimize_shift || prm.optimize_scale || prm.optimize_angles || prm.optimize_defocus))
             REPORT_ERROR(ERR_ARG_MISSING, "none of --optimizeGray, --optimizeShift, --optimizeScale, --optimizeAngles, --optimizeDefocus is given: nothing to search");
@@ -120,8 +114,7 @@ public:
         xhCheck(xh_ctx_create_private(device, &ctx));
         XhOwner<xh_ctx> ctxOwner(ctx);
         DeviceBuffer dvol;
-        dvol.reserve(ctx, vol.size() * sizeof(float));
-        xhCheck(xh_memcpy_h2d(ctx, dvol.p, vol.data(), vol.size() * sizeof(float)));
+        dvol.upload(ctx, vol.data(), vol.size() * sizeof(float));
         xh_ca2 *h = nullptr;
         xhCheck(xh_ca2_create(ctx, dvol.as<float>(), (int)D, &prm, batch, &h));
         XhOwner<xh_ca2> hOwner(h);

@@ -105,11 +105,7 @@ public:
         while (ss >> tok) sigma.push_back(atof(tok.c_str()));
         if (sigma.empty()) REPORT_ERROR(ERR_ARG_INCORRECT, "--sigma: no value");
         if (prm.step < 1) REPORT_ERROR(ERR_ARG_INCORRECT, "--step: " + std::to_string(prm.step) + " must be positive");
-        const std::string a = getParam("--dev");
-        char *end = nullptr;
-        const long d = strtol(a.c_str(), &end, 10);
-        if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-        device = (int)d;
+        device = parseGpuDevice(getParam("--dev"));
         if (xh_faz_check(prm.l1, prm.l2, -1) != XH_OK) REPORT_ERROR(ERR_ARG_INCORRECT, std::string("--l1 / --l2: ") + xh_last_error());
     }
 

@@ -52,8 +52,32 @@ struct DeviceBuffer {
     ~DeviceBuffer() { release(); }
     void release() { if (p) xh_free(ctx, p); p = nullptr; bytes = 0; }
     void reserve(xh_ctx *c, size_t b) { if (b <= bytes) return; release(); ctx = c; xhCheck(xh_malloc(c, b, &p)); bytes = b; }
+    void upload(xh_ctx *c, const void *src, size_t b) { reserve(c, b); xhCheck(xh_memcpy_h2d(c, p, src, b)); }
     template <typename T> T *as() { return (T *)p; }
 };
+
+// --dev <id> of the single-device programs: the id
+inline int parseGpuDevice(const std::string &a)
+{
+    char *end = nullptr;
+    const long d = strtol(a.c_str(), &end, 10);
+    if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
+    return (int)d;
+}
+
+// a volume file's values as doubles
+inline void readDoubles(const std::string &fn, std::vector<double> &v, ImageInfo &I)
+{
+    std::vector<float> f;
+    readImage(fn, f, I);
+    v.assign(f.begin(), f.end());
+}
+
+// what: the two things compared, as in "The mask and the half maps"
+inline void sameShape(const ImageInfo &A, const ImageInfo &B, const std::string &what)
+{
+    if (A.x != B.x || A.y != B.y || A.z != B.z) REPORT_ERROR(ERR_MATRIX_DIM, what + " have different dimensions");
+}
 
 // Sampling::readSamplingFile (data/sampling.cpp:1592-1659): blocks extra / neighbors / projectionDirections.
 // my_neighbors[image] is kept as shared lists (fastio.h: NeighbourLists): with every image searching the whole gallery
@@ -309,8 +333,7 @@ public:
                 s.feeder->create(s.device, dim, std::min((size_t)batch, DFexp.size()), std::max(1, hostThreads(readers) / (int)slots.size()), nullptr);
             });
             DeviceBuffer d_refs;
-            d_refs.reserve(ctx, refs.size() * sizeof(float));
-            xhCheck(xh_memcpy_h2d(ctx, d_refs.p, refs.data(), refs.size() * sizeof(float)));
+            d_refs.upload(ctx, refs.data(), refs.size() * sizeof(float));
             xh_pm *pm = nullptr;
             xhCheck(xh_pm_create(ctx, (int)dim, Ri, Ro, (int)total_nr_refs, d_refs.as<float>(), Mctf.empty() ? nullptr : Mctf.data(), paddim, &pm));
             s.pm.reset(pm);
@@ -1170,8 +1193,7 @@ public:
         xhCheck(xh_ctx_create_private(device, &ctx));
         XhOwner<xh_ctx> ctxOwner(ctx);
         DeviceBuffer d_vol, d_out;
-        d_vol.reserve(ctx, vol.size() * sizeof(float));
-        xhCheck(xh_memcpy_h2d(ctx, d_vol.p, vol.data(), vol.size() * sizeof(float)));
+        d_vol.upload(ctx, vol.data(), vol.size() * sizeof(float));
         xh_fp *fp = nullptr;
         xhCheck(xh_fp_create(ctx, d_vol.as<float>(), (int)D, paddFactor, maxFrequency, 3, &fp));
         XhOwner<xh_fp> fpOwner(fp);

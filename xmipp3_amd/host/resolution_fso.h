@@ -54,13 +54,7 @@ public:
         thrs = getDoubleParam("--threshold");
         do_3dfsc_filter = checkParam("--threedfsc_filter");
         Nthreads = (int)getIntParam("--threads");
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         if (fnOut.empty()) REPORT_ERROR(ERR_ARG_MISSING, "-o is empty: the results need an output folder");
         if (!(ang_con > 0 && ang_con < 90)) REPORT_ERROR(ERR_ARG_INCORRECT, "--anglecone " + std::to_string(ang_con) + ": the cone angle must lie inside (0, 90) degrees");
     }
@@ -77,13 +71,6 @@ public:
                   << "threshold: " << thrs << std::endl
                   << "threedfsc_filter: " << (do_3dfsc_filter ? 1 : 0) << std::endl
                   << "threads: " << Nthreads << std::endl;
-    }
-
-    static void readDoubles(const std::string &fn, std::vector<double> &v, ImageInfo &I)
-    {
-        std::vector<float> f;
-        readImage(fn, f, I);
-        v.assign(f.begin(), f.end());
     }
 
     // fscInterpolation :352-374
@@ -110,10 +97,10 @@ public:
         ImageInfo I1, I2, IM;
         readDoubles(fnhalf1, half1, I1);
         readDoubles(fnhalf2, half2, I2);
-        if (I1.x != I2.x || I1.y != I2.y || I1.z != I2.z) REPORT_ERROR(ERR_MATRIX_DIM, "The half maps have different dimensions");
+        sameShape(I1, I2, "The half maps");
         if (!fnmask.empty()) {
             readDoubles(fnmask, mask, IM);
-            if (IM.x != I1.x || IM.y != I1.y || IM.z != I1.z) REPORT_ERROR(ERR_MATRIX_DIM, "The mask and the half maps have different dimensions");
+            sameShape(IM, I1, "The mask and the half maps");
         }
         const size_t X = I1.x, Y = I1.y, Z = I1.z, N = X * Y * Z, L = X / 2 + 1;
         if (X < 8 || Y < 8 || Z < 8) REPORT_ERROR(ERR_MATRIX_DIM, "A box of " + std::to_string(X) + " x " + std::to_string(Y) + " x " + std::to_string(Z) + ": sides below 8 are refused");
@@ -131,13 +118,10 @@ public:
         std::vector<double> gsums(3 * L);
         {
             DeviceBuffer d1, d2, dm;
-            d1.reserve(ctx, vb);
-            xhCheck(xh_memcpy_h2d(ctx, d1.p, half1.data(), vb));
-            d2.reserve(ctx, vb);
-            xhCheck(xh_memcpy_h2d(ctx, d2.p, half2.data(), vb));
+            d1.upload(ctx, half1.data(), vb);
+            d2.upload(ctx, half2.data(), vb);
             if (!mask.empty()) {
-                dm.reserve(ctx, vb);
-                xhCheck(xh_memcpy_h2d(ctx, dm.p, mask.data(), vb));
+                dm.upload(ctx, mask.data(), vb);
             }
             xhCheck(xh_fso_load(h, d1.as<double>(), d2.as<double>(), mask.empty() ? nullptr : dm.as<double>(), gsums.data(), nullptr, nullptr));
         }

@@ -54,13 +54,7 @@ public:
         prm.gaussian = checkParam("--gaussian");
         prm.noise_only_in_halves = checkParam("--noiseonlyinhalves");
         nthrs = (int)getIntParam("--threads");
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         // produceSideInfo :122-127, :162-163
         if (fnMask.empty()) REPORT_ERROR(ERR_ARG_MISSING, "Error: a mask ought to be provided");
         if (prm.freq_step < 0.25) prm.freq_step = 0.25;
@@ -83,20 +77,13 @@ public:
                   << "noiseonlyinhalves: " << prm.noise_only_in_halves << std::endl;
     }
 
-    static void readDoubles(const std::string &fn, std::vector<double> &v, ImageInfo &I)
-    {
-        std::vector<float> f;
-        readImage(fn, f, I);
-        v.assign(f.begin(), f.end());
-    }
-
     // Image<int>::read: the file's values truncated to int
     static void readInts(const std::string &fn, std::vector<int32_t> &v, const ImageInfo &ref, const char *what)
     {
         std::vector<float> f;
         ImageInfo I;
         readImage(fn, f, I);
-        if (I.x != ref.x || I.y != ref.y || I.z != ref.z) REPORT_ERROR(ERR_MATRIX_DIM, std::string(what) + " and input volume have different dimensions");
+        sameShape(I, ref, std::string(what) + " and input volume");
         v.resize(f.size());
         for (size_t i = 0; i < f.size(); ++i) v[i] = (int32_t)f[i];
     }
@@ -111,7 +98,7 @@ public:
         const bool halves = !fnVol2.empty();
         if (halves) {
             readDoubles(fnVol2, v2, I2);
-            if (I1.x != I2.x || I1.y != I2.y || I1.z != I2.z) REPORT_ERROR(ERR_MATRIX_DIM, "Input volumes have different dimensions");
+            sameShape(I1, I2, "Input volumes");
         }
         std::vector<int32_t> mask, excl;
         readInts(fnMask, mask, I1, "Mask");
@@ -126,18 +113,14 @@ public:
         XhOwner<xh_mono> hOwner(h);
         DeviceBuffer dV1, dV2, dMask, dExcl, dMean, dRef, dChim, dRes;
         const size_t vb = sizeof(double) * N, mb = sizeof(int32_t) * N;
-        dV1.reserve(ctx, vb);
-        xhCheck(xh_memcpy_h2d(ctx, dV1.p, v1.data(), vb));
+        dV1.upload(ctx, v1.data(), vb);
         if (halves) {
-            dV2.reserve(ctx, vb);
-            xhCheck(xh_memcpy_h2d(ctx, dV2.p, v2.data(), vb));
+            dV2.upload(ctx, v2.data(), vb);
             dMean.reserve(ctx, vb);
         }
-        dMask.reserve(ctx, mb);
-        xhCheck(xh_memcpy_h2d(ctx, dMask.p, mask.data(), mb));
+        dMask.upload(ctx, mask.data(), mb);
         if (!excl.empty()) {
-            dExcl.reserve(ctx, mb);
-            xhCheck(xh_memcpy_h2d(ctx, dExcl.p, excl.data(), mb));
+            dExcl.upload(ctx, excl.data(), mb);
         }
         dRef.reserve(ctx, mb);
         dChim.reserve(ctx, vb);

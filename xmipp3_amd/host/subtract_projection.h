@@ -74,13 +74,7 @@ public:
         prm.real_space = checkParam("--realSpaceProjection");
         prm.ignore_ctf = checkParam("--ignoreCTF");
         if (checkParam("--save")) std::cerr << "xmipp_subtract_projection: --save is ignored (the reference reads it only under debug defines)" << std::endl;
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         batch = std::max(1, (int)getIntParam("--batch"));
     }
 

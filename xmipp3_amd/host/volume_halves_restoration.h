@@ -104,21 +104,14 @@ public:
                   << "    Kdiff: " << Kdiff << std::endl;
     }
 
-    static void readVolume(const std::string &fn, std::vector<double> &v, ImageInfo &I)
-    {
-        std::vector<float> f;
-        readImage(fn, f, I);
-        v.assign(f.begin(), f.end());
-    }
-
     void run() override
     {
         show();
         std::vector<double> v1, v2;
         ImageInfo I1, I2;
-        readVolume(fnV1, v1, I1);
-        readVolume(fnV2, v2, I2);
-        if (I1.x != I2.x || I1.y != I2.y || I1.z != I2.z) REPORT_ERROR(ERR_MATRIX_DIM, "Input volumes have different dimensions");
+        readDoubles(fnV1, v1, I1);
+        readDoubles(fnV2, v2, I2);
+        sameShape(I1, I2, "Input volumes");
         const size_t X = I1.x, Y = I1.y, Z = I1.z, N = X * Y * Z;
         std::vector<int32_t> mask;
         if (useMask) {
@@ -126,7 +119,7 @@ public:
                 std::vector<float> f;
                 ImageInfo IM;
                 readImage(maskArg, f, IM);
-                if (IM.x != X || IM.y != Y || IM.z != Z) REPORT_ERROR(ERR_MATRIX_DIM, "Mask and input volumes have different dimensions");
+                sameShape(IM, I1, "Mask and input volumes");
                 mask.resize(N);
                 xhCheck(xh_halves_binary_mask(f.data(), N, mask.data()));
             } else {
@@ -142,14 +135,11 @@ public:
         xhCheck(xh_halves_create(ctx, (int)Z, (int)Y, (int)X, &h));
         XhOwner<xh_halves> hOwner(h);
         DeviceBuffer dV1, dV2, dMask, dOut;
-        dV1.reserve(ctx, sizeof(double) * N);
-        dV2.reserve(ctx, sizeof(double) * N);
-        xhCheck(xh_memcpy_h2d(ctx, dV1.p, v1.data(), sizeof(double) * N));
-        xhCheck(xh_memcpy_h2d(ctx, dV2.p, v2.data(), sizeof(double) * N));
+        dV1.upload(ctx, v1.data(), sizeof(double) * N);
+        dV2.upload(ctx, v2.data(), sizeof(double) * N);
         const int32_t *m = nullptr;
         if (!mask.empty()) {
-            dMask.reserve(ctx, sizeof(int32_t) * N);
-            xhCheck(xh_memcpy_h2d(ctx, dMask.p, mask.data(), sizeof(int32_t) * N));
+            dMask.upload(ctx, mask.data(), sizeof(int32_t) * N);
             m = dMask.as<int32_t>();
         }
         xhCheck(xh_halves_load(h, dV1.as<double>(), dV2.as<double>()));

@@ -43,13 +43,7 @@ public:
         Nthread = (int)getIntParam("-n");
         fnOut = getParam("-o");
         fnMD = getParam("--md");
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         if (!(sampling > 0) || !(2 * sampling - 0.2 > 0))
             REPORT_ERROR(ERR_ARG_INCORRECT, "--sampling " + std::to_string(sampling) + ": the first band's wL = sampling / (2 sampling - 0.2) is undefined");
         if (Niter < 1) REPORT_ERROR(ERR_ARG_INCORRECT, "-i " + std::to_string(Niter) + ": without an iteration the sharpened map is never assigned");
@@ -69,13 +63,6 @@ public:
                   << "Nthread: " << Nthread << std::endl;
     }
 
-    static void readDoubles(const std::string &fn, std::vector<double> &v, ImageInfo &I)
-    {
-        std::vector<float> f;
-        readImage(fn, f, I);
-        v.assign(f.begin(), f.end());
-    }
-
     void run() override
     {
         show();
@@ -84,7 +71,7 @@ public:
         ImageInfo IV, IR;
         readDoubles(fnVol, vol, IV);
         readDoubles(fnRes, res, IR);
-        if (IV.x != IR.x || IV.y != IR.y || IV.z != IR.z) REPORT_ERROR(ERR_MATRIX_DIM, "The resolution map and the input volume have different dimensions");
+        sameShape(IV, IR, "The resolution map and the input volume");
         const size_t X = IV.x, Y = IV.y, Z = IV.z, N = X * Y * Z;
 
         xh_ctx *ctx = nullptr;
@@ -95,10 +82,8 @@ public:
         XhOwner<xh_ldb> hOwner(h);
         DeviceBuffer dVol, dRes, dOut;
         const size_t vb = sizeof(double) * N;
-        dVol.reserve(ctx, vb);
-        xhCheck(xh_memcpy_h2d(ctx, dVol.p, vol.data(), vb));
-        dRes.reserve(ctx, vb);
-        xhCheck(xh_memcpy_h2d(ctx, dRes.p, res.data(), vb));
+        dVol.upload(ctx, vol.data(), vb);
+        dRes.upload(ctx, res.data(), vb);
         dOut.reserve(ctx, vb);
         xhCheck(xh_ldb_load(h, dVol.as<double>(), dRes.as<double>(), sampling, K));
         int32_t n = 0, stopped = 0;

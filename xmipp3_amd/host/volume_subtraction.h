@@ -61,13 +61,7 @@ public:
         if (fnVol2A.empty()) fnVol2A = "volume2_adjusted.mrc";
         radavg = checkParam("--radavg");
         computeE = checkParam("--computeEnergy");
-        if (checkParam("--dev")) {
-            const std::string a = getParam("--dev");
-            char *end = nullptr;
-            const long d = strtol(a.c_str(), &end, 10);
-            if (a.empty() || *end || d < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "Invalid GPU device '" + a + "'");
-            device = (int)d;
-        }
+        if (checkParam("--dev")) device = parseGpuDevice(getParam("--dev"));
         if (iter < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "--iter " + std::to_string(iter) + ": a negative number of iterations");
         if (sigma < 0) REPORT_ERROR(ERR_ARG_INCORRECT, "--sigma " + std::to_string(sigma) + ": a negative sigma");
         if (!(lambda >= 0 && lambda <= 1)) REPORT_ERROR(ERR_ARG_INCORRECT, "--lambda " + std::to_string(lambda) + " is outside [0, 1]");
@@ -93,18 +87,6 @@ public:
                   << "Output: " << fnOutVol << std::endl;
     }
 
-    static void readDoubles(const std::string &fn, std::vector<double> &v, ImageInfo &I)
-    {
-        std::vector<float> f;
-        readImage(fn, f, I);
-        v.assign(f.begin(), f.end());
-    }
-
-    static void sameShape(const ImageInfo &A, const ImageInfo &B, const std::string &what)
-    {
-        if (A.x != B.x || A.y != B.y || A.z != B.z) REPORT_ERROR(ERR_MATRIX_DIM, what + " and the reference volume have different dimensions");
-    }
-
     void run() override
     {
         show();
@@ -112,20 +94,20 @@ public:
         ImageInfo I1, I2, IM;
         readDoubles(fnVol1, V1, I1);
         readDoubles(fnVol2, V, I2);
-        sameShape(I2, I1, "The volume to modify");
+        sameShape(I2, I1, "The volume to modify and the reference volume");
         // createMask :317-330: both masks or none
         const bool haveMask = !fnMask1.empty() && !fnMask2.empty();
         if (haveMask) {
             std::vector<double> m2;
             readDoubles(fnMask1, mask, IM);
-            sameShape(IM, I1, "Mask 1");
+            sameShape(IM, I1, "Mask 1 and the reference volume");
             readDoubles(fnMask2, m2, IM);
-            sameShape(IM, I1, "Mask 2");
+            sameShape(IM, I1, "Mask 2 and the reference volume");
             for (size_t n = 0; n < mask.size(); ++n) mask[n] *= m2[n];
         }
         if (performSubtraction && !fnMaskSub.empty()) {
             readDoubles(fnMaskSub, maskSub, IM);
-            sameShape(IM, I1, "The subtraction mask");
+            sameShape(IM, I1, "The subtraction mask and the reference volume");
         }
         const size_t X = I1.x, Y = I1.y, Z = I1.z, N = X * Y * Z;
         if (X < 2 || Y < 2 || Z < 2) REPORT_ERROR(ERR_MATRIX_DIM, "A box of " + std::to_string(X) + " x " + std::to_string(Y) + " x " + std::to_string(Z) + " is no volume");
@@ -145,13 +127,10 @@ public:
         XhOwner<xh_vsub> hOwner(h);
         const size_t vb = sizeof(double) * N;
         DeviceBuffer dV1, dV, dMask, dAdj, dSub, dV1F, dOut;
-        dV1.reserve(ctx, vb);
-        xhCheck(xh_memcpy_h2d(ctx, dV1.p, V1.data(), vb));
-        dV.reserve(ctx, vb);
-        xhCheck(xh_memcpy_h2d(ctx, dV.p, V.data(), vb));
+        dV1.upload(ctx, V1.data(), vb);
+        dV.upload(ctx, V.data(), vb);
         if (haveMask) {
-            dMask.reserve(ctx, vb);
-            xhCheck(xh_memcpy_h2d(ctx, dMask.p, mask.data(), vb));
+            dMask.upload(ctx, mask.data(), vb);
         }
         dAdj.reserve(ctx, vb);
         xhCheck(xh_vsub_set_reference(h, dV1.as<double>(), haveMask ? dMask.as<double>() : nullptr, radavg ? 1 : 0));

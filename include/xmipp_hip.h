@@ -615,6 +615,58 @@ int xh_align_sig_weights(xh_align_sig *h, const float *h_rot, const float *h_til
 int xh_align_sig_update_refs(xh_align_sig *h, const float *d_images, int32_t N, int32_t R, int32_t n_assign, const int32_t *h_ref_idx,
                              const int32_t *h_img_idx, const float *h_weight, const float *h_pose, float *d_out_refs);
 
+/* ---- xmipp_reconstruct_significant (reconstruction/reconstruct_significant.cpp) ----
+ * alignImagesConsideringMirrors (data/filters.cpp:2047-2178) of every (image, gallery projection) pair in double precision, the imed of
+ * every pair, and the program's two significance weightings. A chain is one (pair, mirror, order) triple, order 0 = shift then rotate,
+ * 1 = rotate then shift; chain c = (pair . mirrors + mirror) . 2 + order, pair = image . G + projection. Per step only the chains whose
+ * last increment is over the thresholds (0.95 px, 1 degree; :2072-2110) run, through a list compacted on the device.
+ * create: images of D x D pixels (D even, >= 16, lines that fit the double-precision transform), up to max_gallery projections, batch_chains
+ * chains per batch (1 .. 65532; a batch holds whole pairs, so at least 4; about 24 D^2 + 1 KB bytes of work space per chain). */
+typedef struct xh_rsig xh_rsig;
+int xh_rsig_create(xh_ctx *ctx, int32_t D, int32_t max_gallery, int32_t batch_chains, xh_rsig **out);
+int xh_rsig_destroy(xh_rsig *h);
+/* computeAlignmentTransforms (filters.cpp:2035-2040) of d_gallery [G][D][D] (doubles, G = volumes . directions <= max_gallery), once: the
+ * forward transform as FourierTransformer leaves it (divided by D^2) and polarFourierTransform<true>(.., not conjugated, D / 5, D / 2,
+ * BsplineOrder 1) (polar.cpp:152-176): bilinear samples at the float angle cache's coordinates, zero outside, normalised by
+ * computeAverageAndStddev / normalize (polar.h:488-546), every ring's DFT / nsam. Replaces the gallery loaded before. */
+int xh_rsig_load_gallery(xh_rsig *h, const double *d_gallery, int32_t G);
+/* alignImagesToGallery's inner loop (reconstruct_significant.cpp:198-221) for d_images [N][D][D] (doubles, Xmipp origin) against the
+ * loaded gallery. check_mirrors != 0: alignImagesConsideringMirrors (filters.cpp:2150-2178; the mirror is selfReverseX, and M(0,0),
+ * M(1,0) are negated where it wins on corrMirror > corr); 0: alignImages alone (:211). Each is alignImages (:2047-2129): three rounds of
+ * bestNonwrappingShift (:1903-1985; bestShift without mask or limit, then the three answers a period away, each on a strict > against the
+ * first) and best_rotation over 2 N - 1 angles, in both orders, the image re-interpolated from the original (applyGeometry LINEAR,
+ * IS_NOT_INV, DONT_WRAP) after every step, a step skipped once its last increment is within +-0.95 px on both axes / not above 1 degree
+ * (initially 1.95 px, 2 degrees), corrRS > corrSR at the end.
+ * Device outputs: d_M [N][G][9] as alignImagesConsideringMirrors returns it (before the program's M.inv()), d_corr [N][G], d_imed [N][G]
+ * (imedDistance of the projection and the winning aligned image, filters.cpp:1269-1318, weights from their formula), and, nullable,
+ * d_trace [N][G]: bit 0 the mirror won, bit 1 RS won, bits 2 .. 10 the winning mirror's SR chain, bits 11 .. 19 its RS chain, a chain's nine
+ * bits being, for round r = 0 .. 2, 3 r: the shift step ran, 3 r + 1: the rotation step ran, 3 r + 2: a non-wrapping alternative replaced
+ * bestShift's answer. The four d_chain_* (all or none): every chain's matrix [chains][9], correlation, imed and nine trace bits.
+ * Deviation: applyGeometry's source coordinate of pixel (i, j) is x A00 + y A01 + A02 computed directly, where xmippCore adds A00 along the row. */
+int xh_rsig_align(xh_rsig *h, const double *d_images, int32_t N, int32_t check_mirrors, double *d_M, double *d_corr, double *d_imed, int32_t *d_trace,
+                  double *d_chain_M, double *d_chain_corr, double *d_chain_imed, int32_t *d_chain_trace);
+/* The weights of reconstruct_significant.cpp:222-226 + :288-369 (per image) and :439-492 (per direction) on device arrays [N][G],
+ * G = n_vols . n_dirs, direction g of angles h_rot [G], h_tilt [G] (degrees). one_alpha = 1 - alpha - deltaAlpha2.
+ * First, with max_shift > 0, a pair whose shift (transformationMatrix2Parameters2D of M.inv()) exceeds it on either axis gets corr / 3
+ * and imed . 3, IN PLACE in d_cc and d_imed. Per image: bestCorr, bestImed, ccl = tanh(atanh(bestCorr one_alpha) - 2.96 / sqrt(D^2)), the
+ * cdfs of cc and imed over its G values; a pair is selected when ((apply_fisher && cc >= ccl) || !apply_fisher) && cdfcc >= one_alpha and
+ * its shift is within max_shift; its weight is cdfcc (cc / bestCorr), times (1 - cdfimed)(bestImed / imed) with use_imed; others 0.
+ * Per direction, as written in the reference: the neighbour loop re-reads the direction's own correlations, so the ranked list is its N
+ * values repeated 1 + k times, k = the directions of the same volume sharply closer than ang_distance; weight *= cc (1 / bestCorr) cdf if
+ * (cdf >= one_alpha || !strict) && weight > 0, else 0.
+ * cdf (i) = (1-based ascending rank of element i) / n, equal values ranked by position (the first copy of a repeated value lowest);
+ * ranks are counted, the repeated list is never built: rank = (1 + k) less (i) + equalBefore (i) + 1 of (1 + k) N. */
+int xh_rsig_weights(xh_rsig *h, const double *d_M, double *d_cc, double *d_imed, int32_t N, int32_t n_vols, int32_t n_dirs, const double *h_rot,
+                    const double *h_tilt, double ang_distance, double one_alpha, int32_t apply_fisher, int32_t use_imed, int32_t strict, double max_shift,
+                    double *d_weight);
+/* h_stats [13]: of the last align, the steps launched, the chains that ran the shift step in rounds 1, 2, 3, the chains that ran the
+ * rotation step in rounds 1, 2, 3, its device seconds; of the last weights, the seconds of the per-image and the per-direction stage; of
+ * the last align again, the device seconds inside shift steps and inside rotation steps, 0 unless the run was timed; of the last weights,
+ * the host seconds of counting every direction's neighbours (n_vols n_dirs^2 angles, before any device work) */
+int xh_rsig_stats(const xh_rsig *h, double *h_stats);
+/* on: align puts events around every step and waits for each (one more synchronisation per step); for measurements */
+int xh_rsig_set_timing(xh_rsig *h, int32_t on);
+
 /* ---- xmipp_volume_halves_restoration (reconstruction_cuda/cuda_volume_halves_restorator.cpp, cuda_volume_restoration_kernels.cpp,
  * cuda_cdf.cpp; CPU counterpart reconstruction/volume_halves_restoration.cpp) ----
  * Two half maps [Z][Y][X] (fp64, any size up to 1024 per axis, X >= 2) restored in place by the reference's four stages, in the order of

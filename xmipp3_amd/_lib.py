@@ -185,6 +185,13 @@ SIGNATURES = {
     "xh_align_sig_align": (C.c_int, [vp, vp, i32, vp, vp]),
     "xh_align_sig_weights": (C.c_int, [vp, vp, vp, d, vp, i32, i32, vp]),
     "xh_align_sig_update_refs": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "xh_rsig_create": (C.c_int, [vp, i32, i32, i32, pvp]),
+    "xh_rsig_destroy": (C.c_int, [vp]),
+    "xh_rsig_load_gallery": (C.c_int, [vp, vp, i32]),
+    "xh_rsig_align": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "xh_rsig_weights": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, d, d, i32, i32, i32, d, vp]),
+    "xh_rsig_stats": (C.c_int, [vp, vp]),
+    "xh_rsig_set_timing": (C.c_int, [vp, i32]),
     "xh_halves_create": (C.c_int, [vp, i32, i32, i32, pvp]),
     "xh_halves_destroy": (C.c_int, [vp]),
     "xh_halves_load": (C.c_int, [vp, vp, vp]),

@@ -752,6 +752,85 @@ class AlignSignificant(_Handle):
         return out
 
 
+class ReconstructSignificant(_Handle):
+    """The device side of xmipp_reconstruct_significant: alignImagesConsideringMirrors of every (image, gallery projection) pair in
+    double precision, in batches of chains (one chain = pair, mirror, order), the imed of every pair and the two significance
+    weightings. See include/xmipp_hip.h for the arithmetic and the trace bits."""
+
+    _destroy = "xh_rsig_destroy"
+    STATS = ("steps", "shift_round1", "shift_round2", "shift_round3", "rotation_round1", "rotation_round2", "rotation_round3", "align_seconds",
+             "image_weights_seconds", "direction_weights_seconds", "shift_steps_seconds", "rotation_steps_seconds",
+             "neighbour_count_host_seconds")
+
+    def __init__(self, ctx, D, max_gallery, batch_chains=4096):
+        self.ctx, self.D = ctx, int(D)
+        h = C.c_void_p()
+        check(lib().xh_rsig_create(ctx.h, self.D, int(max_gallery), int(batch_chains), C.byref(h)))
+        super().__init__(ctx, h)
+        self.G = 0
+
+    def _images(self, t):
+        torch = _torch()
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 3 and tuple(t.shape[1:]) == (self.D, self.D)
+        return t
+
+    def load_gallery(self, gallery):
+        """gallery [G, D, D] float64 on the device, G = volumes x directions"""
+        gallery = self._images(gallery)
+        check(lib().xh_rsig_load_gallery(self.h, _ptr(gallery), gallery.shape[0]))
+        self.G = gallery.shape[0]
+
+    def align(self, images, check_mirrors=True, trace=False, chains=False):
+        """images [N, D, D] float64 -> (M [N, G, 3, 3], corr [N, G], imed [N, G]) float64 tensors on the device; with trace, the int32
+        flags [N, G] as a fourth; with chains, a dict of every chain's M [N, G, mirrors, 2, 3, 3], corr, imed and trace as the last"""
+        torch = _torch()
+        images = self._images(images)
+        N, G, dev = images.shape[0], self.G, images.device
+        M = torch.empty((N, G, 3, 3), dtype=torch.float64, device=dev)
+        corr = torch.empty((N, G), dtype=torch.float64, device=dev)
+        imed = torch.empty((N, G), dtype=torch.float64, device=dev)
+        tr = torch.empty((N, G), dtype=torch.int32, device=dev) if trace else None
+        ch = None
+        if chains:
+            shape = (N, G, 2 if check_mirrors else 1, 2)
+            ch = {"M": torch.empty(shape + (3, 3), dtype=torch.float64, device=dev), "corr": torch.empty(shape, dtype=torch.float64, device=dev),
+                  "imed": torch.empty(shape, dtype=torch.float64, device=dev), "trace": torch.empty(shape, dtype=torch.int32, device=dev)}
+        check(lib().xh_rsig_align(self.h, _ptr(images), N, int(bool(check_mirrors)), _ptr(M), _ptr(corr), _ptr(imed), _ptr(tr), _ptr(ch["M"]) if ch else None,
+                                  _ptr(ch["corr"]) if ch else None, _ptr(ch["imed"]) if ch else None, _ptr(ch["trace"]) if ch else None))
+        out = (M, corr, imed)
+        if trace:
+            out += (tr,)
+        if chains:
+            out += (ch,)
+        return out
+
+    def weights(self, M, cc, imed, n_vols, rot, tilt, ang_distance, one_alpha, apply_fisher=False, use_imed=False, strict=False, max_shift=-1.0):
+        """Both weighting stages: M [N, G, 3, 3], cc and imed [N, G] float64 on the device (cc and imed take the maxShift penalty IN
+        PLACE), direction angles rot, tilt [G] in degrees -> weight [N, G] on the device. one_alpha = 1 - alpha - deltaAlpha2.
+        apply_fisher is the program's applyFisher, which its --dontApplyFisher switches ON (reconstruct_significant.cpp:88)."""
+        torch = _torch()
+        for t in (M, cc, imed):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        N, G = cc.shape
+        assert tuple(M.shape) == (N, G, 3, 3) and tuple(imed.shape) == (N, G) and G % int(n_vols) == 0
+        rot, tilt = np.ascontiguousarray(rot, np.float64), np.ascontiguousarray(tilt, np.float64)
+        assert rot.shape == (G,) and tilt.shape == (G,)
+        out = torch.empty_like(cc)
+        check(lib().xh_rsig_weights(self.h, _ptr(M), _ptr(cc), _ptr(imed), N, int(n_vols), G // int(n_vols), _np_ptr(rot), _np_ptr(tilt), float(ang_distance),
+                                    float(one_alpha), int(bool(apply_fisher)), int(bool(use_imed)), int(bool(strict)), float(max_shift), _ptr(out)))
+        return out
+
+    def set_timing(self, on):
+        """a timed align waits for every step and reports the seconds inside shift and rotation steps"""
+        check(lib().xh_rsig_set_timing(self.h, int(bool(on))))
+
+    def stats(self):
+        """of the last align and the last weights, a dict in the order of STATS"""
+        v = np.zeros(len(self.STATS))
+        check(lib().xh_rsig_stats(self.h, _np_ptr(v)))
+        return dict(zip(self.STATS, v.tolist()))
+
+
 class HalvesRestoration(_VolumeHandle):
     """The device side of xmipp_volume_halves_restoration (VolumeHalvesRestorator<double>): two half maps [Z, Y, X] float64 restored in
     place by denoise, deconvolve, filter_bank and difference, in that order, as the reference's apply runs them."""

@@ -1247,6 +1247,48 @@ int xh_vsub_subtract(xh_vsub *h, const double *d_V1_raw, const double *d_Vadj, c
 int xh_vsub_set_timing(xh_vsub *h, int32_t on);
 int xh_vsub_stage_ms(const xh_vsub *h, double *h_ms);
 
+/* ---- xmipp_transform_symmetrize (libraries/reconstruction/symmetrize.{h,cpp}, ProgSymmetrize; data/symmetries.cpp:1574-1705) ----
+ * Real-space symmetrisation of a volume by a point group or a helix, and of an image stack by a rotation order, with xmippCore's 3-D
+ * applyGeometry (LINEAR and BSPLINE3, WRAP and DONT_WRAP) and the 3-D spline prefilter behind it. Everything is fp64; volumes are
+ * [Z][Y][X], logical coordinates start at -(dim / 2). xmippCore is not in the reference tree: applyGeometry is the 2-D branch the oracle
+ * restates (oracle/xo_bspline.cpp:89-217) with a z axis added; source coordinates are computed directly (x A00 + y A01 + z A02), not by
+ * adding A00 along the row. The kernels and the behaviours kept as written are listed at the head of xmipp3_amd/csrc/xh_sym.hip.
+ * create: a box of 2 .. 1024 a side; Z = 1 makes a handle for image stacks (symmetrize_images only), Z >= 2 one for volumes. */
+typedef struct xh_sym xh_sym;
+int xh_sym_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, xh_sym **out);
+int xh_sym_destroy(xh_sym *h);
+/* the list of a point group: h_R [n][3][3], row-major, the R of SymList::getMatrices without the identity, n = SL.symsNo() (0 .. 1024).
+ * Entry i is applied as applyGeometry(.., R.transpose(), IS_NOT_INV, ..) (symmetrize.cpp:150-159): the kernel reads inv(R^T), formed by
+ * cofactors. Refused: entries that are not finite, singular matrices, inverses with an entry above 1000 */
+int xh_sym_set_matrices(xh_sym *h, const double *h_R, int32_t n);
+/* symmetrizeVolume without helix and mask (symmetrize.cpp:117-169): d_out = (V_in + sum_i applyGeometry(degree, V_in, R_i^T, wrap, avg)) times
+ * 1.0 / (n + 1.0f) unless sum; avg is the outside mean when !wrap (do_outside_avg = !wrap, :263), else 0. degree 1 or 3 (3: the
+ * coefficients are formed first). The sum is kept in a register in the list's order; d_out may not be d_in */
+int xh_sym_symmetrize(xh_sym *h, const double *d_in, int32_t degree, int32_t wrap, int32_t sum, double *d_out);
+/* symmetrizeImage (symmetrize.cpp:187-214) of a stack d_in [n][Y][X] in one launch, on a Z = 1 handle: I + sum_{i=1}^{order-1}
+ * rotate(degree, I, 360.0 / order * i, 'Z', wrap, avg), times 1.0 / order unless sum; avg per image over r^2 >= (min(X, Y) / 2)^2 when !wrap */
+int xh_sym_symmetrize_images(xh_sym *h, const double *d_in, int32_t n, int32_t order, int32_t degree, int32_t wrap, int32_t sum, double *d_out);
+/* symmetry_Helical (data/symmetries.cpp:1632-1705, mask == nullptr) with interpolatedElement3DHelical (:1577-1630); zHelical in voxels,
+ * the angles in radians. dihedral != 0 is symmetrizeVolume's helicalDihedral branch (symmetrize.cpp:172-179): the dihedral copies inside the
+ * helix, then rotate(degree, Vrotated, V_out, 180.0, 'X', WRAP) and (V_out + Vrotated) * 0.5. Refused, before any launch: Cn outside 1 .. 99,
+ * and parameters for which xh_sym_helical_depth gives -1 */
+int xh_sym_helical(xh_sym *h, const double *d_in, double zHelical, double rotHelical, double rotPhaseHelical, int32_t Cn, int32_t dihedral, double heightFraction,
+                   int32_t degree, double *d_out);
+/* host only: the depth interpolatedElement3DHelical's recursion reaches for the sample points of symmetry_Helical on Z planes: 0 or 1, or -1
+ * where it has no bound (zHelical <= 1 voxel, where the reference never terminates; zHelical > Z; heightFraction outside (0, 1]) */
+int xh_sym_helical_depth(int32_t Z, double zHelical, double heightFraction, int32_t dihedral, int32_t *depth);
+/* hooks for tests and later programs. apply_geometry3d: xmippCore applyGeometry(degree, V2, V1, A, IS_NOT_INV, wrap, outside) for one 3 x 3
+ * matrix h_A (row-major, no shifts); an A within 1e-6 of the identity copies (isIdentity). coefficients: produceSplineCoefficients(BSPLINE3)
+ * of a volume, x then y then z lines (d_out may be d_in). outside_mean: the mean over r^2 >= (min(dims) / 2)^2 (BinaryCircularMask
+ * OUTSIDE_MASK, data/mask.cpp:193-217; the radius by integer division, symmetrize.cpp:133-135), summed in a fixed order. Synchronous */
+int xh_sym_apply_geometry3d(xh_sym *h, const double *d_in, const double *h_A, int32_t degree, int32_t wrap, double outside, double *d_out);
+int xh_sym_coefficients(xh_sym *h, const double *d_in, double *d_out);
+int xh_sym_outside_mean(xh_sym *h, const double *d_in, double *h_mean);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[3] = the coefficients, the outside mean, the symmetry pass
+ * (the helix and its dihedral pass included), summed since set_timing */
+int xh_sym_set_timing(xh_sym *h, int32_t on);
+int xh_sym_stage_ms(const xh_sym *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,18 @@ SIGNATURES = {
     "xh_vsub_subtract": (C.c_int, [vp, vp, vp, vp, d, vp, vp]),
     "xh_vsub_set_timing": (C.c_int, [vp, i32]),
     "xh_vsub_stage_ms": (C.c_int, [vp, vp]),
+    "xh_sym_create": (C.c_int, [vp, i32, i32, i32, pvp]),
+    "xh_sym_destroy": (C.c_int, [vp]),
+    "xh_sym_set_matrices": (C.c_int, [vp, vp, i32]),
+    "xh_sym_symmetrize": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "xh_sym_symmetrize_images": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "xh_sym_helical": (C.c_int, [vp, vp, d, d, d, i32, i32, d, i32, vp]),
+    "xh_sym_helical_depth": (C.c_int, [i32, d, d, i32, C.POINTER(i32)]),
+    "xh_sym_apply_geometry3d": (C.c_int, [vp, vp, vp, i32, i32, d, vp]),
+    "xh_sym_coefficients": (C.c_int, [vp, vp, vp]),
+    "xh_sym_outside_mean": (C.c_int, [vp, vp, C.POINTER(C.c_double)]),
+    "xh_sym_set_timing": (C.c_int, [vp, i32]),
+    "xh_sym_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

@@ -1269,6 +1269,70 @@ class VolumeSubtraction(_StageTimes, _VolumeHandle):
         return out, v1f
 
 
+class Symmetrize(_StageTimes, _VolumeHandle):
+    """The device side of xmipp_transform_symmetrize: a volume through a point group or a helix, an image stack through a rotation order,
+    and xmippCore's 3-D applyGeometry and spline coefficients under them. float64 tensors on the device; a shape (1, Y, X) makes a handle for
+    image stacks [n, Y, X], any other a handle for volumes [Z, Y, X]."""
+
+    _destroy = "xh_sym_destroy"
+    _PREFIX = "sym"
+
+    STAGES = ("coefficients", "outside_mean", "pass")
+
+    def set_matrices(self, R):
+        """the R of SymList::getMatrices, [n, 3, 3] on the host, identity excluded"""
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1, 3, 3))
+        check(lib().xh_sym_set_matrices(self.h, _np_ptr(R), len(R)))
+        self.n_matrices = len(R)
+
+    def symmetrize(self, v, degree=3, wrap=True, sum=False):
+        """symmetrizeVolume over the matrices set: (V + sum_i applyGeometry(V, R_i^T)) / (n + 1), or the sum alone"""
+        out = self._new()
+        check(lib().xh_sym_symmetrize(self.h, _ptr(self._vol(v)), int(degree), int(bool(wrap)), int(bool(sum)), _ptr(out)))
+        return out
+
+    def symmetrize_images(self, imgs, order, degree=3, wrap=True, sum=False):
+        """symmetrizeImage of every image of a stack [n, Y, X] (a handle of shape (1, Y, X))"""
+        n = int(imgs.shape[0])
+        self._vol(imgs, "stack", shape=(n,) + self.shape[1:])
+        out = _torch().empty_like(imgs)
+        check(lib().xh_sym_symmetrize_images(self.h, _ptr(imgs), n, int(order), int(degree), int(bool(wrap)), int(bool(sum)), _ptr(out)))
+        return out
+
+    def helical(self, v, z_helical, rot_helical, rot_phase=0.0, cn=1, dihedral=False, height_fraction=0.95, degree=3):
+        """symmetry_Helical; z_helical in voxels, the angles in radians. dihedral: the helicalDihedral branch of symmetrizeVolume"""
+        out = self._new()
+        check(lib().xh_sym_helical(self.h, _ptr(self._vol(v)), float(z_helical), float(rot_helical), float(rot_phase), int(cn), int(bool(dihedral)),
+                                   float(height_fraction), int(degree), _ptr(out)))
+        return out
+
+    def apply_geometry3d(self, v, A, degree=3, wrap=True, outside=0.0):
+        """applyGeometry(degree, ., V, A, IS_NOT_INV, wrap, outside) for one 3 x 3 matrix on the host"""
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64).reshape(3, 3))
+        out = self._new()
+        check(lib().xh_sym_apply_geometry3d(self.h, _ptr(self._vol(v)), _np_ptr(A), int(degree), int(bool(wrap)), float(outside), _ptr(out)))
+        return out
+
+    def coefficients(self, v):
+        """produceSplineCoefficients(BSPLINE3) of a volume"""
+        out = self._new()
+        check(lib().xh_sym_coefficients(self.h, _ptr(self._vol(v)), _ptr(out)))
+        return out
+
+    def outside_mean(self, v):
+        """the mean over r^2 >= (min(shape) // 2)^2"""
+        m = C.c_double()
+        check(lib().xh_sym_outside_mean(self.h, _ptr(self._vol(v)), C.byref(m)))
+        return m.value
+
+
+def sym_helical_depth(Z, z_helical, height_fraction=0.95, dihedral=False):
+    """the depth the helical interpolation's recursion reaches on Z planes: 0 or 1, or -1 where Symmetrize.helical refuses (host only)"""
+    depth = C.c_int32()
+    check(lib().xh_sym_helical_depth(int(Z), float(z_helical), float(height_fraction), int(bool(dihedral)), C.byref(depth)))
+    return depth.value
+
+
 def vsub_radial_bins(shape):
     """(the bins of the radial average of a [Z, Y, X] box, the largest bin its octant writes); --radavg is refused where the second
     reaches the first (host only)"""

@@ -282,13 +282,23 @@ inline ImageInfo readInfo(const std::string &path)
 
 // reads image `index` (1-based for stacks; 0 => the only image / whole volume) as float
 // the bytes of one image as the file holds them (I.mode tells what they are): the movie program sends counts to the device
+// consecutive reads usually hit the same stack: its header and its stream are kept, one per host thread. A program that rewrites a
+// file it has read (xmipp_transform_symmetrize without -o) calls forgetImageReadCache() after the write, so that the next read of the
+// same process opens the file anew
+struct ImageReadCache { std::string path; ImageInfo info; std::ifstream f; };
+inline ImageReadCache &imageReadCache() { static thread_local ImageReadCache c; return c; }
+inline void forgetImageReadCache()
+{
+    ImageReadCache &c = imageReadCache();
+    c.f.close();
+    c.f.clear();
+    c.path.clear();
+}
+
 inline void readImageRaw(const std::string &name, std::vector<unsigned char> &raw, ImageInfo &I)
 {
     FileName fn(name);
-    // consecutive reads usually hit the same stack: keep its header and its stream (one per host thread; a file
-    // that is rewritten between reads of the same process must not be read through this cache -- none is)
-    struct Cached { std::string path; ImageInfo info; std::ifstream f; };
-    static thread_local Cached cache;
+    ImageReadCache &cache = imageReadCache();
     if (cache.path != fn.path || !cache.f.is_open()) {
         cache.info = readInfo(fn.path);
         cache.f.close();
@@ -433,6 +443,7 @@ public:
 
 // ------------------------------------------------------------------ symmetries (cyclic groups)
 class SymList {
+    bool closure = true;
     // rotation by 360/fold about axis (unit-normalised), Rodrigues
     static std::vector<double> rotAxis(double ang, double x, double y, double z)
     {
@@ -461,6 +472,16 @@ class SymList {
     void close(const std::vector<std::vector<double>> &gens)
     {
         const std::vector<double> I = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (!closure) {
+            // accuracy = -1 (--no_group of xmipp_transform_symmetrize): the fold - 1 powers of every generator line, no products between lines
+            R.clear();
+            for (const auto &g : gens)
+                for (auto P = g; !same(P, I); P = mul(P, g)) {
+                    R.push_back(P);
+                    if (R.size() > 240) REPORT_ERROR(ERR_VALUE_INCORRECT, "SymList: a generator has no finite order");
+                }
+            return;
+        }
         std::vector<std::vector<double>> G = {I};
         bool grew = true;
         while (grew) {
@@ -505,8 +526,10 @@ public:
     // determinant -1 as well; the left matrices L of xmippCore are not kept: the reference's reconstruction
     // reads R only (reconstruct_fourier_accel.cpp:252-254) and its sampling fixtures are met with L = I
     // (tests/test_sampling.py).
-    void readSymmetryFile(const std::string &sym)
+    // accuracy > 0 (the default of every caller but one): the subgroup the lines generate; accuracy = -1: the lines' own powers only
+    void readSymmetryFile(const std::string &sym, double accuracy = 1e-6)
     {
+        closure = accuracy > 0;
         R.clear();
         std::ifstream f(sym);
         if (f.good()) {

@@ -1289,6 +1289,39 @@ int xh_sym_outside_mean(xh_sym *h, const double *d_in, double *h_mean);
 int xh_sym_set_timing(xh_sym *h, int32_t on);
 int xh_sym_stage_ms(const xh_sym *h, double *h_ms);
 
+/* ---- xmipp_volume_align (reconstruction/volume_align_prog.cpp, ProgAlignVolumes; CPU only in the reference): the fitness of many trials
+ * per pass over V1 and the mask, fp64. A trial is the reference's 10-vector p: flip, greyScale, greyShift, rot, tilt, psi, scale, z, y, x.
+ * Its Vaux = applyTransformation(V2, p, wrap) (:56-97) is never stored: the fit kernel forms every voxel of it in a register and adds what
+ * correlationIndex (method 1, COVARIANCE; the fit is minus the index) or rms (method 2, LEAST_SQUARES) need, within the mask (nonzero =
+ * inside). The kernels, the one-pass form of the sums and the behaviours kept are listed at the head of xmipp3_amd/csrc/xh_valign.hip.
+ * create: a box of 2 .. 1024 a side; capacity (1 .. 2^20) is the most trials of one launch. No output depends on it. */
+typedef struct xh_valign xh_valign;
+int xh_valign_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t capacity, xh_valign **out);
+int xh_valign_destroy(xh_valign *h);
+/* uploads V1, V2 [Z][Y][X] and the mask (null: every voxel) from the host, and forms n, mean_x, stddev_x (computeAvgStdev's rule with the
+ * integer N / (N - 1)) and S0 = sum (x - mean_x) of V1 within the mask, in raster order. stats: those four, h_stats[4]. Synchronous */
+int xh_valign_set_volumes(xh_valign *h, const double *h_V1, const double *h_V2, const int32_t *h_mask);
+int xh_valign_stats(const xh_valign *h, double *h_stats);
+/* host only: applyTransformation's A = Euler(rot, tilt, psi) with column 2 times flip, times T(x, y, z; z = -z + 1 for flip < 0), times
+ * S(scale), h_A [16] row-major; its inverse h_Ainv [16] (cofactor inverse of the 3 x 3 block, -Rinv t); ident: A within 1e-6 of the identity */
+int xh_valign_matrix(const double *h_p, double *h_A, double *h_Ainv, int32_t *ident);
+/* host only: the trials of the exhaustive search (:363-384) in the reference's order. h_ranges [9][3]: (first, last, step) of grey_scale,
+ * grey_shift, rot, tilt, psi, scale, z, y, x; a zero step is 1; the loop variables are doubles advanced by += and tested with <=.
+ * h_p [count][10] (null: count only); times (nullable): the progress bar's count (:330-352), which is not the trip count. Refused: more
+ * than `limit` trials, and a range whose loop would never end (a negative or vanishing step with first <= last) */
+int xh_valign_trials(const double *h_ranges, int32_t consider_mirror, int64_t limit, double *h_p, int64_t *count, int64_t *times);
+/* h_fit [m] = fitness(p) of every trial of h_p [m][10], any m, in launches of at most `capacity` trials. search: also the index and fit of
+ * the first minimum in trial order (fit < best, :388); h_fit may be null. Synchronous. Refused: a trial with an entry that is not finite
+ * or a singular matrix (scale 0) */
+int xh_valign_fit(xh_valign *h, const double *h_p, int64_t m, int32_t method, int32_t wrap, double *h_fit);
+int xh_valign_search(xh_valign *h, const double *h_p, int64_t m, int32_t method, int32_t wrap, int64_t *best_index, double *best_fit, double *h_fit);
+/* d_out [Z][Y][X] = applyTransformation(V2, p, wrap), the grey values included. Synchronous */
+int xh_valign_apply(xh_valign *h, const double *h_p, int32_t wrap, double *d_out);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[3] = gather and workgroup sums, finish, choice, summed since
+ * set_timing */
+int xh_valign_set_timing(xh_valign *h, int32_t on);
+int xh_valign_stage_ms(const xh_valign *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

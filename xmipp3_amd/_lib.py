@@ -279,6 +279,17 @@ SIGNATURES = {
     "xh_sym_outside_mean": (C.c_int, [vp, vp, C.POINTER(C.c_double)]),
     "xh_sym_set_timing": (C.c_int, [vp, i32]),
     "xh_sym_stage_ms": (C.c_int, [vp, vp]),
+    "xh_valign_create": (C.c_int, [vp, i32, i32, i32, i32, pvp]),
+    "xh_valign_destroy": (C.c_int, [vp]),
+    "xh_valign_set_volumes": (C.c_int, [vp, vp, vp, vp]),
+    "xh_valign_stats": (C.c_int, [vp, vp]),
+    "xh_valign_matrix": (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
+    "xh_valign_trials": (C.c_int, [vp, i32, i64, vp, C.POINTER(i64), C.POINTER(i64)]),
+    "xh_valign_fit": (C.c_int, [vp, vp, i64, i32, i32, vp]),
+    "xh_valign_search": (C.c_int, [vp, vp, i64, i32, i32, C.POINTER(i64), C.POINTER(C.c_double), vp]),
+    "xh_valign_apply": (C.c_int, [vp, vp, i32, vp]),
+    "xh_valign_set_timing": (C.c_int, [vp, i32]),
+    "xh_valign_stage_ms": (C.c_int, [vp, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

@@ -1333,6 +1333,86 @@ def sym_helical_depth(Z, z_helical, height_fraction=0.95, dihedral=False):
     return depth.value
 
 
+class VolumeAlign(_StageTimes, _VolumeHandle):
+    """The device side of xmipp_volume_align: the fitness of many trials per pass over V1 and the mask. A trial is the reference's
+    10-vector (flip, greyScale, greyShift, rot, tilt, psi, scale, z, y, x); volumes, masks and trials come from the host as numpy arrays.
+    capacity: the most trials of one launch; no result depends on it."""
+
+    _destroy = "xh_valign_destroy"
+    _PREFIX = "valign"
+
+    STAGES = ("gather", "finish", "select")
+    COVARIANCE, LEAST_SQUARES = 1, 2
+
+    def __init__(self, ctx, shape, capacity=256):
+        super().__init__(ctx, shape, int(capacity))
+        self.capacity = int(capacity)
+
+    def set_volumes(self, V1, V2, mask=None):
+        """V1 (fixed) and V2 (moved), float64 [Z, Y, X]; mask: int32, nonzero = inside, or None"""
+        V1 = np.ascontiguousarray(V1, np.float64)
+        V2 = np.ascontiguousarray(V2, np.float64)
+        if V1.shape != self.shape or V2.shape != self.shape:
+            raise XhError(f"VolumeAlign: volumes of shape {V1.shape} and {V2.shape}, the handle {self.shape}")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32)
+            if mask.shape != self.shape:
+                raise XhError(f"VolumeAlign: the mask has shape {mask.shape}, the handle {self.shape}")
+        check(lib().xh_valign_set_volumes(self.h, _np_ptr(V1), _np_ptr(V2), _np_ptr(mask)))
+
+    def stats(self):
+        """(n, mean_x, stddev_x, sum (x - mean_x)) of V1 within the mask"""
+        s = np.zeros(4)
+        check(lib().xh_valign_stats(self.h, _np_ptr(s)))
+        return tuple(s)
+
+    @staticmethod
+    def _trials(p):
+        return np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 10))
+
+    def fit(self, trials, method=1, wrap=True):
+        """fitness of every trial [m, 10]: minus correlationIndex (method 1) or rms (method 2) of V1 against the transformed V2"""
+        p = self._trials(trials)
+        out = np.zeros(len(p))
+        check(lib().xh_valign_fit(self.h, _np_ptr(p), len(p), int(method), int(bool(wrap)), _np_ptr(out)))
+        return out
+
+    def search(self, trials, method=1, wrap=True, fits=False):
+        """(index, fit) of the first minimum in trial order; with fits=True also every trial's fit"""
+        p = self._trials(trials)
+        out = np.zeros(len(p)) if fits else None
+        idx, best = C.c_int64(), C.c_double()
+        check(lib().xh_valign_search(self.h, _np_ptr(p), len(p), int(method), int(bool(wrap)), C.byref(idx), C.byref(best), _np_ptr(out)))
+        return (idx.value, best.value, out) if fits else (idx.value, best.value)
+
+    def apply(self, trial, wrap=True):
+        """applyTransformation(V2, trial, wrap) as a float64 device tensor"""
+        p = self._trials(trial)
+        assert len(p) == 1
+        out = self._new()
+        check(lib().xh_valign_apply(self.h, _np_ptr(p), int(bool(wrap)), _ptr(out)))
+        return out
+
+    @staticmethod
+    def matrix(trial):
+        """(A, Ainv, isIdentity) of a trial: 4 x 4 arrays (host only)"""
+        p = np.ascontiguousarray(trial, np.float64).reshape(10)
+        A, Ai, ident = np.zeros((4, 4)), np.zeros((4, 4)), C.c_int32()
+        check(lib().xh_valign_matrix(_np_ptr(p), _np_ptr(A), _np_ptr(Ai), C.byref(ident)))
+        return A, Ai, bool(ident.value)
+
+
+def valign_trials(ranges, consider_mirror=False, limit=1 << 21):
+    """the exhaustive search's trials [count, 10] in the reference's order and its progress-bar count (host only). ranges: (first, last,
+    step) of grey_scale, grey_shift, rot, tilt, psi, scale, z, y, x"""
+    r = np.ascontiguousarray(ranges, np.float64).reshape(9, 3)
+    n, times = C.c_int64(), C.c_int64()
+    check(lib().xh_valign_trials(_np_ptr(r), int(bool(consider_mirror)), int(limit), None, C.byref(n), C.byref(times)))
+    p = np.zeros((n.value, 10))
+    check(lib().xh_valign_trials(_np_ptr(r), int(bool(consider_mirror)), int(limit), _np_ptr(p), C.byref(n), None))
+    return p, times.value
+
+
 def vsub_radial_bins(shape):
     """(the bins of the radial average of a [Z, Y, X] box, the largest bin its octant writes); --radavg is refused where the second
     reaches the first (host only)"""

@@ -18,14 +18,14 @@
 //                   most one level deep for the parameters the entry point accepts (sy_helical_depth) and is written as two
 //                   nested levels. helicalDihedral: the pass with one matrix (180 degrees about X, WRAP), (V_out + Vrotated) * 0.5.
 //
+// The per-voxel applyGeometry (range test per axis, linear and cubic taps) and the cofactor inverse are in xh_applygeo.h, shared with xh_valign.hip.
 // xmippCore is not in the reference tree: applyGeometry's 3-D branch is its 2-D branch, as k_rs_apply of xh_rsig.hip has it,
 // with a z axis added. The one deviation: a source coordinate is x A00 + y A01 + z A02, not A00 added along the row.
 // Reference behaviours kept as written: the (int) truncation of the linear taps (a coordinate in (-1, 0) extrapolates from taps 0 and 1),
 // m2 >= dim -> 0 under wrap, the w != 0 && m2 < dim guards, one mirror per spline tap, 1.0 / (n + 1.0f), Llength + 1 terms of the helix
 // and its edge weights.
-#include "xh_volume.h"
+#include "xh_applygeo.h"
 #include "xh_reduce.h"
-#include "xh_bspline.h"
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -33,7 +33,6 @@
 
 namespace {
 
-constexpr double SY_ACC = 1e-6;        // XMIPP_EQUAL_ACCURACY
 constexpr double SY_PI = 3.14159265358979323846;
 constexpr int SY_MAX_MATRICES = 1024;
 constexpr int SY_MAX_CN = 99;          // "n must be an integer number with no more than 2 digits"
@@ -123,93 +122,6 @@ __global__ void __launch_bounds__(256) k_sy_outside_images(const double *__restr
         __syncthreads();
         xh_tree256(red, a);
         if (threadIdx.x == 0) avg[img] = red[0][0] / red[1][0];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------- sampling
-__device__ __forceinline__ int sy_clamp(int v, int n) { return min(max(v, 0), n - 1); }
-__device__ __forceinline__ int sy_mirror(int l, int n) { return sy_clamp(l < 0 ? -l - 1 : (l >= n ? 2 * n - l - 1 : l), n); }
-
-// one axis of applyGeometry's range test: true = the voxel gets the outside value (DONT_WRAP only)
-template <bool WRAP> __device__ __forceinline__ bool sy_axis(double &c, int dim)
-{
-    const int cen = dim / 2;
-    const double lo = -cen, hi = dim - cen - 1;
-    if (c < lo - SY_ACC || c > hi + SY_ACC) {
-        if (!WRAP) return true;
-        c = d_realwrap(c, lo - 0.5, hi + 0.5);
-    }
-    return false;
-}
-
-// the value of the source (degree 1: the volume; degree 3: its coefficients) at the logical point (xp, yp, zp), inside the range
-template <int DEG, bool WRAP>
-__device__ __forceinline__ double sy_interp3(const double *__restrict__ src, XhDims d, double xp, double yp, double zp)
-{
-    const size_t sy = d.X, sz = (size_t)d.Y * d.X;
-    if (DEG == 1) {
-        double wx = xp + d.X / 2;
-        int m1 = (int)wx;
-        wx = wx - m1;
-        int m2 = m1 + 1;
-        double wy = yp + d.Y / 2;
-        int n1 = (int)wy;
-        wy = wy - n1;
-        int n2 = n1 + 1;
-        double wz = zp + d.Z / 2;
-        int o1 = (int)wz;
-        wz = wz - o1;
-        int o2 = o1 + 1;
-        if (WRAP) {
-            if (m2 >= d.X) m2 = 0;
-            if (n2 >= d.Y) n2 = 0;
-            if (o2 >= d.Z) o2 = 0;
-        }
-        m1 = sy_clamp(m1, d.X); n1 = sy_clamp(n1, d.Y); o1 = sy_clamp(o1, d.Z);      // in range already; a stray coordinate reads inside
-        m2 = max(m2, 0); n2 = max(n2, 0); o2 = max(o2, 0);
-        const bool mx = wx != 0 && m2 < d.X, my = wy != 0 && n2 < d.Y, mz = wz != 0 && o2 < d.Z;
-        const double wx_1 = 1 - wx, wy_1 = 1 - wy, wz_1 = 1 - wz;
-        double tmp = wz_1 * wy_1 * wx_1 * src[o1 * sz + n1 * sy + m1];
-        if (mx) tmp += wz_1 * wy_1 * wx * src[o1 * sz + n1 * sy + m2];
-        if (my) {
-            tmp += wz_1 * wy * wx_1 * src[o1 * sz + n2 * sy + m1];
-            if (mx) tmp += wz_1 * wy * wx * src[o1 * sz + n2 * sy + m2];
-        }
-        if (mz) {
-            tmp += wz * wy_1 * wx_1 * src[o2 * sz + n1 * sy + m1];
-            if (mx) tmp += wz * wy_1 * wx * src[o2 * sz + n1 * sy + m2];
-            if (my) {
-                tmp += wz * wy * wx_1 * src[o2 * sz + n2 * sy + m1];
-                if (mx) tmp += wz * wy * wx * src[o2 * sz + n2 * sy + m2];
-            }
-        }
-        return tmp;
-    } else {
-        const double x = xp + d.X / 2, y = yp + d.Y / 2, z = zp + d.Z / 2;
-        const int l1 = (int)ceil(x - 2), m1 = (int)ceil(y - 2), n1 = (int)ceil(z - 2);
-        double wx[4], wy[4], wz[4];
-        d_bspline03_w4<double>(x, l1, wx);
-        d_bspline03_w4<double>(y, m1, wy);
-        d_bspline03_w4<double>(z, n1, wz);
-        int el[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) el[t] = sy_mirror(l1 + t, d.X);
-        double slices = 0;
-#pragma unroll
-        for (int tz = 0; tz < 4; ++tz) {
-            const double *pz = src + sy_mirror(n1 + tz, d.Z) * sz;
-            double columns = 0;
-#pragma unroll
-            for (int ty = 0; ty < 4; ++ty) {
-                const double *ref = pz + sy_mirror(m1 + ty, d.Y) * sy;
-                double rows = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) rows += ref[el[u]] * wx[u];
-                columns += rows * wy[ty];
-            }
-            slices += columns * wz[tz];
-        }
-        return slices;
     }
 }
 
@@ -514,17 +426,6 @@ k_sy_helical(const double *__restrict__ vin, XhDims d, SyHelix H, const double *
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host helpers
-// the inverse by cofactors: adjugate entries times 1 / det, det expanded along the first row (the tests' restatement forms it the same way)
-void sy_inv3x3(const double *A, double *B)
-{
-    const double a = A[0], b = A[1], c = A[2], d = A[3], e = A[4], f = A[5], g = A[6], h = A[7], i = A[8];
-    const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-    const double id = 1.0 / det;
-    B[0] = (e * i - f * h) * id; B[1] = (c * h - b * i) * id; B[2] = (b * f - c * e) * id;
-    B[3] = (f * g - d * i) * id; B[4] = (a * i - c * g) * id; B[5] = (c * d - a * f) * id;
-    B[6] = (d * h - e * g) * id; B[7] = (b * g - a * h) * id; B[8] = (a * e - b * d) * id;
-}
-
 // A (IS_NOT_INV) -> the record the kernels read
 int sy_make_mat(const char *who, const double *A, SyMat &M)
 {

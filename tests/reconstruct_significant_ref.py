@@ -412,3 +412,86 @@ def reference(D):
         gallery, _, _, images = population(D)
         _reference[D] = align_all(gallery, images, True)
     return _reference[D]
+
+
+# ---------------------------------------------------------------- weights past one tile of 256 and one block
+WEIGHT_D, WEIGHT_MAX_SHIFT, WEIGHT_ONE_ALPHA = 20, 3.0, 0.5
+WEIGHT_SEED = 42             # (41 drew a direction of (5, 300) whose five correlations are equal: nothing for one_alpha to split under 40 degrees)
+# (N, G): (volumes, directions per volume). The device ranks an image's G values through tiles of 256 (k_rs_image_weights) and a
+# direction's N values through tiles of 256 in blocks of 256 images (k_rs_direction_weights)
+WEIGHT_SHAPES = {(261, 12): (2, 6),          # N: two blocks, tiles 256 + 5
+                 (5, 300): (2, 150),         # G: tiles 256 + 44
+                 (257, 256): (1, 256)}       # N: a tile of one; G: one exact tile
+# (apply_fisher, use_imed, strict, max_shift)
+WEIGHT_OPTIONS = [(False, False, False, -1.0), (True, True, True, 3.0), (False, True, False, 3.0), (True, False, True, -1.0)]
+WEIGHT_ANG = (10.0, 40.0)
+_SIX = (np.array([0., 0., 0., 90., 180., 270.]), np.array([20., 28., 50., 90., 90., 120.]))   # 0 and 1 are 8 degrees apart, 2 is 30 from 0
+_weight_population, _weight_stage = {}, {}
+
+
+def weight_population(shape):
+    """Hand-made inputs of both weighting stages, (M [N, G, 3, 3], cc [N, G], imed [N, G], n_vols, rot [G], tilt [G]). cc: multiples of
+    1 / 64 in (0.05, 0.95), drawn towards the low end so that the Fisher limit of an image (a little below half its best correlation)
+    lies among the values its percentile keeps, and up to a level of the image's own (1, 0.84, 0.68, 0.51, 0.35 of the range, in turn), so that what an image
+    keeps lies on both sides of its directions' medians and --strictDirection has something to cut; imed: multiples of 1 / 8 in (1, 40): equal values are common. M: a rotation, for every
+    fourth pair a mirror, and a shift of up to 2.9 px per axis, for roughly a tenth of the pairs 3.1 .. 6 px on one axis"""
+    if shape not in _weight_population:
+        N, G = shape
+        nv, nd = WEIGHT_SHAPES[shape]
+        rng = np.random.default_rng(WEIGHT_SEED + N + G)
+        level = (1.0 - 0.65 * (np.arange(N) % 5) / 4.0)[:, None]
+        cc = (4 + np.floor(57 * level * rng.uniform(0, 1, shape) ** 2)) / 64.0
+        imed = rng.integers(9, 320, shape) / 8.0
+        ang = rng.uniform(0, 2 * np.pi, shape)
+        sh = rng.uniform(-2.9, 2.9, shape + (2,))
+        far = rng.uniform(0, 1, shape) < 0.1
+        axis = rng.integers(0, 2, shape)
+        big = rng.uniform(3.1, 6.0, shape) * np.where(rng.integers(0, 2, shape) == 1, 1.0, -1.0)
+        for a in range(2):
+            sh[..., a] = np.where(far & (axis == a), big, sh[..., a])
+        A = np.zeros(shape + (3, 3))
+        c, s = np.cos(ang), np.sin(ang)
+        flip = np.where(rng.integers(0, 4, shape) == 0, -1.0, 1.0)
+        A[..., 0, 0], A[..., 0, 1], A[..., 0, 2] = flip * c, flip * s, sh[..., 0]
+        A[..., 1, 0], A[..., 1, 1], A[..., 1, 2] = -s, c, sh[..., 1]
+        A[..., 2, 2] = 1.0
+        M = np.ascontiguousarray(np.linalg.inv(A))
+        if nd == 6:
+            rot, tilt = (np.tile(a, nv) for a in _SIX)
+        else:
+            dirs = synth.fibonacci_directions(nd)
+            rot, tilt = np.tile(dirs[:, 0], nv), np.tile(dirs[:, 1], nv)
+        _weight_population[shape] = (M, cc, imed, nv, rot, tilt)
+    return _weight_population[shape]
+
+
+def all_shifts(M):
+    """shifts_of for every pair -> (shiftX [N, G], shiftY [N, G])"""
+    N, G = M.shape[:2]
+    out = np.array([shifts_of(M[n, g])[1:3] for n in range(N) for g in range(G)]).reshape(N, G, 2)
+    return out[..., 0], out[..., 1]
+
+
+def direction_angles(rot, tilt, n_vols):
+    """the angles neighbour_counts compares with ang_distance: every ordered pair of different directions of one volume, in degrees"""
+    nd = len(rot) // n_vols
+    a, b = np.radians(rot), np.radians(tilt)
+    d = np.stack([np.sin(b) * np.cos(a), np.sin(b) * np.sin(a), np.cos(b)], 1)
+    return np.array([np.degrees(np.arccos(np.clip(d[v * nd + d1] @ d[v * nd + d2], -1.0, 1.0)))
+                     for v in range(n_vols) for d1 in range(nd) for d2 in range(nd) if d1 != d2])
+
+
+def weights_of(shape, ang_distance, options):
+    """weights() of a weight_population, with what the options share (the penalty per max_shift, the neighbour counts per
+    ang_distance, the per-image stage) computed once: the same calls in the same order as weights()"""
+    M, cc0, imed0, nv, rot, tilt = weight_population(shape)
+    apply_fisher, use_imed, strict, max_shift = options
+
+    def once(key, f):
+        if key not in _weight_stage:
+            _weight_stage[key] = f()
+        return _weight_stage[key]
+    cc, imed = once((shape, "penalise", max_shift), lambda: penalise(M, cc0, imed0, max_shift))
+    k = once((shape, "neighbours", ang_distance), lambda: neighbour_counts(rot, tilt, nv, ang_distance))
+    w = once((shape, "image", apply_fisher, use_imed, max_shift), lambda: image_weights(M, cc, imed, WEIGHT_D, WEIGHT_ONE_ALPHA, apply_fisher, use_imed, max_shift))
+    return once((shape, "direction", ang_distance, options), lambda: direction_weights(w, cc, k, WEIGHT_ONE_ALPHA, strict)), cc, imed

@@ -1,6 +1,7 @@
 """GPU tests of xmipp_reconstruct_significant's device side (xh_rsig_*): alignImagesConsideringMirrors of every (image, projection)
 pair against the numpy restatement (tests/reconstruct_significant_ref.py) chain by chain, the two weighting stages against their
-restatement, and the handle's argument checks.
+restatement, and the handle's argument checks. Batches of more than 256 chains and weights past one tile of 256 and one block of
+images: tests/test_gpu_reconstruct_significant_laps.py.
 
 Parity bound of align. A chain is about 10^2 reductions of D^2 fp64 terms; device and restatement differ in the order of every sum
 (trees against serial loops), in the line transforms (radix 2 / Bluestein against the oracle's) and in applyGeometry's source

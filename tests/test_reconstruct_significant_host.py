@@ -1,5 +1,6 @@
 """CPU checks of xmipp_reconstruct_significant: properties of the numpy restatement of alignImages (tests/reconstruct_significant_ref.py),
-the cumulative density function and both weightings by hand on tiny arrays, the branch population of the GPU parity cases, and the
+the cumulative density function and both weightings by hand on tiny arrays, the branch population of the GPU parity cases, the
+preconditions of the weight populations that pass one tile of 256 and one block (ties, margins, every option at work), and the
 program's option parsing, show() text and refusals, which all come before any device is touched."""
 import os
 import subprocess
@@ -224,3 +225,71 @@ def test_dont_reconstruct_forces_one_iteration(prog):
     assert "Setting iterations to 1 because of --dontReconstruct" in r.stdout
     assert "Number of iterations        : 1" in r.stdout.splitlines() and "Reconstruct                 : 0" in r.stdout.splitlines()
     assert [l.strip() for l in r.stdout.splitlines() if l.strip().startswith("iteration ")] == ["iteration 1: alpha 0.05, significance 0.95"]
+
+
+# ---------------------------------------------------------------- the weight populations past one tile and one block
+def _ties(v):
+    """(equal values inside the first 256 entries of v, an entry at 256 or later equal to one before 256)"""
+    head, tail = v[:256], v[256:]
+    return len(np.unique(head)) < len(head), bool(np.isin(tail, head).any())
+
+
+@pytest.mark.parametrize("shape", sorted(R.WEIGHT_SHAPES))
+def test_weight_populations_meet_their_preconditions(shape):
+    """What the device comparison of tests/test_gpu_reconstruct_significant.py rests on, asserted on the restatement for every pair:
+    equal values inside a tile of 256 and across the 255 | 256 boundary, along G (an image's ranking) and along N (a direction's); no
+    correlation within 1e-9 of its image's Fisher limit, no |shift| within 1e-9 of max_shift, no two directions within 1e-9 degrees of
+    ang_distance; every option changes the weights; under strict, one_alpha cuts some and keeps some in every image and direction.
+    (261, 12): blocks 256 + 5 of images, tiles 256 + 5 over N. (5, 300): tiles 256 + 44 over G. (257, 256): a tile of one over N, one
+    exact tile over G. The ranks are integer quotients formed the same way on both sides and need no margin"""
+    N, G = shape
+    M, cc0, imed0, nv, rot, tilt = R.weight_population(shape)
+    assert (N > 256 or G > 256) and G == nv * (G // nv)
+    assert np.all((cc0 > 0.05) & (cc0 < 0.95) & (cc0 * 64 == np.round(cc0 * 64))) and np.all((imed0 > 1) & (imed0 < 40) & (imed0 * 8 == np.round(imed0 * 8)))
+    sx, sy = R.all_shifts(M)
+    far = (np.abs(sx) > R.WEIGHT_MAX_SHIFT) | (np.abs(sy) > R.WEIGHT_MAX_SHIFT)
+    assert 0.05 < far.mean() < 0.2
+    assert min(np.abs(np.abs(sx) - R.WEIGHT_MAX_SHIFT).min(), np.abs(np.abs(sy) - R.WEIGHT_MAX_SHIFT).min()) >= 1e-9
+    ang = R.direction_angles(rot, tilt, nv)
+    for a in R.WEIGHT_ANG:
+        assert np.abs(ang - a).min() >= 1e-9
+    assert (ang < 10.0).sum() < (ang < 40.0).sum()
+    for max_shift in (-1.0, R.WEIGHT_MAX_SHIFT):
+        cc, imed = R.penalise(M, cc0, imed0, max_shift)
+        # ties, in the values the kernels rank
+        rows = [_ties(cc[n]) + _ties(imed[n]) for n in range(N)]
+        cols = [_ties(cc[:, g]) for g in range(G)]
+        assert any(r[0] for r in rows) and any(r[2] for r in rows) and any(c[0] for c in cols)
+        if G > 256:
+            assert any(r[1] for r in rows) and any(r[3] for r in rows), "no tie across the 255 | 256 boundary of an image's ranking"
+        if N > 256:
+            assert any(c[1] for c in cols), "no tie across the 255 | 256 boundary of a direction's ranking"
+        # the Fisher limit of every image against every correlation of it
+        best = cc.max(1)
+        ccl = np.tanh(0.5 * np.log((1 + best * R.WEIGHT_ONE_ALPHA) / (1 - best * R.WEIGHT_ONE_ALPHA)) - 2.96 * np.sqrt(1.0 / (R.WEIGHT_D * R.WEIGHT_D)))
+        assert np.all(np.isfinite(ccl)) and np.abs(cc - ccl[:, None]).min() >= 1e-9
+        # one_alpha cuts some and keeps some: in every image, and under strict in every direction for both neighbour counts
+        for n in range(N):
+            keep = R.cdf(cc[n]) >= R.WEIGHT_ONE_ALPHA
+            assert 0 < keep.sum() < G
+        for a in R.WEIGHT_ANG:
+            k = R.neighbour_counts(rot, tilt, nv, a)
+            for g in range(G):
+                keep = R.repeated_list_cdf(cc[:, g], 1 + int(k[g])) >= R.WEIGHT_ONE_ALPHA
+                assert 0 < keep.sum() < N
+    # every option, flipped alone in each of the compared sets (at 40 degrees), changes the weights; so does ang_distance under strict
+    a = R.WEIGHT_ANG[1]
+    for fisher, use_imed, strict, max_shift in R.WEIGHT_OPTIONS:
+        w = R.weights_of(shape, a, (fisher, use_imed, strict, max_shift))[0]
+        assert 0 < np.count_nonzero(w) < w.size
+        for other in ((not fisher, use_imed, strict, max_shift), (fisher, not use_imed, strict, max_shift), (fisher, use_imed, not strict, max_shift),
+                      (fisher, use_imed, strict, -1.0 if max_shift > 0 else R.WEIGHT_MAX_SHIFT)):
+            assert not np.array_equal(R.weights_of(shape, a, other)[0], w), (shape, a, other)
+    for options in R.WEIGHT_OPTIONS:
+        if options[2]:
+            assert not np.array_equal(R.weights_of(shape, 10.0, options)[0], R.weights_of(shape, 40.0, options)[0]), options
+    # the shared stages are weights() itself
+    o = R.WEIGHT_OPTIONS[1]
+    plain = R.weights(M, cc0, imed0, R.WEIGHT_D, nv, rot, tilt, 40.0, R.WEIGHT_ONE_ALPHA, *o)
+    for x, y in zip(plain, R.weights_of(shape, 40.0, o)):
+        assert np.array_equal(x, y)

@@ -1,6 +1,7 @@
 """CPU checks of the xmipp_volume_align restatement (tests/volume_align_ref.py) and of the library's host-only entries: xh_valign_matrix
 against numpy, xh_valign_trials against the reference's loops in Python, the restatement's search on a planted pose, the preconditions of
-every device case, and the derivation of the device tests' bound. None needs a device."""
+every device case (the boxes of 288 and 560 bricks, the tile cases, the lists of the long search and the degenerate exits among them),
+the derivation of the device tests' bound, and the restatement against the exact sums (R.fitness_exact). None needs a device."""
 import math
 
 import numpy as np
@@ -101,13 +102,20 @@ def test_onepass_identity_and_stats():
     assert abs(R.correlation_index(V1, V1, mask) - 1.0) <= 1e-14
 
 
+def _rel(a, b):
+    return float((np.abs(np.asarray(a) - b) / np.maximum(1.0, np.abs(b))).max())
+
+
 def test_device_cases_meet_their_preconditions_and_give_the_bound():
     """The tolerance of the device tests, and the preconditions of their cases, on the restatement alone.
     Preconditions: no tested coordinate of any trial within 1e-9 of a threshold min - 1e-6 / max + 1e-6, none within 1e-9 of a wrap edge
     (0 found: no case and no voxel is left out); the best trial beats the runner-up by at least 1e-6.
     Bound: for every trial of every case the two-pass fit and the one-pass identity form; 16 times their largest difference relative to
-    max(1, |fit|), rounded up to a power of ten, is R.BOUND."""
-    worst = 0.0
+    max(1, |fit|), rounded up to a power of ten, is R.BOUND. The cases include the boxes of 288 and 560 bricks (R.BIG_SHAPES: smallest
+    margin 1.0e-6, 0 edge voxels, largest difference 4.4e-16, under the 5.0e-16 of the smaller boxes).
+    Exact sums: the device adds the 10^5 terms of those boxes in another order than numpy, so the device tests assert against
+    R.fitness_exact (math.fsum); here the restatement, in both forms, must lie within R.BOUND of it too (largest: 6.1e-16)."""
+    worst, exact = 0.0, {}
     for shape, method, wrap, masked in R.parity_cases():
         tr = R.trial_list(shape, method, wrap)
         margin, edge = R.preconditions(shape, tr, wrap)
@@ -118,6 +126,94 @@ def test_device_cases_meet_their_preconditions_and_give_the_bound():
         _, _, one = R.search(V1, V2, tr, method, wrap, mask, onepass=True)
         assert np.sort(two)[1] - best >= 1e-6, (shape, method, wrap, masked, two)
         worst = max(worst, float((np.abs(two - one) / np.maximum(1.0, np.abs(two))).max()))
+        ex = np.array([R.fitness_exact(V1, V2, p, method, wrap, mask) for p in tr])
+        exact[shape] = max(exact.get(shape, 0.0), _rel(two, ex), _rel(one, ex))
     print(f"largest relative difference of the two-pass and one-pass fits: {worst:.3e}")
+    for shape, v in exact.items():
+        print(f"{shape}, {R.bricks(shape)} bricks: restatement to exact sums {v:.3e}")
+        assert v <= R.BOUND
     assert worst > 0
     assert R.BOUND == 10.0 ** math.ceil(math.log10(16 * worst))
+    assert [R.bricks(s) for s in R.BIG_SHAPES] == [288, 560] and all(d % 8 and d % 4 for s in R.BIG_SHAPES for d in s)
+
+
+def test_exact_fit_is_the_restatement_with_exact_sums():
+    """on values whose sums are exact in any order (multiples of 1/8 below 2^10) the two agree to the finish's own rounding"""
+    rng = np.random.default_rng(5)
+    shape = (9, 10, 12)
+    V1, V2 = (rng.integers(-40, 41, shape) / 8.0 for _ in range(2))
+    mask = R.case_mask(shape, True)
+    ident = [1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+    shift = [1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 2.0, -1.0, 3.0]
+    for p, method, m in ((ident, R.LEAST_SQUARES, None), (shift, R.LEAST_SQUARES, mask), (ident, R.COVARIANCE, mask), (shift, R.COVARIANCE, None)):
+        a, b = R.fitness(V1, V2, p, method, True, m, onepass=True), R.fitness_exact(V1, V2, p, method, True, m)
+        assert abs(a - b) <= 4 * np.finfo(float).eps, (p, method, a, b)
+    assert R.fitness_exact(V1, V2, ident, R.LEAST_SQUARES, True) == math.sqrt(float(((V1 - V2) ** 2).sum()) / V1.size)
+    # the exits: n = 0, n = 1, no deviation
+    none, one = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    one[4, 5, 6] = 1
+    for method in (R.COVARIANCE, R.LEAST_SQUARES):
+        for mk in (none, one):
+            assert R.fitness_exact(V1, V2, shift, method, True, mk) == R.fitness(V1, V2, shift, method, True, mk)
+    assert R.fitness_exact(np.full(shape, 0.37), V2, shift, R.COVARIANCE, True) == 0
+
+
+def test_tile_cases_reach_a_second_tile():
+    """13 and 10 trials at capacities 8, 9, 13 and 64: launches and their tiles (blockIdx.y) as the device cuts them"""
+    assert R.launches(13, 8) == [[8], [5]] and R.launches(13, 9) == [[8, 1], [4]] and R.launches(13, 13) == R.launches(13, 64) == [[8, 5]]
+    assert R.launches(10, 8) == [[8], [2]] and R.launches(10, 9) == [[8, 1], [1]] and R.launches(10, 13) == R.launches(10, 64) == [[8, 2]]
+    assert R.launches(13, 5) == [[5], [5], [3]]                        # the capacity of every other test: one tile per launch
+    for method, wrap, masked in R.TILE_CASES:
+        assert len(R.trial_list((17, 17, 17), method, wrap)) == (13 if method == R.LEAST_SQUARES else 10)
+        assert ((17, 17, 17), method, wrap, masked) in R.parity_cases()     # preconditions and bound: the test above
+
+
+def test_long_search_lists():
+    """588 trials in one launch: preconditions (margin 1.7e-6, 0 edge voxels, the best 5.8e-3 below the runner-up) and where the copies of
+    the best trial fall in k_va_select's chunks"""
+    tr, fits, best, lists = R.long_search()
+    assert len(tr) == 588 and np.array_equal(tr[best], R.PLANTED)
+    margin, edge = R.preconditions(R.LONG_SHAPE, tr, R.LONG_WRAP)
+    print(f"margin {margin:.3e}, edge voxels {edge}, best below the runner-up by {np.sort(fits)[1] - fits[best]:.3e}")
+    assert margin >= 1e-9 and edge == 0 and np.sort(fits)[1] - fits[best] >= 1e-6
+    at = {k: list(np.flatnonzero(v == best)) for k, v in lists.items()}
+    assert at == {"planted": [4, 5, 299, 300, 301, 302, 594], "late": [297, 298, 299, 300, 592], "last": [588]}
+    assert {k: len(v) for k, v in lists.items()} == {"planted": 595, "late": 593, "last": 589}
+    # one launch of everything: per = 3
+    assert all(R.select_chunks(len(v)) == 3 for v in lists.values())
+    assert 4 // 3 == 5 // 3 and 299 // 3 + 1 == 300 // 3 and 595 % 3 == 1 and 297 // 3 == 299 // 3 and 299 // 3 + 1 == 300 // 3 and 589 % 3 == 1
+    # launches of 300: per = 2 in each, the copies at 299 | 300 in two launches, local 1 | 2 of the second in two chunks
+    assert R.select_chunks(300) == 2 and R.select_chunks(295) == 2 and R.select_chunks(289) == 2 and (301 - 300) // 2 + 1 == (302 - 300) // 2
+    assert 297 // 2 + 1 == 298 // 2 and 295 % 2 == 1 and 289 % 2 == 1
+    assert R.select_chunks(256) == 1
+    # the first minimum of every list, by the reference's rule
+    for name, v in lists.items():
+        idx, b, f = R.search(*R.volumes(R.LONG_SHAPE, R.LONG_WRAP), tr[v[:6]], R.LONG_METHOD, R.LONG_WRAP)
+        assert np.array_equal(f, fits[v[:6]])                          # a list's fits are the pool's
+        assert int(np.argmin(fits[v])) == at[name][0]
+
+
+def test_degenerate_cases_meet_their_preconditions():
+    """margins and wrap edges of every degenerate case (the box 2 x 3 x 5 among them: margin 1.0e-6, 0 edge voxels), what each exit returns
+    on the restatement, and the restatement against the exact sums"""
+    cases = R.degenerate_cases()
+    worst = 0.0
+    for name, (shape, V1, V2, mask, _) in cases.items():
+        for method in (R.COVARIANCE, R.LEAST_SQUARES):
+            for wrap in (True, False):
+                tr = R.degenerate_trials(name, method, wrap)
+                margin, edge = R.preconditions(shape, tr, wrap)
+                assert margin >= 1e-9 and edge == 0, (name, method, wrap, margin, edge)
+                fits = R.search(V1, V2, tr, method, wrap, mask)[2]
+                ex = np.array([R.fitness_exact(V1, V2, p, method, wrap, mask) for p in tr])
+                worst = max(worst, _rel(fits, ex))
+                if name == "mask of zeros" or (method == R.COVARIANCE and name in ("mask of one voxel", "constant V1")):
+                    assert np.all(fits == 0), (name, method, wrap)
+                if name == "constant V2" and method == R.COVARIANCE and wrap:
+                    assert np.all(fits == 0)
+                if name.startswith("all outside") and not wrap:
+                    assert fits[-1] == (0 if method == R.COVARIANCE else R.rms(V1, np.zeros(shape), mask))
+    print(f"degenerate cases: restatement to exact sums {worst:.3e}")
+    assert worst <= R.BOUND
+    assert cases["mask of one voxel"][3].sum() == 1 and set(np.unique(cases["mask values 2 and -1"][3])) == {-1, 0, 2}
+    assert np.array_equal(cases["mask values 2 and -1"][3] != 0, R.case_mask(R.DEGENERATE_SHAPE, True) != 0)

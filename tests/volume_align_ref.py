@@ -6,7 +6,7 @@ xmippCore is not in the reference tree. correlationIndex follows oracle/xo_bspli
 a mask added; the trilinear rule, realWRAP and the range tests are tests/symmetrize_ref.py's. `onepass` switches the fit between the
 reference's two passes over Vaux (mean_y first, then sum (x - mean_x)(y - mean_y)) and the one-pass identity the device uses
 (sum (x - mean_x) y - mean_y sum (x - mean_x)); the device tolerance is derived from the difference of the two
-(tests/test_volume_align_ref.py)."""
+(tests/test_volume_align_ref.py). fitness_exact is the one-pass form with every sum taken exactly (math.fsum)."""
 import math
 
 import numpy as np
@@ -150,6 +150,31 @@ def fitness(V1, V2, p, method, wrap, mask=None, onepass=False, coords=None):
     return rms(V1, vaux, mask)
 
 
+def fitness_exact(V1, V2, p, method, wrap, mask=None):
+    """the fit from exact sums: the per-voxel fp64 terms of the one-pass form (y, y^2, (x - mean_x) y, (x - y)^2, and x, x^2, x - mean_x
+    for what depends on V1 alone), every sum taken with math.fsum (the correctly rounded sum of its terms, whatever their order), then the
+    finish in double as the device writes it. It decides whose rounding a difference between the device and the restatement is"""
+    vaux = apply_transformation(V2, p, wrap)
+    m = _inside(V1, mask)
+    xs, ys = V1[m], vaux[m]
+    n = xs.size
+    if method == LEAST_SQUARES:
+        if n == 0:
+            return 0.0
+        d = xs - ys
+        return math.sqrt(math.fsum(d * d) / n)
+    if n <= 1:
+        return -0.0
+    mean_x = math.fsum(xs) / n
+    sd_x = math.sqrt(abs((math.fsum(xs * xs) / n - mean_x * mean_x) * float(n // (n - 1))))
+    mean_y = math.fsum(ys) / n
+    sd_y = math.sqrt(abs((math.fsum(ys * ys) / n - mean_y * mean_y) * float(n // (n - 1))))
+    if abs(sd_x) < ACC or abs(sd_y) < ACC:
+        return -0.0
+    dx = xs - mean_x
+    return -((math.fsum(dx * ys) - mean_y * math.fsum(dx)) / ((sd_x * sd_y) * n))
+
+
 def stats(V1, mask=None):
     """what the device forms once: n, mean_x, stddev_x, sum (x - mean_x)"""
     xs = V1[_inside(V1, mask)]
@@ -251,7 +276,15 @@ def ftol_halfwidths(V1, V2, best, method, wrap, mask=None, ftol=0.01, only_shift
 
 
 # ---------------------------------------------------------------- the device tests' cases and bound
-SHAPES = [(16, 16, 16), (17, 17, 17), (9, 10, 12), (20, 18, 13)]
+# bricks are 8 x 8 x 4 (X, Y, Z). (29, 41, 43): 6 x 6 x 8 = 288 bricks, past one step of the finish's stride of 256; (37, 49, 57):
+# 8 x 7 x 10 = 560, so that threads 0 .. 47 of the finish add three bricks and the others two. Both leave a remainder on every axis
+BIG_SHAPES = [(29, 41, 43), (37, 49, 57)]
+SHAPES = [(16, 16, 16), (17, 17, 17), (9, 10, 12), (20, 18, 13)] + BIG_SHAPES
+
+
+def bricks(shape):
+    Z, Y, X = shape
+    return ((X + 7) // 8) * ((Y + 7) // 8) * ((Z + 3) // 4)
 # 16 times the largest relative difference (to max(1, |fit|)) between the two-pass fit and the one-pass identity over every trial of
 # parity_cases(), rounded up to a power of ten (tests/test_volume_align_ref.py derives and asserts it)
 BOUND = 1e-14
@@ -321,3 +354,93 @@ def preconditions(shape, tr, wrap):
     margin = min((threshold_margin(shape, t) for t in coords), default=np.inf)
     edge = int(wrap_edge_mask(shape, coords).sum()) if wrap else 0
     return margin, edge
+
+
+# ---------------------------------------------------------------- more than one tile of trials
+TILE = 8                                            # VA_TILE: the trials of one workgroup
+TILE_CAPACITIES = (8, 9, 13, 64)
+# (method, wrap, masked) on 17^3: 13, 13 and 10 trials
+TILE_CASES = [(LEAST_SQUARES, True, True), (LEAST_SQUARES, False, False), (COVARIANCE, True, False)]
+
+
+def launches(m, capacity):
+    """the trials of every launch of a list of m, and of every tile (blockIdx.y) of each"""
+    out = []
+    for t0 in range(0, m, capacity):
+        mb = min(capacity, m - t0)
+        out.append([min(TILE, mb - a) for a in range(0, mb, TILE)])
+    return out
+
+
+# ---------------------------------------------------------------- a search of more than 256 trials in one launch
+LONG_SHAPE, LONG_METHOD, LONG_WRAP = (9, 10, 12), COVARIANCE, True
+LONG_RANGES = [(1, 1, 1), (0, 0, 1), (1.7, 25.7, 4), (29.3, 53.3, 4), (-39.9, -15.9, 4), (0.93, 0.93, 1), (1.3, 1.3, 1), (-2.6, -2.6, 1), (0.4, 0.4, 1)]
+LONG_CAPACITIES = (1024, 300, 256)
+_LONG = {}
+
+
+def long_search():
+    """(pool of distinct trials [588, 10] with the restatement's fit of each, the index of the best in the pool, {name: indices into the
+    pool}): the lists of the long search. The best trial is taken out of its place in the grid (a filler takes it) and planted
+      "planted": at 4 and 5 (one chunk of k_va_select when per = 3), at 299 .. 302 and as the last of 595 entries.
+                 per = 3: 299 | 300 are the last of chunk 99 and the first of chunk 100; 595 = 198 . 3 + 1, the last chunk holds one trial.
+                 Launches of 300: 299 | 300 are the last of one launch and the first of the next, and 301 | 302 of the second launch
+                 (295 trials, per = 2, local 1 | 2) lie in two chunks; the last chunk holds one trial.
+      "late":    the same without the two at 4 and 5: the winner, 297, is the first of four; per = 3 keeps 297 .. 299 in chunk 99 and
+                 300 in chunk 100; launches of 300 (per = 2) cut 297 | 298 into two chunks and 300 into the next launch.
+      "last":    the last entry alone, index 588 of 589 = 196 . 3 + 1: a chunk of its own when per = 3 and when per = 2 (289 trials)."""
+    if not _LONG:
+        tr, _ = trials(LONG_RANGES, consider_mirror=True)
+        V1, V2 = volumes(LONG_SHAPE, LONG_WRAP)
+        idx, best, fits = search(V1, V2, tr, LONG_METHOD, LONG_WRAP)
+        filler = 0 if idx != 0 else 1
+        grid = [filler if t == idx else t for t in range(len(tr))]
+        planted = grid[:4] + [idx, idx] + grid[4:297] + [idx] * 4 + grid[297:] + [idx]
+        late = planted[:4] + planted[6:]
+        last = grid + [idx]
+        _LONG.update(tr=tr, fits=fits, best=idx, lists={"planted": np.array(planted), "late": np.array(late), "last": np.array(last)})
+    return _LONG["tr"], _LONG["fits"], _LONG["best"], _LONG["lists"]
+
+
+def select_chunks(m):
+    """per of k_va_select for a launch of m fits"""
+    return (m + 255) // 256
+
+
+# ---------------------------------------------------------------- degenerate exits
+DEGENERATE_SHAPE = (9, 10, 12)
+SMALLEST_SHAPE = (2, 3, 5)
+
+
+def degenerate_cases():
+    """{name: (shape, V1, V2, mask, {wrap: extra trials})}: what leaves the fit by an early exit. Every case runs R.trial_list of its shape
+    under both methods and both wraps, with the extra trials appended"""
+    shape = DEGENERATE_SHAPE
+    Z, Y, X = shape
+    V1, V2 = volumes(shape, True)
+    disc = case_mask(shape, True)
+    one = np.zeros(shape, np.int32)
+    one[Z // 2 + 1, Y // 2 - 2, X // 2 + 3] = 1
+    odd = disc.copy()
+    odd[disc != 0] = np.where(np.arange(int(disc.sum())) % 2 == 0, 2, -1)
+    # twice the box away along every axis: under dontWrap every voxel is outside, COVARIANCE gives 0 and LEAST_SQUARES rms(V1)
+    away = {False: [[1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 2.0 * Z, 2.0 * Y, 2.0 * X]], True: []}
+    none = {False: [], True: []}
+    s1, s2 = volumes(SMALLEST_SHAPE, True)
+    edge = np.ones(SMALLEST_SHAPE, np.int32)
+    edge[0, 0, 0] = edge[1, 2, 4] = 0
+    return {"mask of zeros": (shape, V1, V2, np.zeros(shape, np.int32), none),
+            "mask of one voxel": (shape, V1, V2, one, none),
+            "mask values 2 and -1": (shape, V1, V2, odd, none),
+            "constant V1": (shape, np.full(shape, 0.37), V2, None, none),
+            "constant V2": (shape, V1, np.full(shape, 0.37), None, none),
+            "all outside": (shape, V1, V2, None, away),
+            "all outside, masked": (shape, V1, V2, disc, away),
+            "2 x 3 x 5": (SMALLEST_SHAPE, s1, s2, None, none),
+            "2 x 3 x 5, masked": (SMALLEST_SHAPE, s1, s2, edge, none)}
+
+
+def degenerate_trials(name, method, wrap):
+    shape, _, _, _, extra = degenerate_cases()[name]
+    tr = trial_list(shape, method, wrap)
+    return np.concatenate([tr, np.array(extra[wrap], dtype=np.float64).reshape(-1, 10)])

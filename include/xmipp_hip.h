@@ -1322,6 +1322,66 @@ int xh_valign_apply(xh_valign *h, const double *h_p, int32_t wrap, double *d_out
 int xh_valign_set_timing(xh_valign *h, int32_t on);
 int xh_valign_stage_ms(const xh_valign *h, double *h_ms);
 
+/* ---- xmipp_volume_find_symmetry (libraries/reconstruction/volume_find_symmetry.cpp, ProgVolumeFindSymmetry; data/symmetries.cpp:1574-1705
+ * for the helix; CPU threads in the reference): the correlation of a volume with its own symmetrised copy for many trials per pass over
+ * the volume and the mask, fp64. No symmetrised volume is stored. The kernels, the behaviours kept, the deviations and the refusals are
+ * listed at the head of xmipp3_amd/csrc/xh_fsym.hip.
+ * create: a box of 2 .. 1024 a side; capacity (1 .. 2^20) is the most trials of one launch. No output depends on it. */
+typedef struct xh_fsym xh_fsym;
+int xh_fsym_create(xh_ctx *ctx, int32_t Z, int32_t Y, int32_t X, int32_t capacity, xh_fsym **out);
+int xh_fsym_destroy(xh_fsym *h);
+/* uploads V [Z][Y][X] and the mask (null: every voxel; nonzero = inside) from the host and forms n, mean, deviation and sum (x - mean) of
+ * V within the mask as xh_valign_set_volumes does (:390, :401 take correlationIndex within mask_prm's mask). splines != 0: also the cubic
+ * spline coefficients of V (--useSplines, :382-384), through xh_sym_coefficients. stats: those four values, h_stats[4]; clipped != 0:
+ * under the mask clipped for the last helical fit. Synchronous */
+int xh_fsym_set_volume(xh_fsym *h, const double *h_V, const int32_t *h_mask, int32_t splines);
+int xh_fsym_stats(const xh_fsym *h, int32_t clipped, double *h_stats);
+/* host only (:373-381): axis = row 2 of Euler_angles2matrix(rot, tilt, 0); h_A [rot_sym - 1][9] = rotation3DMatrix(360.0 / rot_sym * n, axis)
+ * for n = 1 .. rot_sym - 1, row-major; h_Ainv their cofactor inverses, which the kernel reads. Either may be null. rotation3DMatrix about
+ * an axis is not in the reference tree: the rotation about the unit axis in the sense of rotation3DMatrix(ang, 'Z') */
+int xh_fsym_axis_matrices(double rot, double tilt, int32_t rot_sym, double *h_A, double *h_Ainv);
+/* host only: the trials of an exhaustive search, two nested loops with double loop variables advanced by += and tested with <= (:221-225
+ * rot outer, tilt inner; :293-303 rot outer, z inner). h_p [count][2] = (outer, inner) (null: count only); n_outer, n_inner (nullable):
+ * ydim and xdim of the correlation map (:292-303). Refused: more than `limit` trials, and a loop that would never end */
+int xh_fsym_grid(double first0, double last0, double step0, double first1, double last1, double step1, int64_t limit, double *h_p, int64_t *count, int64_t *n_outer,
+                 int64_t *n_inner);
+/* host only (:396-399): gated = 1 where evaluateSymmetry returns 1e38 without any work: zHelical < 0 || zHelical > 0.4 Z, or outside the
+ * search box [z0, zF] x [rot0, rotF]. zHelical in voxels */
+int xh_fsym_helical_gate(int32_t Z, double zHelical, double rotHelical, double z0, double zF, double rot0, double rotF, int32_t *gated);
+/* host only: the depth interpolatedElement3DHelical's recursion (symmetries.cpp:1577-1630) reaches for the sample points of the masked
+ * symmetry_Helical this program calls: 0, or 1 for the dihedral copies over an even Z covered entirely with 1 <= zHelical <= Z, or -1
+ * where it has no bound or the reference divides by zero (zHelical <= 0, heightFraction outside (0, 1], those dihedral copies with
+ * zHelical < 1 or > Z). xh_sym_helical_depth is the bound of the unmasked caller and stays as it is */
+int xh_fsym_helical_depth(int32_t Z, double zHelical, double heightFraction, int32_t dihedral, int32_t *depth);
+/* --sym rot (:364-391): h_corr [m] = correlationIndex(V, V + sum_n applyGeometry(V, A_n), mask) of every trial (rot, tilt) of
+ * h_rot_tilt [m][2], any m, in launches of at most `capacity` trials; LINEAR, or BSPLINE3 when set_volume had splines; DONT_WRAP. search:
+ * also the first trial whose correlation is strictly above the running best, which starts at 0 (:167, :188): best_index -1 and best_corr 0
+ * where none is, and the caller answers rot = tilt = 0. h_corr may be null in search. Synchronous. Refused: rot_sym outside 2 .. 99,
+ * entries that are not finite */
+int xh_fsym_axis_fit(xh_fsym *h, const double *h_rot_tilt, int64_t m, int32_t rot_sym, double *h_corr);
+int xh_fsym_axis_search(xh_fsym *h, const double *h_rot_tilt, int64_t m, int32_t rot_sym, int64_t *best_index, double *best_corr, double *h_corr);
+/* --sym helical | helicalDihedral (:392-417): h_corr [m] = correlationIndex(V, symmetry_Helical(V, z, DEG2RAD(rot), 0, mask, dihedral,
+ * heightFraction, Cn), mask) of every trial (rot in degrees, z in voxels: the order of Powell's p, :324-325) of h_rot_z [m][2]. The mask
+ * is the one of set_volume zeroed outside [zFirst, zLast] of heightFraction (:280-288), on a copy. h_box (nullable) = z0, zF, rot0, rotF: a
+ * trial the gate refuses gets -1e38 on the host without a launch and is never chosen. search: as for the axis. Refused: Cn outside 1 .. 99,
+ * entries that are not finite, an ungated trial for which xh_fsym_helical_depth gives -1 */
+int xh_fsym_helical_fit(xh_fsym *h, const double *h_rot_z, int64_t m, const double *h_box, int32_t dihedral, double heightFraction, int32_t Cn, double *h_corr);
+int xh_fsym_helical_search(xh_fsym *h, const double *h_rot_z, int64_t m, const double *h_box, int32_t dihedral, double heightFraction, int32_t Cn, int64_t *best_index,
+                           double *best_corr, double *h_corr);
+/* hooks for the tests: the materialised volume_sym of one trial, d_out [Z][Y][X] on the device. axis: every voxel (:378-389); helical:
+ * symmetry_Helical's Vout, 0 outside the clipped mask. Synchronous */
+int xh_fsym_axis_volume(xh_fsym *h, double rot, double tilt, int32_t rot_sym, double *d_out);
+int xh_fsym_helical_volume(xh_fsym *h, double rotHelical, double zHelical, int32_t dihedral, double heightFraction, int32_t Cn, double *d_out);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[3] = gather and workgroup sums, finish, choice, summed since
+ * set_timing */
+int xh_fsym_set_timing(xh_fsym *h, int32_t on);
+int xh_fsym_stage_ms(const xh_fsym *h, double *h_ms);
+/* host only, next to xh_halves_circular_mask: BinaryCylinderMask and BinaryTubeMask (data/mask.cpp:471-486, :261-276) with Mask::readParams'
+ * modes (:1388-1431): every parameter negative keeps the inside with the absolute values, every one positive the outside; a mix is
+ * refused. Kept as written: the cylinder takes |k - z0| <= H / 2, the tube |k| < H (no z0, no half) */
+int xh_halves_cylinder_mask(int32_t Z, int32_t Y, int32_t X, double R, double H, double x0, double y0, double z0, int32_t *h_mask);
+int xh_halves_tube_mask(int32_t Z, int32_t Y, int32_t X, double R1, double R2, double H, double x0, double y0, double z0, int32_t *h_mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,24 @@ SIGNATURES = {
     "xh_valign_apply": (C.c_int, [vp, vp, i32, vp]),
     "xh_valign_set_timing": (C.c_int, [vp, i32]),
     "xh_valign_stage_ms": (C.c_int, [vp, vp]),
+    "xh_fsym_create": (C.c_int, [vp, i32, i32, i32, i32, pvp]),
+    "xh_fsym_destroy": (C.c_int, [vp]),
+    "xh_fsym_set_volume": (C.c_int, [vp, vp, vp, i32]),
+    "xh_fsym_stats": (C.c_int, [vp, i32, vp]),
+    "xh_fsym_axis_matrices": (C.c_int, [d, d, i32, vp, vp]),
+    "xh_fsym_grid": (C.c_int, [d, d, d, d, d, d, i64, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    "xh_fsym_helical_gate": (C.c_int, [i32, d, d, d, d, d, d, C.POINTER(i32)]),
+    "xh_fsym_helical_depth": (C.c_int, [i32, d, d, i32, C.POINTER(i32)]),
+    "xh_fsym_axis_fit": (C.c_int, [vp, vp, i64, i32, vp]),
+    "xh_fsym_axis_search": (C.c_int, [vp, vp, i64, i32, C.POINTER(i64), C.POINTER(C.c_double), vp]),
+    "xh_fsym_helical_fit": (C.c_int, [vp, vp, i64, vp, i32, d, i32, vp]),
+    "xh_fsym_helical_search": (C.c_int, [vp, vp, i64, vp, i32, d, i32, C.POINTER(i64), C.POINTER(C.c_double), vp]),
+    "xh_fsym_axis_volume": (C.c_int, [vp, d, d, i32, vp]),
+    "xh_fsym_helical_volume": (C.c_int, [vp, d, d, i32, d, i32, vp]),
+    "xh_fsym_set_timing": (C.c_int, [vp, i32]),
+    "xh_fsym_stage_ms": (C.c_int, [vp, vp]),
+    "xh_halves_cylinder_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, vp]),
+    "xh_halves_tube_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, d, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "xh_powell_minimize_batch": (C.c_int, [i32, vp, i32, vp, vp, d, i32, BATCH_COST_FN, vp, vp, vp, vp]),
     "xh_ca2_defaults": (None, [C.POINTER(Ca2Params)]),

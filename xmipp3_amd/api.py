@@ -1413,6 +1413,139 @@ def valign_trials(ranges, consider_mirror=False, limit=1 << 21):
     return p, times.value
 
 
+class FindSymmetry(_StageTimes, _VolumeHandle):
+    """The device side of xmipp_volume_find_symmetry: the correlation of a volume with its own symmetrised copy for many trials per pass
+    over the volume and the mask. Axis trials are (rot, tilt) in degrees; helical trials are (rot in degrees, z in voxels), the order of
+    the reference's Powell vector. The volume, the mask and the trials come from the host as numpy arrays. capacity: the most trials of
+    one launch; no result depends on it."""
+
+    _destroy = "xh_fsym_destroy"
+    _PREFIX = "fsym"
+
+    STAGES = ("gather", "finish", "select")
+    GATED = -1e38
+
+    def __init__(self, ctx, shape, capacity=256):
+        super().__init__(ctx, shape, int(capacity))
+        self.capacity = int(capacity)
+
+    def set_volume(self, V, mask=None, splines=False):
+        """V float64 [Z, Y, X]; mask: int32, nonzero = inside, or None; splines: --useSplines for the axis fits"""
+        V = np.ascontiguousarray(V, np.float64)
+        if V.shape != self.shape:
+            raise XhError(f"FindSymmetry: a volume of shape {V.shape}, the handle {self.shape}")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32)
+            if mask.shape != self.shape:
+                raise XhError(f"FindSymmetry: the mask has shape {mask.shape}, the handle {self.shape}")
+        check(lib().xh_fsym_set_volume(self.h, _np_ptr(V), _np_ptr(mask), int(bool(splines))))
+
+    def stats(self, clipped=False):
+        """(n, mean, stddev, sum (x - mean)) of V within the mask; clipped: within the mask of the last helical fit"""
+        s = np.zeros(4)
+        check(lib().xh_fsym_stats(self.h, int(bool(clipped)), _np_ptr(s)))
+        return tuple(s)
+
+    @staticmethod
+    def _trials(p):
+        return np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 2))
+
+    @staticmethod
+    def _box(box):
+        return None if box is None else np.ascontiguousarray(box, np.float64).reshape(4)
+
+    def axis_fit(self, trials, rot_sym):
+        """correlationIndex(V, V + sum_n applyGeometry(V, A_n), mask) of every trial [m, 2]"""
+        p = self._trials(trials)
+        out = np.zeros(len(p))
+        check(lib().xh_fsym_axis_fit(self.h, _np_ptr(p), len(p), int(rot_sym), _np_ptr(out)))
+        return out
+
+    def axis_search(self, trials, rot_sym, corrs=False):
+        """(index, corr) of the first trial above every one before it and above 0; (-1, 0.0) where no correlation is above 0. With
+        corrs=True also every trial's correlation"""
+        p = self._trials(trials)
+        out = np.zeros(len(p)) if corrs else None
+        idx, best = C.c_int64(), C.c_double()
+        check(lib().xh_fsym_axis_search(self.h, _np_ptr(p), len(p), int(rot_sym), C.byref(idx), C.byref(best), _np_ptr(out)))
+        return (idx.value, best.value, out) if corrs else (idx.value, best.value)
+
+    def helical_fit(self, trials, box=None, dihedral=False, height_fraction=1.0, cn=1):
+        """the correlation of every trial [m, 2] = (rot, z); box = (z0, zF, rot0, rotF): trials the reference's gate refuses get GATED"""
+        p, b = self._trials(trials), self._box(box)
+        out = np.zeros(len(p))
+        check(lib().xh_fsym_helical_fit(self.h, _np_ptr(p), len(p), _np_ptr(b), int(bool(dihedral)), float(height_fraction), int(cn), _np_ptr(out)))
+        return out
+
+    def helical_search(self, trials, box=None, dihedral=False, height_fraction=1.0, cn=1, corrs=False):
+        p, b = self._trials(trials), self._box(box)
+        out = np.zeros(len(p)) if corrs else None
+        idx, best = C.c_int64(), C.c_double()
+        check(lib().xh_fsym_helical_search(self.h, _np_ptr(p), len(p), _np_ptr(b), int(bool(dihedral)), float(height_fraction), int(cn), C.byref(idx),
+                                           C.byref(best), _np_ptr(out)))
+        return (idx.value, best.value, out) if corrs else (idx.value, best.value)
+
+    def axis_volume(self, rot, tilt, rot_sym):
+        """the materialised volume_sym of one axis trial as a float64 device tensor (a test hook)"""
+        out = self._new()
+        check(lib().xh_fsym_axis_volume(self.h, float(rot), float(tilt), int(rot_sym), _ptr(out)))
+        return out
+
+    def helical_volume(self, rot, z, dihedral=False, height_fraction=1.0, cn=1):
+        """symmetry_Helical's masked output of one trial as a float64 device tensor (a test hook)"""
+        out = self._new()
+        check(lib().xh_fsym_helical_volume(self.h, float(rot), float(z), int(bool(dihedral)), float(height_fraction), int(cn), _ptr(out)))
+        return out
+
+
+def fsym_axis_matrices(rot, tilt, rot_sym):
+    """(A, Ainv) [rot_sym - 1, 3, 3]: rotation3DMatrix(360 / rot_sym * n, row 2 of Euler(rot, tilt, 0)) and the inverses (host only)"""
+    n = min(max(int(rot_sym) - 1, 1), 98)                   # an order outside 2 .. 99 is refused by the library
+    A, Ai = np.zeros((n, 3, 3)), np.zeros((n, 3, 3))
+    check(lib().xh_fsym_axis_matrices(float(rot), float(tilt), int(rot_sym), _np_ptr(A), _np_ptr(Ai)))
+    return A, Ai
+
+
+def fsym_grid(range0, range1, limit=1 << 21):
+    """the two nested loops of an exhaustive search: (trials [count, 2], n_outer, n_inner); ranges are (first, last, step) (host only)"""
+    a = [float(v) for v in range0] + [float(v) for v in range1]
+    n, no, ni = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().xh_fsym_grid(*a, int(limit), None, C.byref(n), C.byref(no), C.byref(ni)))
+    p = np.zeros((n.value, 2))
+    check(lib().xh_fsym_grid(*a, int(limit), _np_ptr(p), C.byref(n), C.byref(no), C.byref(ni)))
+    return p, no.value, ni.value
+
+
+def fsym_helical_gate(Z, z_helical, rot_helical, z0, zF, rot0, rotF):
+    """True where evaluateSymmetry returns 1e38 without any work (host only)"""
+    g = C.c_int32()
+    check(lib().xh_fsym_helical_gate(int(Z), float(z_helical), float(rot_helical), float(z0), float(zF), float(rot0), float(rotF), C.byref(g)))
+    return bool(g.value)
+
+
+def fsym_helical_depth(Z, z_helical, height_fraction=1.0, dihedral=False):
+    """the depth the helical interpolation's recursion reaches for FindSymmetry's masked helix: 0 or 1, or -1 where it is refused (host only)"""
+    depth = C.c_int32()
+    check(lib().xh_fsym_helical_depth(int(Z), float(z_helical), float(height_fraction), int(bool(dihedral)), C.byref(depth)))
+    return depth.value
+
+
+def halves_cylinder_mask(shape, R, H, center=(0.0, 0.0, 0.0)):
+    """--mask cylinder R H [--center x0 y0 z0] as an int32 array: both negative keep the inside (host only)"""
+    Z, Y, X = (int(s) for s in shape)
+    m = np.zeros((Z, Y, X), np.int32)
+    check(lib().xh_halves_cylinder_mask(Z, Y, X, float(R), float(H), float(center[0]), float(center[1]), float(center[2]), _np_ptr(m)))
+    return m
+
+
+def halves_tube_mask(shape, R1, R2, H, center=(0.0, 0.0, 0.0)):
+    """--mask tube R1 R2 H [--center x0 y0 z0] as an int32 array: all negative keep the inside (host only)"""
+    Z, Y, X = (int(s) for s in shape)
+    m = np.zeros((Z, Y, X), np.int32)
+    check(lib().xh_halves_tube_mask(Z, Y, X, float(R1), float(R2), float(H), float(center[0]), float(center[1]), float(center[2]), _np_ptr(m)))
+    return m
+
+
 def vsub_radial_bins(shape):
     """(the bins of the radial average of a [Z, Y, X] box, the largest bin its octant writes); --radavg is refused where the second
     reaches the first (host only)"""

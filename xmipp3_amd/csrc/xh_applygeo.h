@@ -1,7 +1,7 @@
 // xh_applygeo.h -- xmippCore's 3-D applyGeometry per output voxel, the one place where it is written: the per-axis range test (WRAP:
 // realWRAP; DONT_WRAP: the outside value), the trilinear rule with the behaviours kept as written ((int) truncation, m2 >= dim -> 0 under
 // wrap, the w != 0 && m2 < dim guards), the 4 x 4 x 4 mirrored cubic-spline taps, and the cofactor inverse the host forms for a matrix.
-// Used by xh_sym.hip (xmipp_transform_symmetrize) and xh_valign.hip (xmipp_volume_align); both are built with -ffp-contract=off, because
+// Used by xh_sym.hip (xmipp_transform_symmetrize), xh_valign.hip (xmipp_volume_align) and xh_fsym.hip (xmipp_volume_find_symmetry); all are built with -ffp-contract=off, because
 // the source coordinates feed comparisons. xmippCore is not in the reference tree: INTEGRATION.md 3m says what this restates.
 #ifndef XH_APPLYGEO_H
 #define XH_APPLYGEO_H

@@ -727,4 +727,41 @@ int xh_halves_binary_mask(const float *h_values, size_t n, int32_t *h_mask)
     return XH_OK;
 }
 
+int xh_halves_cylinder_mask(int32_t Z, int32_t Y, int32_t X, double R, double H, double x0, double y0, double z0, int32_t *h_mask)
+{
+    XH_CHECK(Z >= 1 && Y >= 1 && X >= 1 && h_mask, XH_ERR_ARG, "xh_halves_cylinder_mask: bad argument");
+    // BinaryCylinderMask (data/mask.cpp:471-486) with Mask::readParams' mode (:1396-1405)
+    XH_CHECK((R < 0 && H < 0) || (R > 0 && H > 0), XH_ERR_ARG, "xh_halves_cylinder_mask: cannot determine mode for cylinder (R %g, H %g)", R, H);
+    const bool inner = R < 0;
+    const double R2 = std::fabs(R) * std::fabs(R), H_2 = std::fabs(H) / 2;
+    for (int kk = 0; kk < Z; ++kk)
+        for (int ii = 0; ii < Y; ++ii)
+            for (int jj = 0; jj < X; ++jj) {
+                const double k = kk - Z / 2, i = ii - Y / 2, j = jj - X / 2;
+                const double r2 = (i - y0) * (i - y0) + (j - x0) * (j - x0);
+                const bool in = r2 <= R2 && std::fabs(k - z0) <= H_2;
+                h_mask[((size_t)kk * Y + ii) * X + jj] = in == inner ? 1 : 0;
+            }
+    return XH_OK;
+}
+
+int xh_halves_tube_mask(int32_t Z, int32_t Y, int32_t X, double R1, double R2, double H, double x0, double y0, double z0, int32_t *h_mask)
+{
+    XH_CHECK(Z >= 1 && Y >= 1 && X >= 1 && h_mask, XH_ERR_ARG, "xh_halves_tube_mask: bad argument");
+    // BinaryTubeMask (data/mask.cpp:261-276) with Mask::readParams' mode (:1419-1429); z0 is not used there, and H is not halved
+    XH_CHECK((R1 < 0 && R2 < 0 && H < 0) || (R1 > 0 && R2 > 0 && H > 0), XH_ERR_ARG, "xh_halves_tube_mask: cannot determine mode for tube (R1 %g, R2 %g, H %g)", R1, R2, H);
+    (void)z0;
+    const bool inner = R1 < 0;
+    const double R12 = std::fabs(R1) * std::fabs(R1), R22 = std::fabs(R2) * std::fabs(R2), Ha = std::fabs(H);
+    for (int kk = 0; kk < Z; ++kk)
+        for (int ii = 0; ii < Y; ++ii)
+            for (int jj = 0; jj < X; ++jj) {
+                const double k = kk - Z / 2, i = ii - Y / 2, j = jj - X / 2;
+                const double r2 = (i - y0) * (i - y0) + (j - x0) * (j - x0);
+                const bool in = r2 >= R12 && r2 <= R22 && std::fabs(k) < Ha;
+                h_mask[((size_t)kk * Y + ii) * X + jj] = in == inner ? 1 : 0;
+            }
+    return XH_OK;
+}
+
 }  // extern "C"

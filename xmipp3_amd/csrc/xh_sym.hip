@@ -18,13 +18,15 @@
 //                   most one level deep for the parameters the entry point accepts (sy_helical_depth) and is written as two
 //                   nested levels. helicalDihedral: the pass with one matrix (180 degrees about X, WRAP), (V_out + Vrotated) * 0.5.
 //
-// The per-voxel applyGeometry (range test per axis, linear and cubic taps) and the cofactor inverse are in xh_applygeo.h, shared with xh_valign.hip.
+// The per-voxel applyGeometry (range test per axis, linear and cubic taps) and the cofactor inverse are in xh_applygeo.h, shared with xh_valign.hip
+// and xh_fsym.hip; the helix's per-voxel sum and its interpolation are in xh_helix.h, shared with xh_fsym.hip.
 // xmippCore is not in the reference tree: applyGeometry's 3-D branch is its 2-D branch, as k_rs_apply of xh_rsig.hip has it,
 // with a z axis added. The one deviation: a source coordinate is x A00 + y A01 + z A02, not A00 added along the row.
 // Reference behaviours kept as written: the (int) truncation of the linear taps (a coordinate in (-1, 0) extrapolates from taps 0 and 1),
 // m2 >= dim -> 0 under wrap, the w != 0 && m2 < dim guards, one mirror per spline tap, 1.0 / (n + 1.0f), Llength + 1 terms of the helix
 // and its edge weights.
 #include "xh_applygeo.h"
+#include "xh_helix.h"
 #include "xh_reduce.h"
 #include <cmath>
 #include <cstring>
@@ -326,59 +328,7 @@ k_sy_images(const double *__restrict__ src, const double *__restrict__ imgs, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------- helix
-struct SyHelix {
-    double zHelical, izHelical, rotHelical, rot0, sinRot, cosRot;
-    int zFirst, zLast, zHelical2, Llength, Cn, dihedral;
-};
-
-// interpolatedElement3DHelical (symmetries.cpp:1598-1630) with interpolatedElement3DHelicalInt (:1577-1596) for its corners. LEVEL 1 is
-// the point a level-0 corner outside z was sent to; with the accepted parameters its corners lie inside z (sy_helical_depth), a corner
-// that does not reads as zero. Corners of weight exactly 0 are not fetched: l + (h - l) * 0 is l for any finite h.
-template <int LEVEL> __device__ double sy_helical_interp(const double *__restrict__ v, XhDims d, const SyHelix &H, double x, double y, double z);
-
-template <int LEVEL> __device__ __forceinline__ double sy_helical_corner(const double *__restrict__ v, XhDims d, const SyHelix &H, int x, int y, int z)
-{
-    const int sx = -(d.X / 2), sy = -(d.Y / 2), sz = -(d.Z / 2);
-    if (x < sx || x > sx + d.X - 1 || y < sy || y > sy + d.Y - 1) return 0.0;
-    if (z >= sz && z <= sz + d.Z - 1) return v[((size_t)(z - sz) * d.Y + (y - sy)) * d.X + (x - sx)];
-    if constexpr (LEVEL >= 1) return 0.0;
-    else if (z < sz) {
-        const double newx = H.cosRot * x - H.sinRot * y;
-        const double newy = H.sinRot * x + H.cosRot * y;
-        return sy_helical_interp<LEVEL + 1>(v, d, H, newx, newy, z + H.zHelical);
-    } else {
-        const double newx = H.cosRot * x + H.sinRot * y;
-        const double newy = -H.sinRot * x + H.cosRot * y;
-        return sy_helical_interp<LEVEL + 1>(v, d, H, newx, newy, z - H.zHelical);
-    }
-}
-
-template <int LEVEL> __device__ double sy_helical_interp(const double *__restrict__ v, XhDims d, const SyHelix &H, double x, double y, double z)
-{
-    const int x0 = (int)floor(x), y0 = (int)floor(y), z0 = (int)floor(z);
-    const double fx = x - x0, fy = y - y0, fz = z - z0;
-    const int x1 = x0 + 1, y1 = y0 + 1, z1 = z0 + 1;
-    const bool hx = fx != 0, hy = fy != 0, hz = fz != 0;
-    constexpr int L = LEVEL;
-    const double d000 = sy_helical_corner<L>(v, d, H, x0, y0, z0);
-    const double d001 = hx ? sy_helical_corner<L>(v, d, H, x1, y0, z0) : 0.0;
-    const double d010 = hy ? sy_helical_corner<L>(v, d, H, x0, y1, z0) : 0.0;
-    const double d011 = hx && hy ? sy_helical_corner<L>(v, d, H, x1, y1, z0) : 0.0;
-    const double d100 = hz ? sy_helical_corner<L>(v, d, H, x0, y0, z1) : 0.0;
-    const double d101 = hz && hx ? sy_helical_corner<L>(v, d, H, x1, y0, z1) : 0.0;
-    const double d110 = hz && hy ? sy_helical_corner<L>(v, d, H, x0, y1, z1) : 0.0;
-    const double d111 = hz && hx && hy ? sy_helical_corner<L>(v, d, H, x1, y1, z1) : 0.0;
-    // LIN_INTERP(a, l, h) = l + (h - l) * a; a skipped corner stands for its partner so that the product is an exact zero
-    const double dx00 = hx ? d000 + (d001 - d000) * fx : d000;
-    const double dx01 = hz ? (hx ? d100 + (d101 - d100) * fx : d100) : 0.0;
-    const double dx10 = hy ? (hx ? d010 + (d011 - d010) * fx : d010) : 0.0;
-    const double dx11 = hz && hy ? (hx ? d110 + (d111 - d110) * fx : d110) : 0.0;
-    const double dxy0 = hy ? dx00 + (dx10 - dx00) * fy : dx00;
-    const double dxy1 = hz ? (hy ? dx01 + (dx11 - dx01) * fy : dx01) : 0.0;
-    return hz ? dxy0 + (dxy1 - dxy0) * fz : dxy0;
-}
-
-// symmetry_Helical (:1632-1705), mask == nullptr; sinCn / cosCn [Cn] from the host
+// symmetry_Helical (:1632-1705), mask == nullptr; sinCn / cosCn [Cn] from the host. The voxel's sum and the interpolation are in xh_helix.h
 __global__ void __launch_bounds__(256)
 k_sy_helical(const double *__restrict__ vin, XhDims d, SyHelix H, const double *__restrict__ sinCn, const double *__restrict__ cosCn, double *__restrict__ out)
 {
@@ -388,40 +338,7 @@ k_sy_helical(const double *__restrict__ vin, XhDims d, SyHelix H, const double *
         const int i = (int)(r % d.Y) - d.Y / 2, k = (int)(r / d.Y) - d.Z / 2, j = jj - d.X / 2;
         const double rot = atan2((double)i, (double)j) + H.rot0;
         const double rho = sqrt((double)i * i + (double)j * j);
-        const int l0 = (int)ceil((-(d.Z / 2) - k) * H.izHelical);
-        const int lF = l0 + H.Llength;
-        double finalValue = 0, L = 0;
-        for (int il = l0; il <= lF; ++il) {
-            const double l = il;
-            const double kp = k + l * H.zHelical;
-            if (kp >= H.zFirst && kp <= H.zLast) {
-                const double rotp = rot + l * H.rotHelical;
-                const double ip = rho * sin(rotp);
-                const double jp = rho * cos(rotp);
-                double weight = 1.0;
-                if (kp - H.zFirst <= H.zHelical2) weight = (kp - H.zFirst + 1) / (H.zHelical2 + 1);
-                else if (H.zLast - kp <= H.zHelical2) weight = (H.zLast + 1 - kp) / (H.zHelical2 + 1);
-                finalValue += weight * sy_helical_interp<0>(vin, d, H, jp, ip, kp);
-                L += weight;
-                for (int c = 1; c < H.Cn; ++c) {
-                    const double jpp = cosCn[c] * jp - sinCn[c] * ip;
-                    const double ipp = sinCn[c] * jp + cosCn[c] * ip;
-                    finalValue += weight * sy_helical_interp<0>(vin, d, H, jpp, ipp, kp);
-                    L += weight;
-                }
-                if (H.dihedral) {
-                    finalValue += weight * sy_helical_interp<0>(vin, d, H, jp, -ip, -kp);
-                    L += weight;
-                    for (int c = 1; c < H.Cn; ++c) {
-                        const double jpp = cosCn[c] * jp - sinCn[c] * (-ip);
-                        const double ipp = sinCn[c] * jp + cosCn[c] * (-ip);
-                        finalValue += weight * sy_helical_interp<0>(vin, d, H, jpp, ipp, -kp);
-                        L += weight;
-                    }
-                }
-            }
-        }
-        out[n] = finalValue / L;
+        out[n] = sy_helical_value(vin, d, H, sinCn, cosCn, k, rot, rho);
     }
 }
 
@@ -710,25 +627,9 @@ int xh_sym_helical(xh_sym *h, const double *d_in, double zHelical, double rotHel
              "0 < heightFraction <= 1 (at zHelical <= 1 the reference never terminates)", zHelical, heightFraction, d.Z);
     XH_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
-    SyHelix H;
-    const long nz = std::lround(heightFraction * d.Z);            // round(heightFraction * ZSIZE), :1635-1636
-    H.zFirst = -(int)(nz / 2);
-    H.zLast = H.zFirst + (int)nz - 1;
-    H.zHelical = zHelical;
-    H.izHelical = 1.0 / zHelical;
-    H.zHelical2 = (int)std::floor(0.5 * zHelical);
-    H.rotHelical = rotHelical;
-    H.rot0 = rotPhaseHelical;
-    H.sinRot = std::sin(rotHelical);
-    H.cosRot = std::cos(rotHelical);
-    H.Llength = (int)std::ceil(d.Z * H.izHelical);
-    H.Cn = Cn;
-    H.dihedral = dihedral != 0;
+    const SyHelix H = sy_make_helix(d.Z, zHelical, rotHelical, rotPhaseHelical, heightFraction, Cn, dihedral != 0);
     std::vector<double> cs(2 * (size_t)Cn);
-    for (int n = 0; n < Cn; ++n) {
-        cs[n] = std::sin(n * (2 * SY_PI) / Cn);
-        cs[Cn + n] = std::cos(n * (2 * SY_PI) / Cn);
-    }
+    sy_cn_table(Cn, cs.data());
     XH_HIP(hipMemcpyAsync(h->cn.p, cs.data(), sizeof(double) * cs.size(), hipMemcpyHostToDevice, st));
     XH_HIP(hipStreamSynchronize(st));
     XH_TRY(h->tm.start());

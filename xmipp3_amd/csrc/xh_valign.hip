@@ -10,7 +10,7 @@
 //   the finish   one workgroup per trial: thread t adds the partials of bricks t, t + 256, .. in increasing order, the tree adds the 256
 //                sums, thread 0 finishes: COVARIANCE -(Sxy - mean_y S0) / ((stddev_x stddev_y) n), 0 where a deviation is below 1e-6;
 //                LEAST_SQUARES sqrt(sum / n), 0 for n = 0. mean_x, stddev_x, n and S0 = sum (x - mean_x) are formed once by set_volumes
-//                on the host in raster order (compensated sums), with computeAvgStdev's integer N / (N - 1).
+//                on the host in raster order (compensated sums), with computeAvgStdev's integer N / (N - 1); xh_corr.h.
 //   the choice   the first minimum in trial order (strict <, volume_align_prog.cpp:388), carried from batch to batch on the device.
 //   apply        the materialised applyTransformation of V2 (:56-97) for --apply.
 //
@@ -20,6 +20,7 @@
 // sum (x - mean_x)(y - mean_y) = sum (x - mean_x) y - mean_y sum (x - mean_x) and sum (y - mean_y)^2 = sum y^2 - n mean_y^2 in one pass
 // (the second is computeAvgStdev's own form). The rounding difference is what the tests' bound is derived from.
 #include "xh_applygeo.h"
+#include "xh_corr.h"
 #include "xh_reduce.h"
 #include <cmath>
 #include <memory>
@@ -34,7 +35,7 @@ enum { VA_T_GATHER = 0, VA_T_FINISH, VA_T_SELECT, VA_NT };
 
 // what the kernels read of a trial: rows (x', y', z') of the inverse of A with its translation, the grey values, isIdentity
 struct VaTrial { double a[12]; double greyScale, greyShift, ident, pad; };
-struct VaStats { double n, mean_x, stddev_x, S0; };
+typedef XhCorrStats VaStats;                     // n, mean_x, stddev_x, S0 (xh_corr.h, shared with xh_fsym.hip)
 struct VaBest { double fit; long long index; };
 
 // Vaux at voxel n = (k, i, j) of trial T: applyGeometry(LINEAR, Vaux, V2, A, IS_NOT_INV, wrap) with outside value 0, then the grey values
@@ -99,26 +100,11 @@ template <int NK>
 __global__ void __launch_bounds__(256) k_va_finish(const double *__restrict__ partials, int nbricks, VaStats S, double *__restrict__ fit)
 {
     __shared__ double red[NK][256];
-    const double *p = partials + (size_t)blockIdx.x * nbricks * NK;
-    double v[NK];
-    for (int c = 0; c < NK; ++c) v[c] = 0.0;
-    for (int b = threadIdx.x; b < nbricks; b += 256)
-        for (int c = 0; c < NK; ++c) v[c] += p[(size_t)b * NK + c];
-    xh_tree256(red, v);
+    xh_brick_totals<NK>(partials + (size_t)blockIdx.x * nbricks * NK, nbricks, red);
     if (threadIdx.x != 0) return;
     double f = 0.0;
     if constexpr (NK == 3) {
-        // correlationIndex with computeAvgStdev's deviation of y: sqrt(|sum y^2 / n - mean_y^2| (n / (n - 1))), the quotient in integers
-        const double Sy = red[0][0], Sy2 = red[1][0], Sxy = red[2][0];
-        double corr = 0.0;
-        if (S.n > 1) {
-            const double mean_y = Sy / S.n;
-            double sd = Sy2 / S.n - mean_y * mean_y;
-            sd *= (double)((long long)S.n / ((long long)S.n - 1));
-            sd = sqrt(fabs(sd));
-            if (!(fabs(S.stddev_x) < SY_ACC || fabs(sd) < SY_ACC)) corr = (Sxy - mean_y * S.S0) / ((S.stddev_x * sd) * S.n);
-        }
-        f = -corr;
+        f = -xh_corr_index(red[0][0], red[1][0], red[2][0], S);
     } else
         f = S.n != 0 ? sqrt(red[0][0] / S.n) : 0.0;
     fit[blockIdx.x] = f;
@@ -164,19 +150,6 @@ k_va_apply(const double *__restrict__ V2, const VaTrial *__restrict__ trial, XhD
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host helpers
-// A sum in raster order with its rounding errors carried along (Neumaier): a plain running sum of N terms drifts by about sqrt(N) ulp, which
-// the deviation's cancellation (sum x^2 / n - mean^2) multiplies; at 16^3 that alone moved a fit by 1e-14. No FMA contraction in this file
-struct VaSum {
-    double s = 0, c = 0;
-    void add(double v)
-    {
-        const double t = s + v;
-        c += std::fabs(s) >= std::fabs(v) ? (s - t) + v : (v - t) + s;
-        s = t;
-    }
-    double value() const { return s + c; }
-};
-
 // C = A B for 4 x 4, every entry summed from 0 over k in order (xmippCore's Matrix2D product)
 void va_mul4(const double *A, const double *B, double *C)
 {
@@ -350,28 +323,8 @@ int xh_valign_set_volumes(xh_valign *h, const double *h_V1, const double *h_V2, 
     hipStream_t st = h->ctx->stream;
     h->loaded = false;
     // what does not depend on the trial, in raster order: computeAvgStdev within the mask, then sum (x - mean_x)
-    long long n = 0;
-    VaSum sum, sum2, s0;
-    for (size_t e = 0; e < h->N; ++e)
-        if (!h_mask || h_mask[e] != 0) {
-            const double x = h_V1[e];
-            XH_CHECK(std::isfinite(x), XH_ERR_ARG, "xh_valign_set_volumes: the first volume has a value that is not finite");
-            ++n;
-            sum.add(x);
-            sum2.add(x * x);
-        }
-    VaStats S = {(double)n, 0, 0, 0};
-    if (n > 0) {
-        S.mean_x = sum.value() / n;
-        if (n > 1) {
-            double sd = sum2.value() / n - S.mean_x * S.mean_x;
-            sd *= (double)(n / (n - 1));
-            S.stddev_x = std::sqrt(std::fabs(sd));
-        }
-        for (size_t e = 0; e < h->N; ++e)
-            if (!h_mask || h_mask[e] != 0) s0.add(h_V1[e] - S.mean_x);
-        S.S0 = s0.value();
-    }
+    VaStats S;
+    XH_TRY(xh_corr_stats("xh_valign_set_volumes", "the first volume", h_V1, h_mask, h->N, S));
     h->stats = S;
     XH_HIP(hipMemcpyAsync(h->V1.p, h_V1, sizeof(double) * h->N, hipMemcpyHostToDevice, st));
     XH_HIP(hipMemcpyAsync(h->V2.p, h_V2, sizeof(double) * h->N, hipMemcpyHostToDevice, st));

@@ -64,6 +64,7 @@ struct XhDestroy {
     void operator()(xh_rsig *h) const { xh_rsig_destroy(h); }
     void operator()(xh_sym *h) const { xh_sym_destroy(h); }
     void operator()(xh_valign *h) const { xh_valign_destroy(h); }
+    void operator()(xh_fsym *h) const { xh_fsym_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 

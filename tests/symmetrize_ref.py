@@ -120,9 +120,9 @@ def group_matrices(sym, no_group=False):
 
 
 # ---------------------------------------------------------------- spline coefficients
-def prefilter_axis(c, axis):
+def prefilter_axis(c, axis, dtype=np.float64):
     """the recursive filter of the oracle's prefilter1d along one axis, in place semantics on a copy"""
-    c = np.moveaxis(np.array(c, dtype=np.float64), axis, 0).copy()
+    c = np.moveaxis(np.array(c, dtype=dtype), axis, 0).copy()
     n = c.shape[0]
     if n == 1:
         return np.moveaxis(c, 0, axis)
@@ -152,19 +152,21 @@ def prefilter_axis(c, axis):
     return np.moveaxis(c, 0, axis)
 
 
-def prefilter(v):
-    """produceSplineCoefficients(BSPLINE3): x, then y (, then z) lines"""
-    v = np.asarray(v, dtype=np.float64)
+def prefilter(v, dtype=np.float64):
+    """produceSplineCoefficients(BSPLINE3): x, then y (, then z) lines. dtype: the type the filter is carried in"""
+    v = np.asarray(v, dtype=dtype)
     for axis in range(v.ndim - 1, -1, -1):
-        v = prefilter_axis(v, axis)
+        v = prefilter_axis(v, axis, dtype)
     return np.ascontiguousarray(v)
 
 
 def bspline03(x):
+    """in the type of x: 2 / 3 and 1 / 6 are rounded to it"""
+    t = x.dtype.type
     a = np.abs(x)
-    inner = a * a * (a - 2.0) * 0.5 + 2.0 / 3.0
+    inner = a * a * (a - 2.0) * 0.5 + t(2) / t(3)
     b = a - 2.0
-    outer = b * b * b * (-1.0 / 6.0)
+    outer = b * b * b * (-(t(1) / t(6)))
     return np.where(a < 1.0, inner, np.where(a < 2.0, outer, 0.0))
 
 
@@ -398,12 +400,16 @@ def wrap_edge_mask(shape, coords, eps=1e-9):
 def outside_mean(V):
     """computeStats_within_binary_mask's average over BinaryCircularMask(min(dims) / 2, OUTSIDE_MASK)"""
     V = np.asarray(V, dtype=np.float64)
-    rad = min(V.shape) // 2
-    grids = np.meshgrid(*[np.arange(d, dtype=np.float64) - d // 2 for d in V.shape], indexing="ij")
-    r2 = np.zeros(V.shape)
+    return float(V[outside_mask(V.shape)].mean())
+
+
+def outside_mask(shape):
+    rad = min(shape) // 2
+    grids = np.meshgrid(*[np.arange(d, dtype=np.float64) - d // 2 for d in shape], indexing="ij")
+    r2 = np.zeros(shape)
     for g in grids:
         r2 = r2 + g * g
-    return float(V[r2 >= float(rad * rad)].mean())
+    return r2 >= float(rad * rad)
 
 
 def symmetrize_volume(V, R, degree, wrap, sum_=False, direct=True, coords=None):
@@ -430,6 +436,49 @@ def symmetrize_image(I, order, degree, wrap, sum_=False, direct=True, coords=Non
     if not sum_:
         out = out * (1.0 / order)
     return out
+
+
+def symmetrize_image_exact(I, order, degree, wrap):
+    """symmetrize_image's direct form, averaged, evaluated in higher precision, to calibrate a bound where the incremental form drifts
+    (it adds A00 along a row, so its distance to the direct form grows with the row). The source coordinates, and with them every
+    truncation, ceil, comparison and tap index, are the float64 ones of source_coords; the fractions, the weights, the spline coefficients,
+    the outside mean and every sum are carried in np.longdouble (64 bits of mantissa on x86). Not a restatement of the reference's
+    operation order: the bilinear weights are the plain products"""
+    LD = np.longdouble
+    I = np.asarray(I, dtype=np.float64)
+    Y, X = I.shape
+    V = I.astype(LD)
+    out_mask = outside_mask(I.shape)
+    avg = LD(0) if wrap else V[out_mask].sum() / LD(int(out_mask.sum()))
+    C = prefilter(I, LD) if degree == 3 else None
+    out = V.copy()
+    for i in range(1, order):
+        _, final, outm = source_coords(I.shape, inv3x3(rotation2d_matrix(360.0 / order * i)), wrap, True)
+        inside = ~outm
+        x, y = final[0][inside] + X // 2, final[1][inside] + Y // 2          # float64: they decide the taps
+        if degree == 1:
+            m1, n1 = np.trunc(x).astype(np.int64), np.trunc(y).astype(np.int64)
+            wx, wy = x.astype(LD) - m1, y.astype(LD) - n1
+            m2, n2 = m1 + 1, n1 + 1
+            if wrap:
+                m2, n2 = np.where(m2 >= X, 0, m2), np.where(n2 >= Y, 0, n2)
+            mx, my = (wx != 0) & (m2 < X), (wy != 0) & (n2 < Y)
+            m2, n2 = np.minimum(m2, X - 1), np.minimum(n2, Y - 1)
+            val = (1 - wy) * (1 - wx) * V[n1, m1] + np.where(mx, (1 - wy) * wx * V[n1, m2], 0) + np.where(my, wy * (1 - wx) * V[n2, m1], 0)
+            val = val + np.where(my & mx, wy * wx * V[n2, m2], 0)
+        else:
+            l1, q1 = np.ceil(x - 2).astype(np.int64), np.ceil(y - 2).astype(np.int64)
+            xl, yl = x.astype(LD), y.astype(LD)
+            val = np.zeros(x.shape, dtype=LD)
+            for t in range(4):
+                row = np.zeros(x.shape, dtype=LD)
+                for u in range(4):
+                    row = row + C[_mirror(q1 + t, Y), _mirror(l1 + u, X)] * bspline03(xl - (l1 + u))
+                val = val + row * bspline03(yl - (q1 + t))
+        res = np.full(I.shape, avg, dtype=LD)
+        res[inside] = val
+        out = out + res
+    return out * LD(1.0 / order)
 
 
 # ---------------------------------------------------------------- helix
@@ -579,7 +628,124 @@ BOUND = 1e-13
 def parity_cases():
     """(shape, group, degree, wrap) of every point-group case the device is compared on"""
     out = [(s, g, d, w) for s in SMALL for g in GROUPS for d in (1, 3) for w in (True, False)]
-    return out + [(BIG, "c5", d, w) for d in (1, 3) for w in (True, False)]
+    return out + [(BIG, "c5", d, w) for d in (1, 3) for w in (True, False)] + mid_cases()
+
+
+# ---------------------------------------------------------------- the cases past the first lap (tests/test_gpu_symmetrize_laps.py)
+MID = (36, 44, 41)            # every side different, one odd, Y and X leave partial bricks: 9 x 6 x 6 = 324 bricks of 4 x 8 x 8
+MID_GROUPS = ["t", "i1"]
+SY_BOX = 18 * 18 * 18         # the doubles of LDS the spline pass stages a brick's source box in
+# a rotation with no special entries: the product of two turns about oblique axes
+A0 = _mul(_rot_axis(0.7, 0.2, -0.5, 1.0), _rot_axis(-1.9, 1.0, 0.3, 0.1))
+# 16 times the largest relative difference between the two coordinate forms over general_cases(), the list of matrix_list() and A0 at
+# TILE_APPLY, rounded up to a power of ten (tests/test_symmetrize_ref.py derives and asserts it); relative to max|V_in|
+BOUND_GENERAL = 1e-12
+
+
+def mid_cases():
+    """(shape, group, degree, wrap) of the point groups at MID: oblique axes, most bricks interior"""
+    return [(MID, g, d, w) for g in MID_GROUPS for d in (1, 3) for w in (True, False)]
+
+
+def general_matrices():
+    """name -> A (as applyGeometry takes it, IS_NOT_INV) of the matrices that are no rotation. The inverse of s A0 stretches by 1 / s:
+    below about 0.65 a brick's source box passes SY_BOX, at 1.7 nearly every box is staged. The shear's entries are not round, so that no
+    coordinate falls on a wrap edge (tests/test_symmetrize_ref.py asserts it)"""
+    return {
+        "0.5 A0": 0.5 * A0,
+        "0.62 A0": 0.62 * A0,
+        "0.8 A0": 0.8 * A0,
+        "1.7 A0": 1.7 * A0,
+        "diag(0.45, 1, 2) A0": _mul(np.diag([0.45, 1.0, 2.0]), A0),
+        "diag(-1, 1, 1) A0": _mul(np.diag([-1.0, 1.0, 1.0]), A0),
+        "shear": np.array([[1.0, 0.8731, 0.0], [0.0, 1.0, 0.7919], [0.6843, 0.0, 1.0]]),
+    }
+
+
+def general_cases():
+    """(name, degree, wrap) of every single-matrix case at MID"""
+    return [(n, d, w) for n in general_matrices() for d in (1, 3) for w in (True, False)]
+
+
+def matrix_list():
+    """the R of the list that goes through set_matrices at MID: two rotations of t around an identity entry (applyGeometry's copy
+    shortcut, in the middle of a list) and a matrix that is no rotation"""
+    g = group_matrices("t")
+    return np.array([g[0], np.eye(3) + 5e-7, (0.8 * A0).T, g[1]])
+
+
+def staging_census(shape, Ainvs):
+    """The decision of the spline pass (k_sy_pass_staged) for every (brick, matrix) pair, transcribed operation by operation: a brick of
+    4 x 8 x 8 output voxels bounds its source points by the per-term minima and maxima of Ainv times its corners, adds the spline support
+    and stages that box in LDS when it lies inside the volume and holds SY_BOX doubles at the most. Ainvs: the inverses the device forms
+    (inv3x3 of what applyGeometry takes), identity entries left out. A precondition tool: it says which branch a case reaches, and is
+    never used to predict or excuse a device result.
+    Returns staged, border (the box leaves the volume), over (inside, above SY_BOX), largest (staged box, 0 if none) and partial (staged
+    pairs on a brick that the volume cuts)"""
+    Z, Y, X = shape
+    dim = (X, Y, Z)
+    nb_ = ((X + 7) // 8, (Y + 7) // 8, (Z + 3) // 4)
+    side = (8, 8, 4)
+    b = np.meshgrid(*[np.arange(n) for n in nb_], indexing="ij")                     # bx, by, bz
+    p0 = [(b[c] * side[c] - dim[c] // 2).astype(np.float64) for c in range(3)]
+    p1 = [(np.minimum(b[c] * side[c] + side[c] - 1, dim[c] - 1) - dim[c] // 2).astype(np.float64) for c in range(3)]
+    cut = np.zeros(b[0].shape, dtype=bool)
+    for c in range(3):
+        cut |= b[c] * side[c] + side[c] - 1 > dim[c] - 1
+    out = {"staged": 0, "border": 0, "over": 0, "largest": 0, "partial": 0}
+    for Ainv in Ainvs:
+        Ainv = np.asarray(Ainv, dtype=np.float64).reshape(3, 3)
+        inside = np.ones(b[0].shape, dtype=bool)
+        size = np.ones(b[0].shape, dtype=np.int64)
+        for r in range(3):
+            cmin, cmax = np.zeros(b[0].shape), np.zeros(b[0].shape)
+            for c in range(3):
+                u, v = Ainv[r, c] * p0[c], Ainv[r, c] * p1[c]
+                cmin = cmin + np.minimum(u, v)
+                cmax = cmax + np.maximum(u, v)
+            ilo = np.floor(cmin + dim[r] // 2 - 2.0 - 1e-3).astype(np.int64)
+            ihi = np.floor(cmax + dim[r] // 2 + 2.0 + 1e-3).astype(np.int64)
+            inside &= (ilo >= 0) & (ihi <= dim[r] - 1)
+            size = size * (ihi - ilo + 1)
+        staged = inside & (size <= SY_BOX)
+        out["staged"] += int(staged.sum())
+        out["border"] += int((~inside).sum())
+        out["over"] += int((inside & ~staged).sum())
+        out["partial"] += int((staged & cut).sum())
+        if staged.any():
+            out["largest"] = max(out["largest"], int(size[staged].max()))
+    return out
+
+
+def prefilter_tile(X):
+    """the rows of one workgroup of the x prefilter: what 48 KB of LDS hold of rows padded to an odd length, 64 at the most"""
+    return max(1, min(64, 48 * 1024 // (8 * (X | 1))))
+
+
+# shape -> the tile: the last X with the full tile, the first with a smaller one, two tiles with the second partial (78 rows), the size cap
+TILE_SHAPES = {(5, 7, 95): 64, (5, 7, 96): 63, (3, 26, 131): 46, (2, 3, 1024): 5}
+TILE_APPLY = (3, 26, 131)     # one spline applyGeometry (A0, wrap) reads the coefficients of its two tiles
+
+# stacks: 17 images of 250 x 262 pass 256 . 16 pixels per CU on 256 CUs (1 113 500); 65 600 images of 4 x 6 pass the 65 535 workgroups of
+# the outside mean, image i a copy of base image i % 7
+STACK_BIG, STACK_ORDER = (17, 250, 262), 5
+STACK_MANY, STACK_BASE = (65600, 4, 6), 7
+# 16 times the largest relative distance of the direct form to symmetrize_image_exact over the stack cases, rounded up to a power of ten,
+# or BOUND where that is smaller (tests/test_symmetrize_ref.py derives and asserts it); relative to max|I|
+BOUND_IMAGES = BOUND
+
+
+def big_stack():
+    return np.stack([phantom(STACK_BIG[1:], 50 + i) for i in range(STACK_BIG[0])])
+
+
+def base_images():
+    return np.stack([phantom(STACK_MANY[1:], 70 + i) for i in range(STACK_BASE)])
+
+
+# the helix past 256 . 16 voxels per CU on 256 CUs (1 050 600 voxels; Z flat, so that the restatement stays cheap):
+# the box, then zHelical in voxels, rotHelical in degrees, the phase, Cn, heightFraction; not dihedral
+HELIX_LAP = ((25, 206, 204), 4.3, -41.5, 0.2, 2, 0.95)
 
 
 # ---------------------------------------------------------------- test data

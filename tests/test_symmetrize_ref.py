@@ -129,7 +129,8 @@ def test_the_reference_does_not_terminate_below_one_voxel():
 def test_device_bound_is_derived_from_the_two_coordinate_forms():
     """The tolerance of the device tests. For every parity case the restatement runs with the reference's incremental coordinates and with
     the direct ones the device uses; the largest difference relative to max|V_in| times 16, rounded up to a power of ten, is R.BOUND.
-    Measured here: largest relative difference 4.9e-15, so 16 x gives 7.8e-14 and the bound is 1e-13.
+    Measured here: largest relative difference 4.9e-15, so 16 x gives 7.8e-14 and the bound is 1e-13; t and i1 at R.MID, which
+    tests/test_gpu_symmetrize_laps.py compares, are among the cases and do not move it (144 voxels, 0.22 %, on a wrap edge for i1).
     Precondition of every case, on both forms: no tested coordinate within 1e-9 of a threshold min - 1e-6 or max + 1e-6 (0 found).
     Under WRAP the voxels with a coordinate on a wrap edge min - 0.5 + k dim are not compared (R.wrap_edge_mask says why): the case stays,
     those voxels are counted."""
@@ -147,3 +148,173 @@ def test_device_bound_is_derived_from_the_two_coordinate_forms():
     print(f"largest relative difference of the two coordinate forms: {worst:.3e}; most voxels on a wrap edge in one case: {masked}")
     assert worst > 0
     assert R.BOUND == 10.0 ** math.ceil(math.log10(16 * worst))
+
+
+# ---------------------------------------------------------------- the cases of tests/test_gpu_symmetrize_laps.py
+def _inverses(R_list):
+    """the inverses the device forms for a list given to set_matrices, identity entries left out"""
+    return [R.inv3x3(np.asarray(m).T) for m in R_list if not R.is_identity(np.asarray(m).T)]
+
+
+@pytest.mark.parametrize("sym,want", [("t", {"staged": 973, "border": 2591, "over": 0, "largest": 2925, "partial": 62}),
+                                      ("i1", {"staged": 5044, "border": 14072, "over": 0, "largest": 3360, "partial": 298})])
+def test_point_groups_at_mid_stage_most_interior_bricks(sym, want):
+    """what the MID cases are there for: oblique axes, whole source boxes in LDS, staged pairs on bricks the volume cuts. On the boxes of
+    tests/test_gpu_symmetrize.py at most 141 pairs are staged"""
+    got = R.staging_census(R.MID, _inverses(R.group_matrices(sym)))
+    print(f"{sym} at {R.MID}: {got}")
+    assert got == want
+    small = max(R.staging_census(s, _inverses(R.group_matrices(g)))["staged"] for s in R.SMALL for g in R.GROUPS)
+    assert small <= 141 < got["staged"]
+
+
+GENERAL_CENSUS = {
+    "0.5 A0": {"staged": 0, "border": 322, "over": 2, "largest": 0, "partial": 0},
+    "0.62 A0": {"staged": 0, "border": 316, "over": 8, "largest": 0, "partial": 0},
+    "0.8 A0": {"staged": 28, "border": 296, "over": 0, "largest": 4896, "partial": 0},
+    "1.7 A0": {"staged": 298, "border": 26, "over": 0, "largest": 1331, "partial": 85},
+    "diag(0.45, 1, 2) A0": {"staged": 4, "border": 296, "over": 24, "largest": 5814, "partial": 0},
+    "diag(-1, 1, 1) A0": {"staged": 77, "border": 247, "over": 0, "largest": 3360, "partial": 5},
+    "shear": {"staged": 128, "border": 196, "over": 0, "largest": 3136, "partial": 26},
+}
+
+
+def test_general_matrices_reach_the_branches_they_are_there_for():
+    """every matrix that is no rotation: the census class it was chosen for, an inverse the entry points accept (entries up to 1e3), no
+    source coordinate within 1e-9 of a threshold in either coordinate form (measured: 6.0e-6 at the least), and no voxel on a wrap edge,
+    so that the two forms never part"""
+    mats = R.general_matrices()
+    assert sorted(mats) == sorted(GENERAL_CENSUS)
+    for name, A in mats.items():
+        Ainv = R.inv3x3(A)
+        c = R.staging_census(R.MID, [Ainv])
+        assert c == GENERAL_CENSUS[name], (name, c)
+        assert c["staged"] + c["border"] + c["over"] == 324
+        assert np.abs(Ainv).max() <= 1e3 and not R.is_identity(A)
+        margins = []
+        for wrap in (True, False):
+            coords = [R.source_coords(R.MID, Ainv, wrap, direct)[0] for direct in (False, True)]
+            margins.append(min(R.threshold_margin(R.MID, t) for t in coords))
+            assert margins[-1] >= 1e-9, (name, wrap)
+            assert R.threshold_margin_both_forms(R.MID, [A], wrap) == margins[-1]
+            if wrap:
+                assert not R.wrap_edge_mask(R.MID, coords).any(), name
+        print(f"{name}: {c}, margin {min(margins):.2e}")
+    for name in ("0.5 A0", "0.62 A0"):
+        assert GENERAL_CENSUS[name]["over"] >= 1 and GENERAL_CENSUS[name]["staged"] == 0
+    c = GENERAL_CENSUS["diag(0.45, 1, 2) A0"]
+    assert c["staged"] >= 1 and c["border"] >= 1 and c["over"] >= 1 and R.SY_BOX - 18 == c["largest"]      # all three in one launch
+    assert GENERAL_CENSUS["1.7 A0"]["staged"] >= 0.9 * 324
+    assert GENERAL_CENSUS["0.8 A0"]["staged"] >= 1 and GENERAL_CENSUS["0.8 A0"]["largest"] > 3360          # larger than any rotation's box
+    assert np.linalg.det(mats["diag(-1, 1, 1) A0"]) < -0.99 and GENERAL_CENSUS["diag(-1, 1, 1) A0"]["staged"] >= 1
+    assert GENERAL_CENSUS["shear"]["staged"] >= 1 and GENERAL_CENSUS["shear"]["border"] >= 1
+    # the list: the identity entry is the second of four, and the brick kernel stages beside it
+    L = R.matrix_list()
+    assert [R.is_identity(m.T) for m in L] == [False, True, False, False] and not np.array_equal(L[1], np.eye(3))
+    c = R.staging_census(R.MID, _inverses(L))
+    print(f"the list: {c}")
+    assert c == {"staged": 211, "border": 761, "over": 0, "largest": 4896, "partial": 7}
+    for wrap in (True, False):
+        assert R.threshold_margin_both_forms(R.MID, [m.T for m in L], wrap) >= 1e-9
+
+
+def test_general_bound_is_derived_from_the_two_coordinate_forms():
+    """R.BOUND_GENERAL, by the rule of R.BOUND: over every single-matrix case (outside value 0.375), the list, and the rotation A0 on
+    the prefilter's tile shape (3, 26, 131) (splines, wrap), the largest difference of the restatement's incremental and direct coordinate
+    forms relative to max|V_in|, times 16, rounded up to a power of ten. The incremental form adds A00 along a row: an inverse that
+    stretches, or a row of 131 under wrap, makes it drift further than the rotations on rows of up to 70 that R.BOUND is derived on.
+    Measured here: largest relative difference 1.1e-14 (A0 at (3, 26, 131)) and 6.9e-15 at MID (0.62 A0, splines, no wrap); 16 x gives
+    1.8e-13 and the bound is 1e-12. Every case is clear of the thresholds by 1e-9 in both forms
+    (test_general_matrices_reach_the_branches_they_are_there_for, and here for the tile shape).
+    Wrap-edge voxels would be masked here, and only here; there are none."""
+    worst, where, masked = 0.0, None, 0
+    cases = [(n, d, w) for n, d, w in R.general_cases()] + [("list", d, w) for d in (1, 3) for w in (True, False)] + [("tile", 3, True)]
+    for name, degree, wrap in cases:
+        shape = R.TILE_APPLY if name == "tile" else R.MID
+        v = R.phantom(shape, 7)
+        res, coords = [], []
+        for direct in (False, True):
+            if name == "list":
+                res.append(R.symmetrize_volume(v, R.matrix_list(), degree, wrap, False, direct, coords))
+            else:
+                res.append(R.apply_geometry(v, R.A0 if name == "tile" else R.general_matrices()[name], degree, wrap, 0.375, direct, None, coords))
+        if name == "tile":
+            assert min(R.threshold_margin(shape, t) for t in coords) >= 1e-9
+        keep = ~R.wrap_edge_mask(shape, coords) if wrap else np.ones(shape, dtype=bool)
+        masked += int((~keep).sum())
+        diff = np.abs(res[0] - res[1])[keep].max() / np.abs(v).max()
+        if diff > worst:
+            worst, where = diff, (name, degree, wrap)
+    print(f"general matrices: largest relative difference of the two coordinate forms {worst:.3e} at {where}; voxels masked {masked}")
+    assert masked == 0 and worst > 0
+    assert R.BOUND_GENERAL == 10.0 ** math.ceil(math.log10(16 * worst))
+
+
+def test_prefilter_tiles():
+    """the x prefilter's tile: 64 rows up to X = 95, fewer from 96 on, 5 at 1024; the shapes run one short tile, two tiles with the second
+    partial, and more than 32 rows in a tile (threads past the first half wave filter a row)"""
+    assert all(R.prefilter_tile(X) == 64 for X in range(2, 96)) and R.prefilter_tile(96) == 63
+    assert max(s[2] for s in R.SMALL + [R.BIG, R.MID]) < 96
+    for shape, tr in R.TILE_SHAPES.items():
+        assert R.prefilter_tile(shape[2]) == tr
+    rows = {s: s[0] * s[1] for s in R.TILE_SHAPES}
+    assert rows[(5, 7, 95)] == rows[(5, 7, 96)] == 35 > 32
+    assert rows[(3, 26, 131)] == 78 == 46 + 32
+    assert rows[(2, 3, 1024)] == 6 == 5 + 1
+    n, Y, X = R.STACK_BIG
+    assert R.prefilter_tile(X) == 23 and -(-n * Y // 23) == 185 and n * Y - 184 * 23 == 18
+
+
+def test_stack_and_helix_sizes_pass_the_caps_of_256_compute_units():
+    """the grids are capped at 16 workgroups of 256 threads per CU; an MI355X has 256 CUs. The device tests assert the same on the
+    machine they run on"""
+    cap = 256 * 16 * 256
+    n, Y, X = R.STACK_BIG
+    assert n * Y * X == 1113500 > cap
+    n, Y, X = R.STACK_MANY
+    assert n > 65535 and n * Y * X > cap and n * Y * X <= 2 ** 31
+    shape, zh, rot, phase, cn, hf = R.HELIX_LAP
+    assert shape[0] * shape[1] * shape[2] == 1050600 > cap
+    assert R.helical_depth(shape[0], zh, hf, False) == 0
+
+
+def test_image_bound_is_derived_in_higher_precision():
+    """R.BOUND_IMAGES. At 250 x 262 the incremental form is no yardstick: it adds A00 262 times along a row and is 1.6e-14 from the direct
+    form already at 97 x 96. The direct form (what the device computes) is instead held against R.symmetrize_image_exact: the same float64
+    coordinates, truncations and tap indices, the weights, coefficients, outside mean and sums in np.longdouble. 16 times the largest
+    distance relative to max|I|, rounded up to a power of ten, or R.BOUND where that is smaller. Over three images of the large stack in
+    every mode and the seven 4 x 6 base images (splines, no wrap, the mode they run in).
+    Measured here: 3.0e-16 at the most (a 4 x 6 image), so 16 x rounds up to 1e-14, below R.BOUND = 1e-13, which is the bound."""
+    assert np.finfo(np.longdouble).nmant >= 63
+    worst, where = 0.0, None
+    big, base = R.big_stack()[:3], R.base_images()
+    cases = [(img, d, w, "250 x 262") for img in big for d in (1, 3) for w in (True, False)] + [(img, 3, False, "4 x 6") for img in base]
+    for img, degree, wrap, what in cases:
+        want = R.symmetrize_image_exact(img, R.STACK_ORDER, degree, wrap)
+        got = R.symmetrize_image(img, R.STACK_ORDER, degree, wrap, False, True)
+        diff = float(np.abs(got - want).max() / np.abs(img).max())
+        if diff > worst:
+            worst, where = diff, (what, degree, wrap)
+    derived = 10.0 ** math.ceil(math.log10(16 * worst))
+    print(f"images: largest relative distance of the direct form to the higher-precision evaluation {worst:.3e} at {where}; "
+          f"16 x rounds up to {derived:.0e}, R.BOUND is {R.BOUND:.0e}")
+    assert worst > 0
+    assert R.BOUND_IMAGES == max(derived, R.BOUND)
+
+
+def test_stack_cases_are_clear_of_thresholds_and_wrap_edges():
+    """order 5 on 250 x 262 and on 4 x 6: no source coordinate within 1e-9 of a threshold in either coordinate form, none on a wrap
+    edge in the direct form the device is compared on; the base images are positive and all different"""
+    As = [R.rotation2d_matrix(360.0 / R.STACK_ORDER * i) for i in range(1, R.STACK_ORDER)]
+    for shape, wraps in ((R.STACK_BIG[1:], (True, False)), (R.STACK_MANY[1:], (False,))):
+        for wrap in wraps:
+            m = R.threshold_margin_both_forms(shape, As, wrap)
+            print(f"stack {shape} wrap {wrap}: margin {m:.2e}")
+            assert m >= 1e-9
+            if wrap:
+                coords = [R.source_coords(shape, R.inv3x3(A), True, True)[0] for A in As]
+                assert not R.wrap_edge_mask(shape, coords).any()
+    base = R.base_images()
+    assert base.min() > 0 and len({b.tobytes() for b in base}) == R.STACK_BASE
+    out = [R.source_coords(R.STACK_MANY[1:], R.inv3x3(A), False, True)[2] for A in As]
+    assert any(o.any() for o in out) and not all(o.all() for o in out)          # the outside mean is used, and so are the taps

@@ -1382,6 +1382,54 @@ int xh_fsym_stage_ms(const xh_fsym *h, double *h_ms);
 int xh_halves_cylinder_mask(int32_t Z, int32_t Y, int32_t X, double R, double H, double x0, double y0, double z0, int32_t *h_mask);
 int xh_halves_tube_mask(int32_t Z, int32_t Y, int32_t X, double R1, double R2, double H, double x0, double y0, double z0, int32_t *h_mask);
 
+/* ---- xmipp_reconstruct_wbp (reconstruction/reconstruct_wbp.cpp, ProgRecWbp; CPU and an MPI farm in the reference): weighted
+ * back-projection with the arbitrary-geometry filter, fp64. The handle owns the D^3 volume, the buffers of one batch of `capacity` images,
+ * the transform's plans and Tabsinc(0.0001, D) (:538). It reads matrices and direction lists, never angles: the caller forms them, so the
+ * device and a restatement read the same doubles. The kernels and the behaviours kept as written are listed at the head of
+ * xmipp3_amd/csrc/xh_wbp.hip. create: D of 2 .. 1024, odd sizes included; capacity 1 .. 65535 images of one batch. No output depends on it. */
+typedef struct xh_wbp xh_wbp;
+int xh_wbp_create(xh_ctx *ctx, int32_t D, int32_t capacity, xh_wbp **out);
+int xh_wbp_destroy(xh_wbp *h);
+/* a new reconstruction: the volume and count_thr are zero (:526-528). The directions stay */
+int xh_wbp_reset(xh_wbp *h);
+/* mat_g (:308-359, :231-305): h_g [no_mats][4] = x, y, z, count of every projection direction, symmetry copies included, in the
+ * reference's order; threshold: the absolute one, already times totimgs (:304, :358); diameter: 2 * radius, or D (:44, :203-204).
+ * Refused: a diameter above D (the reference then reads past its sinc table), entries that are not finite, x, y, z above 1 */
+int xh_wbp_set_directions(xh_wbp *h, const double *h_g, int32_t no_mats, double threshold, int32_t diameter);
+/* n images through apply2DFilterArbitraryGeometry's loop body (:541-562), in batches of at most `capacity`: h_images [n][D][D] floats,
+ * h_rows [n][22] = shiftX, shiftY, flip (0 or not), the weight the image is multiplied by (1 without --weight), the 3 x 3 of
+ * Euler_angles2matrix(-rot, tilt, -psi) (:447) and the 3 x 3 inverse of Euler_angles2matrix(rot, -tilt, psi) (:373-374), row-major.
+ * prepare (:552-557): A of getTransformationMatrix(A, true) = shifts in column 2, a flip negates A00 and A01; unless A is the identity
+ * within 1e-6, selfApplyGeometry(BSPLINE3, ., A, IS_INV, WRAP); times the weight. Then FourierTransform, the filter (:451-487, count_thr
+ * grows), InverseFourierTransform and simpleBackprojection into the handle's volume, image after image in list order.
+ * h_filtered (nullable): receives the filtered images [n][D][D], what simpleBackprojection read. Synchronous */
+int xh_wbp_add(xh_wbp *h, const float *h_images, const double *h_rows, int32_t n, double *h_filtered);
+/* :566-579: with nsym > 0 symmetrizeVolume(SL, V, Vaux) at its defaults (symmetrize.h:99-104: BSPLINE3, WRAP, no outside average, no sum)
+ * over h_R [nsym][3][3], the R of SL.getMatrices, through xh_sym_symmetrize, then the inner sphere r^2 <= (diameter / 2.)^2;
+ * nsym = 0 leaves the volume as it is */
+int xh_wbp_finish(xh_wbp *h, const double *h_R, int32_t nsym);
+/* the volume [D][D][D] as doubles, to a host or a device pointer; the number of Fourier pixels below the threshold so far (:480) */
+int xh_wbp_volume(xh_wbp *h, double *out);
+int xh_wbp_count_thr(xh_wbp *h, int64_t *count);
+/* hooks for the tests. weights: the filter's weight at every cell for one image's row, h_weights [D][D] in the transform's uncentred
+ * layout (cell (iy, jx) holds logical i = iy or iy - D); neither the volume nor count_thr changes. table: the sinc table, *n its
+ * length, h_table nullable. tile: the directions of one LDS tile of the filter */
+int xh_wbp_weights(xh_wbp *h, const double *h_row, double *h_weights);
+int xh_wbp_table(const xh_wbp *h, double *h_table, int64_t *n);
+int xh_wbp_tile(void);
+/* host only, what the program forms before any device is opened. image_matrices: h_dir[3] = row 2 of Euler_angles2matrix(rot, -tilt, psi)
+ * (:327-330), h_filter[9] = Euler_angles2matrix(-rot, tilt, -psi) (:447), h_back[9] = the cofactor inverse of Euler_angles2matrix(rot,
+ * -tilt, psi) (:373-374). even_distribution: make_even_distribution(rotList, tiltList, sampling, SL, true) of reconstruction/directions.cpp
+ * :133-183 for an empty SL (directions_are_unique with Euler_another_set = (rot + 180, -tilt)); *n the count, h_rot / h_tilt nullable.
+ * nearest_direction: find_nearest_direction (:194-237) for an empty SL, -1 for an empty list */
+int xh_wbp_image_matrices(double rot, double tilt, double psi, double *h_dir, double *h_filter, double *h_back);
+int xh_wbp_even_distribution(double sampling, double *h_rot, double *h_tilt, int32_t capacity, int32_t *n);
+int xh_wbp_nearest_direction(double rot, double tilt, const double *h_rot, const double *h_tilt, int32_t n, int32_t *index);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[5] = prepare, both transforms, the filter, the
+ * back-projection, finish, summed since set_timing */
+int xh_wbp_set_timing(xh_wbp *h, int32_t on);
+int xh_wbp_stage_ms(const xh_wbp *h, double *h_ms);
+
 #ifdef __cplusplus
 }
 #endif

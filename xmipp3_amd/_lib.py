@@ -306,6 +306,22 @@ SIGNATURES = {
     "xh_fsym_helical_volume": (C.c_int, [vp, d, d, i32, d, i32, vp]),
     "xh_fsym_set_timing": (C.c_int, [vp, i32]),
     "xh_fsym_stage_ms": (C.c_int, [vp, vp]),
+    "xh_wbp_create": (C.c_int, [vp, i32, i32, pvp]),
+    "xh_wbp_destroy": (C.c_int, [vp]),
+    "xh_wbp_reset": (C.c_int, [vp]),
+    "xh_wbp_set_directions": (C.c_int, [vp, vp, i32, d, i32]),
+    "xh_wbp_add": (C.c_int, [vp, vp, vp, i32, vp]),
+    "xh_wbp_finish": (C.c_int, [vp, vp, i32]),
+    "xh_wbp_volume": (C.c_int, [vp, vp]),
+    "xh_wbp_count_thr": (C.c_int, [vp, C.POINTER(i64)]),
+    "xh_wbp_weights": (C.c_int, [vp, vp, vp]),
+    "xh_wbp_table": (C.c_int, [vp, vp, C.POINTER(i64)]),
+    "xh_wbp_tile": (C.c_int, []),
+    "xh_wbp_image_matrices": (C.c_int, [d, d, d, vp, vp, vp]),
+    "xh_wbp_even_distribution": (C.c_int, [d, vp, vp, i32, C.POINTER(i32)]),
+    "xh_wbp_nearest_direction": (C.c_int, [d, d, vp, vp, i32, C.POINTER(i32)]),
+    "xh_wbp_set_timing": (C.c_int, [vp, i32]),
+    "xh_wbp_stage_ms": (C.c_int, [vp, vp]),
     "xh_halves_cylinder_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, vp]),
     "xh_halves_tube_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, d, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

@@ -1625,6 +1625,117 @@ def vds_zsh(l1, n, l2, m, xr, yr, zr, r):
     return v.value
 
 
+class ReconstructWbp(_StageTimes, _VolumeHandle):
+    """The device side of xmipp_reconstruct_wbp: weighted back-projection with the arbitrary-geometry filter. The caller forms the
+    direction list mat_g and every image's two matrices on the host; images are float32 [n, D, D] numpy arrays. capacity: the images of
+    one batch; no result depends on it."""
+
+    _destroy = "xh_wbp_destroy"
+    _PREFIX = "wbp"
+
+    STAGES = ("prepare", "transforms", "filter", "backprojection", "finish")
+    ROW = 22
+
+    def __init__(self, ctx, D, capacity=64):
+        self.ctx = ctx
+        self.D, self.capacity = int(D), int(capacity)
+        self.shape = (self.D,) * 3
+        h = C.c_void_p()
+        check(lib().xh_wbp_create(ctx.h, self.D, self.capacity, C.byref(h)))
+        _Handle.__init__(self, ctx, h)
+
+    @staticmethod
+    def rows(shifts_x, shifts_y, flips, weights, filter_matrices, backprojection_matrices):
+        """[n, 22] rows of add(): shiftX, shiftY, flip, weight, Euler_angles2matrix(-rot, tilt, -psi), inv(Euler_angles2matrix(rot, -tilt, psi))"""
+        n = len(shifts_x)
+        r = np.zeros((n, 22))
+        r[:, 0], r[:, 1], r[:, 2], r[:, 3] = shifts_x, shifts_y, np.asarray(flips, dtype=bool), weights
+        r[:, 4:13] = np.asarray(filter_matrices, dtype=np.float64).reshape(n, 9)
+        r[:, 13:22] = np.asarray(backprojection_matrices, dtype=np.float64).reshape(n, 9)
+        return r
+
+    def reset(self):
+        """a new reconstruction: zero volume, zero count_thr; the directions stay"""
+        check(lib().xh_wbp_reset(self.h))
+
+    def set_directions(self, mat_g, threshold, diameter=None):
+        """mat_g [no_mats, 4] = x, y, z, count; the absolute threshold (relative times the sum of the counts); diameter (default D)"""
+        g = np.ascontiguousarray(np.asarray(mat_g, dtype=np.float64).reshape(-1, 4))
+        check(lib().xh_wbp_set_directions(self.h, _np_ptr(g), len(g), float(threshold), int(self.D if diameter is None else diameter)))
+        self.no_mats = len(g)
+
+    def add(self, images, rows, filtered=False):
+        """filters and back-projects the images in list order; filtered=True returns the filtered images float64 [n, D, D]"""
+        images = np.ascontiguousarray(images, np.float32)
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, self.ROW))
+        if images.shape != (len(rows), self.D, self.D):
+            raise XhError(f"ReconstructWbp: images of shape {images.shape} for {len(rows)} rows, the handle D = {self.D}")
+        out = np.zeros(images.shape) if filtered else None
+        check(lib().xh_wbp_add(self.h, _np_ptr(images), _np_ptr(rows), len(rows), _np_ptr(out)))
+        return out
+
+    def finish(self, R=None):
+        """with the R of SymList::getMatrices [n, 3, 3]: symmetrizeVolume at its defaults, then the inner sphere of the diameter"""
+        R = np.zeros((0, 3, 3)) if R is None else np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1, 3, 3))
+        check(lib().xh_wbp_finish(self.h, _np_ptr(R) if len(R) else None, len(R)))
+
+    def volume(self):
+        """the volume as a float64 device tensor [D, D, D]"""
+        out = self._new()
+        check(lib().xh_wbp_volume(self.h, _ptr(out)))
+        return out
+
+    def count_thr(self):
+        """Fourier pixels for which the threshold was not reached, over the images added since reset"""
+        c = C.c_int64()
+        check(lib().xh_wbp_count_thr(self.h, C.byref(c)))
+        return c.value
+
+    def weights(self, row):
+        """the filter's weights of one image's row, [D, D] with the logical origin at (D // 2, D // 2) as after CenterFFT (test hook)"""
+        row = np.ascontiguousarray(np.asarray(row, dtype=np.float64).reshape(self.ROW))
+        w = np.zeros((self.D, self.D))
+        check(lib().xh_wbp_weights(self.h, _np_ptr(row), _np_ptr(w)))
+        return np.roll(w, (self.D // 2, self.D // 2), axis=(0, 1))
+
+    def table(self):
+        """the sinc table Tabsinc(0.0001, D) (test hook)"""
+        n = C.c_int64()
+        check(lib().xh_wbp_table(self.h, None, C.byref(n)))
+        t = np.zeros(n.value)
+        check(lib().xh_wbp_table(self.h, _np_ptr(t), C.byref(n)))
+        return t
+
+
+def wbp_image_matrices(rot, tilt, psi):
+    """(row 2 of Euler_angles2matrix(rot, -tilt, psi), Euler_angles2matrix(-rot, tilt, -psi), inv(Euler_angles2matrix(rot, -tilt, psi))) (host only)"""
+    g, F, B = np.zeros(3), np.zeros((3, 3)), np.zeros((3, 3))
+    check(lib().xh_wbp_image_matrices(float(rot), float(tilt), float(psi), _np_ptr(g), _np_ptr(F), _np_ptr(B)))
+    return g, F, B
+
+
+def wbp_even_distribution(sampling):
+    """make_even_distribution without symmetry, mirrors included: (rot [n], tilt [n]) in degrees (host only)"""
+    n = C.c_int32()
+    check(lib().xh_wbp_even_distribution(float(sampling), None, None, 0, C.byref(n)))
+    rot, tilt = np.zeros(n.value), np.zeros(n.value)
+    check(lib().xh_wbp_even_distribution(float(sampling), _np_ptr(rot), _np_ptr(tilt), n.value, C.byref(n)))
+    return rot, tilt
+
+
+def wbp_nearest_direction(rot, tilt, rot_list, tilt_list):
+    """find_nearest_direction without symmetry: the index into the lists, -1 for empty lists (host only)"""
+    r, t = np.ascontiguousarray(rot_list, np.float64), np.ascontiguousarray(tilt_list, np.float64)
+    i = C.c_int32()
+    check(lib().xh_wbp_nearest_direction(float(rot), float(tilt), _np_ptr(r), _np_ptr(t), len(r), C.byref(i)))
+    return i.value
+
+
+def wbp_tile():
+    """the directions of one LDS tile of the filter kernel (host only)"""
+    return lib().xh_wbp_tile()
+
+
 def vds_normalize_robust(v, clip=1.3284):
     """normalize_Robust of a float64 array with a zero background mask; returns a new array (host only)"""
     out = np.ascontiguousarray(v, np.float64).copy()

@@ -1430,6 +1430,48 @@ int xh_wbp_nearest_direction(double rot, double tilt, const double *h_rot, const
 int xh_wbp_set_timing(xh_wbp *h, int32_t on);
 int xh_wbp_stage_ms(const xh_wbp *h, double *h_ms);
 
+/* ---- xmipp_ctf_estimate_from_micrograph --dont_estimate_ctf and xmipp_psd_estimate: the PSD of a micrograph by periodogram averaging
+ * (reconstruction/ctf_estimate_from_micrograph.cpp run() :289-584 in doubles, reconstruction/psd_estimator.cpp estimatePSD :74-148 in
+ * floats). The handle holds one micrograph [Y][X] in float32, the two separable taper vectors of constructPieceSmoother (:143-189), a
+ * half-spectrum intermediate of `capacity` pieces and the running sums. The kernels are listed at the head of xmipp3_amd/csrc/xh_psd.hip.
+ * create: piece sides py, px of 2 .. 1024, odd ones included; the double path (is_double) takes square pieces; capacity 1 .. 65535 pieces
+ * of one batch. No output depends on the capacity. */
+typedef struct xh_psd xh_psd;
+int xh_psd_create(xh_ctx *ctx, int32_t Y, int32_t X, int32_t py, int32_t px, int32_t capacity, int32_t is_double, xh_psd **out);
+int xh_psd_destroy(xh_psd *h);
+/* the micrograph [Y][X] from a host (pageable or page-locked) or a device pointer: M_in.read (:373). The running sums stay */
+int xh_psd_load(xh_psd *h, const float *micrograph);
+/* the pieces at h_corners [n][2] = (top row, left column), in list order, `capacity` at a time (:416-463; psd_estimator.cpp:100-117).
+ * flags: 1 statisticsAdjust(0, 1) (:422; psd_estimator.cpp:105), 2 normalize_ramp (:423, data/normalize.cpp:333-425; double only).
+ * h_stack null: every piece's PSD is added to the running sums (in double its square too), in list order whatever the capacity.
+ * h_stack [n][py][px] of the element type: receives each piece's own complete PSD and the sums stay (the regions and particles modes,
+ * :497-508). Refused: a corner whose piece leaves the micrograph. Synchronous */
+int xh_psd_add(xh_psd *h, const int32_t *h_corners, int32_t n, int32_t flags, void *h_stack);
+/* [py][px] of the element type, mirrored by half2whole (psd_estimator.h:52-73). double: avg = sum * (1 / n) and
+ * std = sqrt(max(0, sum2 * (1 / n) - avg^2)) (:572-583). float: h_avg receives the SUM of the magnitudes, which is what
+ * psd_estimator.cpp:115-121 keeps, h_std zeros. h_std and n nullable; *n the pieces added since reset */
+int xh_psd_result(xh_psd *h, void *h_avg, void *h_std, int64_t *n);
+/* zero sums, zero pieces; the micrograph stays */
+int xh_psd_reset(xh_psd *h);
+/* test hooks: the taper (1 * maskY[i]) * maskX[j] [py][px] as the kernels form it; the prepared pieces [n][py][px] before the transform */
+int xh_psd_smoother(xh_psd *h, void *h_out);
+int xh_psd_piece(xh_psd *h, const int32_t *h_corners, int32_t n, int32_t flags, void *h_out);
+/* the columns of the half spectrum one workgroup of the column pass owns */
+int xh_psd_strip(void);
+/* for the benchmark: with timing on every stage is followed by a wait; h_ms[4] = statistics, rows, columns + accumulate, finish */
+int xh_psd_set_timing(xh_psd *h, int32_t on);
+int xh_psd_stage_ms(const xh_psd *h, double *h_ms);
+/* host only. pieces: the corner list of run() (:310-327, :371-414) with the skip rule and the clamp to the far edge. mode 0 micrograph
+ * (step (int)((1 - overlap) pieceDim)), 1 regions (step pieceDim; fewer than 2 skipBorders + 1 divisions is the reference's own error),
+ * 2 particles (h_pos [npos][2] = x, y of the centres; a coordinate below pieceDim / 2 is refused: the reference's unsigned subtraction
+ * wraps there). h_corners [capacity][2], h_slots [capacity] (the reference's 1-based N of each kept piece), both nullable: *n alone.
+ * Refused: a list with no piece, where the reference divides by zero. *div_number (nullable): div_Number.
+ * patches: getPatchesLocation (psd_estimator.cpp:35-71), its asserts as refusals */
+int xh_psd_pieces(int32_t Y, int32_t X, int32_t pieceDim, double overlap, int32_t skipBorders, int32_t mode, const int64_t *h_pos, int32_t npos,
+                  int32_t *h_corners, int32_t *h_slots, int32_t capacity, int32_t *n, int32_t *div_number);
+int xh_psd_patches(int32_t Y, int32_t X, int32_t py, int32_t px, int32_t borderX, int32_t borderY, float overlap, int32_t *h_corners, int32_t capacity,
+                   int32_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -322,6 +322,19 @@ SIGNATURES = {
     "xh_wbp_nearest_direction": (C.c_int, [d, d, vp, vp, i32, C.POINTER(i32)]),
     "xh_wbp_set_timing": (C.c_int, [vp, i32]),
     "xh_wbp_stage_ms": (C.c_int, [vp, vp]),
+    "xh_psd_create": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, pvp]),
+    "xh_psd_destroy": (C.c_int, [vp]),
+    "xh_psd_load": (C.c_int, [vp, vp]),
+    "xh_psd_add": (C.c_int, [vp, vp, i32, i32, vp]),
+    "xh_psd_result": (C.c_int, [vp, vp, vp, C.POINTER(i64)]),
+    "xh_psd_reset": (C.c_int, [vp]),
+    "xh_psd_smoother": (C.c_int, [vp, vp]),
+    "xh_psd_piece": (C.c_int, [vp, vp, i32, i32, vp]),
+    "xh_psd_strip": (C.c_int, []),
+    "xh_psd_set_timing": (C.c_int, [vp, i32]),
+    "xh_psd_stage_ms": (C.c_int, [vp, vp]),
+    "xh_psd_pieces": (C.c_int, [i32, i32, i32, d, i32, i32, vp, i32, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "xh_psd_patches": (C.c_int, [i32, i32, i32, i32, i32, i32, C.c_float, vp, i32, C.POINTER(i32)]),
     "xh_halves_cylinder_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, vp]),
     "xh_halves_tube_mask": (C.c_int, [i32, i32, i32, d, d, d, d, d, d, vp]),
     "xh_powell_minimize": (C.c_int, [i32, vp, vp, d, COST_FN, vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

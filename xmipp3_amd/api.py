@@ -1736,6 +1736,105 @@ def wbp_tile():
     return lib().xh_wbp_tile()
 
 
+class PsdEstimator(_StageTimes, _Handle):
+    """The device side of the PSD stage of xmipp_ctf_estimate_from_micrograph (dtype float64: statisticsAdjust, normalize_ramp, the
+    taper, |F|^2 pieceDim^2, avg and std) and of xmipp_psd_estimate (dtype float32: statisticsAdjust, the taper, the sum of the
+    magnitudes). One micrograph [Y, X] lives on the device as float32; pieces are [n, 2] top-left corners (row, column), `capacity` of
+    them run at a time and no result depends on it."""
+
+    _destroy = "xh_psd_destroy"
+    _PREFIX = "psd"
+
+    STAGES = ("statistics", "rows", "columns", "finish")
+    ADJUST, RAMP = 1, 2
+
+    def __init__(self, ctx, Y, X, py, px=None, capacity=64, dtype=np.float64):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise XhError(f"PsdEstimator: dtype {self.dtype} (float32 or float64)")
+        self.Y, self.X, self.py, self.px, self.capacity = int(Y), int(X), int(py), int(py if px is None else px), int(capacity)
+        self.flags = self.ADJUST | (self.RAMP if self.dtype == np.float64 else 0)
+        h = C.c_void_p()
+        check(lib().xh_psd_create(ctx.h, self.Y, self.X, self.py, self.px, self.capacity, int(self.dtype == np.float64), C.byref(h)))
+        super().__init__(ctx, h)
+
+    def _corners(self, corners):
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.int32).reshape(-1, 2))
+        return c
+
+    def load(self, micrograph):
+        """a float32 [Y, X] numpy array, or a torch tensor (device, or page-locked host memory)"""
+        if isinstance(micrograph, np.ndarray):
+            m = np.ascontiguousarray(micrograph, np.float32)
+            if m.shape != (self.Y, self.X):
+                raise XhError(f"PsdEstimator: a micrograph of shape {m.shape}, the handle {(self.Y, self.X)}")
+            check(lib().xh_psd_load(self.h, _np_ptr(m)))
+            return
+        t = micrograph
+        if tuple(t.shape) != (self.Y, self.X) or t.dtype != _torch().float32 or not t.is_contiguous():
+            raise XhError(f"PsdEstimator: the micrograph must be a contiguous float32 tensor of shape {(self.Y, self.X)}")
+        check(lib().xh_psd_load(self.h, C.c_void_p(t.data_ptr())))
+
+    def add(self, corners, stack=False, flags=None):
+        """adds the pieces' PSDs to the running sums in list order; stack=True returns each piece's own PSD [n, py, px] instead"""
+        c = self._corners(corners)
+        out = np.zeros((len(c), self.py, self.px), self.dtype) if stack else None
+        check(lib().xh_psd_add(self.h, _np_ptr(c), len(c), self.flags if flags is None else int(flags), _np_ptr(out)))
+        return out
+
+    def result(self):
+        """(avg, std, n) in float64; (the sum of the magnitudes, zeros, n) in float32; [py, px], mirrored to the whole plane"""
+        avg, std = np.zeros((self.py, self.px), self.dtype), np.zeros((self.py, self.px), self.dtype)
+        n = C.c_int64()
+        check(lib().xh_psd_result(self.h, _np_ptr(avg), _np_ptr(std), C.byref(n)))
+        return avg, std, n.value
+
+    def reset(self):
+        """zero sums and zero pieces; the micrograph stays"""
+        check(lib().xh_psd_reset(self.h))
+
+    def smoother(self):
+        """the taper [py, px] as the kernels form it (test hook)"""
+        out = np.zeros((self.py, self.px), self.dtype)
+        check(lib().xh_psd_smoother(self.h, _np_ptr(out)))
+        return out
+
+    def piece(self, corners, flags=None):
+        """the prepared pieces [n, py, px] before the transform (test hook)"""
+        c = self._corners(corners)
+        out = np.zeros((len(c), self.py, self.px), self.dtype)
+        check(lib().xh_psd_piece(self.h, _np_ptr(c), len(c), self.flags if flags is None else int(flags), _np_ptr(out)))
+        return out
+
+
+def psd_pieces(Y, X, pieceDim, overlap=0.5, skipBorders=2, mode="micrograph", pos=None):
+    """the piece list of xmipp_ctf_estimate_from_micrograph: (corners [n, 2] = row, column; slots [n], the reference's 1-based N;
+    div_Number). mode: micrograph, regions or particles (pos [n, 2] = x, y of the centres) (host only)"""
+    m = {"micrograph": 0, "regions": 1, "particles": 2}[mode]
+    p = None if pos is None else np.ascontiguousarray(np.asarray(pos, dtype=np.int64).reshape(-1, 2))
+    n, div = C.c_int32(), C.c_int32()
+    args = (int(Y), int(X), int(pieceDim), float(overlap), int(skipBorders), m, _np_ptr(p), 0 if p is None else len(p))
+    check(lib().xh_psd_pieces(*args, None, None, 0, C.byref(n), C.byref(div)))
+    corners, slots = np.zeros((n.value, 2), np.int32), np.zeros(n.value, np.int32)
+    check(lib().xh_psd_pieces(*args, _np_ptr(corners), _np_ptr(slots), n.value, C.byref(n), C.byref(div)))
+    return corners, slots, div.value
+
+
+def psd_patches(Y, X, py, px, borderX=0, borderY=0, overlap=0.5):
+    """getPatchesLocation of xmipp_psd_estimate: corners [n, 2] = row, column (host only)"""
+    n = C.c_int32()
+    args = (int(Y), int(X), int(py), int(px), int(borderX), int(borderY), float(overlap))
+    check(lib().xh_psd_patches(*args, None, 0, C.byref(n)))
+    corners = np.zeros((n.value, 2), np.int32)
+    check(lib().xh_psd_patches(*args, _np_ptr(corners), n.value, C.byref(n)))
+    return corners
+
+
+def psd_strip():
+    """the half-spectrum columns one workgroup of the column pass owns (host only)"""
+    return lib().xh_psd_strip()
+
+
 def vds_normalize_robust(v, clip=1.3284):
     """normalize_Robust of a float64 array with a zero background mask; returns a new array (host only)"""
     out = np.ascontiguousarray(v, np.float64).copy()

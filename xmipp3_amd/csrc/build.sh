@@ -48,8 +48,10 @@ $HIPCC $COMMON -ffp-contract=off -c xh_valign.hip -o build/xh_valign.o & pids+=(
 $HIPCC $COMMON -ffp-contract=off -c xh_fsym.hip -o build/xh_fsym.o & pids+=($!)
 # the sinc table's index is the (int) of a quotient, the back-projection's taps the (int) of a coordinate, and the threshold, sphere and image cuts compare doubles: they must round like the scalar code
 $HIPCC $COMMON -ffp-contract=off -c xh_wbp.hip -o build/xh_wbp.o & pids+=($!)
+# the deviation of normalize_ramp feeds a comparison (> 1e-6) and every value before the transform is formed with the reference's roundings
+$HIPCC $COMMON -ffp-contract=off -c xh_psd.hip -o build/xh_psd.o & pids+=($!)
 fail=0
 for p in "${pids[@]}"; do wait $p || fail=1; done
 if [ $fail -ne 0 ]; then echo "build.sh: compilation FAILED" >&2; exit 1; fi
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libxmipp_hip.so build/xh_rf.o build/xh_ctx.o build/xh_pm.o build/xh_fp.o build/xh_fft2d.o build/xh_fsc.o build/xh_ctfops.o build/xh_flexalign.o build/xh_estimators.o build/xh_align_sig.o build/xh_halves.o build/xh_ca2.o build/xh_vds.o build/xh_asa.o build/xh_faz.o build/xh_powell.o build/xh_rsp.o build/xh_sub.o build/xh_mono.o build/xh_ldb.o build/xh_fso.o build/xh_vsub.o build/xh_rsig.o build/xh_sym.o build/xh_valign.o build/xh_fsym.o build/xh_wbp.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o ../libxmipp_hip.so build/xh_rf.o build/xh_ctx.o build/xh_pm.o build/xh_fp.o build/xh_fft2d.o build/xh_fsc.o build/xh_ctfops.o build/xh_flexalign.o build/xh_estimators.o build/xh_align_sig.o build/xh_halves.o build/xh_ca2.o build/xh_vds.o build/xh_asa.o build/xh_faz.o build/xh_powell.o build/xh_rsp.o build/xh_sub.o build/xh_mono.o build/xh_ldb.o build/xh_fso.o build/xh_vsub.o build/xh_rsig.o build/xh_sym.o build/xh_valign.o build/xh_fsym.o build/xh_wbp.o build/xh_psd.o
 echo "built $(cd .. && pwd)/libxmipp_hip.so"

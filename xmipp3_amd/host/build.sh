@@ -31,5 +31,7 @@ $CXX $FLAGS transform_symmetrize_main.cpp -o ../bin/xmipp_transform_symmetrize $
 $CXX $FLAGS volume_align_main.cpp -o ../bin/xmipp_volume_align $LINK &
 $CXX $FLAGS volume_find_symmetry_main.cpp -o ../bin/xmipp_volume_find_symmetry $LINK &
 $CXX $FLAGS reconstruct_wbp_main.cpp -o ../bin/xmipp_reconstruct_wbp $LINK &
+$CXX $FLAGS ctf_estimate_from_micrograph_main.cpp -o ../bin/xmipp_ctf_estimate_from_micrograph $LINK &
+$CXX $FLAGS psd_estimate_main.cpp -o ../bin/xmipp_psd_estimate $LINK &
 wait
-echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph,angular_sph_alignment,forward_art_zernike3d,subtract_projection,resolution_monogenic_signal,volume_local_sharpening,resolution_fso,volume_subtraction,reconstruct_significant,transform_symmetrize,volume_align,volume_find_symmetry,reconstruct_wbp}"
+echo "built $(cd ../bin && pwd)/xmipp_{angular_projection_matching,reconstruct_fourier_accel,reconstruct_fourier,angular_project_library,resolution_fsc,ctf_phase_flip,ctf_correct_wiener2d,movie_alignment_correlation,movie_filter_dose,align_significant,volume_halves_restoration,angular_continuous_assign2,volume_deform_sph,angular_sph_alignment,forward_art_zernike3d,subtract_projection,resolution_monogenic_signal,volume_local_sharpening,resolution_fso,volume_subtraction,reconstruct_significant,transform_symmetrize,volume_align,volume_find_symmetry,reconstruct_wbp,ctf_estimate_from_micrograph,psd_estimate}"

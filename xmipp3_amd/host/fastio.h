@@ -66,6 +66,7 @@ struct XhDestroy {
     void operator()(xh_valign *h) const { xh_valign_destroy(h); }
     void operator()(xh_fsym *h) const { xh_fsym_destroy(h); }
     void operator()(xh_wbp *h) const { xh_wbp_destroy(h); }
+    void operator()(xh_psd *h) const { xh_psd_destroy(h); }
 };
 template <class T> using XhOwner = std::unique_ptr<T, XhDestroy>;
 
